@@ -46,6 +46,16 @@ submit_clouds() / collect() wrap), with one and two frames in flight: PCIe-inclu
 N > 1 without a launcher around it (`python bench.py --gpus 8`): bench.py starts its own ranks.  `--single-process`: the N devices behind ONE
 csky_multi handle (no torch.distributed).  `--groups G`: consecutive frames go to G groups of devices / ranks in turn (throughput workloads).
 
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) does only what the headline needs: set-up, the W warm-up and K timed steps,
+`--dump-outputs DIR` if given, and the line (`metric`, `value`, `unit`, `ms_per_step`, `higher_is_better`, `dtype`, ...).  Everything else above --
+the clock pre-warm and `value_prewarmed`, `value_one_frame_at_a_time`, `value_host_form`, `config.with_early_out`, `roofline`, `cpu_baseline`,
+`per_rank_share_ms`, the frame checks (`config.finite`, `gathered_frame_check`, `multi_stats`) -- runs with `--full` only; their fields are null otherwise.
+
+`--dump-outputs DIR`: what the timed path delivered in its last timed step, as float32 .npy files (clouds.npy = the H x W x 4 RGBA16F frame;
+sky_lut.npy = the 100 x 200 x 4 sky LUT where the path delivers one); a frame over 48 MB is written as a fixed, seeded sample of its rows
+(clouds.npy + clouds_rows.npy, the row indices).  The inputs are fixed (shipped assets, seeded shape noise, constant push constants), so two builds
+run with the same arguments can be compared array for array.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -131,6 +141,29 @@ def cpu_baseline(large, small, weather, params, sun, W, H, primary, light, every
                       "gcc -O2 fp32, OpenMP %d threads" % (every, W, H, rays, dt, dt * cores, cores),
             "single_thread": {"value": nb1 * 8 * w1 / dt1 / 1e6, "unit": "Mrays/s", "cores": 1,
                               "sample": "every 16th 8-row band, columns 0..%d (%d rays, %.2f s)" % (w1 - 1, nb1 * 8 * w1, dt1)}}
+
+
+DUMP_FRAME_LIMIT = 48 << 20   # --dump-outputs: a float32 frame above this is sampled by rows (everything written stays under 64 MB)
+
+
+def dump_outputs(out_dir, frame, sky_lut=None):
+    """--dump-outputs: the last timed step's frame (int16 tensor holding RGBA16F, H x W x 4) and sky LUT (the same as a tensor, or the float16
+    array of read_sky_lut; None where the path delivers none) as float32 .npy files.  A frame over DUMP_FRAME_LIMIT keeps a fixed, seeded
+    sample of its rows, whose indices go to clouds_rows.npy."""
+    def f32(x):
+        if not isinstance(x, np.ndarray):
+            x = x.cpu().numpy().view(np.float16)
+        return x.astype(np.float32)
+
+    os.makedirs(out_dir, exist_ok=True)
+    fr = f32(frame)
+    if fr.nbytes > DUMP_FRAME_LIMIT:
+        rows = np.sort(np.random.default_rng(0).choice(fr.shape[0], DUMP_FRAME_LIMIT // fr[0].nbytes, replace=False))
+        fr = fr[rows]
+        np.save(os.path.join(out_dir, "clouds_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "clouds.npy"), fr)
+    if sky_lut is not None:
+        np.save(os.path.join(out_dir, "sky_lut.npy"), f32(sky_lut))
 
 
 def free_port():
@@ -230,9 +263,11 @@ def main_single_process(args):
 
     # both protocols, as in the process-per-GPU form below: `value` = as asked (run first, cold); then the clock pre-warm and the same region again -> `value_prewarmed`
     elapsed, n_last = region()
+    if args.dump_outputs:                                                 # the frame of the last timed step and the LUT its devices rendered (read through device 0)
+        dump_outputs(args.dump_outputs, frames[(n_last - 1) % slots], m.ctx(0).read_sky_lut())
     prewarmed = None
     prewarm_frames = 0
-    if not args.no_prewarm:
+    if args.full and not args.no_prewarm:
         est_ms = 1.7 * tiles_per_dev / 32768.0 * primary / 128.0
         prewarm_frames = int(min(1024, max(16, np.ceil(120.0 / max(est_ms, 1e-3))))) * G
         for _ in range(prewarm_frames):
@@ -243,28 +278,30 @@ def main_single_process(args):
         prewarmed = {"value": W * H * args.steps / e_warm / 1e6, "ms_per_step": e_warm / args.steps * 1e3}
     as_asked = {"value": W * H * args.steps / elapsed / 1e6, "ms_per_step": elapsed / args.steps * 1e3}
     # every device's share alone (one launch at a time on that device): what bounds the split
-    share_ms = []
-    for i in range(n):
+    share_ms = [] if args.full else None
+    for i in range(n if args.full else 0):
         k = i % per
         total = H // 8
         nb = (total - k + per - 1) // per
         ms, _ = m.ctx(i).time_clouds(params, W, (8, k, per, nb), warmup=1, iters=3)
         share_ms.append(ms)
     fr = frames[(n_last - 1) % slots].view(torch.float16)               # the last frame the last region rendered (region() returns how many it ran)
-    # the handle's preconditions (peer access of every device to the first) and, outside the timed regions, HIP-event timings of one more frame:
-    # every device's march of its bands and (staged form) its peer copy -- csky_multi_get_stats
-    sync_all()
-    m.set_timing(True)
-    fp_t, fs_t = (params, sun_n) if sweep is None else sweep[0]
-    m.render_sky_lut(fs_t, 200, 100)
-    scratch = torch.zeros((H, W, 4), dtype=torch.int16, device=dev)
-    m.render_clouds_device(fp_t, W, H, scratch.data_ptr(), W * 8, streams[0].cuda_stream)
-    multi_stats = m.stats()
-    multi_stats["warning"] = m.last_warning()
-    m.set_timing(False)
-    alpha_mean = float(fr[..., 3].float().mean().item())
-    finite = bool(torch.isfinite(fr.float()).all().item())
-    if True:                                                              # the assembled frame must equal a single-context render of the same frame (outside the timed region)
+    multi_stats = alpha_mean = finite = frame_check = None
+    if args.full:
+        # the handle's preconditions (peer access of every device to the first) and, outside the timed regions, HIP-event timings of one more frame:
+        # every device's march of its bands and (staged form) its peer copy -- csky_multi_get_stats
+        sync_all()
+        m.set_timing(True)
+        fp_t, fs_t = (params, sun_n) if sweep is None else sweep[0]
+        m.render_sky_lut(fs_t, 200, 100)
+        scratch = torch.zeros((H, W, 4), dtype=torch.int16, device=dev)
+        m.render_clouds_device(fp_t, W, H, scratch.data_ptr(), W * 8, streams[0].cuda_stream)
+        multi_stats = m.stats()
+        multi_stats["warning"] = m.last_warning()
+        m.set_timing(False)
+        alpha_mean = float(fr[..., 3].float().mean().item())
+        finite = bool(torch.isfinite(fr.float()).all().item())
+    if args.full:                                                         # the assembled frame must equal a single-context render of the same frame (outside the timed region)
         c0 = m.ctx(0)
         full = torch.zeros((H, W, 4), dtype=torch.int16, device=dev)
         k_last = n_last - 1
@@ -295,7 +332,7 @@ def main_single_process(args):
                    "texture_size": [W, H], "primary_steps": primary, "light_steps": light, "early_out_eps": args.early_out,
                    "parallelism": "single-process csky_multi: %d group(s) x %d-way bands, %s" % (G, per, "staged peer copies" if args.staged else "in-place xGMI peer stores"),
                    "frames_in_flight": fif, "frame_groups": G, "clock_prewarm_frames": prewarm_frames, "device_ids": ids, "alpha_mean": alpha_mean, "finite": finite},
-        "roofline": None, "note": "roofline and cpu_baseline are reported by the N = 1 run (same kernel); this line times the multi-device step only",
+        "roofline": None, "note": "roofline and cpu_baseline are reported by the N = 1 run with --full (same kernel); this line times the multi-device step only",
     }
     print(json.dumps(out), flush=True)
     m.close()
@@ -389,6 +426,9 @@ def main():
                                                         "perlin_octaves, worley_freq, perlin_gain, dilate, centre, contrast, offset), to see what the missing asset's character does to "
                                                         "the frame time (config.workload says so; roofline census / executed_tap_bytes then describe another frame than the pinned one)")
     ap.add_argument("--coverage", type=float, default=0.2, help="cloud_coverage of the push-constant block (0.2 = clouds_sky.tres = the benchmark workload)")
+    ap.add_argument("--full", action="store_true", help="also run every secondary measurement and check (pre-warmed rerun, one frame at a time, host form, "
+                                                         "early-out leg, roofline, CPU baseline, frame checks); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step delivered to DIR/<name>.npy (float32)")
     args = ap.parse_args()
 
     if args.gpus > 1 and not args.single_process and "WORLD_SIZE" not in os.environ:
@@ -613,9 +653,11 @@ def main():
     # the clocks up and the same W + K run again -> `value_prewarmed` / `ms_per_step_prewarmed` (what rounds 4-5 called `value`).  `value_as_asked` stays
     # as an alias of `value` for one round so that r05 and r06 records compare key by key.  --no-prewarm: one region, the two are the same number.
     elapsed, k_total, k_launches = region()
+    if args.dump_outputs and rank == 0:              # what the last timed step delivered, before anything else renders into the buffer sets
+        dump_outputs(args.dump_outputs, frame[0], ctx.read_sky_lut() if world == 1 else (sky_lut[0] if split_lut else None))
     prewarmed = None
     prewarm_frames = 0
-    if not args.no_prewarm:
+    if args.full and not args.no_prewarm:
         est_ms = 1.7 * (((W + 7) // 8) * mb) / 32768.0 * primary / 128.0       # from the LARGEST rank share: every rank must run the same number of frames (collectives)
         prewarm_frames = int(min(1024, max(16, np.ceil(120.0 / max(est_ms, 1e-3))))) * G
         for _ in range(prewarm_frames):
@@ -639,24 +681,25 @@ def main():
     # on each launch's stream, inside libcloudsky; what rocprofv3 --kernel-trace reports for this command); k_solo = the same kernel with the
     # GPU to itself, timed over solo launches right here (also reads the sample counters).
     k_inflight = k_total / max(1, k_launches)
-    k_solo, st = ctx.time_clouds(params, W, bands, warmup=1, iters=max(3, args.kernel_iters))
-    # every rank's share alone (solo launches): what bounds the split; gathered so that rank 0 can print them
-    share_ms = [k_solo]
-    ranks_seen = 1
-    if world > 1:
-        ranks_seen = dist.get_world_size()
-        t = torch.zeros(world, dtype=torch.float64, device="cpu" if debug_one_gpu else dev)
-        t[rank] = k_solo
-        dist.all_reduce(t, op=dist.ReduceOp.SUM)
-        share_ms = [float(x) for x in t.tolist()]
-    rays_launch = bands[3] * bands[0] * W
-    f_incloud = st["incloud_samples"] / max(1, st["primary_samples"])
-    floor_bytes = rays_launch * (8 + BYTES_PER_SAMPLE * primary)                           # 10 248 B/ray at 128 steps
-    total_bytes = rays_launch * 8 + BYTES_PER_SAMPLE * (st["primary_samples"] + (light + 1) * st["incloud_samples"])
+    ranks_seen = dist.get_world_size() if world > 1 else 1
+    share_ms = f_incloud = None
+    if args.full:
+        k_solo, st = ctx.time_clouds(params, W, bands, warmup=1, iters=max(3, args.kernel_iters))
+        # every rank's share alone (solo launches): what bounds the split; gathered so that rank 0 can print them
+        share_ms = [k_solo]
+        if world > 1:
+            t = torch.zeros(world, dtype=torch.float64, device="cpu" if debug_one_gpu else dev)
+            t[rank] = k_solo
+            dist.all_reduce(t, op=dist.ReduceOp.SUM)
+            share_ms = [float(x) for x in t.tolist()]
+        rays_launch = bands[3] * bands[0] * W
+        f_incloud = st["incloud_samples"] / max(1, st["primary_samples"])
+        floor_bytes = rays_launch * (8 + BYTES_PER_SAMPLE * primary)                           # 10 248 B/ray at 128 steps
+        total_bytes = rays_launch * 8 + BYTES_PER_SAMPLE * (st["primary_samples"] + (light + 1) * st["incloud_samples"])
 
     # the same K frames strictly one at a time (sky LUT + set-up + march [+ gather] per frame, nothing overlapped): N = 1 only
     one_at_a_time = None
-    if world == 1 and fif > 1:
+    if args.full and world == 1 and fif > 1:
         ctx.set_frames_in_flight(1)
         s0 = streams[0]
         def step1(k):
@@ -678,7 +721,7 @@ def main():
     # The host form (N = 1): frames delivered into PINNED HOST memory per second through csky_submit_clouds / csky_collect (what the GDExtension's
     # submit_clouds() / collect() wrap), with 1 and 2 frames in flight.  PCIe-inclusive: never the headline `value` (frames resident in HBM).
     host_form = None
-    if world == 1 and not args.no_host_form:
+    if args.full and world == 1 and not args.no_host_form:
         host_form = {}
         nh = max(10, min(args.steps, 100))
         for slots in (1, 2):
@@ -709,7 +752,7 @@ def main():
     # have T < eps = 1e-3; clouds.glsl:172-212 has no early-out, so `value` keeps eps = 0).  max_abs_err_vs_eps0 = the largest |difference| of any RGBA16F
     # value between one frame rendered with and without it (the tail a ray drops is bounded by eps x the largest radiance).  --no-early-out-leg skips it.
     early = None
-    if world == 1 and args.early_out == 0.0 and not args.no_early_out_leg:
+    if args.full and world == 1 and args.early_out == 0.0 and not args.no_early_out_leg:
         ref_frame = torch.zeros((bands[3] * bands[0], W, 4), dtype=torch.int16, device=dev)
         eo_frame = torch.zeros_like(ref_frame)
         s0e = streams[0].cuda_stream
@@ -741,10 +784,10 @@ def main():
 
     if rank == 0:
         fr = frame[0].view(torch.float16)
-        alpha_mean = float(fr[..., 3].float().mean().item())
-        finite = bool(torch.isfinite(fr.float()).all().item())
+        alpha_mean = float(fr[..., 3].float().mean().item()) if args.full else None
+        finite = bool(torch.isfinite(fr.float()).all().item()) if args.full else None
         frame_check = None
-        if world > 1:                     # the gathered frame must equal a single-context full-frame render of the same push constants (outside the timed region)
+        if args.full and world > 1:       # the gathered frame must equal a single-context full-frame render of the same push constants (outside the timed region)
             full = torch.zeros((H, W, 4), dtype=torch.int16, device=dev)
             ctx.set_segments(1)
             fp_l, fs_l = (params, sun_n) if sweep is None else sweep[frame_k[0] % len(sweep)]   # the frame rank 0 holds (the last one gathered, whatever group rendered it)
@@ -766,9 +809,9 @@ def main():
                 if not same:
                     raise SystemExit("bench.py: the sky LUT assembled from the ranks' rows differs from the whole LUT")
         # ---- hardware counters of the cloud kernel, collected now (child processes; the timed region is over)
-        pmc, pmc_note = None, "not collected: N > 1 or --no-pmc"
+        pmc, pmc_note = None, "not collected: N > 1, --no-pmc or no --full"
         pmc_cfg = "C5frame" if args.config == "C5" else args.config          # the sweep's frames cost the same: profile one of them
-        if world == 1 and not args.no_pmc and not off_workload:
+        if args.full and world == 1 and not args.no_pmc and not off_workload:
             sys.path.insert(0, os.path.join(ROOT, "tools"))
             import pmc_collect
             t_p = time.perf_counter()
@@ -782,8 +825,8 @@ def main():
         # SQ_BUSY_CYCLES / 32 is NOT the kernel's duration in cycles when shader engines idle in the launch tail (C3 alone: 2.01 "GHz", C5 alone: 2.31,
         # profiles/r02), so cycles available = duration x the shader clock SAMPLED during that region (tools/sclk.py: amdgpu hwmon freq1_input).
         # Every region is re-run for >= 0.4 s with the sampler on; the headline `value` above was timed without it.
-        clocks, census, census_note = None, None, "not collected: N > 1 or --no-pmc"
-        if world == 1 and not args.no_pmc and not off_workload:
+        clocks, census, census_note = None, None, "not collected: N > 1, --no-pmc or no --full"
+        if args.full and world == 1 and not args.no_pmc and not off_workload:
             import sclk
             import isa_profile
             pr = torch.cuda.get_device_properties(local_rank)
@@ -831,7 +874,7 @@ def main():
         # the contractual 80 B/sample: why the algorithmic figure exceeds the HBM peak without any work being skipped
         executed_taps = None
         tap_file = os.path.join(ROOT, "profiles", "r04", "executed_tap_bytes_C3.json")
-        if args.config == "C3" and world == 1 and not off_workload and os.path.exists(tap_file):
+        if args.full and args.config == "C3" and world == 1 and not off_workload and os.path.exists(tap_file):
             et = json.load(open(tap_file))
             executed_taps = {"bytes_per_launch": et["executed_tap_bytes"], "over_algorithmic": et["executed_over_algorithmic"], "primary": et["primary"]["bytes"], "light": et["light"]["bytes"],
                              "achieved_GBps_solo": et["executed_tap_bytes"] / (k_solo * 1e-3) / 1e9, "source": "profiles/r04/executed_tap_bytes_C3.json (host walk of cloud_core.h, lane-level)",
@@ -864,7 +907,7 @@ def main():
                        "parallelism": "bands%d%s%s" % (per, "+overlapped-gather" if overlap else "", " x %d frame groups" % G if G > 1 else ""), "frames_in_flight": fif, "frame_groups": G,
                        "clock_prewarm_frames": prewarm_frames,
                        "alpha_mean": alpha_mean, "finite": finite},
-            "roofline": dict(valu_roofline(census, clocks, pmc, vi, k_solo, elapsed / args.steps * 1e3), **{
+            "roofline": None if not args.full else dict(valu_roofline(census, clocks, pmc, vi, k_solo, elapsed / args.steps * 1e3), **{
                 # neither "hbm" nor "mfma" binds this path (docstring): the top-level fields are the VALU-issue roof, the one closest to 1
                 "bound": "valu", "kernel": "the cloud march.  Top level: clouds_kernel<3,1> alone (one launch with the GPU to itself) at the guide's issue rates; `timed_region`: the same body as clouds_kernel_persistent<3> over the timed region, two launches overlapping",
                 "unit": "SIMD issue cycles per launch",
@@ -897,7 +940,7 @@ def main():
                         "valu_issue_class_counter_model is round 2's model (hardware class counters, 28 % unclassified) kept for comparison; l1_gather = TA_TA_BUSY / (256 CUs x "
                         "kernel cycles by SQ_BUSY_CYCLES/32), ~1.0 in every saturated pattern of tools/ubench/gather_rates.hip"}),
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(large, small, weather, params, sun_n, W, H, primary, light)
         print(json.dumps(out), flush=True)
     if world > 1:
