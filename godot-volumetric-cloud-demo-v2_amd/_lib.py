@@ -38,6 +38,11 @@ class CompositeParams(C.Structure):
                 ("blend_amount", C.c_float), ("sun_disk_scale", C.c_float), ("light_direction", C.c_float * 3)]
 
 
+class RadianceParams(C.Structure):
+    """csky_radiance_params (include/cloudsky.h): face size S, layer count L, source-cube size Ss (0 = min(S, 64))."""
+    _fields_ = [("face_size", C.c_int), ("layers", C.c_int), ("source_size", C.c_int)]
+
+
 class CloudStats(C.Structure):
     _fields_ = [("rays", C.c_uint64), ("primary_samples", C.c_uint64), ("incloud_samples", C.c_uint64)]
 
@@ -107,6 +112,11 @@ SYMBOLS = [
     ("csky_read_sky_lut", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("csky_composite_sky", C.c_int, [C.c_void_p, C.POINTER(CompositeParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("csky_composite_view", C.c_int, [C.c_void_p, C.POINTER(CompositeParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("csky_render_radiance_device", C.c_int, [C.c_void_p, C.POINTER(CompositeParams), C.POINTER(RadianceParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    ("csky_render_radiance", C.c_int, [C.c_void_p, C.POINTER(CompositeParams), C.POINTER(RadianceParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_int, C.c_int, C.c_void_p]),
+    ("csky_prefilter_cube", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     ("csky_time_clouds", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.c_int, C.POINTER(Bands), C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(CloudStats)]),
     ("csky_get_cloud_stats", C.c_int, [C.c_void_p, C.POINTER(CloudStats)]),
     ("csky_set_kernel_timing", C.c_int, [C.c_void_p, C.c_int]),
@@ -166,7 +176,7 @@ SYMBOLS = [
 
 
 DEFAULT_VARIANT = 3   # include/cloudsky.h CSKY_DEFAULT_VARIANT ("compact"); set_variant(-1) selects it
-ABI_VERSION = 7       # include/cloudsky.h CSKY_ABI_VERSION
+ABI_VERSION = 8       # include/cloudsky.h CSKY_ABI_VERSION
 
 
 def library_path():
@@ -440,6 +450,50 @@ class Context:
         out = np.zeros((out_h, out_w, 4), np.uint16)
         self._chk(self._L.csky_composite_view(self._h, C.byref(p), C.cast(v, C.c_void_p), _ptr(a[0]), _ptr(a[1]), _ptr(a[2]), _ptr(a[3]), _ptr(out)))
         return out.view(np.float16)
+
+    def render_radiance(self, cloud_from, cloud_to, sky_from, sky_to, light_dir, blend_amount=0.0, sun_disk_scale=2.0, face_size=64, layers=8, source_size=0,
+                        first_layer=0, n_layers=None, out=None):
+        """The sky's radiance cubemap (csky_render_radiance): layer 0 = clouds.gdshader sky() on the six faces, layers 1..L-1 GGX-prefiltered.
+        Inputs float16 [h, w, 4] host arrays.  Returns float16 [L, 6, S, S, 4]; only layers [first_layer, first_layer + n_layers) are written
+        (into `out` when given)."""
+        S, L = int(face_size), int(layers)
+        n_layers = L - int(first_layer) if n_layers is None else int(n_layers)
+        a = [np.ascontiguousarray(x).view(np.uint16) for x in (cloud_from, cloud_to, sky_from, sky_to)]
+        p = CompositeParams(S, S, a[0].shape[1], a[0].shape[0], a[2].shape[1], a[2].shape[0], float(blend_amount), float(sun_disk_scale))
+        for k in range(3):
+            p.light_direction[k] = float(light_dir[k])
+        rp = RadianceParams(S, L, int(source_size))
+        if out is None:
+            out = np.zeros((L, 6, S, S, 4), np.float16)
+        if out.shape != (L, 6, S, S, 4) or out.dtype != np.float16 or not out.flags.c_contiguous:
+            raise ValueError("render_radiance: out must be a contiguous float16 [%d, 6, %d, %d, 4] array" % (L, S, S))
+        self._chk(self._L.csky_render_radiance(self._h, C.byref(p), C.byref(rp), _ptr(a[0]), _ptr(a[1]), _ptr(a[2]), _ptr(a[3]), int(first_layer), n_layers,
+                                               _ptr(out)))
+        return out
+
+    def render_radiance_device(self, d_cloud_from, d_cloud_to, d_sky_from, d_sky_to, cloud_wh, sky_wh, light_dir, blend_amount, sun_disk_scale, face_size,
+                               layers, source_size, first_layer, n_layers, d_out, stream=None):
+        """csky_render_radiance_device: device pointers in and out (d_out: the whole [L, 6, S, S, 4] half array), asynchronous on `stream`."""
+        S = int(face_size)
+        p = CompositeParams(S, S, int(cloud_wh[0]), int(cloud_wh[1]), int(sky_wh[0]), int(sky_wh[1]), float(blend_amount), float(sun_disk_scale))
+        for k in range(3):
+            p.light_direction[k] = float(light_dir[k])
+        rp = RadianceParams(S, int(layers), int(source_size))
+        ptrs = [C.c_void_p(int(x) if x else 0) for x in (d_cloud_from, d_cloud_to, d_sky_from, d_sky_to)]
+        self._chk(self._L.csky_render_radiance_device(self._h, C.byref(p), C.byref(rp), *ptrs, int(first_layer), int(n_layers), C.c_void_p(int(d_out)),
+                                                      C.c_void_p(stream or 0)))
+
+    def prefilter_cube(self, cube, layers=8, source_size=0, first_layer=0, n_layers=None):
+        """csky_prefilter_cube: the radiance filter applied to a caller cube, float16 [6, S, S, 4] -> float16 [L, 6, S, S, 4] (layer 0 = the
+        input; layers outside [first_layer, first_layer + n_layers) stay zero)."""
+        c = np.ascontiguousarray(cube, np.float16)
+        if c.ndim != 4 or c.shape[0] != 6 or c.shape[1] != c.shape[2] or c.shape[3] != 4:
+            raise ValueError("prefilter_cube: expected float16 [6, S, S, 4]")
+        S, L = c.shape[1], int(layers)
+        n_layers = L - int(first_layer) if n_layers is None else int(n_layers)
+        out = np.zeros((L, 6, S, S, 4), np.float16)
+        self._chk(self._L.csky_prefilter_cube(self._h, _ptr(c), S, L, int(source_size), int(first_layer), n_layers, _ptr(out)))
+        return out
 
     def generate_shape_noise(self, seed=1, n=128, **knobs):
         """GPU bake of the stand-in shape volume: uint8 [n, n, n, 4], byte-identical to assets.generate_shape_noise (knobs: ShapeNoiseParams fields)."""

@@ -110,6 +110,11 @@ class CloudSky:
         self.rank, self.world_size, self.dist = int(rank), int(world_size), dist
         self.last_frame = None
         self._side_stream = None
+        # the sky's radiance cubemap (radiance_cubemap / update_radiance): [L, 6, S, S, 4] float16, its (S, L, Ss) and the layer the next
+        # update_radiance() call refreshes
+        self.radiance = None
+        self._radiance_geom = None
+        self._radiance_next = 0
         # render-thread side (cloud_sky.gd:218-232): the C-ABI context owns every device resource
         self.ctx = ctx if ctx is not None else Context(device_id)
         self.transmittance_tex = TransmittanceLut(self.ctx)                    # cloud_sky.gd:92
@@ -267,6 +272,57 @@ class CloudSky:
         bf, bt = host(self.textures[self.texture_to_blend_from]), host(self.textures[self.texture_to_blend_to])
         sf, st = (host(t) for t in self.sky_lut.back_texture)
         return self.ctx.composite_view(bf, bt, sf, st, self.frame_data.LIGHT_DIRECTION, basis, fov_y_degrees, self.blend_amount, self.sun_disk_scale, out_w, out_h)
+
+    def radiance_cubemap(self, face_size=64, layers=8, source_size=0):
+        """The sky's radiance cubemap, all layers now: layer 0 = the same sky() as sky_panorama on the six faces of a face_size cube map,
+        layers 1..L-1 GGX-prefiltered for roughness k / (L-1) (csky_render_radiance; layout and maths: include/cloudsky.h).  clouds_sky.tres
+        asks the engine for 64 x 64 faces; 8 layers is the engine's default.  float16 [L, 6, S, S, 4] (a torch CUDA tensor with
+        device_buffers=True).  Not called by update_sky()."""
+        self._radiance_setup(face_size, layers, source_size)
+        self._radiance_render(0, layers)
+        self._radiance_next = 0
+        return self.radiance
+
+    def update_radiance(self, face_size=64, layers=8, source_size=0):
+        """Incremental processing (the engine's PROCESS_MODE_INCREMENTAL, clouds_sky.tres process_mode = 2): each call refreshes ONE layer,
+        cycling 0, 1, ..., L-1; layer 0 re-renders the faces and takes the source cube the following layers filter.  A change of
+        (face_size, layers, source_size) starts over at layer 0.  Returns the cubemap array (self.radiance)."""
+        if self._radiance_geom != (int(face_size), int(layers), int(source_size)):
+            self._radiance_setup(face_size, layers, source_size)
+            self._radiance_next = 0
+        k = self._radiance_next
+        self._radiance_render(k, 1)
+        self._radiance_next = (k + 1) % int(layers)
+        return self.radiance
+
+    def _radiance_setup(self, face_size, layers, source_size):
+        S, L = int(face_size), int(layers)
+        geom = (S, L, int(source_size))
+        if self._radiance_geom != geom or self.radiance is None:
+            if self.device_buffers:
+                import torch
+                self.radiance = torch.zeros((L, 6, S, S, 4), dtype=torch.float16, device=torch.device("cuda", self.ctx.device_id))
+            else:
+                self.radiance = np.zeros((L, 6, S, S, 4), np.float16)
+            self._radiance_geom = geom
+
+    def _radiance_render(self, first_layer, n_layers):
+        S, L, Ss = self._radiance_geom
+        self.flush()
+        bf, bt = self.textures[self.texture_to_blend_from], self.textures[self.texture_to_blend_to]
+        sf, st = self.sky_lut.back_texture           # the same blend textures and sky-LUT ring copies as sky_panorama
+        if first_layer == 0 and (bf is None or bt is None or sf is None or st is None):
+            raise RuntimeError("radiance: no sky yet (call update_sky() first)")
+        fd = self.frame_data
+        if not self.device_buffers:
+            self.ctx.render_radiance(bf, bt, sf, st, fd.LIGHT_DIRECTION, self.blend_amount, self.sun_disk_scale, S, L, Ss, first_layer, n_layers, out=self.radiance)
+            return
+        stream, done = self._march_stream()
+        ptr = lambda t: t.data_ptr() if (first_layer == 0 and t is not None) else 0   # noqa: E731  (layers >= 1 read only the snapshot)
+        wh = lambda t: (t.shape[1], t.shape[0]) if t is not None else (1, 1)           # noqa: E731
+        self.ctx.render_radiance_device(ptr(bf), ptr(bt), ptr(sf), ptr(st), wh(bf), wh(sf), fd.LIGHT_DIRECTION,
+                                        self.blend_amount, self.sun_disk_scale, S, L, Ss, first_layer, n_layers, self.radiance.data_ptr(), stream)
+        done()
 
     # ---- render thread ------------------------------------------------------------------------------------
     def _march_stream(self):

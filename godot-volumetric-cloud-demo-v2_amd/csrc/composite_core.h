@@ -20,7 +20,8 @@ struct CompositeArgs {
     int out_w, out_h;
     // projection of output pixel -> EYEDIR: 0 = equirectangular panorama; 1 = perspective camera (what the engine feeds the sky shader: one
     // EYEDIR per SCREEN pixel, clouds.gdshader:105-116): cam = Camera3D.global_transform.basis columns (x right, y up, z back), Godot's
-    // vertical field of view and the viewport's aspect ratio
+    // vertical field of view and the viewport's aspect ratio; 2 = the six faces of a cube map stacked vertically (the radiance pass; cam,
+    // tan_half_fov_y and aspect unused)
     int view_mode;
     float cam[9];                                                       // column-major: cam[0..2] = basis.x, [3..5] = basis.y, [6..8] = basis.z
     float tan_half_fov_y, aspect;
@@ -47,14 +48,32 @@ CSKY_HD C4 tap_half_clamp(const uint16_t* t, int w, int h, float sx, float sy) {
 CSKY_HD float mixf(float a, float b, float t) { return a * (1.0f - t) + b * t; }
 CSKY_HD float smoothstepf(float e0, float e1, float x) { const float t = sat((x - e0) / (e1 - e0)); return t * t * (3.0f - 2.0f * t); }
 
+// basis columns (right, up, back) of the camera that sees cube face f (+X, -X, +Y, -Y, +Z, -Z) through a square 90-degree screen
+CSKY_HD void cube_face_camera(int f, float* b) {
+    static constexpr float T[6][9] = {{0, 0, -1, 0, 1, 0, -1, 0, 0}, {0, 0, 1, 0, 1, 0, 1, 0, 0}, {1, 0, 0, 0, 0, -1, 0, -1, 0},
+                                      {1, 0, 0, 0, 0, 1, 0, 1, 0},   {1, 0, 0, 0, 1, 0, 0, 0, -1}, {-1, 0, 0, 0, 1, 0, 0, 0, 1}};
+    for (int k = 0; k < 9; k++) b[k] = T[f][k];
+}
+
 // EYEDIR of output pixel (i, j)
 CSKY_HD void composite_eyedir(const CompositeArgs& A, int i, int j, float& ex, float& ey, float& ez) {
-    const float u = ((float)i + 0.5f) / (float)A.out_w, v = ((float)j + 0.5f) / (float)A.out_h;
-    if (A.view_mode == 1) {
+    float u = ((float)i + 0.5f) / (float)A.out_w, v = ((float)j + 0.5f) / (float)A.out_h;
+    const float* cam = A.cam;
+    float tanh = A.tan_half_fov_y, aspect = A.aspect, face_cam[9];
+    if (A.view_mode == 2) {
+        // cube-map face texel: out_h = 6 out_w, face f = rows [f out_w, (f+1) out_w).  The camera of face f (90 degrees, square) whose
+        // screen is the Vulkan major-axis face: texel (i, j) -> (sc, tc) = (2u-1, 2v-1) -> +X (1,-tc,-sc), -X (-1,-tc,sc), +Y (sc,1,tc),
+        // -Y (sc,-1,-tc), +Z (sc,-tc,1), -Z (-sc,-tc,-1)
+        const int n = A.out_w, f = j / n;
+        v = ((float)(j - f * n) + 0.5f) / (float)n;
+        cube_face_camera(f, face_cam);
+        cam = face_cam; tanh = 1.0f; aspect = 1.0f;
+    }
+    if (A.view_mode >= 1) {
         // screen pixel -> view-space ray (x right, y up, looking down -z) -> world space through the camera basis, normalised: the EYEDIR the
         // engine hands a sky shader for this screen pixel
-        const float vx = (u * 2.0f - 1.0f) * A.tan_half_fov_y * A.aspect, vy = (1.0f - v * 2.0f) * A.tan_half_fov_y, vz = -1.0f;
-        const float wx = A.cam[0] * vx + A.cam[3] * vy + A.cam[6] * vz, wy = A.cam[1] * vx + A.cam[4] * vy + A.cam[7] * vz, wz = A.cam[2] * vx + A.cam[5] * vy + A.cam[8] * vz;
+        const float vx = (u * 2.0f - 1.0f) * tanh * aspect, vy = (1.0f - v * 2.0f) * tanh, vz = -1.0f;
+        const float wx = cam[0] * vx + cam[3] * vy + cam[6] * vz, wy = cam[1] * vx + cam[4] * vy + cam[7] * vz, wz = cam[2] * vx + cam[5] * vy + cam[8] * vz;
         const float l = sqrtf(wx * wx + wy * wy + wz * wz);
         ex = wx / l; ey = wy / l; ez = wz / l;
         return;

@@ -63,6 +63,14 @@ hipError_t launch_bake32(const uint8_t* d_large_chain, const uint8_t* d_small_ch
 // test hook: cloud_core.h::sqrt_shell over an array
 hipError_t launch_sqrt_shell(const float* d_in, float* d_out, size_t n, hipStream_t s);
 
+// radiance cubemap (radiance.hip, radiance_core.h): source records of an ns x ns cube from the n x n layer 0 (RGBA16F, device), the bounding
+// cones of the 8x8 blocks of an n x n cube, and nl >= 1 prefiltered layers (ly[0..nl)) written back to back from d_out
+struct RadLayer;
+hipError_t launch_radiance_source(const uint16_t* d_layer0, int n, int ns, float4* d_tab, hipStream_t s);
+hipError_t launch_radiance_cones(int n, float4* d_cones, hipStream_t s);
+hipError_t launch_radiance_filter(const float4* d_tab, const float4* d_src_cones, const float4* d_out_cones, int n, int ns, const RadLayer* ly, int nl, bool cull,
+                                  uint2* d_out, hipStream_t s);
+
 int cloud_variant_count();
 const char* cloud_variant_name(int v);
 

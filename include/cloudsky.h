@@ -20,7 +20,8 @@
  * runtime reads it at its first call; with the default of 4 the streams of two frames in flight share hardware queues and do not overlap; a rank share with eight frames
  * in flight needs more than 8: 0.30 ms per frame with 8 queues, 0.23 with 16).
  * CSKY_NO_ENV=1 in the environment disables that; csky_set_frames_in_flight(>= 2) then leaves a warning in csky_last_warning when the
- * variable is not in effect.  Other variables read (all optional, A/B switches): CSKY_PERSISTENT, CSKY_PERSISTENT_WGS, CSKY_MULTI_STAGED.
+ * variable is not in effect.  Other variables read (all optional, A/B switches): CSKY_PERSISTENT, CSKY_PERSISTENT_WGS, CSKY_MULTI_STAGED,
+ * CSKY_RADIANCE_CULL.
  *
  * Images are tightly packed little-endian RGBA half floats (DATA_FORMAT_R16G16B16A16_SFLOAT,
  * cloud_sky.gd:369; sky_lut.gd:84; transmittance_lut.gd:37), row-major, row 0 = pixel y == 0.
@@ -40,7 +41,7 @@ extern "C" {
 #define CSKY_ERR_IO (-4)         /* asset file problem                                       */
 #define CSKY_ERR_STATE (-5)      /* e.g. clouds requested before noise / LUTs exist          */
 
-#define CSKY_ABI_VERSION 7  /* 7: csky_multi_last_warning (csky_multi_create no longer fails without peer access: it falls back to staged copies and says so); 6: the measurement / tuning / test entry points moved to cloudsky_internal.h (same library), csky_generate_shape_noise_tuned[_device]; 5: csky_last_warning (warnings no longer sit in csky_last_error), exact fp32-coefficient texture cells, csky_render_sky_lut_rows_device, csky_interleave_bands_device, csky_encode_bc7, rings eight deep; 4: csky_submit_* / csky_collect, csky_multi_set_groups / _set_staged, csky_composite_view, csky_external_frame_* (incl. _fence / _ready / _wait); 3: csky_set_noise_mips, csky_decode_bc7, csky_load_ctex[3d]; 2: csky_multi_*, device asset builders */
+#define CSKY_ABI_VERSION 8  /* 8: csky_render_radiance[_device], csky_prefilter_cube (the radiance cubemap); 7: csky_multi_last_warning (csky_multi_create no longer fails without peer access: it falls back to staged copies and says so); 6: the measurement / tuning / test entry points moved to cloudsky_internal.h (same library), csky_generate_shape_noise_tuned[_device]; 5: csky_last_warning (warnings no longer sit in csky_last_error), exact fp32-coefficient texture cells, csky_render_sky_lut_rows_device, csky_interleave_bands_device, csky_encode_bc7, rings eight deep; 4: csky_submit_* / csky_collect, csky_multi_set_groups / _set_staged, csky_composite_view, csky_external_frame_* (incl. _fence / _ready / _wait); 3: csky_set_noise_mips, csky_decode_bc7, csky_load_ctex[3d]; 2: csky_multi_*, device asset builders */
 
 typedef struct csky_ctx csky_ctx; /* opaque: owns every device allocation, the HIP stream and events */
 
@@ -244,6 +245,38 @@ int csky_composite_sky(csky_ctx* ctx, const csky_composite_params* p, const uint
 typedef struct { float basis[9]; float fov_y_degrees; } csky_view;
 int csky_composite_view(csky_ctx* ctx, const csky_composite_params* p, const csky_view* view, const uint16_t* cloud_from, const uint16_t* cloud_to,
                         const uint16_t* sky_from, const uint16_t* sky_to, uint16_t* out_rgba16f);
+
+/* ---- radiance cubemap: the sky's second pass ------------------------------------------------------
+ * The engine also evaluates clouds.gdshader sky() into a cubemap and filters it into roughness layers, the reflections and ambient light
+ * of every PBR material (clouds_sky.tres: radiance_size = 64 x 64 faces, process_mode = incremental: one layer per frame).
+ * Output: L layers x 6 faces x S x S texels of RGBA16F, tightly packed, [layer][face][row][col] (the layer order of a cube-map array of 6 L
+ * layers); faces +X, -X, +Y, -Y, +Z, -Z; alpha 1.  Texel (col i, row j) of a face of size n has sc = 2(i+0.5)/n - 1, tc = 2(j+0.5)/n - 1
+ * and direction normalize(+X: (1,-tc,-sc), -X: (-1,-tc,sc), +Y: (sc,1,tc), -Y: (sc,-1,-tc), +Z: (sc,-tc,1), -Z: (-sc,-tc,-1)).
+ * Layer 0 = sky() at every texel direction (the compositor's per-pixel code and inputs: csky_composite_params with out_w = out_h = S).
+ * Source cube: layer 0 reduced per face to source_size Ss (the fp32 mean of (S/Ss)^2 texels).  Layer k = 1..L-1, roughness r = k/(L-1),
+ * alpha = r^2, split-sum N = V = R: the exact discrete form of the integral the engine's GGX importance sampler estimates,
+ *     P_k(N) = sum_t w C_t / sum_t w,   c = N.L_t,   w = c Omega_t / (c (alpha^2-1)/2 + (alpha^2+1)/2)^2  for c > 0, else 0,
+ * over every source texel t (L_t its centre direction, Omega_t its exact solid angle).  At r = 1 it is the cosine-weighted hemisphere mean
+ * (irradiance / pi).  Deterministic (no sample noise), so NOT bit-comparable with the engine's 32-sample Monte Carlo filter; parity with
+ * the engine's radiance is not pinned.  Ranges: 1 <= L <= 10, S a power of two in [8, 512], Ss = 0 (= min(S, 64)) or a power of two <= S.
+ * Optional environment switch CSKY_RADIANCE_CULL=0 turns off the (conservative, byte-identical) back-face culling of source blocks. */
+typedef struct { int face_size, layers, source_size; } csky_radiance_params;
+/* Device form: cloud_from/to, sky_from/to are DEVICE RGBA16F images (sizes in *sky); writes only layers [first_layer, first_layer + n_layers)
+ * of d_out (the whole L-layer array), asynchronously on hip_stream (the context's own stream if NULL).  A call whose range includes layer 0
+ * renders the faces and snapshots the source cube inside the context; a call that starts at layer >= 1 filters from the last snapshot
+ * (CSKY_ERR_STATE without one or when its (S, L, Ss) differ) and does not read sky or the four images (they may be NULL).  Incremental
+ * processing (one layer per frame): {0,1}, {1,1}, ..., {L-1,1}; the snapshot is written and read on the calls' streams, so keep the calls of
+ * one cubemap on one stream. */
+int csky_render_radiance_device(csky_ctx* ctx, const csky_composite_params* sky, const csky_radiance_params* rp, const void* d_cloud_from,
+                                const void* d_cloud_to, const void* d_sky_from, const void* d_sky_to, int first_layer, int n_layers, void* d_out_rgba16f,
+                                void* hip_stream);
+/* The same with host buffers (out: the whole L x 6 x S x S x 4 half array; only the requested layers are written); blocks. */
+int csky_render_radiance(csky_ctx* ctx, const csky_composite_params* sky, const csky_radiance_params* rp, const uint16_t* cloud_from, const uint16_t* cloud_to,
+                         const uint16_t* sky_from, const uint16_t* sky_to, int first_layer, int n_layers, uint16_t* out_rgba16f);
+/* The same filter applied to any caller cube (6 x S x S RGBA16F, host): layer 0 of out is the input; stateless (the snapshot of
+ * csky_render_radiance* is left alone); blocks. */
+int csky_prefilter_cube(csky_ctx* ctx, const uint16_t* cube_rgba16f, int face_size, int layers, int source_size, int first_layer, int n_layers,
+                        uint16_t* out_rgba16f);
 
 /* ---- frames in flight ---------------------------------------------------------------------------- */
 /* Policy hint for the automatic segment / schedule choice: n = 2..8: the caller keeps n frames in flight by rotating n streams
