@@ -51,18 +51,19 @@ CSKY_HD double rad_solid_angle(int i, int j, int n) {
 CSKY_HD int rad_block_size(int n) { return n < 8 ? n : 8; }
 CSKY_HD int rad_block_count(int n) { const int nb = n / rad_block_size(n); return 6 * nb * nb; }
 
-// Source texel (f, i, j) of an ns x ns source cube: the fp32 mean of its k x k texels of the n x n layer 0 (RGBA16F, faces back to back),
-// k = n / ns, summed row by row; the record goes to rec[2 * (block index * bs^2 + texel in block)]
+// Source texel (f, i, j) of an ns x ns source cube: the mean of its k x k texels of the n x n layer 0 (RGBA16F, faces back to back),
+// k = n / ns, summed row by row in double and rounded once to fp32 (an fp32 sum drifts by several fp16 ulp at k = 512 with HDR texels;
+// k = 1 gives the texel itself); the record goes to rec[2 * (block index * bs^2 + texel in block)]
 CSKY_HD void rad_source_texel(const uint16_t* layer0, int n, int ns, int f, int i, int j, float4* tab) {
     const int k = n / ns;
-    float r = 0.0f, g = 0.0f, b = 0.0f;
+    double sr = 0.0, sg = 0.0, sb = 0.0;
     for (int y = 0; y < k; y++)
         for (int x = 0; x < k; x++) {
             const uint16_t* p = layer0 + (((size_t)f * n + (size_t)j * k + y) * n + (size_t)i * k + x) * 4;
-            r += h2f(p[0]); g += h2f(p[1]); b += h2f(p[2]);
+            sr += h2f(p[0]); sg += h2f(p[1]); sb += h2f(p[2]);
         }
-    const float inv = 1.0f / (float)(k * k);                       // a power of two: exact
-    r *= inv; g *= inv; b *= inv;
+    const double inv = 1.0 / ((double)k * k);                      // a power of two: exact
+    const float r = (float)(sr * inv), g = (float)(sg * inv), b = (float)(sb * inv);
     float lx, ly, lz;
     rad_texel_dir(f, i, j, ns, lx, ly, lz);
     const float om = (float)rad_solid_angle(i, j, ns);

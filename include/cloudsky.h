@@ -253,8 +253,9 @@ int csky_composite_view(csky_ctx* ctx, const csky_composite_params* p, const csk
  * layers); faces +X, -X, +Y, -Y, +Z, -Z; alpha 1.  Texel (col i, row j) of a face of size n has sc = 2(i+0.5)/n - 1, tc = 2(j+0.5)/n - 1
  * and direction normalize(+X: (1,-tc,-sc), -X: (-1,-tc,sc), +Y: (sc,1,tc), -Y: (sc,-1,-tc), +Z: (sc,-tc,1), -Z: (-sc,-tc,-1)).
  * Layer 0 = sky() at every texel direction (the compositor's per-pixel code and inputs: csky_composite_params with out_w = out_h = S).
- * Source cube: layer 0 reduced per face to source_size Ss (the fp32 mean of (S/Ss)^2 texels).  Layer k = 1..L-1, roughness r = k/(L-1),
- * alpha = r^2, split-sum N = V = R: the exact discrete form of the integral the engine's GGX importance sampler estimates,
+ * Source cube: layer 0 reduced per face to source_size Ss (the mean of (S/Ss)^2 texels, summed in double, rounded once to fp32).
+ * Layer k = 1..L-1, roughness r = k/(L-1), alpha = r^2, split-sum N = V = R: the exact discrete form of the integral the engine's GGX
+ * importance sampler estimates,
  *     P_k(N) = sum_t w C_t / sum_t w,   c = N.L_t,   w = c Omega_t / (c (alpha^2-1)/2 + (alpha^2+1)/2)^2  for c > 0, else 0,
  * over every source texel t (L_t its centre direction, Omega_t its exact solid angle).  At r = 1 it is the cosine-weighted hemisphere mean
  * (irradiance / pi).  Deterministic (no sample noise), so NOT bit-comparable with the engine's 32-sample Monte Carlo filter; parity with

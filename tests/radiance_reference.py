@@ -98,3 +98,19 @@ def smooth_cube(S, seed=0):
     d = face_dirs(S)
     rgb = (1.0 + 0.8 * d[..., 1:2] + 0.3 * d[..., 0:1] * d[..., 2:3]) * np.array([1.0, 0.8, 0.6]) + 0.2 * rng.random((6, S, S, 3))
     return np.concatenate([rgb, np.ones((6, S, S, 1))], -1).astype(np.float16)
+
+
+DISC_DIR = np.array([0.5, 0.6, 0.62]) / np.linalg.norm([0.5, 0.6, 0.62])   # near the +Y / +Z seam
+DISC_RADIUS = 0.02
+
+
+def disc_angle(S):
+    """Angle [6, S, S] (radians) between each texel-centre direction and the centre of hdr_cube's disc."""
+    return np.arccos(np.clip(face_dirs(S) @ DISC_DIR, -1.0, 1.0))
+
+
+def hdr_cube(S, value=30000.0, seed=3):
+    """A high-dynamic-range test cube: smooth_cube(S, seed) with a sun-like disc (radius DISC_RADIUS around DISC_DIR) of RGB `value`."""
+    cube = smooth_cube(S, seed)
+    cube[disc_angle(S) < DISC_RADIUS, :3] = value
+    return cube

@@ -44,7 +44,7 @@ smooth_cube = R.smooth_cube
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("S", [16, 64])
+@pytest.mark.parametrize("S", [8, 16, 64, 256])
 @pytest.mark.parametrize("sun", sorted(SUNS))
 def test_layer0_faces_match_the_view_compositor(gpu_ctx, oracle, rscene, S, sun):
     """Layer 0, face f == csky_composite_view through the camera of face f (header table), fov 90, S x S: the compositor's gate."""
@@ -156,6 +156,154 @@ def test_culling_off_gives_identical_bytes(gpu_ctx, tmp_path):
     r = subprocess.run([sys.executable, "-c", CULL_CHILD, path], env=dict(os.environ, CSKY_RADIANCE_CULL="0"), capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
     assert (np.load(path) == on).all()
+
+
+# ------------------------------------------------------------------------------------------------ the header's whole range
+# (S, Ss, L): together S in {8, 16, 64, 128, 256, 512}, Ss in {1, 2, 4, ..., 256} and every L in 2..10 (filter kernel NL = 1..9); the
+# expensive source sizes (numpy cost ~ receivers x 6 Ss^2) get few layers
+SWEEP = [(8, 1, 4), (8, 8, 10), (16, 2, 9), (16, 16, 8), (64, 4, 7), (64, 64, 3), (128, 32, 6), (128, 128, 2), (256, 8, 5), (256, 256, 2),
+         (512, 16, 3)]
+DISC = [(512, 1, 3), (512, 2, 3), (512, 4, 3), (512, 64, 3)]        # hdr_cube(512): the block mean over up to 512 x 512 texels
+
+
+def ref_chunk(Ss):
+    """Receivers per chunk of R.prefilter: about 32 MB per float64 [chunk, 6 Ss^2] temporary."""
+    return max(1, (1 << 22) // (6 * Ss * Ss))
+
+
+def sampled_receivers(S, seed, extra=None):
+    """(face, row, col) of 2000 random receivers, the four corner texels of every face, row 0 of every face (a seam with a neighbouring face)
+    and the texels `extra`."""
+    rng = np.random.default_rng(seed)
+    f, j, i = [rng.integers(0, 6, 2000)], [rng.integers(0, S, 2000)], [rng.integers(0, S, 2000)]
+    c = np.array([0, S - 1])
+    F, J, I = np.meshgrid(np.arange(6), c, c, indexing="ij")
+    f.append(F.ravel()); j.append(J.ravel()); i.append(I.ravel())
+    F, I = np.meshgrid(np.arange(6), np.arange(S), indexing="ij")
+    f.append(F.ravel()); j.append(np.zeros(F.size, int)); i.append(I.ravel())
+    if extra is not None:
+        f.append(extra[0]); j.append(extra[1]); i.append(extra[2])
+    return np.concatenate(f), np.concatenate(j), np.concatenate(i)
+
+
+def check_prefiltered(out, cube, L, Ss, seed=0, extra=None):
+    """prefilter_cube's result against numpy: every texel where that is cheap (S <= 32 or Ss <= 4), else sampled_receivers."""
+    S = cube.shape[1]
+    assert out.shape == (L, 6, S, S, 4)
+    assert np.isfinite(out.astype(np.float32)).all() and (out[1:, ..., 3] == 1).all()
+    assert (out[0].view(np.uint16) == cube.view(np.uint16)).all()
+    c64 = cube.astype(np.float64)
+    if S <= 32 or Ss <= 4:
+        check_filtered(out[1:, ..., :3], R.prefilter(c64, L, Ss, chunk=ref_chunk(Ss)).reshape(L - 1, 6, S, S, 3))
+    else:
+        f, j, i = sampled_receivers(S, seed, extra)
+        check_filtered(out[1:, f, j, i, :3], R.prefilter(c64, L, Ss, texels=(f, j, i), chunk=ref_chunk(Ss)))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("S,Ss,L", SWEEP)
+def test_prefilter_geometry_sweep_matches_numpy(gpu_ctx, S, Ss, L):
+    cube = smooth_cube(S, 100 + S + Ss)
+    check_prefiltered(gpu_ctx.prefilter_cube(cube, layers=L, source_size=Ss), cube, L, Ss, seed=S + Ss)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("S,Ss,L", DISC)
+def test_prefilter_bright_disc_matches_numpy(gpu_ctx, S, Ss, L):
+    """A 30000 sun disc: every texel where Ss <= 4 (512 x 512 down to 1 x 1 is where an fp32 block mean drifted by 4 ulp), else sampled
+    receivers plus every texel within 0.1 rad of the disc."""
+    cube = R.hdr_cube(S, 30000.0)
+    out = gpu_ctx.prefilter_cube(cube, layers=L, source_size=Ss)
+    check_prefiltered(out, cube, L, Ss, seed=Ss, extra=np.nonzero(R.disc_angle(S) < 0.1))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("S,Ss,L", [(64, 16, 5), (16, 1, 6)])
+def test_prefilter_three_black_faces(gpu_ctx, S, Ss, L):
+    cube = smooth_cube(S, 21)
+    cube[[0, 2, 4], ..., :3] = 0                                       # +X, +Y, +Z black
+    out = gpu_ctx.prefilter_cube(cube, layers=L, source_size=Ss)
+    # black outputs where every weighted source texel is black (at Ss = 1 the six face centres), lit ones elsewhere: numpy decides which
+    assert (out[1:, ..., :3].astype(np.float32) > 0).any()
+    check_filtered(out[1:, ..., :3], R.prefilter(cube.astype(np.float64), L, Ss).reshape(L - 1, 6, S, S, 3))
+    assert np.isfinite(out.astype(np.float32)).all() and (out[1:, ..., 3] == 1).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("S,Ss,L", [(32, 4, 6), (32, 32, 4)])
+def test_prefilter_subnormal_cube(gpu_ctx, S, Ss, L):
+    """Values ~1e-6, fp16 subnormals in and out: f2h must round them, not flush them."""
+    cube = smooth_cube(S, 22)
+    cube[..., :3] = (cube[..., :3].astype(np.float32) * 1e-6).astype(np.float16)
+    rgb = np.abs(cube[..., :3].astype(np.float32))
+    assert (rgb > 0).all() and (rgb < 6.1e-5).all()
+    out = gpu_ctx.prefilter_cube(cube, layers=L, source_size=Ss)
+    f = out[1:, ..., :3].astype(np.float32)
+    assert (f > 0).all() and (f < 6.1e-5).all()
+    check_prefiltered(out, cube, L, Ss)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("S,Ss,L", SWEEP + DISC)
+def test_culling_leaves_bytes_unchanged_at_every_geometry(gpu_ctx, monkeypatch, S, Ss, L):
+    """rad_filter reads CSKY_RADIANCE_CULL at every call: source blocks that are whole faces (Ss <= 8) and the smallest receiver cones
+    (S = 512) included."""
+    cube = R.hdr_cube(S, 30000.0) if (S, Ss, L) in DISC else smooth_cube(S, 100 + S + Ss)
+    on = gpu_ctx.prefilter_cube(cube, layers=L, source_size=Ss)
+    monkeypatch.setenv("CSKY_RADIANCE_CULL", "0")
+    off = gpu_ctx.prefilter_cube(cube, layers=L, source_size=Ss)
+    assert (off.view(np.uint16) == on.view(np.uint16)).all()
+
+
+# one context through geometries that grow and shrink every buffer of rad_prepare and rebuild both cone tables of both sets
+SEQUENCE = [(512, 8, 64), (8, 2, 1), (128, 5, 128), (16, 9, 2), (512, 8, 64)]
+
+
+@pytest.mark.gpu
+def test_geometry_sequence_on_one_context_matches_fresh_contexts(pkg, rscene):
+    s = rscene["in_view"]
+    fresh = {}
+
+    def run(ctx, kind, S, L, Ss):
+        if kind == "render":
+            return radiance(ctx, s, S, L=L, Ss=Ss)
+        return ctx.prefilter_cube(smooth_cube(S, 300 + S), layers=L, source_size=Ss)
+
+    def expected(kind, S, L, Ss):
+        if (kind, S, L, Ss) not in fresh:
+            c = pkg.Context(0)
+            try:
+                fresh[kind, S, L, Ss] = run(c, kind, S, L, Ss)
+            finally:
+                c.close()
+        return fresh[kind, S, L, Ss]
+
+    ctx = pkg.Context(0)
+    try:
+        for step, (S, L, Ss) in enumerate(SEQUENCE):
+            got = {}
+            for kind in (("render", "prefilter") if step % 2 == 0 else ("prefilter", "render")):
+                got[kind] = run(ctx, kind, S, L, Ss)
+                assert (got[kind].view(np.uint16) == expected(kind, S, L, Ss).view(np.uint16)).all(), (step, kind)
+            whole = got["render"]
+            # the snapshot survives prefilter_cube calls: layers 1..L-1 again from it, and they are the filter of its own layer 0
+            inc = np.zeros_like(whole)
+            radiance(ctx, s, S, L=L, Ss=Ss, first=1, n=L - 1, out=inc)
+            assert (inc[1:].view(np.uint16) == whole[1:].view(np.uint16)).all(), step
+            again = ctx.prefilter_cube(whole[0], layers=L, source_size=Ss)
+            assert (again.view(np.uint16) == whole.view(np.uint16)).all(), step
+    finally:
+        ctx.close()
+
+
+@pytest.mark.gpu
+def test_incremental_equals_all_layers_at_a_non_default_geometry(gpu_ctx, rscene):
+    s = rscene["below"]
+    whole = radiance(gpu_ctx, s, 128, L=10, Ss=16)
+    inc = np.zeros_like(whole)
+    for k in range(10):
+        radiance(gpu_ctx, s, 128, L=10, Ss=16, first=k, n=1, out=inc)
+    assert (inc.view(np.uint16) == whole.view(np.uint16)).all()
 
 
 @pytest.mark.gpu

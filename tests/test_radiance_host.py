@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import radiance_reference as R
+from conftest import ulp_diff
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -67,14 +68,39 @@ def test_block_cones_bound_their_texels(rh, n):
                 k += 1
 
 
-@pytest.mark.parametrize("S,Ss,L", [(8, 8, 8), (16, 16, 8), (16, 8, 5), (16, 4, 10)])
-def test_host_filter_matches_numpy(rh, S, Ss, L):
-    cube = R.smooth_cube(S, S + Ss)
+def host_prefilter(rh, cube, L, Ss):
+    S = cube.shape[1]
     out = np.zeros((L - 1, 6, S, S, 4), np.float32)
     rh.rad_host_prefilter(P(cube.view(np.uint16)), S, L, Ss, P(out))
+    return out
+
+
+# every layer count 2..10 (filter kernel NL = 1..9), source blocks smaller than 8 x 8 (Ss < 8) with a non-constant cube
+@pytest.mark.parametrize("S,Ss,L", [(8, 8, 8), (16, 16, 8), (16, 8, 5), (16, 4, 10), (8, 8, 2), (16, 2, 3), (8, 1, 4), (16, 16, 6), (32, 4, 7),
+                                    (16, 8, 9)])
+def test_host_filter_matches_numpy(rh, S, Ss, L):
+    cube = R.smooth_cube(S, S + Ss)
+    out = host_prefilter(rh, cube, L, Ss)
     ref = R.prefilter(cube.astype(np.float64), L, Ss).reshape(L - 1, 6, S, S, 3)
     rel = np.abs(out[..., :3] - ref) / np.abs(ref)
     assert rel.max() < 1e-5, rel.max()
+
+
+# (S, Ss, relative bound).  At 512/2 one receiver sees the disc's source texel at c = N.L ~ 2e-3, where the filter's fp32 c = 1 - e2/2
+# (about 1e-7 absolute) is 1e-5 relative: that is the filter's own arithmetic, not the block mean, hence 2e-5 there
+@pytest.mark.parametrize("S,Ss,rtol", [(512, 1, 1e-5), (512, 2, 2e-5), (512, 4, 1e-5), (256, 1, 1e-5)])
+def test_host_filter_bright_disc_large_reduction(rh, S, Ss, rtol):
+    """A 30000 disc in a smooth cube, source texels that average up to 512 x 512 layer-0 texels: the block mean must stay accurate (the GPU
+    gate of tests/test_radiance_gpu.py check_filtered, and a relative gate)."""
+    L = 3
+    cube = R.hdr_cube(S, 30000.0)
+    out = host_prefilter(rh, cube, L, Ss)
+    ref = R.prefilter(cube.astype(np.float64), L, Ss, chunk=65536).reshape(L - 1, 6, S, S, 3)
+    assert np.isfinite(out).all()
+    d = ulp_diff(out[..., :3].astype(np.float16), ref.astype(np.float16))
+    assert d.max() <= 2 and (d <= 1).mean() >= 0.99, (d.max(), (d <= 1).mean())
+    rel = np.abs(out[..., :3] - ref) / np.abs(ref)
+    assert rel.max() < rtol, rel.max()
 
 
 def test_numpy_reference_known_answers():
