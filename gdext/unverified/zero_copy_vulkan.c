@@ -3,7 +3,7 @@
  *
  * COMPILE-GUARDED: neither <vulkan/vulkan.h> nor an engine exist in this image, so nothing here is built or run by this repository
  * (gdext/Makefile builds it only with CSKY_HAVE_VULKAN=1).  The HIP half it calls IS built and lives in libcloudsky.so:
- * csky_external_frame_import_fd / _import_semaphore_fd / _signal / _fence / _ready / _wait / _release (include/cloudsky.h, csrc/api.cpp);
+ * csky_external_frame_import_fd / _import_semaphore_fd / _signal / _fence / _ready / _wait / _release (include/cloudsky.h, csrc/api_external.cpp);
  * its memory half is exercised on the GPU against a foreign allocator (tools/ext_frame_roundtrip.py).
  *
  * Design.  cloud_sky.gd keeps three RGBA16F textures created with rd.texture_create() (cloud_sky.gd:368-378) and hands one of them to the

@@ -1,5 +1,5 @@
 // bake.h -- host-side conversion of the 8-bit mip chains into the device texture layouts of csky_common.h.
-// Internal to libcloudsky (api.cpp); also included by the host-compiled kernel-core unit test (tests/hostsim).
+// Internal to libcloudsky (api.cpp, clouds_launch.cpp); also included by the host-compiled kernel-core unit test (tests/hostsim).
 #pragma once
 #include <cmath>
 #include <vector>

@@ -220,7 +220,7 @@ template <class Fetch> CSKY_HD void frame_setup_f(const CloudParams& P, Fetch fe
     fc.primary_steps = primary_steps; fc.light_steps = light_steps; fc.steps_f = (float)primary_steps;
     fc.early_eps = early_eps;
     fc.hf_lo = hf_lo; fc.hf_hi = hf_hi;
-    fc.ct_mode = 0;                   // set by the caller that knows the weather map's range (api.cpp; kernels.hip frame_setup_kernel)
+    fc.ct_mode = 0;                   // set by the caller that knows the weather map's range (clouds_launch.cpp::clouds_dev; kernels.hip frame_setup_kernel)
 }
 CSKY_HD void frame_setup(const CloudParams& P, const float4* sky, int sky_w, int sky_h, int primary_steps, int light_steps,
                          float early_eps, float hf_lo, float hf_hi, FrameConsts& fc) {

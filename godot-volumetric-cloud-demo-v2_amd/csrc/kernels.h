@@ -26,7 +26,7 @@ hipError_t launch_frame_setup_taps(const CloudParams& p, const float sun[3], con
 // clouds.glsl main() over the rows described by `g`.  d_stats (may be null): [0] += in-cloud samples,
 // [1] += rays above the horizon.
 // seg = ray segments per ray (1, 2 or 4; variant 1 only): a workgroup covers 4/seg tiles of 8x8 pixels.
-// d_order[grid]: physical workgroup -> workgroup-footprint id (0xffffffff = idle), see api.cpp::build_schedule.
+// d_order[grid]: physical workgroup -> workgroup-footprint id (0xffffffff = idle), see clouds_launch.cpp::clouds_dev.
 hipError_t launch_clouds(int variant, int seg, const TexSet& t, const FrameConsts* d_fc, const RenderGeom& g, const uint32_t* d_order, int grid,
                          uint2* d_out, unsigned long long* d_stats, uint32_t* d_wg_cost, hipStream_t s, uint32_t* d_heads = nullptr, int resident = 0,
                          const TexSet32* t32 = nullptr);   // t32: march on the exact fp32-coefficient cells (variant 3, seg 1 only)

@@ -900,7 +900,7 @@ __global__ __launch_bounds__(1024) void clouds_kernel_lds(TexSet T, const FrameC
 //              combined front to back through LDS (L = L0 + T0*L1 + ..., T = prod T_s, 1-alpha = prod (1-alpha_s)):
 //              a wavefront's latency (0.65 ms for 128 steps) is what limits small launches (one GPU's 1/8 frame), and
 //              segments divide it by SEG.  Sample positions stay bit-identical; the compositing sums are re-associated.
-// Workgroup order: physical workgroup b runs on XCD b % 8 (observed, speed only); `order` (api.cpp::build_schedule)
+// Workgroup order: physical workgroup b runs on XCD b % 8 (observed, speed only); `order` (clouds_launch.cpp::clouds_dev)
 // maps b to a workgroup footprint.
 #ifndef CSKY_COMPACT_WAVES
 #define CSKY_COMPACT_WAVES 7   // waves/SIMD asked of the "compact" variant.  With the eager light-march fetches (three gathers of a sample in flight
@@ -991,7 +991,7 @@ __global__ __launch_bounds__(256, VARIANT == 3 ? CSKY_COMPACT_WAVES : 7) void cl
 //     structurizer wrapped the body in a lane loop that re-entered with ticket 0.
 //   * heads[0..7] = the sequences' pop counters, heads[8] = wavefronts that have left; all nine are zero at launch and the last
 //     wavefront out zeroes them again (a memset node in front of every launch cost 46 us on a busy chip).
-// Used for launches of 12 Ki - 64 Ki wavefronts while two frames are in flight (api.cpp::clouds_dev has the policy and the
+// Used for launches of 12 Ki - 64 Ki wavefronts while two frames are in flight (launch_policy.h has the policy and the
 // numbers; profiles/r02/persistent_launch_ab.txt).
 template <int VARIANT>
 __global__ __launch_bounds__(256, VARIANT == 3 ? CSKY_COMPACT_WAVES : 7) void clouds_kernel_persistent(TexSet T, const FrameConsts* __restrict__ fcp, RenderGeom G,
@@ -1073,10 +1073,10 @@ __global__ __launch_bounds__(256, VARIANT == 3 ? CSKY_COMPACT_WAVES : 7) void cl
 //   * mixed-segment launch: the order's last 10-25 % as 2-/4-segment workgroups in the SAME launch: occupancy integral 72 -> 85-87 %,
 //     frame 2.06-2.28 vs 2.09 ms: segments add 17 % wave-time and the launch is VALU/L1-throughput bound     (timeline_static_vs_mixed_segment_tail.txt)
 //   * adaptive segments per workgroup from previous-frame costs, for one GPU's 1/4..1/16 share             0.446 vs 0.434 ms at 1/8 (share_matrix_adaptive_segments.txt)
-// What does fill the tail is the NEXT frame's workgroups (two frames in flight, api.cpp): 2.12 -> 1.80 ms per frame, and with them
+// What does fill the tail is the NEXT frame's workgroups (two frames in flight, launch_policy.h): 2.12 -> 1.80 ms per frame, and with them
 // in flight the persistent form above (cross-XCD stealing at the end of a launch): 1.81 -> 1.72 ms per frame.
 
-// ---- cost-feedback schedule (api.cpp, schedule mode 7) -----------------------------------------------------------------
+// ---- cost-feedback schedule (clouds_launch.cpp, schedule mode 7) ------------------------------------------------------------
 // Workgroups differ 10x in cost (in-cloud samples per tile) and a C3 frame is only ~4 waves of resident workgroups deep, so
 // the order they start in decides the tail.  Every launch records a cost per workgroup (wg_cost: in-cloud samples + live rays);
 // these three kernels turn it into the NEXT launch's order, heaviest first (longest-processing-time-first list scheduling;
@@ -1115,7 +1115,7 @@ __global__ __launch_bounds__(256) void lpt_scatter_kernel(uint32_t* __restrict__
         cost[i] = 0u;                                          // the next launch accumulates into a clean array: no memset nodes per frame
     }
 }
-// d_cost[n] and d_scratch[2 * LPT_BUCKETS] must be zero before their first use (api.cpp clears them at allocation); both are left zeroed
+// d_cost[n] and d_scratch[2 * LPT_BUCKETS] must be zero before their first use (clouds_launch.cpp clears them at allocation); both are left zeroed
 hipError_t launch_lpt_order(uint32_t* d_cost, int n, int shift, uint32_t* d_scratch, uint32_t* d_order, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     lpt_hist_kernel<<<(n + 255) / 256, 256, 0, s>>>(d_cost, n, shift, d_scratch);
@@ -1124,7 +1124,7 @@ hipError_t launch_lpt_order(uint32_t* d_cost, int n, int shift, uint32_t* d_scra
     return hipGetLastError();
 }
 
-// ---- static workgroup orders, generated on the device (api.cpp::ensure_order) -------------------------------------------
+// ---- static workgroup orders, generated on the device (clouds_launch.cpp::ensure_order) --------------------------------
 // Physical workgroup b runs on XCD b % 8 (observed placement, used for speed only).  A "slab" is one 32 x 8 pixel workgroup
 // footprint (bw x 8 for segmented launches); `grid` entries, 0xffffffff = idle padding.
 //   mode 2: natural order

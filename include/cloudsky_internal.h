@@ -47,7 +47,7 @@ int csky_set_variant(csky_ctx* ctx, int variant);
  * 0 disables it (A/B measurement, identical results). */
 int csky_set_height_window(csky_ctx* ctx, int enabled);
 int csky_variant_count(void);
-/* Workgroup -> XCD schedule (tuning knob, results are identical): -1 = auto (see api.cpp::clouds_dev for the launch-size policy);
+/* Workgroup -> XCD schedule (tuning knob, results are identical): -1 = auto (see csrc/launch_policy.h for the launch-size policy);
  * 5 = slab rows round-robin over the XCDs; 1 = contiguous eighths; 2 = natural order (all three written on the device);
  * 7 = cost feedback: every launch records a cost per workgroup (in-cloud samples) and the next launch of the same geometry
  *     and view starts its workgroups heaviest first (the first launch runs in a static order);

@@ -12,6 +12,7 @@
 #include "../../godot-volumetric-cloud-demo-v2_amd/csrc/composite_core.h"
 #include "../../godot-volumetric-cloud-demo-v2_amd/csrc/bc7enc_core.h"
 #include "../../godot-volumetric-cloud-demo-v2_amd/csrc/bc7_tables.h"
+#include "../../godot-volumetric-cloud-demo-v2_amd/csrc/launch_policy.h"
 
 using namespace csky;
 
@@ -239,5 +240,13 @@ int hostsim_frame_setup_two_ways(const float params[28], const uint16_t* sky_h, 
     frame_setup_f(P, [&](int tap, int corner, int, int) { return texel[tap * 4 + corner]; }, sw, sh, 128, 6, 0.0f, -1.0f, 2.0f, b);
     memcpy(fc_whole, &a, sizeof a); memcpy(fc_taps, &b, sizeof b);
     return (int)sizeof(FrameConsts);
+}
+}
+
+extern "C" {
+// launch_policy.h::plan_launch: out = {variant, seg, mode, static_mode, bw, feedback, persist}
+void hostsim_plan_launch(int variant, int cell32, int segments, int sched_mode, int frames_in_flight, int persistent, long long waves, int out[7]) {
+    const LaunchPlan p = plan_launch({variant, cell32 != 0, segments, sched_mode, frames_in_flight, persistent}, waves);
+    out[0] = p.variant; out[1] = p.seg; out[2] = p.mode; out[3] = p.static_mode; out[4] = p.bw; out[5] = p.feedback; out[6] = p.persist;
 }
 }

@@ -184,7 +184,10 @@ def cmd_build(args):
          "-input=dev.out", "-output=dev.hipfb"])
     run(["/opt/rocm/bin/hipcc"] + FLAGS + ["--cuda-host-only", "-Xclang", "-fcuda-include-gpubinary", "-Xclang", "dev.hipfb", "-c", os.path.join(CSRC, "kernels.hip"), "-o", "kernels_host.o"])
     out = os.path.join(ROOT, "godot-volumetric-cloud-demo-v2_amd", "libcloudsky_census.so")
-    subprocess.check_call(["/opt/rocm/bin/hipcc"] + FLAGS + ["-shared", "-o", out, os.path.join(work, "kernels_host.o"), "bc7enc.hip", "radiance.hip", "api.cpp", "assets.cpp", "godot_import.cpp"], cwd=CSRC)
+    # the product library's sources (the Makefile's SRCS), with kernels.hip replaced by its instrumented object
+    srcs = re.search(r"^SRCS\s*=(.*)$", open(os.path.join(CSRC, "Makefile")).read(), re.M).group(1).split()
+    others = [f for f in srcs if f != "kernels.hip"]
+    subprocess.check_call(["/opt/rocm/bin/hipcc"] + FLAGS + ["-shared", "-o", out, os.path.join(work, "kernels_host.o")] + others, cwd=CSRC)
     # static census of the PRODUCT assembly (block indices are shared with the instrumentation: same splitting rule)
     static = {}
     for tag, pre in KERNELS.items():
