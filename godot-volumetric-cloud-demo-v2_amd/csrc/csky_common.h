@@ -110,6 +110,8 @@ struct FrameConsts {
     float early_eps;                  // wave early-out threshold on T (0 = off; not in the reference)
     float hf_lo, hf_hi;               // height-fraction window outside which density() is provably 0 (bake.h height_window)
     int ct_mode;                      // cloud-type range of the bound weather map: 1 = every texel >= 0.5, 2 = every texel < 0.5, 0 = mixed (density_height_gradient)
+    int sat_skip;                     // 1: the frame's constants meet the assumptions of the saturation skip (cloud_core.h ray_saturated) and the caller left it on
+    float sat_kT, sat_kL;             // its slop factors on B*T and on L, sized from primary_steps (frame_setup_f)
 };
 
 // Which rows a launch renders (cloudsky.h csky_bands) + output addressing.

@@ -310,17 +310,18 @@ hipError_t launch_composite(const CompositeArgs& a, uint2* d_out, hipStream_t s)
 
 // ------------------------------------------------------------------------------------------------ clouds
 __global__ __launch_bounds__(64) void frame_setup_kernel(CloudParams p, const float4* __restrict__ sky, int sw, int sh, int primary_steps,
-                                                         int light_steps, float early_eps, float hf_lo, float hf_hi, int ct_mode, FrameConsts* __restrict__ out) {
+                                                         int light_steps, float early_eps, float hf_lo, float hf_hi, int ct_mode, int sat_skip, FrameConsts* __restrict__ out) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
         FrameConsts fc;
         frame_setup(p, sky, sw, sh, primary_steps, light_steps, early_eps, hf_lo, hf_hi, fc);
         fc.ct_mode = ct_mode;
+        if (!sat_skip) fc.sat_skip = 0;
         *out = fc;
     }
 }
 hipError_t launch_frame_setup(const CloudParams& p, const float4* d_sky, int sw, int sh, int primary_steps, int light_steps, float early_eps,
-                              float hf_lo, float hf_hi, int ct_mode, FrameConsts* d_fc, hipStream_t s) {
-    frame_setup_kernel<<<1, 64, 0, s>>>(p, d_sky, sw, sh, primary_steps, light_steps, early_eps, hf_lo, hf_hi, ct_mode, d_fc);
+                              float hf_lo, float hf_hi, int ct_mode, int sat_skip, FrameConsts* d_fc, hipStream_t s) {
+    frame_setup_kernel<<<1, 64, 0, s>>>(p, d_sky, sw, sh, primary_steps, light_steps, early_eps, hf_lo, hf_hi, ct_mode, sat_skip, d_fc);
     return hipGetLastError();
 }
 // The same for a context that holds no sky LUT of its own (one rank of an N-way frame split renders only its rows of it, straight into the
@@ -329,7 +330,7 @@ hipError_t launch_frame_setup(const CloudParams& p, const float4* d_sky, int sw,
 // arithmetic is sky_lut_cell's in both places, so every texel the set-up asks for is one rendered here: the constants are bit-identical to
 // those filtered from a whole LUT.
 __global__ __launch_bounds__(384) void frame_setup_taps_kernel(CloudParams p, Sun3 sun, const float4* __restrict__ trans, int tw, int th, int sw, int sh,
-                                                              int primary_steps, int light_steps, float early_eps, float hf_lo, float hf_hi, int ct_mode,
+                                                              int primary_steps, int light_steps, float early_eps, float hf_lo, float hf_hi, int ct_mode, int sat_skip,
                                                               FrameConsts* __restrict__ out) {
     __shared__ float steps[12][IN_SCATTERING_STEPS][8];
     __shared__ float4 texel[12];
@@ -345,13 +346,14 @@ __global__ __launch_bounds__(384) void frame_setup_taps_kernel(CloudParams p, Su
         FrameConsts fc;
         frame_setup_f(p, [&](int tap, int corner, int, int) { return texel[tap * 4 + corner]; }, sw, sh, primary_steps, light_steps, early_eps, hf_lo, hf_hi, fc);
         fc.ct_mode = ct_mode;
+        if (!sat_skip) fc.sat_skip = 0;
         *out = fc;
     }
 }
 hipError_t launch_frame_setup_taps(const CloudParams& p, const float sun[3], const float4* d_trans, int tw, int th, int sw, int sh, int primary_steps,
-                                   int light_steps, float early_eps, float hf_lo, float hf_hi, int ct_mode, FrameConsts* d_fc, hipStream_t s) {
+                                   int light_steps, float early_eps, float hf_lo, float hf_hi, int ct_mode, int sat_skip, FrameConsts* d_fc, hipStream_t s) {
     Sun3 sv; sv.v[0] = sun[0]; sv.v[1] = sun[1]; sv.v[2] = sun[2];
-    frame_setup_taps_kernel<<<1, 384, 0, s>>>(p, sv, d_trans, tw, th, sw, sh, primary_steps, light_steps, early_eps, hf_lo, hf_hi, ct_mode, d_fc);
+    frame_setup_taps_kernel<<<1, 384, 0, s>>>(p, sv, d_trans, tw, th, sw, sh, primary_steps, light_steps, early_eps, hf_lo, hf_hi, ct_mode, sat_skip, d_fc);
     return hipGetLastError();
 }
 
@@ -545,8 +547,15 @@ __device__ __forceinline__ void light_march_terms(const TS& T, const FrameConsts
     shade_terms(fc, eph, et, ehf, dt, cd, Dr, Dg, Db, rq);                                             // :202-209
 }
 
-template <class TS>
+// WHOLE: the call marches whole rays (step_begin == 0, step_end == primary_steps; render_block with SEG == 1).  Only then, and only for the fp16-pair
+// texture set, the saturation skip applies (cloud_core.h ray_saturated: exact reject (4)): ray segments are combined as fp32 partial (L, T, alpha), which
+// the proof does not cover, and TexSet32 and variants 0-2 stay as they are for A/B.  A lane whose ray is saturated LATCHES: it keeps taking its primary
+// samples, but a t > 0 one is counted (ballot + popcount into a wave-uniform tally) instead of queued, so its light march and shading are never run and
+// `incloud` is what the full march counts.  The test runs once per flush, after the replay, on the state already in registers, and only when some lane not
+// yet latched has reached the alpha threshold; samples a latched ray still has in the queue are composited as usual (the bound covers any subset).
+template <bool WHOLE, class TS>
 __device__ __forceinline__ MarchOut march_compact(const TS& T, const FrameConsts& fc, Ray ray, float* __restrict__ q, int step_begin, int step_end) {
+    constexpr bool SAT = WHOLE && !TS::cell32;
     float* __restrict__ ev_px = q;
     float* __restrict__ ev_py = q + CQ_CAP;
     float* __restrict__ ev_pz = q + 2 * CQ_CAP;
@@ -569,6 +578,8 @@ __device__ __forceinline__ MarchOut march_compact(const TS& T, const FrameConsts
     const float nd = -fc.density;
     bool live = ray.above;
     int count = 0, cs = 0;                                    // queued samples / steps owning them (uniform)
+    bool latched = false;                                     // saturation skip: this lane's ray is saturated (SAT only)
+    unsigned skipped = 0u;                                    // in-cloud samples of latched rays, counted and not queued (uniform)
     unsigned* __restrict__ tally = st_base + CQ_STEPS;          // in-cloud samples composited by this wavefront, kept in LDS (round 4: neither a per-lane accumulator register
     if (lane == 0) tally[0] = 0u;                             // in the march loops nor a scalar one in the SGPR-starved persistent form; one ds_add per flush)
     // the two per-ray constants a queued sample carries (step length, phase value) live in LDS, not in registers held across the whole march: the
@@ -595,6 +606,10 @@ __device__ __forceinline__ MarchOut march_compact(const TS& T, const FrameConsts
                 t = CSKY_PRIMARY_SAMPLE(T, fc, px, py, pz, hf, fc.wpos_x, fc.wpos_y, 0, 0);                    // :174, :177
                 have = t > 0.0f;                                                                               // :184
                 below_top = !(hf >= fc.hf_hi);
+            }
+            if constexpr (SAT) {
+                skipped += (unsigned)__popcll(__builtin_amdgcn_ballot_w64(have && latched));
+                have = have && !latched;
             }
             // Exact early end of the march: a ray starts on the inner shell and |p| only grows along it (>= 14 m per step at 128 steps even
             // for a grazing ray, 1.7 m at 1024 steps, against 0.5 m of fp32 noise; every ray of the C3 / C5 frames is walked by
@@ -641,6 +656,15 @@ __device__ __forceinline__ MarchOut march_compact(const TS& T, const FrameConsts
             }
             if (s == cs - 1) carry = __builtin_amdgcn_ballot_w64(mine && slot >= n);
         }
+        if constexpr (SAT) {
+            const bool cand = !latched && alpha >= SAT_ALPHA_MIN;
+            if (fc.sat_skip != 0 && __builtin_amdgcn_ballot_w64(cand) != 0ull) {
+                float B[3];
+                ray_saturation_bound(fc, ray_ph[lane], B);
+                const float L[3] = {Lr, Lg, Lb};
+                latched = latched || (cand && ray_saturated(fc, Tr, alpha, L, B));
+            }
+        }
         acc[lane] = Tr; acc[64 + lane] = alpha; acc[128 + lane] = Lr; acc[192 + lane] = Lg; acc[256 + lane] = Lb;
         wave_lds_fence();
         // ---- keep what was not evaluated: samples n..count-1 move to the front, the last step keeps its unevaluated lanes
@@ -664,7 +688,7 @@ __device__ __forceinline__ MarchOut march_compact(const TS& T, const FrameConsts
     }
     wave_lds_fence();
     o.r = acc[128 + lane]; o.g = acc[192 + lane]; o.b = acc[256 + lane]; o.a = sat(acc[64 + lane]); o.t = acc[lane];   // :213-214
-    o.incloud = lane == 0 ? tally[0] : 0u;
+    o.incloud = lane == 0 ? tally[0] + skipped : 0u;
     return o;
 }
 
@@ -936,7 +960,7 @@ __device__ __forceinline__ void render_block(TS T, const FrameConsts* __restrict
     } else {
         __shared__ float lds[4][VARIANT == 3 ? CQ_FLOATS : Q_FLOATS];
         const int s0 = (fc.primary_steps * seg) / SEG, s1 = (fc.primary_steps * (seg + 1)) / SEG;
-        if constexpr (VARIANT == 3) o = march_compact(T, fc, ray, &lds[wave][0], s0, s1);
+        if constexpr (VARIANT == 3) o = march_compact<SEG == 1>(T, fc, ray, &lds[wave][0], s0, s1);
         else o = march_queue(T, fc, ray, &lds[wave][0], s0, s1);
         if constexpr (SEG > 1) {
             __shared__ float comb[4][5][64];

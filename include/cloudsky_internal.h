@@ -43,8 +43,10 @@ int csky_get_kernel_ms(csky_ctx* ctx, float* total_ms, int* launches);
  * (CSKY_DEFAULT_VARIANT, "compact").  Unknown ids -> CSKY_ERR_INVALID. */
 #define CSKY_DEFAULT_VARIANT 3
 int csky_set_variant(csky_ctx* ctx, int variant);
-/* Exact height-window reject (density() provably 0 above/below the cloud body for the bound weather map): on by default;
- * 0 disables it (A/B measurement, identical results). */
+/* The exact specialisations of the march, switched together: the height-window reject (density() provably 0 above/below the cloud
+ * body for the bound weather map), the frame-wide cloud-type branch of the height gradient, and the saturation skip (whole-ray
+ * "compact" marches leave out the light march of a ray whose stored RGBA16F pixel can no longer change: csrc/cloud_core.h
+ * ray_saturated).  On by default; 0 disables all three (A/B measurement: identical frames and sample tallies). */
 int csky_set_height_window(csky_ctx* ctx, int enabled);
 int csky_variant_count(void);
 /* Workgroup -> XCD schedule (tuning knob, results are identical): -1 = auto (see csrc/launch_policy.h for the launch-size policy);

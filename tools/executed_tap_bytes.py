@@ -7,6 +7,9 @@ served by L1 / L2 / Infinity Cache, AND the exact rejects skip most of them.  Th
 density() evaluation gets; a lane that reaches a tap requests that tap's cell -- 16 B (weather xy cell of r and b), 32 B (shape xyz cells of r
 and the fBm numerator), 16 B (detail xyz cell).  Primary samples fetch lazily (a cell only when its stage is reached); light samples fetch all
 three cells of an in-window sample together (sample_density_eager; LOD 5 of the detail volume is one texel and needs no tap).
+--saturation-skip: the march as the kernel runs it since round 9, the light marches of saturated rays left out (cloud_core.h ray_saturated; the host
+walk latches a ray at the earliest sample, the kernel at its next flush, so the skipped share is an upper bound).  Off by default: the committed
+profiles/r04 file, which bench.py quotes, counts the unskipped march.
 Output: JSON with the counts, the executed bytes and the ratio to the algorithmic 80 B/sample; bench.py quotes it next to `hbm_algorithmic`."""
 import argparse
 import ctypes as C
@@ -27,6 +30,7 @@ import pmc_collect  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("size", nargs="*", type=int, default=[2048, 1024])
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r04", "executed_tap_bytes_C3.json"))
+ap.add_argument("--saturation-skip", action="store_true", help="leave out the light marches of saturated rays, as the kernel does (default: the unskipped march)")
 a = ap.parse_args()
 W, H = a.size
 steps, ls = 128, 6
@@ -41,7 +45,8 @@ P = lambda x: x.ctypes.data_as(C.c_void_p)
 st = np.zeros((H, W, steps), np.uint8)
 hist = np.zeros((7, 5), np.uint64)
 win = np.zeros(2, np.float32)
-L.stage_trace(P(lc), P(sc), P(weather), P(p), steps, ls, W, H, P(st), P(hist), P(win))
+skipped = np.zeros(2, np.uint64)
+L.stage_trace_ex(P(lc), P(sc), P(weather), P(p), steps, ls, W, H, P(st), P(hist), P(win), int(a.saturation_skip), P(skipped))
 valid = st != 255                                               # samples of rays above the horizon
 prim = {"samples": int(valid.sum()), "weather": int((valid & (st >= 1)).sum()), "shape": int((valid & (st >= 2)).sum()), "detail": int((valid & (st >= 3)).sum()),
         "in_cloud": int((valid & (st >= 4)).sum())}
@@ -57,6 +62,7 @@ for j in range(7):
     light_bytes += b
 algo = 80 * (prim["samples"] + light["samples"])
 out = {"config": "C3 %dx%d, %d x %d steps, sun 45 degrees, default textures, wind frozen" % (W, H, steps, ls), "source_hash": pmc_collect.source_hash(),
+       "saturation_skip": {"applied": bool(a.saturation_skip), "rays_latched": int(skipped[0]), "in_cloud_samples_without_light_march": int(skipped[1])},
        "cell_bytes": {"weather": 16, "shape": 32, "detail": 16}, "height_window": [float(win[0]), float(win[1])],
        "primary": dict(prim, bytes=prim_bytes), "light": dict(light, bytes=light_bytes),
        "executed_tap_bytes": prim_bytes + light_bytes, "algorithmic_bytes_80_per_sample": algo, "executed_over_algorithmic": (prim_bytes + light_bytes) / algo,

@@ -1,6 +1,8 @@
 #!/usr/bin/env python
 """Where do density() evaluations stop, and how full are the wavefronts at each stage?  (host analysis, no GPU)
-Runs tools/stage_trace/stage_trace.cpp (the kernel cores compiled with g++) over the headline view at reduced resolution."""
+Runs tools/stage_trace/stage_trace.cpp (the kernel cores compiled with g++) over the headline view at reduced resolution.
+Counts the UNSKIPPED march: every in-cloud sample with its light march (the saturation skip of round 9 is behind stage_trace_ex(skip = 1),
+which tools/executed_tap_bytes.py --saturation-skip uses)."""
 import ctypes as C
 import os
 import subprocess
