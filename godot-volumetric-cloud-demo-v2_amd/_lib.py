@@ -9,6 +9,27 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 
 OK, ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_IO, ERR_STATE = 0, -1, -2, -3, -4, -5
+TLUT_REFERENCE, TLUT_BRUNETON = 0, 1   # include/cloudsky.h CSKY_TLUT_*: the transmittance LUT's parametrization
+_TLUT_NAMES = {"reference": TLUT_REFERENCE, "bruneton": TLUT_BRUNETON}
+
+
+def tlut_mapping(mapping):
+    """'reference' / 'bruneton' (or CSKY_TLUT_* itself) -> the C ABI's value."""
+    if isinstance(mapping, str):
+        if mapping not in _TLUT_NAMES:
+            raise ValueError("transmittance mapping must be 'reference' or 'bruneton', got %r" % (mapping,))
+        return _TLUT_NAMES[mapping]
+    return int(mapping)
+
+
+def transmittance_uv(r_km, mu, mapping=TLUT_BRUNETON, w=256, h=64):
+    """csky_transmittance_uv (host only, no GPU): where a reader taps a w x h transmittance LUT for radius r_km and zenith cosine mu.
+    Returns (u, v, hits_ground); a ray that hits the ground has transmittance 0 in the Bruneton mapping and is not tapped."""
+    uv, hit = (C.c_float * 2)(), C.c_int(0)
+    rc = lib().csky_transmittance_uv(tlut_mapping(mapping), int(w), int(h), float(r_km), float(mu), uv, C.byref(hit))
+    if rc != OK:
+        raise CloudSkyError(rc, (lib().csky_last_error(None) or b"").decode())
+    return float(uv[0]), float(uv[1]), bool(hit.value)
 
 
 class CloudSkyError(RuntimeError):
@@ -88,6 +109,10 @@ SYMBOLS = [
     ("csky_encode_bc7_quality", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     ("csky_set_march", C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     ("csky_set_early_out", C.c_int, [C.c_void_p, C.c_float]),
+    ("csky_set_transmittance_mapping", C.c_int, [C.c_void_p, C.c_int]),
+    ("csky_get_transmittance_mapping", C.c_int, [C.c_void_p]),
+    ("csky_multi_set_transmittance_mapping", C.c_int, [C.c_void_p, C.c_int]),
+    ("csky_transmittance_uv", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     ("csky_render_transmittance", C.c_int, [C.c_void_p, C.POINTER(TransParams), C.c_void_p]),
     ("csky_render_sky_lut", C.c_int, [C.c_void_p, C.POINTER(SkyParams), C.c_void_p]),
     ("csky_render_clouds", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
@@ -176,7 +201,7 @@ SYMBOLS = [
 
 
 DEFAULT_VARIANT = 3   # include/cloudsky.h CSKY_DEFAULT_VARIANT ("compact"); set_variant(-1) selects it
-ABI_VERSION = 8       # include/cloudsky.h CSKY_ABI_VERSION
+ABI_VERSION = 9       # include/cloudsky.h CSKY_ABI_VERSION
 
 
 def library_path():
@@ -290,6 +315,14 @@ class Context:
 
     def set_march(self, primary_steps=128, light_steps=6):
         self._chk(self._L.csky_set_march(self._h, primary_steps, light_steps))
+
+    def set_transmittance_mapping(self, mapping):
+        """'reference' (default) or 'bruneton' (cloudsky.h CSKY_TLUT_*).  A change drops the transmittance LUT, the sky LUT and the radiance
+        snapshot: render a sky LUT again before the next frame."""
+        self._chk(self._L.csky_set_transmittance_mapping(self._h, tlut_mapping(mapping)))
+
+    def transmittance_mapping(self):
+        return self._L.csky_get_transmittance_mapping(self._h)
 
     def set_early_out(self, eps):
         self._chk(self._L.csky_set_early_out(self._h, float(eps)))
@@ -648,6 +681,9 @@ class MultiContext:
 
     def set_march(self, primary_steps=128, light_steps=6):
         self._chk(self._L.csky_multi_set_march(self._h, primary_steps, light_steps))
+
+    def set_transmittance_mapping(self, mapping):
+        self._chk(self._L.csky_multi_set_transmittance_mapping(self._h, tlut_mapping(mapping)))
 
     def set_frames_in_flight(self, frames):
         """2..8: consecutive render_clouds_device calls rotate that many consumer streams (per frame group); every device does too."""

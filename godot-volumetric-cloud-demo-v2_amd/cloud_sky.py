@@ -74,7 +74,7 @@ class CloudSky:
     FRAMES_TO_UPDATE_CHOICES = (1, 4, 16, 64, 256)   # cloud_sky.gd:36 plus 1 = full hemisphere per call
 
     def __init__(self, device_id=0, texture_size=768, frames_to_update=1, noise=None, clock=None, device_buffers=False,
-                 rank=0, world_size=1, dist=None, ctx=None, async_host=False):
+                 rank=0, world_size=1, dist=None, ctx=None, async_host=False, mapping=None):
         # exported properties, cloud_sky.gd:5-50 with the defaults of the script (clouds_sky.tres overrides some)
         self.wind_direction = 0.0
         self.wind_speed = 1.0
@@ -117,7 +117,8 @@ class CloudSky:
         self._radiance_next = 0
         # render-thread side (cloud_sky.gd:218-232): the C-ABI context owns every device resource
         self.ctx = ctx if ctx is not None else Context(device_id)
-        self.transmittance_tex = TransmittanceLut(self.ctx)                    # cloud_sky.gd:92
+        self.mapping = mapping           # the transmittance LUT's parametrization: 'reference', 'bruneton' (cloudsky.h CSKY_TLUT_*) or None = the context's own (reference unless changed)
+        self.transmittance_tex = TransmittanceLut(self.ctx, mapping=mapping)   # cloud_sky.gd:92
         self.sky_lut = SkyLut(self.ctx, self.transmittance_tex, device_buffers=self.device_buffers)   # cloud_sky.gd:91
         large, small, weather = noise if noise is not None else _assets.load_default_noise()
         self.ctx.set_noise(large, small, weather)                              # _create_noise_uniform_set, :298-341

@@ -15,6 +15,7 @@
 #include "context.h"
 #include "bake_core.h"
 #include "cloud_core.h"
+#include "lut_core.h"
 
 using namespace csky;
 
@@ -73,7 +74,7 @@ int ensure_sky(csky_ctx* c, int w, int h) {
 
 int render_trans_dev(csky_ctx* c, int w, int h, hipStream_t s) {
     int rc; if ((rc = ensure_trans(c, w, h))) return rc;
-    HIPCHK(c, launch_transmittance(w, h, c->d_trans_h, c->d_trans_f, s));
+    HIPCHK(c, launch_transmittance(w, h, c->d_trans_h, c->d_trans_f, s, c->tlut));
     c->have_trans = true; return CSKY_OK;
 }
 
@@ -428,6 +429,31 @@ int csky_set_height_window(csky_ctx* c, int enabled) {
     if (!c) return fail(nullptr, CSKY_ERR_INVALID, "csky_set_height_window: ctx is NULL");
     c->use_window = enabled != 0; return CSKY_OK;
 }
+int csky_set_transmittance_mapping(csky_ctx* c, int mapping) {
+    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "csky_set_transmittance_mapping: ctx is NULL");
+    if (mapping != CSKY_TLUT_REFERENCE && mapping != CSKY_TLUT_BRUNETON) return fail(c, CSKY_ERR_INVALID, "csky_set_transmittance_mapping: CSKY_TLUT_REFERENCE (0) or CSKY_TLUT_BRUNETON (1)");
+    if (mapping == c->tlut) return CSKY_OK;
+    int rc; if ((rc = bind(c))) return rc;
+    HIPCHK(c, hipDeviceSynchronize());                         // readers of the old table may be in flight, on caller streams too (csky_render_transmittance)
+    // everything rendered through the old table goes: the table itself (re-rendered on demand), the sky LUT and the radiance snapshot
+    c->tlut = mapping; c->have_trans = false; c->have_sky = false; c->sky_partial = false; c->sky_in_memory = false; c->lut_writers.clear(); c->rad.valid = false;
+    return CSKY_OK;
+}
+int csky_get_transmittance_mapping(const csky_ctx* c) { return c ? c->tlut : CSKY_ERR_INVALID; }
+int csky_transmittance_uv(int mapping, int w, int h, float r_km, float mu, float uv[2], int* hits_ground) {
+    if (!uv) return fail(nullptr, CSKY_ERR_INVALID, "csky_transmittance_uv: uv is NULL");
+    if (mapping == CSKY_TLUT_REFERENCE) {                      // transmittance_from_lut (sky-lut.glsl:137-142); the table stores every ray
+        if (w < 1 || h < 1) return fail(nullptr, CSKY_ERR_INVALID, "csky_transmittance_uv: empty table");
+        uv[0] = sat(mu * 0.5f + 0.5f); uv[1] = sat((r_km - EARTH_RADIUS) / ATMOSPHERE_THICKNESS);
+        if (hits_ground) *hits_ground = 0;
+        return CSKY_OK;
+    }
+    if (mapping != CSKY_TLUT_BRUNETON) return fail(nullptr, CSKY_ERR_INVALID, "csky_transmittance_uv: CSKY_TLUT_REFERENCE (0) or CSKY_TLUT_BRUNETON (1)");
+    if (w < 2 || h < 2) return fail(nullptr, CSKY_ERR_INVALID, "csky_transmittance_uv: CSKY_TLUT_BRUNETON needs a table of at least 2 x 2");
+    const bool hit = tlut_uv(w, h, r_km, mu, uv[0], uv[1]);
+    if (hits_ground) *hits_ground = hit ? 1 : 0;
+    return CSKY_OK;
+}
 int csky_variant_count(void) { return cloud_variant_count(); }
 const char* csky_variant_name(int v) { return cloud_variant_name(v); }
 
@@ -444,6 +470,7 @@ int csky_render_transmittance(csky_ctx* c, const csky_transmittance_params* p, u
     if (!p) return fail(c, CSKY_ERR_INVALID, "csky_render_transmittance: params is NULL");
     const int w = (int)p->texture_size[0], h = (int)p->texture_size[1];
     if (w < 1 || h < 1 || w > 8192 || h > 8192) return fail(c, CSKY_ERR_INVALID, "csky_render_transmittance: texture_size out of range");
+    if (c->tlut == CSKY_TLUT_BRUNETON && (w < 2 || h < 2)) return fail(c, CSKY_ERR_INVALID, "csky_render_transmittance: CSKY_TLUT_BRUNETON needs a table of at least 2 x 2 (texel centres sit on the ends of both ranges)");
     int rc; if ((rc = bind(c))) return rc;
     // sky LUTs in flight read the old transmittance LUT: whole ones and the set-ups' own texels on the prologue stream, a rank's rows
     // (csky_render_sky_lut_rows_device) on CALLER streams; the LUT is rendered once at load (transmittance_lut.gd:15-18), so wait for the device
@@ -464,7 +491,7 @@ int csky_render_sky_lut_device(csky_ctx* c, const csky_sky_params* p, void* hip_
     if (!c->have_trans && (rc = render_trans_dev(c, 256, 64, c->pro))) return rc;   // transmittance_lut.gd:6 default size
     if ((rc = ensure_sky(c, w, h))) return rc;
     const int k = (c->have_sky && c->sky_in_memory) ? c->sky_cur ^ 1 : c->sky_cur;  // the other ring slot: frame set-ups still reading the current one are ahead on `pro`
-    HIPCHK(c, launch_sky_lut(w, h, p->sun_direction, c->d_trans_f, c->tw, c->th, c->sky_h_ring[k], c->sky_f_ring[k], c->pro));
+    HIPCHK(c, launch_sky_lut(w, h, p->sun_direction, c->d_trans_f, c->tw, c->th, c->sky_h_ring[k], c->sky_f_ring[k], c->pro, c->tlut));
     c->sky_cur = k; c->d_sky_h = c->sky_h_ring[k]; c->d_sky_f = c->sky_f_ring[k];
     c->have_sky = true; c->sky_partial = false; c->sky_in_memory = true; c->lut_writers.clear();
     return CSKY_OK;
@@ -486,7 +513,7 @@ int csky_render_sky_lut_rows_device(csky_ctx* c, const csky_sky_params* p, int f
     // (Round 5 measured them on a side stream BESIDE the march that follows, joined behind it: a 1/8 share one frame at a time 0.409 -> 0.460 ms, eight
     // in flight 0.241 -> 0.244: two more cross-stream hops cost more than the rows they take off the critical path; profiles/r05/rows_overlap_ab.txt.)
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    HIPCHK(c, launch_sky_lut_rows(w, h, first_row, row_stride, p->sun_direction, c->d_trans_f, c->tw, c->th, reinterpret_cast<uint2*>(d_rows_out), nullptr, s));
+    HIPCHK(c, launch_sky_lut_rows(w, h, first_row, row_stride, p->sun_direction, c->d_trans_f, c->tw, c->th, reinterpret_cast<uint2*>(d_rows_out), nullptr, s, c->tlut));
     for (int i = 0; i < 3; i++) c->sky_sun[i] = p->sun_direction[i];
     c->psw = w; c->psh = h; c->sky_partial = true; c->have_sky = true; c->sky_in_memory = false; c->lut_writers.clear();
     return CSKY_OK;

@@ -193,6 +193,12 @@ int csky_multi_set_march(csky_multi* m, int primary_steps, int light_steps) {
     for (size_t i = 0; i < m->ctx.size(); i++) { const int rc = csky_set_march(m->ctx[i], primary_steps, light_steps); if (rc) return mpass(m, (int)i, rc); }
     return CSKY_OK;
 }
+int csky_multi_set_transmittance_mapping(csky_multi* m, int mapping) {
+    if (!m) return mfail(nullptr, CSKY_ERR_INVALID, "csky_multi_set_transmittance_mapping: handle is NULL");
+    if (mapping != CSKY_TLUT_REFERENCE && mapping != CSKY_TLUT_BRUNETON) return mfail(m, CSKY_ERR_INVALID, "csky_multi_set_transmittance_mapping: CSKY_TLUT_REFERENCE (0) or CSKY_TLUT_BRUNETON (1)");
+    for (size_t i = 0; i < m->ctx.size(); i++) { const int rc = csky_set_transmittance_mapping(m->ctx[i], mapping); if (rc) return mpass(m, (int)i, rc); }
+    return CSKY_OK;
+}
 int csky_multi_set_frames_in_flight(csky_multi* m, int frames) {
     if (!m) return mfail(nullptr, CSKY_ERR_INVALID, "csky_multi_set_frames_in_flight: handle is NULL");
     if (frames < 1 || frames > RING) return mfail(m, CSKY_ERR_INVALID, "csky_multi_set_frames_in_flight: 1 .. 8 per frame group (the per-device rings are eight deep)");
@@ -244,7 +250,7 @@ int csky_multi_render_sky_lut(csky_multi* m, const csky_sky_params* p) {
         hipError_t e = i ? hipStreamWaitEvent(c->pro, m->ev_lut_begin, 0) : hipSuccess;
         // rows i, i + n, ... stored into the first device's LUT -- or, when some device cannot reach that memory, every row by the first device itself
         if (e == hipSuccess && (m->all_peer || i == 0))
-            e = launch_sky_lut_rows(w, h, m->all_peer ? i : 0, m->all_peer ? n : 1, p->sun_direction, c->d_trans_f, c->tw, c->th, reinterpret_cast<uint2*>(c0->sky_h_ring[k]), c0->sky_f_ring[k], c->pro);
+            e = launch_sky_lut_rows(w, h, m->all_peer ? i : 0, m->all_peer ? n : 1, p->sun_direction, c->d_trans_f, c->tw, c->th, reinterpret_cast<uint2*>(c0->sky_h_ring[k]), c0->sky_f_ring[k], c->pro, c->tlut);
         if (e == hipSuccess) e = hipEventRecord(m->ev_lut[i], c->pro);
         if (e != hipSuccess) return mfail(m, CSKY_ERR_HIP, "csky_multi_render_sky_lut: device index %d: %s", i, hipGetErrorString(e));
         for (int q = 0; q < 3; q++) c->sky_sun[q] = p->sun_direction[q];

@@ -53,7 +53,7 @@ int composite_impl(csky_ctx* c, const csky_composite_params* p, const csky_view*
         a.tan_half_fov_y = tanf(view->fov_y_degrees * 0.5f * 3.14159265358979323846f / 180.0f);
         a.aspect = (float)p->out_w / (float)p->out_h;
     }
-    if (e == hipSuccess) e = launch_composite(a, reinterpret_cast<uint2*>(d + 2 * cb + 2 * sb), c->stream);
+    if (e == hipSuccess) e = launch_composite(a, reinterpret_cast<uint2*>(d + 2 * cb + 2 * sb), c->stream, c->tlut);
     if (e == hipSuccess) e = hipMemcpyAsync(out, d + 2 * cb + 2 * sb, ob, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) return fail(c, CSKY_ERR_HIP, "csky_composite_sky: %s", hipGetErrorString(e));
@@ -115,7 +115,7 @@ int radiance_dev(csky_ctx* c, const char* fn, const csky_composite_params* p, in
         c->rad.valid = false;
         CompositeArgs a = composite_args(c, p, cloud_from, cloud_to, sky_from, sky_to);
         a.out_w = S; a.out_h = 6 * S; a.view_mode = 2;
-        HIPCHK(c, launch_composite(a, d_first, s));
+        HIPCHK(c, launch_composite(a, d_first, s, c->tlut));
         if ((rc = rad_prepare(c, c->rad, S, Ss, s))) return rc;
         HIPCHK(c, launch_radiance_source(reinterpret_cast<const uint16_t*>(d_first), S, Ss, c->rad.tab, s));
         c->rad.S = S; c->rad.L = L; c->rad.Ss = Ss; c->rad.valid = true;

@@ -5,6 +5,7 @@
 // maths, FP contraction off.
 #pragma once
 #include "csky_common.h"
+#include "tlut_core.h"
 
 namespace csky {
 #pragma clang fp contract(off)
@@ -82,7 +83,8 @@ CSKY_HD void composite_eyedir(const CompositeArgs& A, int i, int j, float& ex, f
     ex = cosf(el) * cosf(az); ey = sinf(el); ez = cosf(el) * sinf(az);
 }
 
-CSKY_HD C3 composite_pixel(const CompositeArgs& A, int i, int j) {
+// TLUT: the parametrization of A.trans (tlut_core.h), selected at compile time; 0 is the shader's own getValFromTLUT
+template <int TLUT = TLUT_REFERENCE> CSKY_HD C3 composite_pixel(const CompositeArgs& A, int i, int j) {
     float ex, ey, ez;
     composite_eyedir(A, i, j, ex, ey, ez);                                               // EYEDIR
     // G:106-110: clamp below the horizon, hemi-octahedral encode of norm.xzy
@@ -136,15 +138,24 @@ CSKY_HD C3 composite_pixel(const CompositeArgs& A, int i, int j) {
             float tux = 256.0f * clampf(0.5f + 0.5f * sunCos, 0.0f, 1.0f);
             float tuy = 64.0f * fmaxf(0.0f, fminf(1.0f, (height - 6.360f) / (float)(6.460 - 6.360)));   // (the constant difference folds to 0.1, not to 6.46f - 6.36f)
             tux /= 256.0f; tuy /= 64.0f;
-            const float ux = tux * (float)A.tw - 0.5f, uy = tuy * (float)A.th - 0.5f;
-            const float fx0 = floorf(ux), fy0 = floorf(uy), ax = ux - fx0, ay = uy - fy0;
-            int x0 = (int)fx0, y0 = (int)fy0, x1 = x0 + 1, y1 = y0 + 1;
-            x0 = x0 < 0 ? 0 : (x0 > A.tw - 1 ? A.tw - 1 : x0); x1 = x1 < 0 ? 0 : (x1 > A.tw - 1 ? A.tw - 1 : x1);
-            y0 = y0 < 0 ? 0 : (y0 > A.th - 1 ? A.th - 1 : y0); y1 = y1 < 0 ? 0 : (y1 > A.th - 1 ? A.th - 1 : y1);
-            const float4 p = A.trans[y0 * A.tw + x0], q = A.trans[y0 * A.tw + x1], r = A.trans[y1 * A.tw + x0], s = A.trans[y1 * A.tw + x1];
-            br += sl * lerpf(lerpf(p.x, q.x, ax), lerpf(r.x, s.x, ax), ay);             // .rgb of the 4-wavelength LUT (reference quirk)
-            bg += sl * lerpf(lerpf(p.y, q.y, ax), lerpf(r.y, s.y, ax), ay);
-            bb += sl * lerpf(lerpf(p.z, q.z, ax), lerpf(r.z, s.z, ax), ay);
+            bool lit = true;
+            if constexpr (TLUT == TLUT_BRUNETON) {
+                // a mapping-1 table: mu = dot(up, sun) at r = Rg + hn (Rt - Rg) with the shader's own normalised height hn (= tuy: 64 hn / 64 is
+                // exact); a sun ray that meets the ground adds nothing (the table holds no such ray)
+                const float hn = tuy;
+                lit = !tlut_uv(A.tw, A.th, (float)TLUT_RG + hn * (float)(TLUT_RT - TLUT_RG), sunCos, tux, tuy);
+            }
+            if (lit) {
+                const float ux = tux * (float)A.tw - 0.5f, uy = tuy * (float)A.th - 0.5f;
+                const float fx0 = floorf(ux), fy0 = floorf(uy), ax = ux - fx0, ay = uy - fy0;
+                int x0 = (int)fx0, y0 = (int)fy0, x1 = x0 + 1, y1 = y0 + 1;
+                x0 = x0 < 0 ? 0 : (x0 > A.tw - 1 ? A.tw - 1 : x0); x1 = x1 < 0 ? 0 : (x1 > A.tw - 1 ? A.tw - 1 : x1);
+                y0 = y0 < 0 ? 0 : (y0 > A.th - 1 ? A.th - 1 : y0); y1 = y1 < 0 ? 0 : (y1 > A.th - 1 ? A.th - 1 : y1);
+                const float4 p = A.trans[y0 * A.tw + x0], q = A.trans[y0 * A.tw + x1], r = A.trans[y1 * A.tw + x0], s = A.trans[y1 * A.tw + x1];
+                br += sl * lerpf(lerpf(p.x, q.x, ax), lerpf(r.x, s.x, ax), ay);         // .rgb of the 4-wavelength LUT (reference quirk)
+                bg += sl * lerpf(lerpf(p.y, q.y, ax), lerpf(r.y, s.y, ax), ay);
+                bb += sl * lerpf(lerpf(p.z, q.z, ax), lerpf(r.z, s.z, ax), ay);
+            }
         }
     }
     // G:114-115

@@ -30,6 +30,7 @@ struct csky_ctx {
     float win_cov = -1e30f, win_lo = -1.0f, win_hi = 2.0f; bool use_window = true;
     // LUTs: RGBA16F image + float4 copy of the rounded values
     uint16_t* d_trans_h = nullptr; float4* d_trans_f = nullptr; int tw = 0, th = 0; bool have_trans = false;
+    int tlut = CSKY_TLUT_REFERENCE;                   // the transmittance LUT's parametrization (csky_set_transmittance_mapping, tlut_core.h): its writer and every reader get it
     uint16_t* d_sky_h = nullptr; float4* d_sky_f = nullptr; int sw = 0, sh = 0; bool have_sky = false;   // = ring slot sky_cur
     csky::FrameConsts* d_fc = nullptr;                                                                    // = ring slot fc_cur
     // Frame prologue pipeline.  The sky LUT and the frame set-up of frame k+1 are small dependent kernels; enqueued behind the

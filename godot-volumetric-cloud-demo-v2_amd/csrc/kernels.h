@@ -9,20 +9,21 @@ namespace csky {
 
 // transmittance-lut.glsl main(): writes the RGBA16F image and a float4 copy of the fp16-ROUNDED values
 // (what a sampler would read back), so later kernels sample floats without per-tap half unpacking.
-hipError_t launch_transmittance(int w, int h, uint16_t* d_half, float4* d_float, hipStream_t s);
+// `tlut` (here and below): the parametrization the table is written / read in, tlut_core.h (0 = the reference's, 1 = Bruneton's)
+hipError_t launch_transmittance(int w, int h, uint16_t* d_half, float4* d_float, hipStream_t s, int tlut = 0);
 // sky-lut.glsl main()
 hipError_t launch_sky_lut(int w, int h, const float sun[3], const float4* d_trans, int tw, int th, uint16_t* d_half,
-                          float4* d_float, hipStream_t s);
+                          float4* d_float, hipStream_t s, int tlut = 0);
 // rows row0, row0 + row_stride, ... of that LUT (one rank / device of an N-way frame split): d_whole_f == nullptr: compact RGBA16F into d_rows;
 // otherwise at their own place in the whole LUT d_rows (RGBA16F) + d_whole_f (the float copy)
 hipError_t launch_sky_lut_rows(int w, int h, int row0, int row_stride, const float sun[3], const float4* d_trans, int tw, int th, uint2* d_rows, float4* d_whole_f,
-                               hipStream_t s);
+                               hipStream_t s, int tlut = 0);
 // per-frame constants of clouds.glsl:143-170 (one wave)
 hipError_t launch_frame_setup(const CloudParams& p, const float4* d_sky, int sw, int sh, int primary_steps, int light_steps,
                               float early_eps, float hf_lo, float hf_hi, int ct_mode, int sat_skip, FrameConsts* d_fc, hipStream_t s);
 // the same without a sky LUT in memory: renders the <= 12 texels the set-up filters itself (sw x sh LUT of the sun `sun`)
 hipError_t launch_frame_setup_taps(const CloudParams& p, const float sun[3], const float4* d_trans, int tw, int th, int sw, int sh, int primary_steps,
-                                   int light_steps, float early_eps, float hf_lo, float hf_hi, int ct_mode, int sat_skip, FrameConsts* d_fc, hipStream_t s);
+                                   int light_steps, float early_eps, float hf_lo, float hf_hi, int ct_mode, int sat_skip, FrameConsts* d_fc, hipStream_t s, int tlut = 0);
 // clouds.glsl main() over the rows described by `g`.  d_stats (may be null): [0] += in-cloud samples,
 // [1] += rays above the horizon.
 // seg = ray segments per ray (1, 2 or 4; variant 1 only): a workgroup covers 4/seg tiles of 8x8 pixels.
@@ -39,7 +40,7 @@ hipError_t launch_lpt_order(uint32_t* d_cost, int n, int shift, uint32_t* d_scra
 // static workgroup orders 1, 2, 5 written on the device (kernels.hip); grid = padded number of physical workgroups
 hipError_t launch_static_order(int mode, int tiles_x, int slabs, int grid, uint32_t* d_order, hipStream_t s);
 // clouds.gdshader sky() on an equirectangular panorama (all pointers in `a` are device pointers)
-hipError_t launch_composite(const CompositeArgs& a, uint2* d_out, hipStream_t s);
+hipError_t launch_composite(const CompositeArgs& a, uint2* d_out, hipStream_t s, int tlut = 0);
 
 // stand-in shape noise bake: n^3 RGBA8 voxels (little-endian u32 = r | g<<8 | b<<16 | a<<24)
 hipError_t launch_shape_noise(uint32_t seed, int n, const ShapeNoiseParams& P, uint32_t* d_out, hipStream_t s);

@@ -21,13 +21,14 @@ namespace csky {
 // correctly rounded transcendentals, independent of the others), park extinction * dt in LDS, then lane 0 replays the sum in the reference's
 // order (T:186-192; bit-identical to the one-lane-per-texel form, 40x shorter critical path).  Round 1 had the GLSL's own dispatch shape here
 // (8x8 groups, one texel per lane, a 40-step serial loop: 2 048 one-wave groups on 6 % of the chip).
-__global__ __launch_bounds__(256) void transmittance_kernel(int w, int h, uint16_t* __restrict__ out_h, float4* __restrict__ out_f) {
+// TLUT: the table's parametrization (tlut_core.h), one instantiation per mapping (here and in the sky-LUT, set-up and compositor kernels below).
+template <int TLUT> __global__ __launch_bounds__(256) void transmittance_kernel(int w, int h, uint16_t* __restrict__ out_h, float4* __restrict__ out_f) {
     __shared__ float terms[4][TRANSMITTANCE_STEPS][4];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int texel = blockIdx.x * 4 + wave;
     const bool live = texel < w * h;                              // (T:159 tests `>`; the extra row/column would be an out-of-image store)
     const int px = live ? texel % w : 0, py = live ? texel / w : 0;
-    const TransRay r = transmittance_ray(px, py, (float)w, (float)h);
+    const TransRay r = transmittance_ray<TLUT>(px, py, (float)w, (float)h);
     if (lane < TRANSMITTANCE_STEPS) {
         const F4 e = transmittance_step(r, lane);
         float* d = terms[wave][lane];
@@ -50,11 +51,11 @@ struct Sun3 { float v[3]; };
 // in LDS, then lane 0 of the half replays the front-to-back accumulation in the reference's order (bit-identical to the
 // one-lane-per-texel form, 4x shorter critical path: this kernel sits on the critical path of every frame).
 // One texel; store(px, py, hx, hy, hz, hw) takes the four fp16 values (lane 0 of the half wavefront, live texels only).
-template <class Store> __device__ __forceinline__ void sky_texel(float (*steps)[8], int sub, bool live, int px, int py, int w, int h, const Sun3& sun,
+template <int TLUT, class Store> __device__ __forceinline__ void sky_texel(float (*steps)[8], int sub, bool live, int px, int py, int w, int h, const Sun3& sun,
                                                                  const float4* __restrict__ trans, int tw, int th, Store store) {
     const SkyRay r = sky_ray(px, py, (float)w, (float)h, sun.v);
     if (sub < IN_SCATTERING_STEPS) {
-        const SkyStep s = sky_step(r, sub, trans, tw, th);
+        const SkyStep s = sky_step<TLUT>(r, sub, trans, tw, th);
         float* d = steps[sub];
         d[0] = s.S_int.x; d[1] = s.S_int.y; d[2] = s.S_int.z; d[3] = s.S_int.w;
         d[4] = s.step_tr.x; d[5] = s.step_tr.y; d[6] = s.step_tr.z; d[7] = s.step_tr.w;
@@ -74,14 +75,14 @@ template <class Store> __device__ __forceinline__ void sky_texel(float (*steps)[
 __device__ __forceinline__ uint2 pack_half4(uint16_t hx, uint16_t hy, uint16_t hz, uint16_t hw) {
     return make_uint2((uint32_t)hx | ((uint32_t)hy << 16), (uint32_t)hz | ((uint32_t)hw << 16));
 }
-__global__ __launch_bounds__(256) void sky_lut_kernel(int w, int h, Sun3 sun, const float4* __restrict__ trans, int tw, int th,
+template <int TLUT> __global__ __launch_bounds__(256) void sky_lut_kernel(int w, int h, Sun3 sun, const float4* __restrict__ trans, int tw, int th,
                                                      uint16_t* __restrict__ out_h, float4* __restrict__ out_f) {
     __shared__ float steps[8][IN_SCATTERING_STEPS][8];
     const int half = threadIdx.x >> 5, sub = threadIdx.x & 31;
     const int texel = blockIdx.x * 8 + half;                      // rows 100..103 of the reference dispatch are discarded stores (S:281)
     const bool live = texel < w * h;
     const int px = live ? texel % w : 0, py = live ? texel / w : 0;
-    sky_texel(steps[half], sub, live, px, py, w, h, sun, trans, tw, th, [=](int x, int y, uint16_t hx, uint16_t hy, uint16_t hz, uint16_t hw) {
+    sky_texel<TLUT>(steps[half], sub, live, px, py, w, h, sun, trans, tw, th, [=](int x, int y, uint16_t hx, uint16_t hy, uint16_t hz, uint16_t hw) {
         reinterpret_cast<uint2*>(out_h)[y * w + x] = pack_half4(hx, hy, hz, hw);
         out_f[y * w + x] = make_float4(h2f(hx), h2f(hy), h2f(hz), h2f(hw));
     });
@@ -90,34 +91,37 @@ __global__ __launch_bounds__(256) void sky_lut_kernel(int w, int h, Sun3 sun, co
 // (csky_render_sky_lut_rows_device): stored COMPACT and as RGBA16F only, straight into the buffer that travels to the gathering rank with the
 // rank's bands.  out_f != nullptr (csky_multi_render_sky_lut): stored at the texel's own place in the whole LUT (half + float copies) of the
 // handle's first device, over xGMI peer access, like the frame's bands.
-__global__ __launch_bounds__(256) void sky_lut_rows_kernel(int w, int h, int row0, int row_stride, int n_rows, Sun3 sun, const float4* __restrict__ trans,
+template <int TLUT> __global__ __launch_bounds__(256) void sky_lut_rows_kernel(int w, int h, int row0, int row_stride, int n_rows, Sun3 sun, const float4* __restrict__ trans,
                                                           int tw, int th, uint2* __restrict__ out_h, float4* __restrict__ out_f) {
     __shared__ float steps[8][IN_SCATTERING_STEPS][8];
     const int half = threadIdx.x >> 5, sub = threadIdx.x & 31;
     const int t = blockIdx.x * 8 + half;
     const bool live = t < w * n_rows;
     const int px = live ? t % w : 0, py = live ? row0 + (t / w) * row_stride : 0;
-    sky_texel(steps[half], sub, live, px, py, w, h, sun, trans, tw, th, [=](int x, int y, uint16_t hx, uint16_t hy, uint16_t hz, uint16_t hw) {
+    sky_texel<TLUT>(steps[half], sub, live, px, py, w, h, sun, trans, tw, th, [=](int x, int y, uint16_t hx, uint16_t hy, uint16_t hz, uint16_t hw) {
         if (out_f) { out_h[y * w + x] = pack_half4(hx, hy, hz, hw); out_f[y * w + x] = make_float4(h2f(hx), h2f(hy), h2f(hz), h2f(hw)); }
         else out_h[t] = pack_half4(hx, hy, hz, hw);
     });
 }
 
-hipError_t launch_transmittance(int w, int h, uint16_t* d_half, float4* d_float, hipStream_t s) {
-    transmittance_kernel<<<(w * h + 3) / 4, 256, 0, s>>>(w, h, d_half, d_float);
+hipError_t launch_transmittance(int w, int h, uint16_t* d_half, float4* d_float, hipStream_t s, int tlut) {
+    if (tlut == TLUT_BRUNETON) transmittance_kernel<TLUT_BRUNETON><<<(w * h + 3) / 4, 256, 0, s>>>(w, h, d_half, d_float);
+    else transmittance_kernel<TLUT_REFERENCE><<<(w * h + 3) / 4, 256, 0, s>>>(w, h, d_half, d_float);
     return hipGetLastError();
 }
 hipError_t launch_sky_lut(int w, int h, const float sun[3], const float4* d_trans, int tw, int th, uint16_t* d_half, float4* d_float,
-                          hipStream_t s) {
+                          hipStream_t s, int tlut) {
     Sun3 sv; sv.v[0] = sun[0]; sv.v[1] = sun[1]; sv.v[2] = sun[2];
-    sky_lut_kernel<<<(w * h + 7) / 8, 256, 0, s>>>(w, h, sv, d_trans, tw, th, d_half, d_float);
+    if (tlut == TLUT_BRUNETON) sky_lut_kernel<TLUT_BRUNETON><<<(w * h + 7) / 8, 256, 0, s>>>(w, h, sv, d_trans, tw, th, d_half, d_float);
+    else sky_lut_kernel<TLUT_REFERENCE><<<(w * h + 7) / 8, 256, 0, s>>>(w, h, sv, d_trans, tw, th, d_half, d_float);
     return hipGetLastError();
 }
 hipError_t launch_sky_lut_rows(int w, int h, int row0, int row_stride, const float sun[3], const float4* d_trans, int tw, int th, uint2* d_rows, float4* d_whole_f,
-                               hipStream_t s) {
+                               hipStream_t s, int tlut) {
     Sun3 sv; sv.v[0] = sun[0]; sv.v[1] = sun[1]; sv.v[2] = sun[2];
     const int n_rows = row0 < h ? (h - row0 + row_stride - 1) / row_stride : 0;
-    if (n_rows) sky_lut_rows_kernel<<<(w * n_rows + 7) / 8, 256, 0, s>>>(w, h, row0, row_stride, n_rows, sv, d_trans, tw, th, d_rows, d_whole_f);
+    if (n_rows && tlut == TLUT_BRUNETON) sky_lut_rows_kernel<TLUT_BRUNETON><<<(w * n_rows + 7) / 8, 256, 0, s>>>(w, h, row0, row_stride, n_rows, sv, d_trans, tw, th, d_rows, d_whole_f);
+    else if (n_rows) sky_lut_rows_kernel<TLUT_REFERENCE><<<(w * n_rows + 7) / 8, 256, 0, s>>>(w, h, row0, row_stride, n_rows, sv, d_trans, tw, th, d_rows, d_whole_f);
     return hipGetLastError();
 }
 
@@ -297,14 +301,15 @@ hipError_t launch_sqrt_shell(const float* d_in, float* d_out, size_t n, hipStrea
 
 // ------------------------------------------------------------------------------------------------ compositor
 // clouds.gdshader sky() on an equirectangular panorama, one pixel per lane
-__global__ __launch_bounds__(256) void composite_kernel(CompositeArgs A, uint2* __restrict__ out) {
+template <int TLUT> __global__ __launch_bounds__(256) void composite_kernel(CompositeArgs A, uint2* __restrict__ out) {
     const int i = blockIdx.x * 32 + (threadIdx.x & 31), j = blockIdx.y * 8 + (threadIdx.x >> 5);
     if (i >= A.out_w || j >= A.out_h) return;
-    const C3 c = composite_pixel(A, i, j);
+    const C3 c = composite_pixel<TLUT>(A, i, j);
     out[(size_t)j * A.out_w + i] = make_uint2((uint32_t)f2h(c.x) | ((uint32_t)f2h(c.y) << 16), (uint32_t)f2h(c.z) | ((uint32_t)f2h(1.0f) << 16));
 }
-hipError_t launch_composite(const CompositeArgs& a, uint2* d_out, hipStream_t s) {
-    composite_kernel<<<dim3((a.out_w + 31) / 32, (a.out_h + 7) / 8), 256, 0, s>>>(a, d_out);
+hipError_t launch_composite(const CompositeArgs& a, uint2* d_out, hipStream_t s, int tlut) {
+    if (tlut == TLUT_BRUNETON) composite_kernel<TLUT_BRUNETON><<<dim3((a.out_w + 31) / 32, (a.out_h + 7) / 8), 256, 0, s>>>(a, d_out);
+    else composite_kernel<TLUT_REFERENCE><<<dim3((a.out_w + 31) / 32, (a.out_h + 7) / 8), 256, 0, s>>>(a, d_out);
     return hipGetLastError();
 }
 
@@ -329,7 +334,7 @@ hipError_t launch_frame_setup(const CloudParams& p, const float4* d_sky, int sw,
 // per-texel code of sky_lut_kernel (fp16-rounded like the stored LUT), parked in LDS, and lane 0 runs the set-up on them.  The cell
 // arithmetic is sky_lut_cell's in both places, so every texel the set-up asks for is one rendered here: the constants are bit-identical to
 // those filtered from a whole LUT.
-__global__ __launch_bounds__(384) void frame_setup_taps_kernel(CloudParams p, Sun3 sun, const float4* __restrict__ trans, int tw, int th, int sw, int sh,
+template <int TLUT> __global__ __launch_bounds__(384) void frame_setup_taps_kernel(CloudParams p, Sun3 sun, const float4* __restrict__ trans, int tw, int th, int sw, int sh,
                                                               int primary_steps, int light_steps, float early_eps, float hf_lo, float hf_hi, int ct_mode, int sat_skip,
                                                               FrameConsts* __restrict__ out) {
     __shared__ float steps[12][IN_SCATTERING_STEPS][8];
@@ -338,7 +343,7 @@ __global__ __launch_bounds__(384) void frame_setup_taps_kernel(CloudParams p, Su
     float sx, sy, ax, ay; int x0, x1, y0, y1;
     frame_setup_tap_uv(p.LIGHT_DIRECTION, k >> 2, sx, sy);
     sky_lut_cell(sw, sh, sx, sy, x0, x1, y0, y1, ax, ay);
-    sky_texel(steps[k], sub, true, (k & 1) ? x1 : x0, (k & 2) ? y1 : y0, sw, sh, sun, trans, tw, th, [&](int, int, uint16_t hx, uint16_t hy, uint16_t hz, uint16_t hw) {
+    sky_texel<TLUT>(steps[k], sub, true, (k & 1) ? x1 : x0, (k & 2) ? y1 : y0, sw, sh, sun, trans, tw, th, [&](int, int, uint16_t hx, uint16_t hy, uint16_t hz, uint16_t hw) {
         texel[k] = make_float4(h2f(hx), h2f(hy), h2f(hz), h2f(hw));
     });
     __syncthreads();
@@ -351,9 +356,10 @@ __global__ __launch_bounds__(384) void frame_setup_taps_kernel(CloudParams p, Su
     }
 }
 hipError_t launch_frame_setup_taps(const CloudParams& p, const float sun[3], const float4* d_trans, int tw, int th, int sw, int sh, int primary_steps,
-                                   int light_steps, float early_eps, float hf_lo, float hf_hi, int ct_mode, int sat_skip, FrameConsts* d_fc, hipStream_t s) {
+                                   int light_steps, float early_eps, float hf_lo, float hf_hi, int ct_mode, int sat_skip, FrameConsts* d_fc, hipStream_t s, int tlut) {
     Sun3 sv; sv.v[0] = sun[0]; sv.v[1] = sun[1]; sv.v[2] = sun[2];
-    frame_setup_taps_kernel<<<1, 384, 0, s>>>(p, sv, d_trans, tw, th, sw, sh, primary_steps, light_steps, early_eps, hf_lo, hf_hi, ct_mode, sat_skip, d_fc);
+    if (tlut == TLUT_BRUNETON) frame_setup_taps_kernel<TLUT_BRUNETON><<<1, 384, 0, s>>>(p, sv, d_trans, tw, th, sw, sh, primary_steps, light_steps, early_eps, hf_lo, hf_hi, ct_mode, sat_skip, d_fc);
+    else frame_setup_taps_kernel<TLUT_REFERENCE><<<1, 384, 0, s>>>(p, sv, d_trans, tw, th, sw, sh, primary_steps, light_steps, early_eps, hf_lo, hf_hi, ct_mode, sat_skip, d_fc);
     return hipGetLastError();
 }
 

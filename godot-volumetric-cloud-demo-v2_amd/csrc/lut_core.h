@@ -5,6 +5,7 @@
 // Citations: T: = cloud_sky/transmittance-lut.glsl, S: = cloud_sky/sky-lut.glsl.  Units: km.
 #pragma once
 #include "csky_common.h"
+#include "tlut_core.h"
 
 namespace csky {
 #pragma clang fp contract(off)
@@ -82,9 +83,19 @@ CSKY_HD Coeffs atmosphere_collision_coefficients(float h) {
 // T:157-196 main() for texel (px,py) of a w x h LUT, split like the sky LUT below so that the 40 optical-depth steps of one texel can be
 // evaluated by 40 lanes in parallel: every step's extinction * dt is independent of the others, only the running sum (T:191) is
 // sequential, and it is replayed in the reference's order (bit-identical to the one-lane form).
+// TLUT selects the table's parametrization (tlut_core.h) at compile time: 0 is the reference's code, untouched; 1 marches the ray its texel stores.
 struct TransRay { float sdx, sdz, d, dt; };
-CSKY_HD TransRay transmittance_ray(int px, int py, float w, float h) {
+template <int TLUT = TLUT_REFERENCE> CSKY_HD TransRay transmittance_ray(int px, int py, float w, float h) {
     TransRay r;
+    if constexpr (TLUT == TLUT_BRUNETON) {
+        // from (0, 0, r) along (-sqrt(1 - mu^2), 0, mu) over the texel's OWN length d, not a second sphere intersection: the top row has d = 0
+        // (transmittance exactly 1)
+        float mu, d;
+        tlut_texel_ray(px, py, (int)w, (int)h, r.d, mu, d);
+        r.sdx = -sqrtf(1.0f - mu * mu); r.sdz = mu;
+        r.dt = d / (float)TRANSMITTANCE_STEPS;
+        return r;
+    }
     const float uvx = (float)px / w, uvy = (float)py / h;
     const float c = uvx * 2.0f - 1.0f;
     r.sdx = -sqrtf(1.0f - c * c); r.sdz = c;
@@ -101,8 +112,8 @@ CSKY_HD F4 transmittance_step(const TransRay& r, int i) {            // one term
 }
 CSKY_HD F4 transmittance_finish(const F4& result) { return exp4(f4(-result.x, -result.y, -result.z, -result.w)); }   // T:194
 // the whole texel on one lane (host-compiled unit test; the kernel spreads the steps over lanes)
-CSKY_HD F4 transmittance_texel(int px, int py, float w, float h) {
-    const TransRay r = transmittance_ray(px, py, w, h);
+template <int TLUT = TLUT_REFERENCE> CSKY_HD F4 transmittance_texel(int px, int py, float w, float h) {
+    const TransRay r = transmittance_ray<TLUT>(px, py, w, h);
     F4 result = f4(0, 0, 0, 0);
     for (int i = 0; i < TRANSMITTANCE_STEPS; ++i) result = result + transmittance_step(r, i);
     return transmittance_finish(result);
@@ -122,6 +133,19 @@ CSKY_HD F4 lut_tap_clamp(const float4* t, int w, int h, float sx, float sy) {
 // S:137-142
 CSKY_HD F4 transmittance_from_lut(const float4* t, int tw, int th, float cos_theta, float normalized_altitude) {
     return lut_tap_clamp(t, tw, th, sat(cos_theta * 0.5f + 0.5f), sat(normalized_altitude));
+}
+
+// the same look-up in a mapping-1 table (tlut_core.h): zenith cosine mu at radius r; 0 without a tap for a ray that meets the ground
+CSKY_HD F4 transmittance_from_lut_bruneton(const float4* t, int tw, int th, float mu, float r) {
+    float u, v;
+    if (tlut_uv(tw, th, r, mu, u, v)) return f4(0, 0, 0, 0);
+    return lut_tap_clamp(t, tw, th, u, v);
+}
+
+// one of sky_step's four taps: mapping 0 reads (cosine, normalised altitude), mapping 1 (cosine, radius: the sample's own, or the ground's)
+template <int TLUT> CSKY_HD F4 sky_tlut_tap(const float4* t, int tw, int th, float cos_theta, float normalized_altitude, float r) {
+    if constexpr (TLUT == TLUT_BRUNETON) return transmittance_from_lut_bruneton(t, tw, th, cos_theta, r);
+    else return transmittance_from_lut(t, tw, th, cos_theta, normalized_altitude);
 }
 
 // sky-lut.glsl main() (S:278-315) + compute_inscattering (S:219-276), split so that the 30 in-scattering steps of one
@@ -151,7 +175,7 @@ CSKY_HD SkyRay sky_ray(int px, int py, float w, float h, const float sun[3]) {
 }
 
 // one iteration of the loop at S:234-273, up to (not including) the accumulation
-CSKY_HD SkyStep sky_step(const SkyRay& r, int i, const float4* trans, int tw, int th) {
+template <int TLUT = TLUT_REFERENCE> CSKY_HD SkyStep sky_step(const SkyRay& r, int i, const float4* trans, int tw, int th) {
     const float dt = r.dt;
     const float t = ((float)i + 0.5f) * dt;
     const float x = 0.0f + r.rdx * t, y = 0.0f + r.rdy * t, z = r.oz + r.rdz * t;
@@ -161,11 +185,11 @@ CSKY_HD SkyStep sky_step(const SkyRay& r, int i, const float4* trans, int tw, in
     const float nalt = altitude / ATMOSPHERE_THICKNESS;
     const float sct = zx * r.sdx + zy * r.sdy + zz * r.sdz;                          // S:243
     const Coeffs cf = atmosphere_collision_coefficients(altitude);
-    const F4 t_sun = transmittance_from_lut(trans, tw, th, sct, nalt);               // S:254
+    const F4 t_sun = sky_tlut_tap<TLUT>(trans, tw, th, sct, nalt, dist);             // S:254
     // get_multiple_scattering, S:144-164
     const float omega = (float)(2.0 * LUT_PI) * (1.0f - sqrtf(dist * dist - EARTH_RADIUS * EARTH_RADIUS) / dist);
-    const F4 T_to_ground = transmittance_from_lut(trans, tw, th, sct, 0.0f);
-    const F4 T_g2s = transmittance_from_lut(trans, tw, th, 1.0f, 0.0f) / transmittance_from_lut(trans, tw, th, 1.0f, nalt);
+    const F4 T_to_ground = sky_tlut_tap<TLUT>(trans, tw, th, sct, 0.0f, EARTH_RADIUS);
+    const F4 T_g2s = sky_tlut_tap<TLUT>(trans, tw, th, 1.0f, 0.0f, EARTH_RADIUS) / sky_tlut_tap<TLUT>(trans, tw, th, 1.0f, nalt, dist);
     const float ks = (float)(0.25 * (1.0 / LUT_PI)) * omega * (float)(0.3 / LUT_PI);
     const F4 L_ground = f4(ks, ks, ks, ks) * T_to_ground * T_g2s * sct;
     const float fm = 1.0f / (1.0f + 5.0f * exp_cr(-17.92f * sct));
@@ -188,10 +212,10 @@ CSKY_HD F4 sky_output(const F4& L) {
     return f4(r, g, b, 1.0f);
 }
 // the whole texel on one lane (host-compiled unit test; the kernel spreads the steps over lanes)
-CSKY_HD F4 sky_texel(int px, int py, float w, float h, const float sun[3], const float4* trans, int tw, int th) {
+template <int TLUT = TLUT_REFERENCE> CSKY_HD F4 sky_texel(int px, int py, float w, float h, const float sun[3], const float4* trans, int tw, int th) {
     const SkyRay r = sky_ray(px, py, w, h, sun);
     F4 L = f4(0, 0, 0, 0), Tr = f4(1, 1, 1, 1);
-    for (int i = 0; i < IN_SCATTERING_STEPS; ++i) sky_accumulate(L, Tr, sky_step(r, i, trans, tw, th));
+    for (int i = 0; i < IN_SCATTERING_STEPS; ++i) sky_accumulate(L, Tr, sky_step<TLUT>(r, i, trans, tw, th));
     return sky_output(L);
 }
 

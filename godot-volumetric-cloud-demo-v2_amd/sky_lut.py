@@ -10,8 +10,13 @@ class SkyLut:
     context's internal LUT.  Ring copies are numpy float16 arrays (host form) or torch float16 CUDA tensors filled by an
     asynchronous device copy (`device_buffers=True`: no host hop, no synchronisation in the frame loop)."""
 
-    def __init__(self, ctx, transmittance, texture_size=(200, 100), device_buffers=False):
+    def __init__(self, ctx, transmittance, texture_size=(200, 100), device_buffers=False, mapping=None):
         self.ctx = ctx
+        # the transmittance LUT's parametrization the taps use ('reference' / 'bruneton', cloudsky.h CSKY_TLUT_*): the table's own unless given;
+        # None leaves the context as it is (the reference mapping unless someone changed it)
+        self.mapping = mapping if mapping is not None else getattr(transmittance, "mapping", None)
+        if self.mapping is not None:
+            self.ctx.set_transmittance_mapping(self.mapping)
         self.transmittance_tex = transmittance          # sky_lut.gd:22
         self.texture_size = tuple(int(v) for v in texture_size)   # sky_lut.gd:4
         self.light_direction = np.array([0.0, -1.0, 0.0], np.float32)  # sky_lut.gd:5

@@ -41,7 +41,7 @@ extern "C" {
 #define CSKY_ERR_IO (-4)         /* asset file problem                                       */
 #define CSKY_ERR_STATE (-5)      /* e.g. clouds requested before noise / LUTs exist          */
 
-#define CSKY_ABI_VERSION 8  /* 8: csky_render_radiance[_device], csky_prefilter_cube (the radiance cubemap); 7: csky_multi_last_warning (csky_multi_create no longer fails without peer access: it falls back to staged copies and says so); 6: the measurement / tuning / test entry points moved to cloudsky_internal.h (same library), csky_generate_shape_noise_tuned[_device]; 5: csky_last_warning (warnings no longer sit in csky_last_error), exact fp32-coefficient texture cells, csky_render_sky_lut_rows_device, csky_interleave_bands_device, csky_encode_bc7, rings eight deep; 4: csky_submit_* / csky_collect, csky_multi_set_groups / _set_staged, csky_composite_view, csky_external_frame_* (incl. _fence / _ready / _wait); 3: csky_set_noise_mips, csky_decode_bc7, csky_load_ctex[3d]; 2: csky_multi_*, device asset builders */
+#define CSKY_ABI_VERSION 9  /* 9: csky_set_ / csky_get_ / csky_multi_set_transmittance_mapping, csky_transmittance_uv (CSKY_TLUT_BRUNETON); 8: csky_render_radiance[_device], csky_prefilter_cube (the radiance cubemap); 7: csky_multi_last_warning (csky_multi_create no longer fails without peer access: it falls back to staged copies and says so); 6: the measurement / tuning / test entry points moved to cloudsky_internal.h (same library), csky_generate_shape_noise_tuned[_device]; 5: csky_last_warning (warnings no longer sit in csky_last_error), exact fp32-coefficient texture cells, csky_render_sky_lut_rows_device, csky_interleave_bands_device, csky_encode_bc7, rings eight deep; 4: csky_submit_* / csky_collect, csky_multi_set_groups / _set_staged, csky_composite_view, csky_external_frame_* (incl. _fence / _ready / _wait); 3: csky_set_noise_mips, csky_decode_bc7, csky_load_ctex[3d]; 2: csky_multi_*, device asset builders */
 
 typedef struct csky_ctx csky_ctx; /* opaque: owns every device allocation, the HIP stream and events */
 
@@ -119,6 +119,30 @@ int csky_set_exact_cells(csky_ctx* ctx, int mode);
 /* clouds.glsl:228 (128 primary steps) and clouds.glsl:186 (6 light steps) are literals in the reference;
  * this generalises them (BASELINE config 2 is 64 x 4).  light_steps in [0,6], primary_steps in [1,1024]. */
 int csky_set_march(csky_ctx* ctx, int primary_steps, int light_steps);
+/* The parametrization of the transmittance LUT, honoured by the kernel that writes it and by every reader (the sky LUT in all its forms, the frame
+ * set-up that renders its own sky texels, the compositor's sun disc and radiance layer 0).
+ *   CSKY_TLUT_REFERENCE  transmittance-lut.glsl as written: u linear in the sun's zenith cosine over [-1, 1], v linear in altitude, written for
+ *                        uv = texel / size and sampled at texel centres.  The default; byte for byte what the library rendered before this setting.
+ *   CSKY_TLUT_BRUNETON   the mapping of Bruneton's 2017 implementation (the reference's README.md:29, TODO 2).  Units km, Rg = 6371, Rt = 6471,
+ *                        H = sqrt(Rt^2 - Rg^2).  For radius r in [Rg, Rt] and zenith cosine mu in [-1, 1]:
+ *                          rho = sqrt((r - Rg)(r + Rg)),  d = max(-r mu + sqrt(max(r^2 (mu^2 - 1) + Rt^2, 0)), 0),
+ *                          x_mu = clamp((d - (Rt - r)) / (rho + H - (Rt - r)), 0, 1),  x_r = rho / H,
+ *                          u = 0.5/w + x_mu (1 - 1/w),  v = 0.5/h + x_r (1 - 1/h)          (texel centres sit on the ends of both ranges)
+ *                        and texel (x, y) stores the ray with x_mu = x/(w-1), x_r = y/(h-1), marched over its own length d.  The table holds only
+ *                        rays that reach the top of the atmosphere.  THE ONE SEMANTIC DIFFERENCE: for a ray that meets the ground
+ *                        (mu < 0 and r^2 (mu^2 - 1) + Rg^2 >= 0) every reader takes transmittance 0 and does not tap, where the reference's table
+ *                        holds such rays marched through the planet at ground-level density.  Tables need w, h >= 2.
+ * A change drops what was rendered through the old table: the transmittance LUT (re-rendered on demand, 256 x 64, as before the first use), the
+ * sky LUT and the radiance snapshot -- csky_render_clouds* / csky_read_sky_lut return CSKY_ERR_STATE until a sky LUT is rendered again.  Setting
+ * the current value does nothing.  csky_get_transmittance_mapping: the value, < 0 for a NULL context. */
+#define CSKY_TLUT_REFERENCE 0
+#define CSKY_TLUT_BRUNETON 1
+int csky_set_transmittance_mapping(csky_ctx* ctx, int mapping);
+int csky_get_transmittance_mapping(const csky_ctx* ctx);
+/* Host only, no GPU: where a reader taps a w x h table for radius r_km and zenith cosine mu (both clamped as above), for hosts whose own shader
+ * samples the table (clouds.gdshader getValFromTLUT).  uv in [0, 1]^2 for a LINEAR, clamp-to-edge sampler; *hits_ground (may be NULL) = 1 when the
+ * reader must take 0 instead (CSKY_TLUT_BRUNETON only).  Evaluated in double from the fp32 inputs and rounded once, exactly as the kernels do. */
+int csky_transmittance_uv(int mapping, int w, int h, float r_km, float mu, float uv[2], int* hits_ground);
 /* Wave-level early-out threshold: a wavefront stops marching once every lane's transmittance T < eps.
  * The reference has no early-out; eps = 0 disables it (bit-for-bit reference behaviour).  Default 0. */
 int csky_set_early_out(csky_ctx* ctx, float eps);
@@ -334,6 +358,7 @@ int csky_multi_set_groups(csky_multi* m, int groups);
  * environment at csky_multi_create.  Default 0. */
 int csky_multi_set_staged(csky_multi* m, int staged);
 int csky_multi_set_march(csky_multi* m, int primary_steps, int light_steps);
+int csky_multi_set_transmittance_mapping(csky_multi* m, int mapping);   /* csky_set_transmittance_mapping on every context of the handle */
 /* sky_lut.gd:122-148 for the handle: device i renders rows i, i + n, ... of the LUT and stores them, like its bands, straight into the LUT of the
  * first device (csky_read_sky_lut / csky_copy_sky_lut_device on csky_multi_ctx(m, 0) give the whole LUT and wait for every writer); no device's
  * frame set-up reads that copy, each renders the few texels it filters itself (see csky_render_sky_lut_rows_device), on every device whatever the
