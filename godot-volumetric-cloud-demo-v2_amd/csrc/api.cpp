@@ -20,10 +20,13 @@
 using namespace csky;
 
 // Two frames in flight (csky_set_frames_in_flight) need the caller's two streams on DIFFERENT hardware queues.  The HIP runtime
-// multiplexes a process's streams onto GPU_MAX_HW_QUEUES queues (default 4) in first-use order, and with the library's two internal streams
-// plus a host's own, four are not enough (measured: no overlap at 4, overlap at 8).  The runtime reads the variable when it initialises, at
+// multiplexes a process's streams onto GPU_MAX_HW_QUEUES queues (default 4); each stream that has been used holds on to one, and once all
+// exist a further stream shares one.  Per context the library uses ONE stream of its own (context.h), so the runtime's default of four carries
+// two frames in flight beside a host that uses its default stream: frames + 2 queues are what csky_set_frames_in_flight asks for (measured,
+// profiles/r11/queue_overlap_ab.txt: 1.52 ms per frame at 4 queues and at 16; with a second internal stream, as until round 11, 1.87 at 4).
+// More frames in flight, or a host with further streams of its own, need more queues.  The runtime reads the variable when it initialises, at
 // the first HIP call; this runs when libcloudsky.so is loaded, so a host that cannot set environment variables (a GDExtension inside Godot)
-// still gets the overlap as long as it has not used HIP before loading the library.  An existing value is never overwritten.
+// gets 16 as long as it has not used HIP before loading the library.  An existing value is never overwritten.
 // Opt-out: CSKY_NO_ENV=1 in the environment leaves the process's environment alone (a host that loads other HIP users and wants the runtime's
 // defaults); csky_set_frames_in_flight then warns through csky_last_warning when the variable is not in effect.
 __attribute__((constructor)) static void csky_runtime_defaults() {
@@ -63,7 +66,7 @@ int fail(csky_ctx* c, int code, const char* fmt, ...) {
 
 int ensure_sky(csky_ctx* c, int w, int h) {
     if (c->d_sky_h && c->sw == w && c->sh == h) return CSKY_OK;
-    if (c->pro) HIPCHK(c, hipStreamSynchronize(c->pro));     // a size change is rare: drain the prologue stream, rebuild both slots
+    if (c->stream) HIPCHK(c, hipStreamSynchronize(c->stream));  // a size change is rare: drain the context's stream (every reader of the LUT runs there), rebuild both slots
     for (int k = 0; k < 2; k++) {
         int rc; if ((rc = dev_alloc(c, &c->sky_h_ring[k], (size_t)w * h * 4))) return rc;
         if ((rc = dev_alloc(c, &c->sky_f_ring[k], (size_t)w * h))) return rc;
@@ -129,9 +132,8 @@ int csky_create(csky_ctx** out, int device_id) {
     if ((e = hipEventCreate(&c->ev1)) != hipSuccess) return bail("hipEventCreate", e);
     if ((e = hipEventCreateWithFlags(&c->ev_copy, hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
     if ((e = hipEventCreateWithFlags(&c->ev_rad, hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
-    // (a HIGH-PRIORITY prologue stream was measured in round 2: whole frames with two frames in flight 1.78 -> 2.02 ms, one rank's 1/8 share
-    // 0.329 -> 0.335 ms: the priority queue breaks the overlap of the two frame streams.  Plain stream.)
-    if ((e = hipStreamCreateWithFlags(&c->pro, hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", e);
+    // (The frame prologue runs on `stream` too: context.h.  A HIGH-PRIORITY prologue stream was measured in round 2: whole frames with two frames in
+    // flight 1.78 -> 2.02 ms, one rank's 1/8 share 0.329 -> 0.335 ms: the priority queue breaks the overlap of the two frame streams.)
     for (int k = 0; k < RING; k++) {
         for (long long& v : c->order_key_ring[k]) v = -1;
         for (long long& v : c->lpt_key[k]) v = -1;
@@ -174,7 +176,6 @@ void csky_destroy(csky_ctx* c) {
     hipEvent_t evs[] = {c->ev0, c->ev1, c->ev_copy, c->ev_rad};
     for (hipEvent_t ev : evs) if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : c->kt_ev) if (ev) (void)hipEventDestroy(ev);
-    if (c->pro) (void)hipStreamDestroy(c->pro);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -404,14 +405,19 @@ int csky_set_schedule(csky_ctx* c, int mode) {
 int csky_set_frames_in_flight(csky_ctx* c, int frames) {
     if (!c) return fail(nullptr, CSKY_ERR_INVALID, "csky_set_frames_in_flight: ctx is NULL");
     if (frames < 1 || frames > RING) return fail(c, CSKY_ERR_INVALID, "csky_set_frames_in_flight: 1 .. 8 (the rings are eight deep)");
-    c->frames_in_flight = frames;
+    c->frames_in_flight = c->frames_overlapping = frames;
     c->warn[0] = 0;
     if (frames >= 2) {   // CSKY_OK, but never silent: without enough hardware queues the frames' streams share one and do not overlap (csky_last_warning)
         const char* q = getenv("GPU_MAX_HW_QUEUES");
         const int qn = q ? atoi(q) : 4;                         // the HIP runtime's default
-        if (qn < frames + 1)                                   // the frames' streams + the prologue stream
-            snprintf(c->warn, sizeof c->warn, "csky_set_frames_in_flight: GPU_MAX_HW_QUEUES is %s: %d streams of consecutive frames plus the prologue stream may share a hardware "
-                     "queue and not overlap; set it (16 is what libcloudsky sets at load time unless CSKY_NO_ENV=1) before the process's first HIP call", q ? q : "unset (4)", frames);
+        // a queue per frame stream, one for the context's stream (the prologue runs beside the marches) and one for the host's default stream, which
+        // a host that allocates or copies through HIP has used before the first frame.  Two frames at the default of four: enough (api.cpp, top)
+        if (qn < frames + 2) {
+            c->frames_overlapping = qn - 2 >= 2 ? qn - 2 : 1;   // what the launch policy plans for (clouds_dev): 1 = the forms that are fastest alone
+            snprintf(c->warn, sizeof c->warn, "csky_set_frames_in_flight: GPU_MAX_HW_QUEUES is %s: the %d streams of consecutive frames, the library's stream and the host's default "
+                     "stream need %d hardware queues or some of them share one and do not overlap (planning for %d); set it (16 is what libcloudsky sets at load time "
+                     "unless CSKY_NO_ENV=1) before the process's first HIP call", q ? q : "unset (4)", frames, frames + 2, c->frames_overlapping);
+        }
     }
     return CSKY_OK;
 }
@@ -460,7 +466,6 @@ const char* csky_variant_name(int v) { return cloud_variant_name(v); }
 int csky_sync(csky_ctx* c) {
     if (!c) return fail(nullptr, CSKY_ERR_INVALID, "csky_sync: ctx is NULL");
     int rc; if ((rc = bind(c))) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->pro));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return CSKY_OK;
 }
@@ -487,11 +492,11 @@ int csky_render_sky_lut_device(csky_ctx* c, const csky_sky_params* p, void* hip_
     const int w = (int)p->texture_size[0], h = (int)p->texture_size[1];
     if (w < 1 || h < 1 || w > 8192 || h > 8192) return fail(c, CSKY_ERR_INVALID, "csky_render_sky_lut: texture_size out of range");
     int rc; if ((rc = bind(c))) return rc;
-    (void)hip_stream;   // the LUT has no inputs of the caller's: it is rendered on the prologue stream and its consumers are ordered by events
-    if (!c->have_trans && (rc = render_trans_dev(c, 256, 64, c->pro))) return rc;   // transmittance_lut.gd:6 default size
+    (void)hip_stream;   // the LUT has no inputs of the caller's: it is rendered on the context's stream and its consumers are ordered by events
+    if (!c->have_trans && (rc = render_trans_dev(c, 256, 64, c->stream))) return rc;   // transmittance_lut.gd:6 default size
     if ((rc = ensure_sky(c, w, h))) return rc;
-    const int k = (c->have_sky && c->sky_in_memory) ? c->sky_cur ^ 1 : c->sky_cur;  // the other ring slot: frame set-ups still reading the current one are ahead on `pro`
-    HIPCHK(c, launch_sky_lut(w, h, p->sun_direction, c->d_trans_f, c->tw, c->th, c->sky_h_ring[k], c->sky_f_ring[k], c->pro, c->tlut));
+    const int k = (c->have_sky && c->sky_in_memory) ? c->sky_cur ^ 1 : c->sky_cur;  // the other ring slot: frame set-ups still reading the current one are ahead on `stream`
+    HIPCHK(c, launch_sky_lut(w, h, p->sun_direction, c->d_trans_f, c->tw, c->th, c->sky_h_ring[k], c->sky_f_ring[k], c->stream, c->tlut));
     c->sky_cur = k; c->d_sky_h = c->sky_h_ring[k]; c->d_sky_f = c->sky_f_ring[k];
     c->have_sky = true; c->sky_partial = false; c->sky_in_memory = true; c->lut_writers.clear();
     return CSKY_OK;
@@ -505,9 +510,9 @@ int csky_render_sky_lut_rows_device(csky_ctx* c, const csky_sky_params* p, int f
     const int n_rows = first_row < h ? (h - first_row + row_stride - 1) / row_stride : 0;
     if (capacity_bytes < (size_t)n_rows * w * 8) return fail(c, CSKY_ERR_INVALID, "csky_render_sky_lut_rows_device: %zu bytes given, %d rows of %d bytes needed", capacity_bytes, n_rows, w * 8);
     int rc; if ((rc = bind(c))) return rc;
-    if (!c->have_trans) {                                       // (rendered on the prologue stream: the caller's stream reads it)
-        if ((rc = render_trans_dev(c, 256, 64, c->pro))) return rc;
-        HIPCHK(c, hipStreamSynchronize(c->pro));
+    if (!c->have_trans) {                                       // (rendered on the context's stream: the caller's stream reads it)
+        if ((rc = render_trans_dev(c, 256, 64, c->stream))) return rc;
+        HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     // the rows have no consumer inside the library: they are rendered on the CALLER's stream, in order with the bands they travel with.
     // (Round 5 measured them on a side stream BESIDE the march that follows, joined behind it: a 1/8 share one frame at a time 0.409 -> 0.460 ms, eight
@@ -522,8 +527,8 @@ int csky_render_sky_lut_rows_device(csky_ctx* c, const csky_sky_params* p, int f
 int csky_render_sky_lut(csky_ctx* c, const csky_sky_params* p, uint16_t* out) {
     int rc = csky_render_sky_lut_device(c, p, nullptr);
     if (rc) return rc;
-    if (out) HIPCHK(c, hipMemcpyAsync(out, c->d_sky_h, (size_t)c->sw * c->sh * 8, hipMemcpyDeviceToHost, c->pro));
-    HIPCHK(c, hipStreamSynchronize(c->pro));
+    if (out) HIPCHK(c, hipMemcpyAsync(out, c->d_sky_h, (size_t)c->sw * c->sh * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return CSKY_OK;
 }
 
@@ -610,7 +615,7 @@ int csky_read_transmittance(csky_ctx* c, uint16_t* out, int* w, int* h) {
     if (!c->have_trans) return fail(c, CSKY_ERR_STATE, "csky_read_transmittance: LUT not rendered yet");
     int rc; if ((rc = bind(c))) return rc;
     if (w) *w = c->tw; if (h) *h = c->th;
-    if (out) { HIPCHK(c, hipStreamSynchronize(c->pro)); HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipMemcpy(out, c->d_trans_h, (size_t)c->tw * c->th * 8, hipMemcpyDeviceToHost)); }
+    if (out) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipMemcpy(out, c->d_trans_h, (size_t)c->tw * c->th * 8, hipMemcpyDeviceToHost)); }
     return CSKY_OK;
 }
 int csky_read_sky_lut(csky_ctx* c, uint16_t* out, int* w, int* h) {
@@ -620,7 +625,7 @@ int csky_read_sky_lut(csky_ctx* c, uint16_t* out, int* w, int* h) {
     int rc; if ((rc = bind(c))) return rc;
     if (w) *w = c->sw; if (h) *h = c->sh;
     if (out) {
-        HIPCHK(c, hipStreamSynchronize(c->pro));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
         for (hipEvent_t ev : c->lut_writers) HIPCHK(c, hipEventSynchronize(ev));       // rows written by the other devices of a csky_multi handle
         HIPCHK(c, hipMemcpy(out, c->d_sky_h, (size_t)c->sw * c->sh * 8, hipMemcpyDeviceToHost));
     }
@@ -711,11 +716,11 @@ int csky_copy_sky_lut_device(csky_ctx* c, void* d_out, void* hip_stream) {
     if (!c->sky_in_memory) return fail(c, CSKY_ERR_STATE, "csky_copy_sky_lut_device: the last LUT went to the caller as rows (csky_render_sky_lut_rows_device), this context holds none");
     int rc; if ((rc = bind(c))) return rc;
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    // the copy runs on the prologue stream right behind the LUT's render (a later render goes to the other ring slot and, like every
+    // the copy runs on the context's stream right behind the LUT's render (a later render goes to the other ring slot and, like every
     // writer of a slot, is queued behind this reader on the same stream); the caller's stream then waits for it
-    for (hipEvent_t ev : c->lut_writers) HIPCHK(c, hipStreamWaitEvent(c->pro, ev, 0));   // rows written by the other devices of a csky_multi handle
-    HIPCHK(c, hipMemcpyAsync(d_out, c->d_sky_h, (size_t)c->sw * c->sh * 8, hipMemcpyDeviceToDevice, c->pro));
-    HIPCHK(c, hipEventRecord(c->ev_copy, c->pro));
+    for (hipEvent_t ev : c->lut_writers) HIPCHK(c, hipStreamWaitEvent(c->stream, ev, 0));   // rows written by the other devices of a csky_multi handle
+    HIPCHK(c, hipMemcpyAsync(d_out, c->d_sky_h, (size_t)c->sw * c->sh * 8, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipEventRecord(c->ev_copy, c->stream));
     HIPCHK(c, hipStreamWaitEvent(s, c->ev_copy, 0));
     return CSKY_OK;
 }

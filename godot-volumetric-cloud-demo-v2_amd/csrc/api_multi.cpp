@@ -14,7 +14,8 @@ struct csky_multi {
     std::vector<csky_ctx*> ctx;
     std::vector<hipEvent_t> ev_done[MULTI_SLOTS];   // [frame slot][device]: its march (and staged copy) of that frame has finished
     hipEvent_t ev_begin[MULTI_SLOTS] = {};          // on the first device: the consumer stream's position when the frame was requested
-    std::vector<hipStream_t> side[RING - 1];        // frames in flight: the streams of a device's 2nd..4th frame in flight (the 1st: the context's own)
+    std::vector<hipStream_t> side[RING];            // [frame in flight][device]: the march streams of the devices behind the first (whose march runs on the consumer's stream);
+                                                    // never the context's own stream: the frame prologue runs there, beside the march (context.h)
     int fif = 1, groups = 1;              // frames in flight PER GROUP, frame groups (csky_multi_set_groups)
     unsigned long long frame_no = 0;
     bool staged = false;                  // CSKY_MULTI_STAGED=1 / csky_multi_set_staged: local band buffer + peer copy instead of in-place peer stores
@@ -70,7 +71,7 @@ int csky_multi_create(csky_multi** out, const int* device_ids, int n) {
             if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return bail(CSKY_ERR_HIP, "hipEventCreate", e);
             m->ev_done[sl].push_back(ev);
         }
-        for (int k = 0; k < RING - 1; k++) {
+        for (int k = 0; k < RING; k++) {
             hipStream_t st = nullptr;
             if ((e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking)) != hipSuccess) return bail(CSKY_ERR_HIP, "hipStreamCreate", e);
             m->side[k].push_back(st);
@@ -123,7 +124,7 @@ void csky_multi_destroy(csky_multi* m) {
         (void)hipSetDevice(m->ctx[i]->device);
         (void)hipDeviceSynchronize();
         for (int sl = 0; sl < MULTI_SLOTS; sl++) if (i < m->ev_done[sl].size() && m->ev_done[sl][i]) (void)hipEventDestroy(m->ev_done[sl][i]);
-        for (int k = 0; k < RING - 1; k++) if (i < m->side[k].size() && m->side[k][i]) (void)hipStreamDestroy(m->side[k][i]);
+        for (int k = 0; k < RING; k++) if (i < m->side[k].size() && m->side[k][i]) (void)hipStreamDestroy(m->side[k][i]);
         for (int k = 0; k < RING; k++) if (i < m->d_stage[k].size() && m->d_stage[k][i]) (void)hipFree(m->d_stage[k][i]);
         if (i < m->ev_lut.size() && m->ev_lut[i]) (void)hipEventDestroy(m->ev_lut[i]);
         for (int k = 0; k < 3; k++) if (i < m->tm[k].size() && m->tm[k][i]) (void)hipEventDestroy(m->tm[k][i]);
@@ -237,21 +238,21 @@ int csky_multi_render_sky_lut(csky_multi* m, const csky_sky_params* p) {
     csky_ctx* c0 = m->ctx[0];
     int rc;
     if (c0->d_sky_h && (c0->sw != w || c0->sh != h))            // a size change re-allocates the first device's LUT slots: no device may still be storing rows into them
-        for (int i = 0; i < n; i++) { if ((rc = bind(m->ctx[i]))) return mpass(m, i, rc); if (hipStreamSynchronize(m->ctx[i]->pro) != hipSuccess) return mfail(m, CSKY_ERR_HIP, "csky_multi_render_sky_lut: hipStreamSynchronize failed"); }
+        for (int i = 0; i < n; i++) { if ((rc = bind(m->ctx[i]))) return mpass(m, i, rc); if (hipStreamSynchronize(m->ctx[i]->stream) != hipSuccess) return mfail(m, CSKY_ERR_HIP, "csky_multi_render_sky_lut: hipStreamSynchronize failed"); }
     if ((rc = bind(c0))) return mpass(m, 0, rc);
     if ((rc = ensure_sky(c0, w, h))) return mpass(m, 0, rc);
     const int k = (c0->have_sky && c0->sky_in_memory) ? c0->sky_cur ^ 1 : c0->sky_cur;     // the other ring slot, as in csky_render_sky_lut_device
     // the readers of slot k (device copies of the LUT before last) sit on the first device's prologue stream: every writer queues behind them
-    if (hipEventRecord(m->ev_lut_begin, c0->pro) != hipSuccess) return mfail(m, CSKY_ERR_HIP, "csky_multi_render_sky_lut: hipEventRecord failed");
+    if (hipEventRecord(m->ev_lut_begin, c0->stream) != hipSuccess) return mfail(m, CSKY_ERR_HIP, "csky_multi_render_sky_lut: hipEventRecord failed");
     for (int i = 0; i < n; i++) {
         csky_ctx* c = m->ctx[i];
         if ((rc = bind(c))) return mpass(m, i, rc);
-        if (!c->have_trans && (rc = render_trans_dev(c, 256, 64, c->pro))) return mpass(m, i, rc);   // transmittance_lut.gd:6 default size
-        hipError_t e = i ? hipStreamWaitEvent(c->pro, m->ev_lut_begin, 0) : hipSuccess;
+        if (!c->have_trans && (rc = render_trans_dev(c, 256, 64, c->stream))) return mpass(m, i, rc);   // transmittance_lut.gd:6 default size
+        hipError_t e = i ? hipStreamWaitEvent(c->stream, m->ev_lut_begin, 0) : hipSuccess;
         // rows i, i + n, ... stored into the first device's LUT -- or, when some device cannot reach that memory, every row by the first device itself
         if (e == hipSuccess && (m->all_peer || i == 0))
-            e = launch_sky_lut_rows(w, h, m->all_peer ? i : 0, m->all_peer ? n : 1, p->sun_direction, c->d_trans_f, c->tw, c->th, reinterpret_cast<uint2*>(c0->sky_h_ring[k]), c0->sky_f_ring[k], c->pro, c->tlut);
-        if (e == hipSuccess) e = hipEventRecord(m->ev_lut[i], c->pro);
+            e = launch_sky_lut_rows(w, h, m->all_peer ? i : 0, m->all_peer ? n : 1, p->sun_direction, c->d_trans_f, c->tw, c->th, reinterpret_cast<uint2*>(c0->sky_h_ring[k]), c0->sky_f_ring[k], c->stream, c->tlut);
+        if (e == hipSuccess) e = hipEventRecord(m->ev_lut[i], c->stream);
         if (e != hipSuccess) return mfail(m, CSKY_ERR_HIP, "csky_multi_render_sky_lut: device index %d: %s", i, hipGetErrorString(e));
         for (int q = 0; q < 3; q++) c->sky_sun[q] = p->sun_direction[q];
         c->psw = w; c->psh = h; c->sky_partial = true; c->have_sky = true;
@@ -284,7 +285,7 @@ int csky_multi_render_clouds_device(csky_multi* m, const csky_cloud_params* p, i
         if ((rc = bind(c))) return mpass(m, i, rc);
         const int nb = k < total ? (total - k + per - 1) / per : 0;
         if (nb == 0) continue;
-        hipStream_t s = (i == 0) ? consumer : (dslot ? m->side[dslot - 1][i] : c->stream);
+        hipStream_t s = (i == 0) ? consumer : m->side[dslot][i];
         if (i != 0 && hipStreamWaitEvent(s, m->ev_begin[slot], 0) != hipSuccess) return mfail(m, CSKY_ERR_HIP, "csky_multi_render_clouds_device: hipStreamWaitEvent failed");
         const csky_bands b = {8, k, per, nb};
         const bool tmg = m->timing && m->tm[0][i];
@@ -388,7 +389,7 @@ int csky_multi_sync(csky_multi* m) {
     if (!m) return mfail(nullptr, CSKY_ERR_INVALID, "csky_multi_sync: handle is NULL");
     for (size_t i = 0; i < m->ctx.size(); i++) {
         const int rc = csky_sync(m->ctx[i]); if (rc) return mpass(m, (int)i, rc);
-        for (int k = 0; k < RING - 1; k++)                     // the streams of a device's 2nd..4th frame in flight
+        for (int k = 0; k < RING; k++)                         // the march streams of a device's frames in flight
             if (hipStreamSynchronize(m->side[k][i]) != hipSuccess) return mfail(m, CSKY_ERR_HIP, "csky_multi_sync: hipStreamSynchronize failed on device index %d", (int)i);
     }
     return CSKY_OK;

@@ -1,4 +1,4 @@
-// clouds_launch.cpp -- one launch of the cloud kernel (clouds_dev): frame set-up on the prologue stream, the workgroup order of the launch
+// clouds_launch.cpp -- one launch of the cloud kernel (clouds_dev): frame set-up on the context's stream, the workgroup order of the launch
 // (static tables, cost feedback), per-launch timing events, and the launch itself.  Which kernel runs and how is launch_policy.h's decision.
 #include <cstring>
 #include "context.h"
@@ -50,7 +50,7 @@ int ensure_order(csky_ctx* c, int slot, int mode, int tile_w, int tiles_x, int s
             for (long long& v : c->order_key_ring[k]) v = -1;
         }
     }
-    // the last reader of this slot's table is the march of two frames ago; the caller has already ordered `s` behind it (ev_clouds -> pro ->
+    // the last reader of this slot's table is the march of two frames ago; the caller has already ordered `s` behind it (ev_clouds -> the context's stream ->
     // ev_setup -> s), exactly like the frame constants of the slot
     HIPCHK(c, launch_static_order(mode, tiles_x, slabs, grid, c->d_order_ring[slot], s));
     c->order_grid_ring[slot] = grid;
@@ -99,16 +99,16 @@ int clouds_dev(csky_ctx* c, const csky_cloud_params* p, int tile_w, const csky_b
             c->win_cov = cp.cloud_coverage;
         }
         const float lo = c->use_window ? c->win_lo : -1.0f, hi = c->use_window ? c->win_hi : 2.0f;
-        // frame set-up on the prologue stream into the other constants slot (its last reader, the march two frames ago, must be done)
+        // frame set-up on the context's stream (beside the caller's: context.h) into the other constants slot (its last reader, the march two frames ago, must be done)
         const int f = (c->fc_cur + 1) % RING;
-        if (c->clouds_pending[f]) HIPCHK(c, hipStreamWaitEvent(c->pro, c->ev_clouds[f], 0));
+        if (c->clouds_pending[f]) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_clouds[f], 0));
         // cloud-type range of the weather map (texel values 0..255): all >= 128 or all <= 127 fixes the branch of the height gradient
         const int ctm = !c->use_window ? 0 : (c->w_rmin * 255.0 >= 127.5 ? 1 : (c->w_rmax * 255.0 <= 127.5 ? 2 : 0));
         if (c->sky_partial)                              // no LUT in memory: the set-up renders the texels of its three taps (clouds.glsl:163-167) itself
-            HIPCHK(c, launch_frame_setup_taps(cp, c->sky_sun, c->d_trans_f, c->tw, c->th, c->psw, c->psh, c->primary_steps, c->light_steps, c->early_eps, lo, hi, ctm, c->use_window ? 1 : 0, c->fc_ring[f], c->pro, c->tlut));
+            HIPCHK(c, launch_frame_setup_taps(cp, c->sky_sun, c->d_trans_f, c->tw, c->th, c->psw, c->psh, c->primary_steps, c->light_steps, c->early_eps, lo, hi, ctm, c->use_window ? 1 : 0, c->fc_ring[f], c->stream, c->tlut));
         else
-            HIPCHK(c, launch_frame_setup(cp, c->d_sky_f, c->sw, c->sh, c->primary_steps, c->light_steps, c->early_eps, lo, hi, ctm, c->use_window ? 1 : 0, c->fc_ring[f], c->pro));
-        HIPCHK(c, hipEventRecord(c->ev_setup[f], c->pro));
+            HIPCHK(c, launch_frame_setup(cp, c->d_sky_f, c->sw, c->sh, c->primary_steps, c->light_steps, c->early_eps, lo, hi, ctm, c->use_window ? 1 : 0, c->fc_ring[f], c->stream));
+        HIPCHK(c, hipEventRecord(c->ev_setup[f], c->stream));
         c->fc_cur = f; c->d_fc = c->fc_ring[f];
         // (Round 5 bounded what folding the set-up INTO the march launch could return by simply not waiting here -- legal in a timing run with constant
         // parameters: whole frame one at a time 2.014 -> 2.000 ms, a 1/8 share 0.408 -> 0.404, eight in flight 0.224 -> 0.227: the prologue of frame k + 1
@@ -118,7 +118,9 @@ int clouds_dev(csky_ctx* c, const csky_cloud_params* p, int tile_w, const csky_b
     RenderGeom g; g.tile_w = tile_w; g.band_rows = b->band_rows; g.first_band = b->first_band; g.band_stride = b->band_stride; g.n_bands = b->n_bands;
     g.pitch_px = (uint32_t)(pitch_bytes / 8); g.out_full = out_full ? 1 : 0;
     const long long waves = ((long long)(tile_w + 7) / 8) * (((long long)b->n_bands * b->band_rows + 7) / 8);
-    const LaunchPlan pl = plan_launch({c->variant, c->cell32, c->segments, c->sched_mode, c->frames_in_flight, c->persistent}, waves);
+    // the policy is told how many frames CAN overlap (csky_set_frames_in_flight): where the hardware queues cannot keep the frames' streams apart the launches
+    // run one after the other, and the forms chosen for overlapping launches (the persistent one above all) are the slower ones alone
+    const LaunchPlan pl = plan_launch({c->variant, c->cell32, c->segments, c->sched_mode, c->frames_overlapping, c->persistent}, waves);
     const int tiles_x = (g.tile_w + pl.bw - 1) / pl.bw, slabs = (g.n_bands * g.band_rows + 7) >> 3, nblocks = tiles_x * slabs;
     const int slot = c->fc_cur;
     uint32_t* const heads = pl.persist ? c->d_heads + slot * 16 : nullptr;

@@ -16,6 +16,11 @@ constexpr int HOST_RING = 8;   // pinned host frames of the asynchronous host fo
 
 struct csky_ctx {
     int device = 0;
+    // The context's ONE stream: loads and bakes, the LUTs, the frame prologue (below), the blocking host forms, and what a NULL hip_stream selects.
+    // One and not two (until round 11 the prologue had a stream of its own): the HIP runtime spreads a process's streams over GPU_MAX_HW_QUEUES
+    // hardware queues, four by default, and a stream that has been used keeps its share of one for good.  With two internal streams, the host's
+    // default stream and two frame streams, the second frame stream landed on the first one's queue and two frames in flight ran strictly one
+    // after the other (profiles/r11/queue_overlap_ab.txt); with one, the four queues go round.
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_copy = nullptr;
     // noise set (cloud_sky.gd:298-341)
@@ -35,11 +40,11 @@ struct csky_ctx {
     csky::FrameConsts* d_fc = nullptr;                                                                    // = ring slot fc_cur
     // Frame prologue pipeline.  The sky LUT and the frame set-up of frame k+1 are small dependent kernels; enqueued behind the
     // cloud kernel of frame k they cost their run time plus two launch gaps per frame (6 % of one GPU's 1/8-frame share).  They
-    // run on the context's own prologue stream instead, into the next slot of a ring (the sky LUT two deep: every reader of it runs on `pro`;
-    // the frame constants RING deep: the marches of up to RING frames in flight read them) (the reference keeps three-deep
-    // texture rings for the same reason, sky_lut.gd:143-146), so they overlap the march of the previous frame; events order
-    // set-up -> clouds (ev_setup) and clouds -> the next writer of that slot (ev_clouds).  All sky-LUT readers run on `pro`.
-    hipStream_t pro = nullptr;
+    // run on the context's own stream (`stream`, above) instead, beside the caller's, into the next slot of a ring (the sky LUT two deep: every
+    // reader of it runs on `stream`; the frame constants RING deep: the marches of up to RING frames in flight read them) (the reference keeps
+    // three-deep texture rings for the same reason, sky_lut.gd:143-146), so they overlap the march of the previous frame; events order
+    // set-up -> clouds (ev_setup) and clouds -> the next writer of that slot (ev_clouds).  All sky-LUT readers run on `stream`.
+    // A march that itself runs on `stream` (NULL hip_stream, the blocking host forms) has its prologue in line with it: nothing overlaps there.
     uint16_t* sky_h_ring[2] = {nullptr, nullptr}; float4* sky_f_ring[2] = {nullptr, nullptr}; int sky_cur = 0;
     // csky_render_sky_lut_rows_device: the LUT of sun sky_sun exists only as the rows the caller's buffer received (one rank of an N-way frame
     // split); the texels this context's frame set-up filters are rendered by the set-up kernel itself (clouds_dev)
@@ -56,7 +61,8 @@ struct csky_ctx {
     int variant = CSKY_DEFAULT_VARIANT;
     int sched_mode = -1;                              // -1 = auto (5 for large launches, 2 for small ones)
     int segments = 0;                                 // ray segments per ray: 0 = auto, 1, 2, 4
-    int frames_in_flight = 1;                         // policy hint (csky_set_frames_in_flight): the caller alternates that many streams
+    int frames_in_flight = 1;                         // csky_set_frames_in_flight: the caller alternates that many streams
+    int frames_overlapping = 1;                       // how many of them the hardware queues in effect can keep apart: the launch policy's hint (clouds_dev)
     // static workgroup order (physical workgroup -> slab), written on the device, one table per ring slot (= frame parity, so two
     // frames in flight with different geometries never share one), cached per launch geometry
     uint32_t* d_order_ring[RING] = {}; size_t order_cap[RING] = {}; int order_grid_ring[RING] = {};
