@@ -185,7 +185,7 @@ static int set_noise_impl(csky_ctx* c, const uint8_t* large_rgba8, const uint8_t
     if (!large_rgba8 || !small_rgb8 || !weather_rgb8) return fail(c, CSKY_ERR_INVALID, "csky_set_noise: NULL texture pointer");
     int rc; if ((rc = bind(c))) return rc;
     // The level-0 textures go to the device as they are (9.2 MB); mip chains (mipmaps/generate=true, perlworlnoise.tga.import:24,
-    // worlnoise.bmp.import:24) and the device layouts are built there (kernels.hip::launch_mip_chain / launch_bake).
+    // worlnoise.bmp.import:24) and the device layouts are built there (bake_kernels.hip::launch_mip_chain / launch_bake).
     const size_t large_l0 = (size_t)SHAPE_N * SHAPE_N * SHAPE_N * 4, small_l0 = (size_t)DETAIL_N * DETAIL_N * DETAIL_N * 3, weather_b = (size_t)WEATHER_N * WEATHER_N * 3;
     const size_t large_chain = chain_offset(SHAPE_N, SHAPE_LEVELS, 4), small_chain = chain_offset(DETAIL_N, DETAIL_LEVELS, 3);
     size_t shape_total = 0, detail_total = 0;

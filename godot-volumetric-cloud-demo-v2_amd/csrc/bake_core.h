@@ -1,5 +1,5 @@
 // bake_core.h -- one texel of each device texture layout (csky_common.h) from the 8-bit mip chains, host+device:
-// the GPU bake kernels (kernels.hip) and the host loops of bake.h (tests/hostsim) run the same code, so the two bakes are
+// the GPU bake kernels (bake_kernels.hip) and the host loops of bake.h (tests/hostsim) run the same code, so the two bakes are
 // byte-identical by construction (and tests/test_gpu_round2.py compares them).  Also the 2x2x2 box mip (Godot's
 // mipmaps/generate=true on 3-D textures, perlworlnoise.tga.import:24 / worlnoise.bmp.import:24, as (sum + 4) >> 3).
 #pragma once

@@ -177,7 +177,7 @@ CSKY_HD void sky_lut_tap(const float4* sky, int w, int h, float sx, float sy, fl
     sky_lut_tap_f([sky, w](int, int x, int y) { return sky[y * w + x]; }, w, h, sx, sy, out);
 }
 // where the frame set-up samples the sky LUT (clouds.glsl:163,164,166): tap 0 = towards the light (unnormalised direction), 1 / 2 = 45 degrees
-// above / below the horizon.  One place for frame_setup and for the kernel that renders just those texels (kernels.hip frame_setup_taps_kernel).
+// above / below the horizon.  One place for frame_setup and for the kernel that renders just those texels (lut_kernels.hip frame_setup_taps_kernel).
 CSKY_HD void frame_setup_tap_uv(const float light[3], int tap, float& sx, float& sy) {
     const float inv = 1.0f / sqrtf(1.0f * 1.0f + 1.0f * 1.0f + 0.0f * 0.0f);               // normalize(vec3(1,+-1,0))
     if (tap == 0) { sx = sky_lut_uv_x(light[2], light[0]); sy = sky_lut_uv_y(light[1]); }
@@ -220,7 +220,7 @@ template <class Fetch> CSKY_HD void frame_setup_f(const CloudParams& P, Fetch fe
     fc.primary_steps = primary_steps; fc.light_steps = light_steps; fc.steps_f = (float)primary_steps;
     fc.early_eps = early_eps;
     fc.hf_lo = hf_lo; fc.hf_hi = hf_hi;
-    fc.ct_mode = 0;                   // set by the caller that knows the weather map's range (clouds_launch.cpp::clouds_dev; kernels.hip frame_setup_kernel)
+    fc.ct_mode = 0;                   // set by the caller that knows the weather map's range (clouds_launch.cpp::clouds_dev fills SetupArgs; lut_kernels.hip store_frame_consts)
     // The saturation skip (ray_saturated, section B) is proved for frames whose light, ambient and ground colours are finite and >= 0, whose density is
     // >= 0 (every step transmittance dt = exp(-density t ss) <= 1) and whose march is at most 65536 steps long (the slop terms below are first order
     // in steps * 2^-24).  A push-constant block that breaks one of these (a negative ground or light colour) marks the frame and is marched in full.
@@ -647,7 +647,7 @@ CSKY_HD void shade_sample(const FrameConsts& fc, float phase, float t, float hf,
 }
 
 // ---- EXACT reject (4), the saturation skip: a ray whose STORED pixel can no longer change needs no further light march ------------------
-// The frame is stored as four halfs f2h(L.rgb), f2h(sat(alpha)) (kernels.hip render_block).  Let u = 2^-24 and n <= primary_steps the number
+// The frame is stored as four halfs f2h(L.rgb), f2h(sat(alpha)) (cloud_kernels.hip render_block).  Let u = 2^-24 and n <= primary_steps the number
 // of in-cloud samples the ray may still composite, (T, alpha, L) its running state now, in fp32 as computed.  Assumptions, all checked by
 // frame_setup_f (fc.sat_skip) or true by construction:
 //   (a) gnd_c, amb_c, sun_c >= 0 and finite; phase >= 0 (max of three Henyey-Greenstein values, the one with g = 0.6 is > 0; a NaN or infinite
@@ -673,7 +673,7 @@ CSKY_HD void shade_sample(const FrameConsts& fc, float phase, float t, float hf,
 // Both tests true => leaving out every later in-cloud sample of the ray stores the same four halfs.  The march still takes the ray's primary samples:
 // the in-cloud tally counts t > 0 and is part of the contract.  Headline view, coverage 0.2: 16 % of the rays fire, 9.4 % of the in-cloud samples fall
 // behind the firing (0.35: 27 %, 0.5: 43 %; tests/test_saturation_skip.py walks them and requires zero differing halfs).
-// Used by march_compact for whole-ray marches of the fp16-pair texture set only (kernels.hip); march() below and every other variant take all samples.
+// Used by march_compact for whole-ray marches of the fp16-pair texture set only (cloud_kernels.hip); march() below and every other variant take all samples.
 constexpr float SAT_ALPHA_MIN = 1.0f - 0.000244140625f;       // 1 - 2^-12
 constexpr float SAT_BEERS_MAX = 0.7699f;                      // > 4 / (3 sqrt 3)
 // the half a value is stored as, for 2^-14 <= x < 65520 (normal halfs, where v_cvt_f16_f32 in the default round-to-nearest-even mode is f2h whatever the

@@ -1,367 +1,23 @@
-// kernels.hip -- gfx950 (CDNA4, wave64) kernels of libcloudsky.
+// cloud_kernels.hip -- gfx950 (CDNA4, wave64) kernels of clouds.glsl main(): one ray per lane, one 8x8-pixel tile per wavefront.
 //
-//   transmittance_kernel : transmittance-lut.glsl, one texel per wavefront, 40 steps on 40 lanes   (16 384 wavefronts, once)
-//   sky_lut_kernel       : sky-lut.glsl, one texel per half wavefront, 30 steps on 30 lanes       (20 000 texels, per sun change)
-//   frame_setup_kernel   : the ray-invariant prologue of clouds.glsl march()          (1 lane, per frame)
-//   clouds_kernel        : clouds.glsl main(): one ray per lane, one 8x8-pixel tile per wavefront
+//   march_queue / march_compact / march_interleaved : the wave-cooperative marches (the lock-step one is cloud_core.h march())
+//   render_block, clouds_kernel<VARIANT, SEG, TS>   : a workgroup footprint of 4 / SEG tiles; <3, 1, TexSet> is the product's kernel
+//   clouds_kernel_persistent                        : the same as a launch the size of the chip that pops footprints from the order
+//   clouds_kernel_lds / clouds_kernel_interleaved   : measured alternatives (variant 2, segments 5)
+//   lpt_*_kernel, static_order_kernel               : the launch orders
+//   interleave_bands_kernel, sqrt_shell_kernel      : the band interleave of a gathered frame (what becomes of the bands these kernels
+//                                                     write when N ranks split a frame) and the test hook of cloud_core.h::sqrt_shell
 //
 // No MFMA anywhere: the path is fetch/latency-bound gather + fp32 VALU, not a contraction.
+// What was built here, measured and removed again is recorded in docs/EXPERIMENTS.md §5.
 #include <hip/hip_runtime.h>
 #include "kernels.h"
 #include "cloud_core.h"
-#include "lut_core.h"
-#include "composite_core.h"
-#include "noise_core.h"
-#include "bake_core.h"
+// FP contraction OFF for the code of this file, like section A of cloud_core.h: what a march adds and multiplies itself (the phase value's dot product,
+// the segments' compositing sums) rounds as written.  Stated here because otherwise the last header decides it, and cloud_core.h ends with contraction on.
+#pragma clang fp contract(off)
 
 namespace csky {
-
-// ------------------------------------------------------------------------------------------------ LUTs
-// transmittance-lut.glsl: one texel per wavefront: lanes 0..39 evaluate the 40 optical-depth steps in parallel (each ~150 VALU with five
-// correctly rounded transcendentals, independent of the others), park extinction * dt in LDS, then lane 0 replays the sum in the reference's
-// order (T:186-192; bit-identical to the one-lane-per-texel form, 40x shorter critical path).  Round 1 had the GLSL's own dispatch shape here
-// (8x8 groups, one texel per lane, a 40-step serial loop: 2 048 one-wave groups on 6 % of the chip).
-// TLUT: the table's parametrization (tlut_core.h), one instantiation per mapping (here and in the sky-LUT, set-up and compositor kernels below).
-template <int TLUT> __global__ __launch_bounds__(256) void transmittance_kernel(int w, int h, uint16_t* __restrict__ out_h, float4* __restrict__ out_f) {
-    __shared__ float terms[4][TRANSMITTANCE_STEPS][4];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int texel = blockIdx.x * 4 + wave;
-    const bool live = texel < w * h;                              // (T:159 tests `>`; the extra row/column would be an out-of-image store)
-    const int px = live ? texel % w : 0, py = live ? texel / w : 0;
-    const TransRay r = transmittance_ray<TLUT>(px, py, (float)w, (float)h);
-    if (lane < TRANSMITTANCE_STEPS) {
-        const F4 e = transmittance_step(r, lane);
-        float* d = terms[wave][lane];
-        d[0] = e.x; d[1] = e.y; d[2] = e.z; d[3] = e.w;
-    }
-    __syncthreads();
-    if (lane == 0 && live) {
-        F4 result = f4(0, 0, 0, 0);
-        for (int i = 0; i < TRANSMITTANCE_STEPS; ++i) { const float* d = terms[wave][i]; result = result + f4(d[0], d[1], d[2], d[3]); }
-        const F4 t = transmittance_finish(result);
-        const uint16_t hx = f2h(t.x), hy = f2h(t.y), hz = f2h(t.z), hw = f2h(t.w);
-        reinterpret_cast<uint2*>(out_h)[texel] = make_uint2((uint32_t)hx | ((uint32_t)hy << 16), (uint32_t)hz | ((uint32_t)hw << 16));
-        out_f[texel] = make_float4(h2f(hx), h2f(hy), h2f(hz), h2f(hw));
-    }
-}
-
-struct Sun3 { float v[3]; };
-// sky-lut.glsl: one texel per HALF wavefront: lanes 0..29 evaluate the 30 in-scattering steps in parallel (each step is
-// ~600 VALU with 20 LUT loads and 12 transcendentals and independent of the others), park source term + transmittance
-// in LDS, then lane 0 of the half replays the front-to-back accumulation in the reference's order (bit-identical to the
-// one-lane-per-texel form, 4x shorter critical path: this kernel sits on the critical path of every frame).
-// One texel; store(px, py, hx, hy, hz, hw) takes the four fp16 values (lane 0 of the half wavefront, live texels only).
-template <int TLUT, class Store> __device__ __forceinline__ void sky_texel(float (*steps)[8], int sub, bool live, int px, int py, int w, int h, const Sun3& sun,
-                                                                 const float4* __restrict__ trans, int tw, int th, Store store) {
-    const SkyRay r = sky_ray(px, py, (float)w, (float)h, sun.v);
-    if (sub < IN_SCATTERING_STEPS) {
-        const SkyStep s = sky_step<TLUT>(r, sub, trans, tw, th);
-        float* d = steps[sub];
-        d[0] = s.S_int.x; d[1] = s.S_int.y; d[2] = s.S_int.z; d[3] = s.S_int.w;
-        d[4] = s.step_tr.x; d[5] = s.step_tr.y; d[6] = s.step_tr.z; d[7] = s.step_tr.w;
-    }
-    __syncthreads();
-    if (sub == 0 && live) {
-        F4 L = f4(0, 0, 0, 0), Tr = f4(1, 1, 1, 1);
-        for (int i = 0; i < IN_SCATTERING_STEPS; ++i) {
-            const float* d = steps[i];
-            SkyStep s; s.S_int = f4(d[0], d[1], d[2], d[3]); s.step_tr = f4(d[4], d[5], d[6], d[7]);
-            sky_accumulate(L, Tr, s);
-        }
-        const F4 c = sky_output(L);
-        store(px, py, f2h(c.x), f2h(c.y), f2h(c.z), f2h(c.w));
-    }
-}
-__device__ __forceinline__ uint2 pack_half4(uint16_t hx, uint16_t hy, uint16_t hz, uint16_t hw) {
-    return make_uint2((uint32_t)hx | ((uint32_t)hy << 16), (uint32_t)hz | ((uint32_t)hw << 16));
-}
-template <int TLUT> __global__ __launch_bounds__(256) void sky_lut_kernel(int w, int h, Sun3 sun, const float4* __restrict__ trans, int tw, int th,
-                                                     uint16_t* __restrict__ out_h, float4* __restrict__ out_f) {
-    __shared__ float steps[8][IN_SCATTERING_STEPS][8];
-    const int half = threadIdx.x >> 5, sub = threadIdx.x & 31;
-    const int texel = blockIdx.x * 8 + half;                      // rows 100..103 of the reference dispatch are discarded stores (S:281)
-    const bool live = texel < w * h;
-    const int px = live ? texel % w : 0, py = live ? texel / w : 0;
-    sky_texel<TLUT>(steps[half], sub, live, px, py, w, h, sun, trans, tw, th, [=](int x, int y, uint16_t hx, uint16_t hy, uint16_t hz, uint16_t hw) {
-        reinterpret_cast<uint2*>(out_h)[y * w + x] = pack_half4(hx, hy, hz, hw);
-        out_f[y * w + x] = make_float4(h2f(hx), h2f(hy), h2f(hz), h2f(hw));
-    });
-}
-// One rank's rows of the LUT when N ranks / devices split a frame: rows row0, row0 + row_stride, ... (n_rows of them).  out_f == nullptr
-// (csky_render_sky_lut_rows_device): stored COMPACT and as RGBA16F only, straight into the buffer that travels to the gathering rank with the
-// rank's bands.  out_f != nullptr (csky_multi_render_sky_lut): stored at the texel's own place in the whole LUT (half + float copies) of the
-// handle's first device, over xGMI peer access, like the frame's bands.
-template <int TLUT> __global__ __launch_bounds__(256) void sky_lut_rows_kernel(int w, int h, int row0, int row_stride, int n_rows, Sun3 sun, const float4* __restrict__ trans,
-                                                          int tw, int th, uint2* __restrict__ out_h, float4* __restrict__ out_f) {
-    __shared__ float steps[8][IN_SCATTERING_STEPS][8];
-    const int half = threadIdx.x >> 5, sub = threadIdx.x & 31;
-    const int t = blockIdx.x * 8 + half;
-    const bool live = t < w * n_rows;
-    const int px = live ? t % w : 0, py = live ? row0 + (t / w) * row_stride : 0;
-    sky_texel<TLUT>(steps[half], sub, live, px, py, w, h, sun, trans, tw, th, [=](int x, int y, uint16_t hx, uint16_t hy, uint16_t hz, uint16_t hw) {
-        if (out_f) { out_h[y * w + x] = pack_half4(hx, hy, hz, hw); out_f[y * w + x] = make_float4(h2f(hx), h2f(hy), h2f(hz), h2f(hw)); }
-        else out_h[t] = pack_half4(hx, hy, hz, hw);
-    });
-}
-
-hipError_t launch_transmittance(int w, int h, uint16_t* d_half, float4* d_float, hipStream_t s, int tlut) {
-    if (tlut == TLUT_BRUNETON) transmittance_kernel<TLUT_BRUNETON><<<(w * h + 3) / 4, 256, 0, s>>>(w, h, d_half, d_float);
-    else transmittance_kernel<TLUT_REFERENCE><<<(w * h + 3) / 4, 256, 0, s>>>(w, h, d_half, d_float);
-    return hipGetLastError();
-}
-hipError_t launch_sky_lut(int w, int h, const float sun[3], const float4* d_trans, int tw, int th, uint16_t* d_half, float4* d_float,
-                          hipStream_t s, int tlut) {
-    Sun3 sv; sv.v[0] = sun[0]; sv.v[1] = sun[1]; sv.v[2] = sun[2];
-    if (tlut == TLUT_BRUNETON) sky_lut_kernel<TLUT_BRUNETON><<<(w * h + 7) / 8, 256, 0, s>>>(w, h, sv, d_trans, tw, th, d_half, d_float);
-    else sky_lut_kernel<TLUT_REFERENCE><<<(w * h + 7) / 8, 256, 0, s>>>(w, h, sv, d_trans, tw, th, d_half, d_float);
-    return hipGetLastError();
-}
-hipError_t launch_sky_lut_rows(int w, int h, int row0, int row_stride, const float sun[3], const float4* d_trans, int tw, int th, uint2* d_rows, float4* d_whole_f,
-                               hipStream_t s, int tlut) {
-    Sun3 sv; sv.v[0] = sun[0]; sv.v[1] = sun[1]; sv.v[2] = sun[2];
-    const int n_rows = row0 < h ? (h - row0 + row_stride - 1) / row_stride : 0;
-    if (n_rows && tlut == TLUT_BRUNETON) sky_lut_rows_kernel<TLUT_BRUNETON><<<(w * n_rows + 7) / 8, 256, 0, s>>>(w, h, row0, row_stride, n_rows, sv, d_trans, tw, th, d_rows, d_whole_f);
-    else if (n_rows) sky_lut_rows_kernel<TLUT_REFERENCE><<<(w * n_rows + 7) / 8, 256, 0, s>>>(w, h, row0, row_stride, n_rows, sv, d_trans, tw, th, d_rows, d_whole_f);
-    return hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------------------ band interleave (gathering rank, N > 1)
-// The gather leaves rank-major compact bands ([member][local band][rows]); the frame wants band k = member k % n, local band k / n.  A plain
-// strided copy, deliberately on FEW workgroups: it is HBM-bound (32 MiB per 2048x1024 frame) beside marches that are not, so 48 workgroups
-// streaming 16-byte chunks take it off the critical path instead of sweeping the whole chip for 15 us per frame (torch's permute + copy).
-__global__ __launch_bounds__(256) void interleave_bands_kernel(const uint4* __restrict__ src, size_t member_stride16, int members, uint32_t band16, uint32_t total_bands,
-                                                              uint4* __restrict__ dst) {
-    const size_t total = (size_t)band16 * total_bands;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const uint32_t k = (uint32_t)(i / band16), c = (uint32_t)(i - (size_t)k * band16);
-        dst[i] = src[(size_t)(k % members) * member_stride16 + (size_t)(k / members) * band16 + c];
-    }
-}
-hipError_t launch_interleave_bands(const void* d_gathered, size_t member_stride_bytes, int members, size_t band_bytes, int total_bands, void* d_frame, hipStream_t s) {
-    const size_t chunks = band_bytes / 16 * (size_t)total_bands;
-    if (!chunks) return hipSuccess;
-    const unsigned grid = (unsigned)(chunks / 256 + 1 < 48 ? chunks / 256 + 1 : 48);
-    interleave_bands_kernel<<<grid, 256, 0, s>>>(reinterpret_cast<const uint4*>(d_gathered), member_stride_bytes / 16, members, (uint32_t)(band_bytes / 16), (uint32_t)total_bands,
-                                                 reinterpret_cast<uint4*>(d_frame));
-    return hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------------------ shape-noise bake
-// The stand-in 128^3 RGBA shape volume, one voxel per lane (bit-identical to the host generator: noise_core.h).
-__global__ __launch_bounds__(256) void shape_noise_kernel(uint32_t seed, int n, ShapeNoiseParams P, uint32_t* __restrict__ out) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (size_t)n * n * n) return;
-    const int x = (int)(i % n), y = (int)((i / n) % n), z = (int)(i / ((size_t)n * n));
-    uint8_t o[4];
-    shape_voxel(seed, n, x, y, z, P, o);
-    out[i] = (uint32_t)o[0] | ((uint32_t)o[1] << 8) | ((uint32_t)o[2] << 16) | ((uint32_t)o[3] << 24);
-}
-hipError_t launch_shape_noise(uint32_t seed, int n, const ShapeNoiseParams& P, uint32_t* d_out, hipStream_t s) {
-    const size_t total = (size_t)n * n * n;
-    shape_noise_kernel<<<(unsigned)((total + 255) / 256), 256, 0, s>>>(seed, n, P, d_out);
-    return hipGetLastError();
-}
-
-// the 32^3 RGB detail volume (noise_core.h::detail_voxel), one voxel per lane, 3 bytes each
-__global__ __launch_bounds__(256) void detail_noise_kernel(uint32_t seed, int n, uint8_t* __restrict__ out) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (size_t)n * n * n) return;
-    const int x = (int)(i % n), y = (int)((i / n) % n), z = (int)(i / ((size_t)n * n));
-    uint8_t o[3];
-    detail_voxel(seed, n, x, y, z, o);
-    out[3 * i] = o[0]; out[3 * i + 1] = o[1]; out[3 * i + 2] = o[2];
-}
-hipError_t launch_detail_noise(uint32_t seed, int n, uint8_t* d_out, hipStream_t s) {
-    const size_t total = (size_t)n * n * n;
-    detail_noise_kernel<<<(unsigned)((total + 255) / 256), 256, 0, s>>>(seed, n, d_out);
-    return hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------------------ mip chains + texture bake on the device
-// csky_set_noise uploads the three 8-bit level-0 textures (9.2 MB) and does everything else here: 2x2x2 box mips (Godot's
-// mipmaps/generate=true), then one lane per texel of each device layout (bake_core.h: the same per-texel code as the host bake of
-// tests/hostsim, byte-identical).  Replaces ~1.5 s of host loops + 78 MB of pageable uploads per csky_set_noise by < 1 ms of kernels.
-__global__ __launch_bounds__(256) void mip_level_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int nd, int ch) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, total = (size_t)nd * nd * nd * ch;
-    if (i >= total) return;
-    const int c = (int)(i % ch); const size_t t = i / ch;
-    const int x = (int)(t % nd), y = (int)((t / nd) % nd), z = (int)(t / ((size_t)nd * nd));
-    dst[i] = mip_texel(src, nd * 2, ch, x, y, z, c);
-}
-hipError_t launch_mip_chain(uint8_t* d_chain, int n, int ch, int levels, hipStream_t s) {
-    for (int l = 1; l < levels; l++) {
-        const int nd = n >> l;
-        const size_t total = (size_t)nd * nd * nd * ch;
-        mip_level_kernel<<<(unsigned)((total + 255) / 256), 256, 0, s>>>(d_chain + chain_offset(n, l - 1, ch), d_chain + chain_offset(n, l, ch), nd, ch);
-    }
-    return hipGetLastError();
-}
-__device__ __forceinline__ void bake_tally(unsigned bad, unsigned long long* __restrict__ inexact) {
-    for (int off = 32; off > 0; off >>= 1) bad += __shfl_down(bad, off);
-    if ((threadIdx.x & 63) == 0 && bad) atomicAdd(inexact, (unsigned long long)bad);
-}
-template <int N, int LEVELS> __device__ __forceinline__ bool level_of(size_t i, int& l, int& n, size_t& local) {
-    size_t base = 0;
-    for (l = 0; l < LEVELS; l++) { n = N >> l; const size_t cnt = (size_t)n * n * n; if (i < base + cnt) { local = i - base; return true; } base += cnt; }
-    return false;
-}
-__global__ __launch_bounds__(256) void bake_shape_kernel(const uint8_t* __restrict__ chain, ShapeTexel* __restrict__ out, unsigned long long* __restrict__ inexact) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    int l, n; size_t local; unsigned bad = 0;
-    if (level_of<SHAPE_N, SHAPE_LEVELS>(i, l, n, local)) {
-        const int x = (int)(local % n), y = (int)((local / n) % n), z = (int)(local / ((size_t)n * n));
-        out[(i - local) + shape_cell_index(n, x, y, z)] = bake_shape_texel(chain + chain_offset(SHAPE_N, l, 4), n, x, y, z, bad);
-    }
-    bake_tally(bad, inexact);
-}
-__global__ __launch_bounds__(256) void bake_detail_kernel(const uint8_t* __restrict__ chain, uint4* __restrict__ out, uint16_t* __restrict__ out_h, unsigned long long* __restrict__ inexact) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    int l, n; size_t local; unsigned bad = 0;
-    if (level_of<DETAIL_N, DETAIL_LEVELS>(i, l, n, local)) {
-        const uint8_t* src = chain + chain_offset(DETAIL_N, l, 3);
-        const int x = (int)(local % n), y = (int)((local / n) % n), z = (int)(local / ((size_t)n * n));
-        out[i] = bake_detail_texel(src, n, x, y, z, bad);
-        out_h[i] = f2h((float)detail_numerator(src, n, x, y, z));                 // unpacked fp16 chain: source of the "lds" variant's LDS copy
-    }
-    bake_tally(bad, inexact);
-}
-// also the channel ranges of the map (exact height-window reject, bake.h::height_window): range[0] = min R, [1] = max R, [2] = max B
-__global__ __launch_bounds__(256) void bake_weather_kernel(const uint8_t* __restrict__ rgb, uint4* __restrict__ out, unsigned long long* __restrict__ inexact, int* __restrict__ range) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    unsigned bad = 0;
-    if (i < WEATHER_N * WEATHER_N) {
-        out[i] = bake_weather_texel(rgb, i % WEATHER_N, i / WEATHER_N, bad);
-        int r = rgb[3 * i], b = rgb[3 * i + 2], rmin = r, rmax = r, bmax = b;
-        for (int off = 32; off > 0; off >>= 1) { rmin = min(rmin, __shfl_down(rmin, off)); rmax = max(rmax, __shfl_down(rmax, off)); bmax = max(bmax, __shfl_down(bmax, off)); }
-        if ((threadIdx.x & 63) == 0) { atomicMin(&range[0], rmin); atomicMax(&range[1], rmax); atomicMax(&range[2], bmax); }
-    }
-    bake_tally(bad, inexact);
-}
-hipError_t launch_bake(const uint8_t* d_large_chain, const uint8_t* d_small_chain, const uint8_t* d_weather, ShapeTexel* d_shape, uint4* d_detail, uint16_t* d_detail_h,
-                       uint4* d_weather_out, unsigned long long* d_inexact, int* d_range, hipStream_t s) {
-    size_t shape_total = 0, detail_total = 0;
-    for (int l = 0; l < SHAPE_LEVELS; l++) { const size_t n = SHAPE_N >> l; shape_total += n * n * n; }
-    for (int l = 0; l < DETAIL_LEVELS; l++) { const size_t n = DETAIL_N >> l; detail_total += n * n * n; }
-    bake_shape_kernel<<<(unsigned)((shape_total + 255) / 256), 256, 0, s>>>(d_large_chain, d_shape, d_inexact);
-    bake_detail_kernel<<<(unsigned)((detail_total + 255) / 256), 256, 0, s>>>(d_small_chain, d_detail, d_detail_h, d_inexact);
-    bake_weather_kernel<<<(WEATHER_N * WEATHER_N + 255) / 256, 256, 0, s>>>(d_weather, d_weather_out, d_inexact, d_range);
-    return hipGetLastError();
-}
-
-// exact cells (bake_core.h: fp32 coefficients), built only for textures with coefficients fp16 cannot hold (or on request)
-__global__ __launch_bounds__(256) void bake_shape32_kernel(const uint8_t* __restrict__ chain, float4* __restrict__ out) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    int l, n; size_t local;
-    if (level_of<SHAPE_N, SHAPE_LEVELS>(i, l, n, local)) {
-        const int x = (int)(local % n), y = (int)((local / n) % n), z = (int)(local / ((size_t)n * n));
-        float4 c[4];
-        bake_shape_texel32(chain + chain_offset(SHAPE_N, l, 4), n, x, y, z, c);
-        float4* o = out + 4 * ((i - local) + shape_cell_index(n, x, y, z));
-        o[0] = c[0]; o[1] = c[1]; o[2] = c[2]; o[3] = c[3];
-    }
-}
-__global__ __launch_bounds__(256) void bake_detail32_kernel(const uint8_t* __restrict__ chain, float4* __restrict__ out) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    int l, n; size_t local;
-    if (level_of<DETAIL_N, DETAIL_LEVELS>(i, l, n, local)) {
-        const int x = (int)(local % n), y = (int)((local / n) % n), z = (int)(local / ((size_t)n * n));
-        float4 c[2];
-        bake_detail_texel32(chain + chain_offset(DETAIL_N, l, 3), n, x, y, z, c);
-        out[2 * i] = c[0]; out[2 * i + 1] = c[1];
-    }
-}
-__global__ __launch_bounds__(256) void bake_weather32_kernel(const uint8_t* __restrict__ rgb, float4* __restrict__ out) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < WEATHER_N * WEATHER_N) {
-        float4 c[2];
-        bake_weather_texel32(rgb, i % WEATHER_N, i / WEATHER_N, c);
-        out[2 * i] = c[0]; out[2 * i + 1] = c[1];
-    }
-}
-hipError_t launch_bake32(const uint8_t* d_large_chain, const uint8_t* d_small_chain, const uint8_t* d_weather, float4* d_shape32, float4* d_detail32, float4* d_weather32, hipStream_t s) {
-    size_t shape_total = 0, detail_total = 0;
-    for (int l = 0; l < SHAPE_LEVELS; l++) { const size_t n = SHAPE_N >> l; shape_total += n * n * n; }
-    for (int l = 0; l < DETAIL_LEVELS; l++) { const size_t n = DETAIL_N >> l; detail_total += n * n * n; }
-    bake_shape32_kernel<<<(unsigned)((shape_total + 255) / 256), 256, 0, s>>>(d_large_chain, d_shape32);
-    bake_detail32_kernel<<<(unsigned)((detail_total + 255) / 256), 256, 0, s>>>(d_small_chain, d_detail32);
-    bake_weather32_kernel<<<(WEATHER_N * WEATHER_N + 255) / 256, 256, 0, s>>>(d_weather, d_weather32);
-    return hipGetLastError();
-}
-
-// test hook (csky_test_sqrt_shell): cloud_core.h::sqrt_shell over an array, for the exhaustive check against the host's sqrtf
-__global__ __launch_bounds__(256) void sqrt_shell_kernel(const float* __restrict__ in, float* __restrict__ out, size_t n) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] = sqrt_shell(in[i]);
-}
-hipError_t launch_sqrt_shell(const float* d_in, float* d_out, size_t n, hipStream_t s) {
-    if (n == 0) return hipSuccess;
-    sqrt_shell_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(d_in, d_out, n);
-    return hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------------------ compositor
-// clouds.gdshader sky() on an equirectangular panorama, one pixel per lane
-template <int TLUT> __global__ __launch_bounds__(256) void composite_kernel(CompositeArgs A, uint2* __restrict__ out) {
-    const int i = blockIdx.x * 32 + (threadIdx.x & 31), j = blockIdx.y * 8 + (threadIdx.x >> 5);
-    if (i >= A.out_w || j >= A.out_h) return;
-    const C3 c = composite_pixel<TLUT>(A, i, j);
-    out[(size_t)j * A.out_w + i] = make_uint2((uint32_t)f2h(c.x) | ((uint32_t)f2h(c.y) << 16), (uint32_t)f2h(c.z) | ((uint32_t)f2h(1.0f) << 16));
-}
-hipError_t launch_composite(const CompositeArgs& a, uint2* d_out, hipStream_t s, int tlut) {
-    if (tlut == TLUT_BRUNETON) composite_kernel<TLUT_BRUNETON><<<dim3((a.out_w + 31) / 32, (a.out_h + 7) / 8), 256, 0, s>>>(a, d_out);
-    else composite_kernel<TLUT_REFERENCE><<<dim3((a.out_w + 31) / 32, (a.out_h + 7) / 8), 256, 0, s>>>(a, d_out);
-    return hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------------------ clouds
-__global__ __launch_bounds__(64) void frame_setup_kernel(CloudParams p, const float4* __restrict__ sky, int sw, int sh, int primary_steps,
-                                                         int light_steps, float early_eps, float hf_lo, float hf_hi, int ct_mode, int sat_skip, FrameConsts* __restrict__ out) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        FrameConsts fc;
-        frame_setup(p, sky, sw, sh, primary_steps, light_steps, early_eps, hf_lo, hf_hi, fc);
-        fc.ct_mode = ct_mode;
-        if (!sat_skip) fc.sat_skip = 0;
-        *out = fc;
-    }
-}
-hipError_t launch_frame_setup(const CloudParams& p, const float4* d_sky, int sw, int sh, int primary_steps, int light_steps, float early_eps,
-                              float hf_lo, float hf_hi, int ct_mode, int sat_skip, FrameConsts* d_fc, hipStream_t s) {
-    frame_setup_kernel<<<1, 64, 0, s>>>(p, d_sky, sw, sh, primary_steps, light_steps, early_eps, hf_lo, hf_hi, ct_mode, sat_skip, d_fc);
-    return hipGetLastError();
-}
-// The same for a context that holds no sky LUT of its own (one rank of an N-way frame split renders only its rows of it, straight into the
-// gather buffer): the <= 12 texels the three taps of clouds.glsl:163-167 filter are rendered here first, one per half wavefront with the
-// per-texel code of sky_lut_kernel (fp16-rounded like the stored LUT), parked in LDS, and lane 0 runs the set-up on them.  The cell
-// arithmetic is sky_lut_cell's in both places, so every texel the set-up asks for is one rendered here: the constants are bit-identical to
-// those filtered from a whole LUT.
-template <int TLUT> __global__ __launch_bounds__(384) void frame_setup_taps_kernel(CloudParams p, Sun3 sun, const float4* __restrict__ trans, int tw, int th, int sw, int sh,
-                                                              int primary_steps, int light_steps, float early_eps, float hf_lo, float hf_hi, int ct_mode, int sat_skip,
-                                                              FrameConsts* __restrict__ out) {
-    __shared__ float steps[12][IN_SCATTERING_STEPS][8];
-    __shared__ float4 texel[12];
-    const int k = threadIdx.x >> 5, sub = threadIdx.x & 31;      // texel k: corner k % 4 of tap k / 4
-    float sx, sy, ax, ay; int x0, x1, y0, y1;
-    frame_setup_tap_uv(p.LIGHT_DIRECTION, k >> 2, sx, sy);
-    sky_lut_cell(sw, sh, sx, sy, x0, x1, y0, y1, ax, ay);
-    sky_texel<TLUT>(steps[k], sub, true, (k & 1) ? x1 : x0, (k & 2) ? y1 : y0, sw, sh, sun, trans, tw, th, [&](int, int, uint16_t hx, uint16_t hy, uint16_t hz, uint16_t hw) {
-        texel[k] = make_float4(h2f(hx), h2f(hy), h2f(hz), h2f(hw));
-    });
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        FrameConsts fc;
-        frame_setup_f(p, [&](int tap, int corner, int, int) { return texel[tap * 4 + corner]; }, sw, sh, primary_steps, light_steps, early_eps, hf_lo, hf_hi, fc);
-        fc.ct_mode = ct_mode;
-        if (!sat_skip) fc.sat_skip = 0;
-        *out = fc;
-    }
-}
-hipError_t launch_frame_setup_taps(const CloudParams& p, const float sun[3], const float4* d_trans, int tw, int th, int sw, int sh, int primary_steps,
-                                   int light_steps, float early_eps, float hf_lo, float hf_hi, int ct_mode, int sat_skip, FrameConsts* d_fc, hipStream_t s, int tlut) {
-    Sun3 sv; sv.v[0] = sun[0]; sv.v[1] = sun[1]; sv.v[2] = sun[2];
-    if (tlut == TLUT_BRUNETON) frame_setup_taps_kernel<TLUT_BRUNETON><<<1, 384, 0, s>>>(p, sv, d_trans, tw, th, sw, sh, primary_steps, light_steps, early_eps, hf_lo, hf_hi, ct_mode, sat_skip, d_fc);
-    else frame_setup_taps_kernel<TLUT_REFERENCE><<<1, 384, 0, s>>>(p, sv, d_trans, tw, th, sw, sh, primary_steps, light_steps, early_eps, hf_lo, hf_hi, ct_mode, sat_skip, d_fc);
-    return hipGetLastError();
-}
 
 // ---- wave-cooperative march (variant "queue") --------------------------------------------------------------
 // The lock-step march (cloud_core.h march()) runs the (light_steps+1)-sample light march on all 64 lanes whenever
@@ -388,6 +44,53 @@ __device__ __forceinline__ void wave_lds_fence() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// the phase value of a ray's samples (0 for a ray that does not march)
+__device__ __forceinline__ float ray_phase(const FrameConsts& fc, const Ray& ray) {
+    float phase = 0.0f;
+    if (ray.above) {
+        const float ct = fc.ldir[0] * ray.dx + fc.ldir[1] * ray.dy + fc.ldir[2] * ray.dz;                       // clouds.glsl:158
+        phase = fmaxf(fmaxf(henyey_greenstein(ct, 0.6f), henyey_greenstein(ct, fc.hg_g2)), henyey_greenstein(ct, -0.2f));  // :160
+    }
+    return phase;
+}
+
+// Step B of the queue marches: the nb * (ls + 1) light-march evaluations of nb queued samples (clouds.glsl:186-199), flattened as e = j * nb + k
+// and dealt out 64 per round, so every round runs with all lanes busy no matter which rays were in cloud.  pos(k, x, y, z) delivers sample k's
+// position; the density of its cone sample j (j == ls: the distant sample) goes to lt[j * pitch + k].
+template <class Pos> __device__ __forceinline__ void light_march_batch(const TexSet& T, const FrameConsts& fc, const int ls, const int nb, const int lane, Pos&& pos,
+                                                                      float* __restrict__ lt, const int pitch) {
+    const int total = nb * (ls + 1);
+    const float rn = 1.0f / (float)nb;
+    for (int e0 = 0; e0 < total; e0 += 64) {
+        const int e = e0 + lane;
+        if (e < total) {
+            const int j = (int)(((float)e + 0.5f) * rn);          // e = j*nb + k (exact: e < 672, nb <= 96)
+            const int k = e - j * nb;
+            float lx, ly, lz;
+            pos(k, lx, ly, lz);
+            const bool distant = (j == ls);
+            // cone sample j: lp = p + sum_{i<=j} (ldir + RANDOM_VECTORS[i]*i)*lss, added one by one in fp32 like :187.
+            // e grows with the lane, so j is non-decreasing across the wavefront: the additions up to the first lane's j
+            // are wave-uniform (plain adds under a scalar branch), only the few beyond it need per-lane predication.
+            const int j_lo = __builtin_amdgcn_readfirstlane(j);
+            if (distant) {
+                advance(lx, ly, lz, fc.ldist[0], fc.ldist[1], fc.ldist[2]);                                // :195
+            } else {
+#pragma unroll
+                for (int jj = 0; jj < 6; jj++) {
+                    if (jj <= j_lo) advance(lx, ly, lz, fc.linc[jj][0], fc.linc[jj][1], fc.linc[jj][2]);
+                    else if (jj <= j) advance(lx, ly, lz, fc.linc[jj][0], fc.linc[jj][1], fc.linc[jj][2]);
+                }
+            }
+            const float lhf = height_fraction(length3_shell(lx, ly, lz));                                  // :188 / :196
+            const int lod_s = distant ? 3 : (j > 2 ? j - 2 : 0), lod_d = distant ? 5 : j;                  // textureLod(.., mip-2) / (.., mip)
+            float d = sample_density(T, fc, lx, ly, lz, lhf, distant ? 0.0f : fc.wpos_x, distant ? 0.0f : fc.wpos_y, lod_s, lod_d);  // :189-190 / :197-198
+            if (distant) d = fast_pow(d, (1.0f - lhf) * 0.8f + 0.5f);                                      // :198 second pow
+            lt[j * pitch + k] = d;
+        }
+    }
+}
+
 __device__ __forceinline__ MarchOut march_queue(const TexSet& T, const FrameConsts& fc, Ray ray, float* __restrict__ q, int step_begin, int step_end) {
     float* __restrict__ ev_px = q;
     float* __restrict__ ev_py = q + QCAP;
@@ -402,11 +105,7 @@ __device__ __forceinline__ MarchOut march_queue(const TexSet& T, const FrameCons
     MarchOut o; o.r = o.g = o.b = o.a = 0.0f; o.t = 1.0f; o.incloud = 0;
     const int lane = threadIdx.x & 63;
     const int ls = fc.light_steps, nl = ls + 1;
-    float phase = 0.0f;
-    if (ray.above) {
-        const float ct = fc.ldir[0] * ray.dx + fc.ldir[1] * ray.dy + fc.ldir[2] * ray.dz;                       // clouds.glsl:158
-        phase = fmaxf(fmaxf(henyey_greenstein(ct, 0.6f), henyey_greenstein(ct, fc.hg_g2)), henyey_greenstein(ct, -0.2f));  // :160
-    }
+    const float phase = ray_phase(fc, ray);
     float Tr = 1.0f, alpha = 0.0f, Lr = 0.0f, Lg = 0.0f, Lb = 0.0f;
     float px = ray.px, py = ray.py, pz = ray.pz;
     const float nd = -fc.density;
@@ -437,35 +136,7 @@ __device__ __forceinline__ MarchOut march_queue(const TexSet& T, const FrameCons
         if (count == 0) continue;
         // ---- B: count*(ls+1) light-march evaluations, 64 per round, all lanes busy
         wave_lds_fence();
-        const int total = count * nl;
-        const float rn = 1.0f / (float)count;
-        for (int e0 = 0; e0 < total; e0 += 64) {
-            const int e = e0 + lane;
-            if (e < total) {
-                const int j = (int)(((float)e + 0.5f) * rn);          // e = j*count + k (exact: e < 672, count <= 96)
-                const int k = e - j * count;
-                float lx = ev_px[k], ly = ev_py[k], lz = ev_pz[k];
-                const bool distant = (j == ls);
-                // cone sample j: lp = p + sum_{i<=j} (ldir + RANDOM_VECTORS[i]*i)*lss, added one by one in fp32 like :187.
-                // e grows with the lane, so j is non-decreasing across the wavefront: the additions up to the first lane's j
-                // are wave-uniform (plain adds under a scalar branch), only the few beyond it need per-lane predication.
-                const int j_lo = __builtin_amdgcn_readfirstlane(j);
-                if (distant) {
-                    advance(lx, ly, lz, fc.ldist[0], fc.ldist[1], fc.ldist[2]);                                // :195
-                } else {
-#pragma unroll
-                    for (int jj = 0; jj < 6; jj++) {
-                        if (jj <= j_lo) advance(lx, ly, lz, fc.linc[jj][0], fc.linc[jj][1], fc.linc[jj][2]);
-                        else if (jj <= j) advance(lx, ly, lz, fc.linc[jj][0], fc.linc[jj][1], fc.linc[jj][2]);
-                    }
-                }
-                const float lhf = height_fraction(length3_shell(lx, ly, lz));                                  // :188 / :196
-                const int lod_s = distant ? 3 : (j > 2 ? j - 2 : 0), lod_d = distant ? 5 : j;                  // textureLod(.., mip-2) / (.., mip)
-                float d = sample_density(T, fc, lx, ly, lz, lhf, distant ? 0.0f : fc.wpos_x, distant ? 0.0f : fc.wpos_y, lod_s, lod_d);  // :189-190 / :197-198
-                if (distant) d = fast_pow(d, (1.0f - lhf) * 0.8f + 0.5f);                                      // :198 second pow
-                ev_lt[j * QCAP + k] = d;
-            }
-        }
+        light_march_batch(T, fc, ls, count, lane, [&](int k, float& x, float& y, float& z) { x = ev_px[k]; y = ev_py[k]; z = ev_pz[k]; }, ev_lt, QCAP);
         wave_lds_fence();
         // ---- C: replay the chunk in step order; owners composite (:191,:199 sums in the reference's order, :202-210)
         for (int s = 0; s < cs; s++) {
@@ -526,7 +197,7 @@ constexpr int CQ_FLOATS = 5 * CQ_CAP + CQ_CAP / 4 + 3 * CQ_STEPS + 2 + 128 + 320
 // Step B of the compact march for ONE queued in-cloud sample: the reference's light march (clouds.glsl:186-199) from its position and the
 // state-independent half of its shading (:178, :202-209).  In: position, density t, height fraction, the owner ray's step length and phase
 // value.  Out: D.rgb, 1 / max(1e-7, t), dt (shade_terms).  A function of those seven floats alone (round 4's packet exchange ran it on other
-// CUs' wavefronts and got byte-identical frames: see the record further down).
+// CUs' wavefronts and got byte-identical frames: docs/EXPERIMENTS.md §5).
 // `late(et, ehf, ess, eph)` delivers the four inputs the light march itself does not need AFTER it (the owner reads them from its LDS queue
 // then: four registers fewer across the march).
 template <class TS, class Late>
@@ -575,11 +246,7 @@ __device__ __forceinline__ MarchOut march_compact(const TS& T, const FrameConsts
     MarchOut o; o.r = o.g = o.b = o.a = 0.0f; o.t = 1.0f; o.incloud = 0;
     const int lane = threadIdx.x & 63;
     const int ls = fc.light_steps;
-    float phase = 0.0f;
-    if (ray.above) {
-        const float ct = fc.ldir[0] * ray.dx + fc.ldir[1] * ray.dy + fc.ldir[2] * ray.dz;                       // clouds.glsl:158
-        phase = fmaxf(fmaxf(henyey_greenstein(ct, 0.6f), henyey_greenstein(ct, fc.hg_g2)), henyey_greenstein(ct, -0.2f));  // :160
-    }
+    const float phase = ray_phase(fc, ray);
     float px = ray.px, py = ray.py, pz = ray.pz;
     const float nd = -fc.density;
     bool live = ray.above;
@@ -698,13 +365,26 @@ __device__ __forceinline__ MarchOut march_compact(const TS& T, const FrameConsts
     return o;
 }
 
-// ---- instruction-level parallelism for small launches (round 3: built as kernel variant "compact-ilp", measured, removed) ------------
-// Two primary steps and two light samples in flight per wavefront (their gathers issued together, the exact rejects as selects so that the
-// scheduler interleaves the two dependent chains), 116 VGPRs -> 4 waves per SIMD, which is all one GPU's 1/8 share of a frame has anyway.
-// Parity green (tight gate, sample counts equal to march_compact for seven march shapes), but ms per frame at 1/8 share x1 / x2 / x4 frames in
-// flight: 0.508 / 0.300 / 0.332 against 0.436 / 0.327 / 0.281 for the policy below, whole frame 2.42 vs 2.08: a lone wavefront issues ONE of
-// its own VALU instructions per ~5 cycles whether or not they depend on each other, so independent work inside a wavefront buys only the
-// overlapped gathers.  profiles/r03/share_matrix_compact_ilp_ab.txt; the code is in the history (commit "compact-ilp kernel variant").
+// (two primary steps and two light samples in flight per wavefront, kernel variant "compact-ilp": docs/EXPERIMENTS.md §5, removed experiments)
+
+// ---- the pixel of a lane -----------------------------------------------------------------------------------------------------
+// Workgroup footprint `logical` = slab * tiles_x + bx is bw x 8 pixels; the wavefront's 8x8 tile is its tile-th (lane = ly*8 + lx).  The front ends of
+// the two alternatives below; render_block keeps its own copy of this arithmetic (through this function the product kernel's code is not the parent's).
+struct Pixel { int gx, gy, lr; bool valid; };   // column and row in the frame (gl_GlobalInvocationID), row among the rows this launch renders, inside the launch
+__device__ __forceinline__ Pixel footprint_pixel(const RenderGeom& G, const uint32_t logical, const int tiles_x, const int bw, const int tile, const int lane) {
+    const int local_rows = G.n_bands * G.band_rows;
+    const int slab = (int)logical / tiles_x, bx = (int)logical - slab * tiles_x;
+    Pixel p;
+    p.gx = bx * bw + tile * 8 + (lane & 7);
+    p.lr = slab * 8 + (lane >> 3);
+    p.valid = p.gx < G.tile_w && p.lr < local_rows;
+    const int band = p.lr / G.band_rows, rib = p.lr - band * G.band_rows;
+    p.gy = (G.first_band + band * G.band_stride) * G.band_rows + rib;
+    return p;
+}
+__device__ __forceinline__ void store_pixel(uint2* __restrict__ out, const RenderGeom& G, int gx, int gy, int lr, float r, float g, float b, float a) {
+    out[(size_t)(G.out_full ? gy : lr) * G.pitch_px + gx] = pack_half4(f2h(r), f2h(g), f2h(b), f2h(a));   // imageStore, clouds.glsl:264
+}
 
 // ---- interleaved ray segments (small launches) ------------------------------------------------------------------
 // One workgroup = ONE 8x8 tile; wavefront w marches the primary samples i = 4m + w of every ray of the tile.  In-cloud
@@ -737,11 +417,7 @@ __device__ __forceinline__ void march_interleaved(const TexSet& T, const FrameCo
 
     const int steps = fc.primary_steps, ls = fc.light_steps, nl = ls + 1;
     const float nd = -fc.density;
-    float phase = 0.0f;
-    if (ray.above) {
-        const float ct = fc.ldir[0] * ray.dx + fc.ldir[1] * ray.dy + fc.ldir[2] * ray.dz;
-        phase = fmaxf(fmaxf(henyey_greenstein(ct, 0.6f), henyey_greenstein(ct, fc.hg_g2)), henyey_greenstein(ct, -0.2f));
-    }
+    const float phase = ray_phase(fc, ray);
     float Lr = 0.0f, Lg = 0.0f, Lb = 0.0f;
     float px = ray.px, py = ray.py, pz = ray.pz;
     int replay = wave + 1;                                      // additions of dir*ss needed to reach this wavefront's next sample
@@ -774,33 +450,7 @@ __device__ __forceinline__ void march_interleaved(const TexSet& T, const FrameCo
         // ---- B: light march of the chunk's events, IL_BATCH events at a time, 64 evaluations per round
         for (int b0 = 0; b0 < count; b0 += IL_BATCH) {
             const int nb = (count - b0) < IL_BATCH ? (count - b0) : IL_BATCH;
-            const int total = nb * nl;
-            const float rn = 1.0f / (float)nb;
-            for (int e0 = 0; e0 < total; e0 += 64) {
-                const int e = e0 + lane;
-                if (e < total) {
-                    const int j = (int)(((float)e + 0.5f) * rn);
-                    const int k = e - j * nb;
-                    const int id = ev_idx[b0 + k];
-                    float lx = d_px[id], ly = d_py[id], lz = d_pz[id];
-                    const bool distant = (j == ls);
-                    const int j_lo = __builtin_amdgcn_readfirstlane(j);
-                    if (distant) {
-                        advance(lx, ly, lz, fc.ldist[0], fc.ldist[1], fc.ldist[2]);
-                    } else {
-#pragma unroll
-                        for (int jj = 0; jj < 6; jj++) {
-                            if (jj <= j_lo) advance(lx, ly, lz, fc.linc[jj][0], fc.linc[jj][1], fc.linc[jj][2]);
-                            else if (jj <= j) advance(lx, ly, lz, fc.linc[jj][0], fc.linc[jj][1], fc.linc[jj][2]);
-                        }
-                    }
-                    const float lhf = height_fraction(length3_shell(lx, ly, lz));
-                    const int lod_s = distant ? 3 : (j > 2 ? j - 2 : 0), lod_d = distant ? 5 : j;
-                    float d = sample_density(T, fc, lx, ly, lz, lhf, distant ? 0.0f : fc.wpos_x, distant ? 0.0f : fc.wpos_y, lod_s, lod_d);
-                    if (distant) d = fast_pow(d, (1.0f - lhf) * 0.8f + 0.5f);
-                    lt[j * IL_BATCH + k] = d;
-                }
-            }
+            light_march_batch(T, fc, ls, nb, lane, [&](int k, float& x, float& y, float& z) { const int id = ev_idx[b0 + k]; x = d_px[id]; y = d_py[id]; z = d_pz[id]; }, lt, IL_BATCH);
             wave_lds_fence();
             for (int k = lane; k < nb; k += 64) {               // cd of each event, summed in the reference's order (:191, :199)
                 float cd = 0.0f;
@@ -845,26 +495,19 @@ template <int DUMMY>
 __global__ __launch_bounds__(256) void clouds_kernel_interleaved(TexSet T, const FrameConsts* __restrict__ fcp, RenderGeom G, const uint32_t* __restrict__ order,
                                                                  uint2* __restrict__ out, unsigned long long* __restrict__ stats, uint32_t* __restrict__ wg_cost) {
     extern __shared__ __attribute__((aligned(16))) float il_smem[];
-    const int tiles_x = (G.tile_w + 7) >> 3;
-    const int local_rows = G.n_bands * G.band_rows;
     const uint32_t logical = order[blockIdx.x];
     if (logical == 0xffffffffu) return;
-    const int slab = (int)logical / tiles_x, bx = (int)logical - slab * tiles_x;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int gx = bx * 8 + (lane & 7);
-    const int lr = slab * 8 + (lane >> 3);
-    const bool valid = gx < G.tile_w && lr < local_rows;
-    const int band = lr / G.band_rows, rib = lr - band * G.band_rows;
-    const int gy = (G.first_band + band * G.band_stride) * G.band_rows + rib;
+    const Pixel pix = footprint_pixel(G, logical, (G.tile_w + 7) >> 3, 8, 0, lane);
+    const bool valid = pix.valid;
     const FrameConsts& fc = *fcp;
     T.detail_lds = nullptr;
-    Ray ray = ray_setup(fc, valid ? gx : 0, valid ? gy : 0);
+    Ray ray = ray_setup(fc, valid ? pix.gx : 0, valid ? pix.gy : 0);
     if (!valid) ray.above = false;
     float r, g, b, a; unsigned ic;
     march_interleaved(T, fc, ray, il_smem, wave, lane, r, g, b, a, ic);
     if (valid && wave == 0) {
-        const uint32_t lo = (uint32_t)f2h(r) | ((uint32_t)f2h(g) << 16), hi = (uint32_t)f2h(b) | ((uint32_t)f2h(a) << 16);
-        out[(size_t)(G.out_full ? gy : lr) * G.pitch_px + gx] = make_uint2(lo, hi);
+        store_pixel(out, G, pix.gx, pix.gy, pix.lr, r, g, b, a);
     }
     if (stats) {
         unsigned ab = (ray.above && wave == 0) ? 1u : 0u;
@@ -893,24 +536,17 @@ __global__ __launch_bounds__(1024) void clouds_kernel_lds(TexSet T, const FrameC
     __syncthreads();
     const uint32_t logical = order[blockIdx.x];
     if (logical == 0xffffffffu) return;
-    const int tiles_x = (G.tile_w + 127) >> 7;
-    const int local_rows = G.n_bands * G.band_rows;
-    const int slab = (int)logical / tiles_x, bx = (int)logical - slab * tiles_x;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int gx = bx * 128 + wave * 8 + (lane & 7);
-    const int lr = slab * 8 + (lane >> 3);
-    const bool valid = gx < G.tile_w && lr < local_rows;
-    const int band = lr / G.band_rows, rib = lr - band * G.band_rows;
-    const int gy = (G.first_band + band * G.band_stride) * G.band_rows + rib;
+    const Pixel pix = footprint_pixel(G, logical, (G.tile_w + 127) >> 7, 128, wave, lane);
+    const bool valid = pix.valid;
     const FrameConsts& fc = *fcp;
-    Ray ray = ray_setup(fc, valid ? gx : 0, valid ? gy : 0);
+    Ray ray = ray_setup(fc, valid ? pix.gx : 0, valid ? pix.gy : 0);
     if (!valid) ray.above = false;
     TexSet Tl = T;
     Tl.detail_lds = detail_s;
     const MarchOut o = march_queue(Tl, fc, ray, queues + wave * Q_FLOATS, 0, fc.primary_steps);
     if (valid) {
-        const uint32_t lo = (uint32_t)f2h(o.r) | ((uint32_t)f2h(o.g) << 16), hi = (uint32_t)f2h(o.b) | ((uint32_t)f2h(o.a) << 16);
-        out[(size_t)(G.out_full ? gy : lr) * G.pitch_px + gx] = make_uint2(lo, hi);
+        store_pixel(out, G, pix.gx, pix.gy, pix.lr, o.r, o.g, o.b, o.a);
     }
     if (stats || wg_cost) {
         unsigned ic = o.incloud, ab = ray.above ? 1u : 0u;
@@ -985,8 +621,7 @@ __device__ __forceinline__ void render_block(TS T, const FrameConsts* __restrict
         }
     }
     if (valid && seg == 0) {
-        const uint32_t lo = (uint32_t)f2h(o.r) | ((uint32_t)f2h(o.g) << 16), hi = (uint32_t)f2h(o.b) | ((uint32_t)f2h(o.a) << 16);
-        out[(size_t)(G.out_full ? gy : lr) * G.pitch_px + gx] = make_uint2(lo, hi);  // imageStore, clouds.glsl:264
+        store_pixel(out, G, gx, gy, lr, o.r, o.g, o.b, o.a);
     }
     if (stats || wg_cost) {
         unsigned ic = o.incloud, ab = (ray.above && seg == 0) ? 1u : 0u;
@@ -1080,31 +715,7 @@ __global__ __launch_bounds__(256, VARIANT == 3 ? CSKY_COMPACT_WAVES : 7) void cl
     }
 }
 
-// ---- light-march packet exchange (round 4: built, measured, removed; evidence profiles/r04/exchange_ab.txt; code: commit "exchange: ...") ----
-// the persistent form above whose wavefronts, once every sequence is empty, stay and serve the light marches of the tiles
-// still being marched.  An owner published a flush (the 7 floats x 64 samples march_compact parks in LDS) to a per-XCD ticket queue in global
-// memory instead of running step B, kept marching, and composited the helper's five results per sample IN ORDER later (readlane / ds_bpermute
-// replay, 4-8 packets outstanding per wavefront); helpers ran the same light_march_terms().  Transport per cdna_hip_programming.md G16: 8-byte
-// {tag, value} granules, relaxed agent-scope (sc1) stores and loads, a per-launch epoch in the tags: no fence, no L1 invalidate.
-//   * Frames BYTE-IDENTICAL to clouds_kernel<3,1> in every build (512x256, C3, a rank's 1/8 share), no spin ever hit its bound.
-//   * Slower everywhere.  ms per C3 frame alone / two in flight / 1/8 share x1: product 2.03 / 1.69 / 0.41; four protocols 144.8 -> 65.5
-//     -> 5.94 -> 2.88 / 2.78 / 0.96 (idle helpers scanning shared words; compare-exchange pops: one winner per round trip with hundreds in
-//     flight; owners reading a policy word per flush; finally static per-XCD queues where no shared word is polled at all).  The kernel's own
-//     cost with publication compiled out: 2.23 / 2.22 / 0.86 (helpers hold their slots to the end, so the next frame cannot fill the tail).
-//   * Why: publication -> results read takes ~43 us (six memory hops at 2-5 us each on a loaded chip) against 6.8 us of work per packet;
-//     with four packets outstanding an owner waits ~11 us per flush where running it costs 6.  Hiding it needs ~20 packets in flight per
-//     wavefront plus prefetched results in a kernel at its 72-VGPR budget (the prefetch build: 51 spilled registers, 4.0 ms).  The unit of
-//     work the compact march can hand over is an order of magnitude too small for a cross-CU hand-off on this chip.
-
-// ---- launch-tail / share experiments of round 2 (measured, removed; evidence under profiles/r02/) -----------------------------
-// A whole-frame launch drains for the last ~27 % of its span with the chip 3/4 empty (time-integral of occupancy 72-76 %).  Three
-// ways of filling that tail were built and measured on MI355X, none made the frame faster, and the code was removed again:
-//   * deadline order: static order, previous-frame costs pull late heavy workgroups forward             2.10 vs 2.07 ms (timeline_static_vs_deadline_order.txt)
-//   * mixed-segment launch: the order's last 10-25 % as 2-/4-segment workgroups in the SAME launch: occupancy integral 72 -> 85-87 %,
-//     frame 2.06-2.28 vs 2.09 ms: segments add 17 % wave-time and the launch is VALU/L1-throughput bound     (timeline_static_vs_mixed_segment_tail.txt)
-//   * adaptive segments per workgroup from previous-frame costs, for one GPU's 1/4..1/16 share             0.446 vs 0.434 ms at 1/8 (share_matrix_adaptive_segments.txt)
-// What does fill the tail is the NEXT frame's workgroups (two frames in flight, launch_policy.h): 2.12 -> 1.80 ms per frame, and with them
-// in flight the persistent form above (cross-XCD stealing at the end of a launch): 1.81 -> 1.72 ms per frame.
+// (helpers serving other wavefronts' light marches once the order is empty, and three ways of filling a launch's tail: docs/EXPERIMENTS.md §5, removed experiments)
 
 // ---- cost-feedback schedule (clouds_launch.cpp, schedule mode 7) ------------------------------------------------------------
 // Workgroups differ 10x in cost (in-cloud samples per tile) and a C3 frame is only ~4 waves of resident workgroups deep, so
@@ -1176,6 +787,38 @@ __global__ __launch_bounds__(256) void static_order_kernel(int mode, int tiles_x
 hipError_t launch_static_order(int mode, int tiles_x, int slabs, int grid, uint32_t* d_order, hipStream_t s) {
     if (grid <= 0) return hipSuccess;
     static_order_kernel<<<(grid + 255) / 256, 256, 0, s>>>(mode, tiles_x, slabs, grid, d_order);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------ band interleave (gathering rank, N > 1)
+// The gather leaves rank-major compact bands ([member][local band][rows]); the frame wants band k = member k % n, local band k / n.  A plain
+// strided copy, deliberately on FEW workgroups: it is HBM-bound (32 MiB per 2048x1024 frame) beside marches that are not, so 48 workgroups
+// streaming 16-byte chunks take it off the critical path instead of sweeping the whole chip for 15 us per frame (torch's permute + copy).
+__global__ __launch_bounds__(256) void interleave_bands_kernel(const uint4* __restrict__ src, size_t member_stride16, int members, uint32_t band16, uint32_t total_bands,
+                                                              uint4* __restrict__ dst) {
+    const size_t total = (size_t)band16 * total_bands;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const uint32_t k = (uint32_t)(i / band16), c = (uint32_t)(i - (size_t)k * band16);
+        dst[i] = src[(size_t)(k % members) * member_stride16 + (size_t)(k / members) * band16 + c];
+    }
+}
+hipError_t launch_interleave_bands(const void* d_gathered, size_t member_stride_bytes, int members, size_t band_bytes, int total_bands, void* d_frame, hipStream_t s) {
+    const size_t chunks = band_bytes / 16 * (size_t)total_bands;
+    if (!chunks) return hipSuccess;
+    const unsigned grid = (unsigned)(chunks / 256 + 1 < 48 ? chunks / 256 + 1 : 48);
+    interleave_bands_kernel<<<grid, 256, 0, s>>>(reinterpret_cast<const uint4*>(d_gathered), member_stride_bytes / 16, members, (uint32_t)(band_bytes / 16), (uint32_t)total_bands,
+                                                 reinterpret_cast<uint4*>(d_frame));
+    return hipGetLastError();
+}
+
+// test hook (csky_test_sqrt_shell): cloud_core.h::sqrt_shell over an array, for the exhaustive check against the host's sqrtf
+__global__ __launch_bounds__(256) void sqrt_shell_kernel(const float* __restrict__ in, float* __restrict__ out, size_t n) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = sqrt_shell(in[i]);
+}
+hipError_t launch_sqrt_shell(const float* d_in, float* d_out, size_t n, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    sqrt_shell_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(d_in, d_out, n);
     return hipGetLastError();
 }
 

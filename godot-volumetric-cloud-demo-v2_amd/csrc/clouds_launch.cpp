@@ -25,7 +25,7 @@ TexSet32 texset32(const csky_ctx* c) {
     return t;
 }
 
-// Static workgroup order for ring slot `slot` (kernels.hip::static_order_kernel; modes 1, 2, 5).  Measured on the headline frame
+// Static workgroup order for ring slot `slot` (cloud_kernels.hip::static_order_kernel; modes 1, 2, 5).  Measured on the headline frame
 // (queue kernel, round 1): 5 (slab rows round-robin over the XCDs) 3.93 ms, 1 (contiguous eighths) 4.80 ms, 2 (natural) 4.92 ms;
 // azimuth-wedge and horizon-first orders (5.3-5.8 / 4.77 ms) were dropped in round 2.  The table depends on the launch geometry
 // only (not on update_position: the reference's tile walk re-uses it) and is written by a kernel on the launch's stream.
@@ -104,10 +104,11 @@ int clouds_dev(csky_ctx* c, const csky_cloud_params* p, int tile_w, const csky_b
         if (c->clouds_pending[f]) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_clouds[f], 0));
         // cloud-type range of the weather map (texel values 0..255): all >= 128 or all <= 127 fixes the branch of the height gradient
         const int ctm = !c->use_window ? 0 : (c->w_rmin * 255.0 >= 127.5 ? 1 : (c->w_rmax * 255.0 <= 127.5 ? 2 : 0));
+        const SetupArgs sa = {c->primary_steps, c->light_steps, c->early_eps, lo, hi, ctm, c->use_window ? 1 : 0};
         if (c->sky_partial)                              // no LUT in memory: the set-up renders the texels of its three taps (clouds.glsl:163-167) itself
-            HIPCHK(c, launch_frame_setup_taps(cp, c->sky_sun, c->d_trans_f, c->tw, c->th, c->psw, c->psh, c->primary_steps, c->light_steps, c->early_eps, lo, hi, ctm, c->use_window ? 1 : 0, c->fc_ring[f], c->stream, c->tlut));
+            HIPCHK(c, launch_frame_setup_taps(cp, c->sky_sun, c->d_trans_f, c->tw, c->th, c->psw, c->psh, sa, c->fc_ring[f], c->stream, c->tlut));
         else
-            HIPCHK(c, launch_frame_setup(cp, c->d_sky_f, c->sw, c->sh, c->primary_steps, c->light_steps, c->early_eps, lo, hi, ctm, c->use_window ? 1 : 0, c->fc_ring[f], c->stream));
+            HIPCHK(c, launch_frame_setup(cp, c->d_sky_f, c->sw, c->sh, sa, c->fc_ring[f], c->stream));
         HIPCHK(c, hipEventRecord(c->ev_setup[f], c->stream));
         c->fc_cur = f; c->d_fc = c->fc_ring[f];
         // (Round 5 bounded what folding the set-up INTO the march launch could return by simply not waiting here -- legal in a timing run with constant

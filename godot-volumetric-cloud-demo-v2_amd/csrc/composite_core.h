@@ -1,7 +1,7 @@
 // composite_core.h -- per-pixel body of the sky compositor: clouds.gdshader sky() (cited G:line), SURVEY §8f row 1.
 // Godot supplies EYEDIR per screen pixel; here sky() is evaluated for the pixels of an equirectangular panorama
 // (u -> azimuth (2u-1)*pi, v -> elevation (0.5-v)*pi; EYEDIR = (cos e cos a, sin e, cos e sin a), y up).
-// Host+device like the other cores; the product instantiates it only in kernels.hip.  Small kernel: accurate OCML
+// Host+device like the other cores; the product instantiates it only in lut_kernels.hip.  Small kernel: accurate OCML
 // maths, FP contraction off.
 #pragma once
 #include "csky_common.h"

@@ -156,6 +156,10 @@ CSKY_HD float h2f(uint16_t h) {
     float f; memcpy(&f, &x, 4); return f;
 }
 
+CSKY_HD uint2 pack_half4(uint16_t hx, uint16_t hy, uint16_t hz, uint16_t hw) {   // four halfs as one RGBA16F pixel
+    uint2 r; r.x = (uint32_t)hx | ((uint32_t)hy << 16); r.y = (uint32_t)hz | ((uint32_t)hw << 16); return r;
+}
+
 CSKY_HD float clampf(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
 CSKY_HD float sat(float x) { return fminf(fmaxf(x, 0.0f), 1.0f); }
 CSKY_HD float lerpf(float a, float b, float f) { return a + (b - a) * f; }

@@ -68,7 +68,7 @@ inline LaunchPlan plan_launch(const LaunchKnobs& k, long long waves) {
     p.feedback = mode == 7 && queued && seg != 5;                // kernels that record per-workgroup costs
     if (mode == 7 && !p.feedback) mode = waves >= 12288 ? 5 : 2;
     p.static_mode = mode == 7 ? (waves >= 12288 ? 5 : 2) : mode;   // order of the first launch of a geometry under feedback
-    // Persistent launch form (kernels.hip::clouds_kernel_persistent): as many workgroups as the chip holds, their wavefronts pop
+    // Persistent launch form (cloud_kernels.hip::clouds_kernel_persistent): as many workgroups as the chip holds, their wavefronts pop
     // footprints from per-XCD sequences of the launch order and, at the end, from the other XCDs' sequences.  Measured
     // (profiles/r02/persistent_launch_ab.txt), ms per frame plain -> persistent: whole frame with two frames
     // in flight 1.806 -> 1.724 (bench.py, alternating runs), 1/2 frame 0.938 -> 0.882; one frame at a time 2.12 -> 2.17 (plain

@@ -1,6 +1,6 @@
 // noise_core.h -- the deterministic stand-in generator for the missing cloud_sky/perlworlnoise.tga (128^3 RGBA shape
 // noise, perlworlnoise.tga.import:24-27), host+device.  Used by assets.cpp (csky_generate_shape_noise, threads) and by
-// kernels.hip (shape_noise_kernel; SURVEY §8f row 2 and README.md:30 TODO 3 "generate the noise on the GPU").
+// bake_kernels.hip (shape_noise_kernel; SURVEY §8f row 2 and README.md:30 TODO 3 "generate the noise on the GPU").
 #pragma once
 #include "csky_common.h"
 

@@ -1,5 +1,5 @@
 // radiance.hip -- gfx950 kernels of the sky's radiance cubemap (include/cloudsky.h csky_render_radiance*, csky_prefilter_cube; the maths:
-// radiance_core.h).  Layer 0 is the compositor's own kernel (kernels.hip composite_kernel, view_mode 2); this file holds the source-cube
+// radiance_core.h).  Layer 0 is the compositor's own kernel (lut_kernels.hip composite_kernel, view_mode 2); this file holds the source-cube
 // reduction, the bounding cones of the culling test and the GGX prefilter.
 #include <hip/hip_runtime.h>
 #include "kernels.h"

@@ -317,7 +317,7 @@ int csky_prefilter_cube(csky_ctx* ctx, const uint16_t* cube_rgba16f, int face_si
  * already set it, which works when the library is loaded before the process's first HIP call.  Below n + 2 the call succeeds, says so in
  * csky_last_warning, and the launch policy plans for the frames that can overlap (one: the plain launch form, the faster one alone).
  * With 2, whole-ray launches of 12 Ki - 64 Ki wavefronts (a 2048x1024 frame, half of it) run in the persistent form: one workgroup per
- * resident slot, wavefronts pop tiles from per-XCD sequences of the schedule and steal from the other XCDs at the end (kernels.hip,
+ * resident slot, wavefronts pop tiles from per-XCD sequences of the schedule and steal from the other XCDs at the end (cloud_kernels.hip,
  * clouds_kernel_persistent); frames are byte-identical either way.  Environment variable CSKY_PERSISTENT, read by csky_create, is the A/B
  * switch: 0 = never, 1 = this policy (default), 2 = every whole-ray launch. */
 int csky_set_frames_in_flight(csky_ctx* ctx, int frames);
@@ -413,7 +413,7 @@ int csky_generate_detail_noise_device(csky_ctx* ctx, uint32_t seed, int n, uint8
 size_t csky_mip_offset(int n, int level, int ch);
 /* 3-D mip chain (mipmaps/generate=true of the .import files): 2x2x2 box, (sum + 4) >> 3.  `vol` holds level 0 on entry and has room for
  * csky_mip_offset(n, levels, ch) bytes.  csky_build_mips runs on the host, csky_build_mips_device on the GPU (byte-identical); since round 2
- * csky_set_noise builds its chains and its device layouts on the GPU itself (kernels.hip::launch_mip_chain / launch_bake). */
+ * csky_set_noise builds its chains and its device layouts on the GPU itself (bake_kernels.hip::launch_mip_chain / launch_bake). */
 int csky_build_mips(uint8_t* vol, int n, int ch, int levels);
 int csky_build_mips_device(csky_ctx* ctx, uint8_t* vol, int n, int ch, int levels);
 /* ---- what Godot's importer wrote (godot_import.cpp; host only) ------------------------------------

@@ -55,7 +55,7 @@ int csky_variant_count(void);
  *     and view starts its workgroups heaviest first (the first launch runs in a static order);
  *     Only the ORDER comes from the previous launch; every sample is recomputed.
  * (0, 3, 4, 6 were azimuth-wedge / horizon-first orders of round 1; 8 / 9 the 'deadline' reorder and per-workgroup adaptive ray
- *  segments of round 2: all measured, no gain, removed -- kernels.hip keeps the numbers.) */
+ *  segments of round 2: all measured, no gain, removed -- docs/EXPERIMENTS.md section 5 keeps the numbers.) */
 int csky_set_schedule(csky_ctx* ctx, int mode);
 /* Ray segments: the primary march of every ray is cut into `segments` pieces marched by different wavefronts of one
  * workgroup and composited front to back (T and L are associative).  0 = auto (whole rays for large launches, 2 or 4

@@ -293,7 +293,7 @@ def test_shell_sqrt_is_ieee_exact_on_its_whole_range(gpu_ctx):
 @pytest.mark.parametrize("size", [(2048, 1024), (520, 200), (96, 24)])
 def test_persistent_launch_form_matches_plain_launches(pkg, noise, gpu_ctx, oracle, size, monkeypatch):
     """Whole-ray launches of 12 Ki - 64 Ki wavefronts with two frames in flight run in the persistent form
-    (kernels.hip::clouds_kernel_persistent: workgroups pop footprints from per-XCD sequences and steal from the other XCDs at the
+    (cloud_kernels.hip::clouds_kernel_persistent: workgroups pop footprints from per-XCD sequences and steal from the other XCDs at the
     end; the last workgroup out re-arms the pop counters).  CSKY_PERSISTENT=2 forces it for every whole-ray launch so that a ragged
     frame and one smaller than the resident grid are covered too.  Same rays, same arithmetic: frames must be byte-identical to
     plain launches, under the static and the cost-feedback order, with both ring slots in use and launch after launch."""

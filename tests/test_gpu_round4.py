@@ -18,7 +18,7 @@ def sha(a):
 
 @pytest.mark.parametrize("seed", [1, 7])
 def test_gpu_noise_bake_matches_the_independent_restatement(gpu_ctx, seed):
-    """shape_noise_kernel / detail_noise_kernel (kernels.hip; README.md:30 TODO 3, perlworlnoise.tga.import:24-27 for the layout) against hashes
+    """shape_noise_kernel / detail_noise_kernel (bake_kernels.hip; README.md:30 TODO 3, perlworlnoise.tga.import:24-27 for the layout) against hashes
     and blocks rendered by numpy, not by noise_core.h: round 3 compared the header on gfx950 with the same header on x86."""
     fix = np.load(os.path.join(GOLDEN, "noise_fixture.npz"))
     vol = gpu_ctx.generate_shape_noise(seed, 128)

@@ -3,7 +3,7 @@
 
     python tools/isa_census.py [--kernel SUBSTR] [--asm FILE.s] [--blocks] [--json OUT]
 
-Without --asm the device assembly of csrc/kernels.hip is produced with the Makefile's flags (hipcc -save-temps, gfx950, with
+Without --asm the device assembly of csrc/cloud_kernels.hip (CLOUD_SRC) is produced with the Makefile's flags (hipcc -save-temps, gfx950, with
 -gline-tables-only so that every instruction carries the source line it came from).  The census is STATIC: one entry per basic
 block with the histogram of its instructions by issue class and the loop nest it sits in.  tools/isa_profile.py combines it
 with the dynamic block counts measured on the GPU (the census build of the kernel) into the VALU-issue roofline of bench.py.
@@ -25,6 +25,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "godot-volumetric-cloud-demo-v2_amd", "csrc")
+CLOUD_SRC = "cloud_kernels.hip"      # the file of the march: what the census, the instrumented build and the line profile look at
 
 FULL = ("v_fma_f32", "v_fmac_f32", "v_mul_f32", "v_add_f32", "v_sub_f32", "v_subrev_f32", "v_mov_b32", "v_and_b32", "v_or_b32", "v_xor_b32",
         "v_add_u32", "v_sub_u32", "v_subrev_u32", "v_add_co_u32", "v_addc_co_u32", "v_sub_co_u32", "v_subb_co_u32", "v_not_b32", "v_mac_f32", "v_madak_f32", "v_madmk_f32",
@@ -74,9 +75,9 @@ def classify(mn):
 def build_asm(out_dir, extra=()):
     os.makedirs(out_dir, exist_ok=True)
     flags = ["-O3", "-std=c++17", "-fPIC", "-fno-slp-vectorize", "--offload-arch=gfx950", "-Wno-unused-function", "-Wno-unknown-pragmas", "-Wno-pass-failed",
-             "-gline-tables-only", "-save-temps", "-c", os.path.join(CSRC, "kernels.hip"), "-o", os.path.join(out_dir, "kernels.o")]
+             "-gline-tables-only", "-save-temps", "-c", os.path.join(CSRC, CLOUD_SRC), "-o", os.path.join(out_dir, "kernels.o")]
     subprocess.check_call(["/opt/rocm/bin/hipcc"] + list(extra) + flags, cwd=out_dir, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    return os.path.join(out_dir, "kernels-hip-amdgcn-amd-amdhsa-gfx950.s")
+    return os.path.join(out_dir, CLOUD_SRC[:-4] + "-hip-amdgcn-amd-amdhsa-gfx950.s")
 
 
 LABEL = re.compile(r"^([.\w$]+):")

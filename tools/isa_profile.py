@@ -5,7 +5,7 @@ Why: the roofline of bench.py prices VALU instructions by kind.  Hardware class 
 instructions are in no class counter), PC sampling is "not supported on any of the agents" on this pool
 (profiles/r03/pc_sampling_probe.txt), and a thread trace is a separate tool chain.  So the profiler is built here, at ISA level:
 
-    build   hipcc -save-temps -> the device assembly of kernels.hip (the SAME flags as the product build); every basic block of the chosen
+    build   hipcc -save-temps -> the device assembly of the cloud kernels' file (isa_census.CLOUD_SRC; the SAME flags as the product build); every basic block of the chosen
             kernels gets a counter: lane k of VGPR c of three extra VGPRs (64 counters per register), bumped by
                 s_mov_b64 s[a:b], exec ; s_mov_b32 exec_lo/hi, 1 << k ; v_add_u32 vC, 1, vC ; s_mov_b64 exec, s[a:b]
             (no memory access, no SCC/VCC, only registers above the kernel's own allocation); before every s_endpgm the 256 lane counters
@@ -166,9 +166,9 @@ def cmd_build(args):
     if not own:
         shutil.rmtree(work, ignore_errors=True)
         os.makedirs(work)
-    subprocess.check_call(["/opt/rocm/bin/hipcc"] + FLAGS + ["-save-temps", "-c", os.path.join(CSRC, "kernels.hip"), "-o", os.path.join(work, "k.o")], cwd=work,
+    subprocess.check_call(["/opt/rocm/bin/hipcc"] + FLAGS + ["-save-temps", "-c", os.path.join(CSRC, IC.CLOUD_SRC), "-o", os.path.join(work, "k.o")], cwd=work,
                           stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    asm = os.path.join(work, "kernels-hip-amdgcn-amd-amdhsa-gfx950.s")
+    asm = os.path.join(work, IC.CLOUD_SRC[:-4] + "-hip-amdgcn-amd-amdhsa-gfx950.s")
     shutil.copy(asm, os.path.join(work, "product.s"))
     lines = open(asm).read().split("\n")
     info = {}
@@ -177,16 +177,16 @@ def cmd_build(args):
         info[tag] = nb
     open(os.path.join(work, "census.s"), "w").write("\n".join(lines))
     run = lambda c: subprocess.check_call(c, cwd=work)
-    run([LLVM + "/clang", "-cc1as", "-triple", "amdgcn-amd-amdhsa", "-filetype", "obj", "-main-file-name", "kernels.hip", "-target-cpu", "gfx950", "-mrelocation-model", "pic",
+    run([LLVM + "/clang", "-cc1as", "-triple", "amdgcn-amd-amdhsa", "-filetype", "obj", "-main-file-name", IC.CLOUD_SRC, "-target-cpu", "gfx950", "-mrelocation-model", "pic",
          "-o", "dev.o", "census.s"])
     run([LLVM + "/lld", "-flavor", "gnu", "-m", "elf64_amdgpu", "--no-undefined", "-shared", "-plugin-opt=-amdgpu-internalize-symbols", "-plugin-opt=mcpu=gfx950", "-o", "dev.out", "dev.o"])
     run([LLVM + "/clang-offload-bundler", "-type=o", "-bundle-align=4096", "-targets=host-x86_64-unknown-linux-gnu,hipv4-amdgcn-amd-amdhsa--gfx950", "-input=/dev/null",
          "-input=dev.out", "-output=dev.hipfb"])
-    run(["/opt/rocm/bin/hipcc"] + FLAGS + ["--cuda-host-only", "-Xclang", "-fcuda-include-gpubinary", "-Xclang", "dev.hipfb", "-c", os.path.join(CSRC, "kernels.hip"), "-o", "kernels_host.o"])
+    run(["/opt/rocm/bin/hipcc"] + FLAGS + ["--cuda-host-only", "-Xclang", "-fcuda-include-gpubinary", "-Xclang", "dev.hipfb", "-c", os.path.join(CSRC, IC.CLOUD_SRC), "-o", "kernels_host.o"])
     out = os.path.join(ROOT, "godot-volumetric-cloud-demo-v2_amd", "libcloudsky_census.so")
-    # the product library's sources (the Makefile's SRCS), with kernels.hip replaced by its instrumented object
+    # the product library's sources (the Makefile's SRCS), with the cloud kernels' file replaced by its instrumented object
     srcs = re.search(r"^SRCS\s*=(.*)$", open(os.path.join(CSRC, "Makefile")).read(), re.M).group(1).split()
-    others = [f for f in srcs if f != "kernels.hip"]
+    others = [f for f in srcs if f != IC.CLOUD_SRC]
     subprocess.check_call(["/opt/rocm/bin/hipcc"] + FLAGS + ["-shared", "-o", out, os.path.join(work, "kernels_host.o")] + others, cwd=CSRC)
     # static census of the PRODUCT assembly (block indices are shared with the instrumentation: same splitting rule)
     static = {}
