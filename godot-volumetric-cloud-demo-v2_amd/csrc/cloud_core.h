@@ -670,8 +670,8 @@ CSKY_HD void shade_sample(const FrameConsts& fc, float phase, float t, float hf,
 //   with sat_kT = 1.001 + 4 n u, sat_kL = 2 n u, n = primary_steps (sized from the step count, <= 65536; the fp32 evaluation of hi_c itself errs by
 //   a few u, inside the 1e-3).  f2h is monotone, so f2h(hi_c) == f2h(L_c) pins the stored half.  The same holds for any SUBSET of the remaining
 //   samples in any state order, which is what lets samples a ray already has queued still be composited after the test has fired.
-// Both tests true => leaving out every later in-cloud sample of the ray stores the same four halfs.  The march still takes the ray's primary samples:
-// the in-cloud tally counts t > 0 and is part of the contract.  Headline view, coverage 0.2: 16 % of the rays fire, 9.4 % of the in-cloud samples fall
+// Both tests true => leaving out every later in-cloud sample of the ray stores the same four halfs.  Where the launch delivers the in-cloud tally the march
+// still takes the ray's primary samples (the tally counts t > 0 and is part of the contract); where it does not, the ray stops (march_compact, TALLY).  Headline view, coverage 0.2: 16 % of the rays fire, 9.4 % of the in-cloud samples fall
 // behind the firing (0.35: 27 %, 0.5: 43 %; tests/test_saturation_skip.py walks them and requires zero differing halfs).
 // Used by march_compact for whole-ray marches of the fp16-pair texture set only (cloud_kernels.hip); march() below and every other variant take all samples.
 constexpr float SAT_ALPHA_MIN = 1.0f - 0.000244140625f;       // 1 - 2^-12

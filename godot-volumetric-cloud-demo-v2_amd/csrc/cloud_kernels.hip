@@ -230,9 +230,15 @@ __device__ __forceinline__ void light_march_terms(const TS& T, const FrameConsts
 // samples, but a t > 0 one is counted (ballot + popcount into a wave-uniform tally) instead of queued, so its light march and shading are never run and
 // `incloud` is what the full march counts.  The test runs once per flush, after the replay, on the state already in registers, and only when some lane not
 // yet latched has reached the alpha threshold; samples a latched ray still has in the queue are composited as usual (the bound covers any subset).
-template <bool WHOLE, class TS>
+// TALLY: the launch delivers `incloud` (launch_clouds: it was given d_stats or d_wg_cost).  Without it the count has no reader, and with SAT a latched
+// ray is DEAD: `live` goes false as on the early_eps path, the lane takes no further primary sample (weather, shape and detail taps, pow) and answers
+// false to `below_top`, so the every-4th-step ballot ends the wavefront once every lane is latched or above the window.  The queue receives the same
+// samples in the same order either way (a latched ray's were never queued), so flushes, latch tests and the stored halfs are those of TALLY = true
+// (tests/tilewalk emulates both per tile; tests/test_gpu_latched_rays.py compares the frames).  MarchOut::incloud is 0 and must not be read.
+template <bool WHOLE, bool TALLY, class TS>
 __device__ __forceinline__ MarchOut march_compact(const TS& T, const FrameConsts& fc, Ray ray, float* __restrict__ q, int step_begin, int step_end) {
     constexpr bool SAT = WHOLE && !TS::cell32;
+    constexpr bool DEAD = SAT && !TALLY;                      // a latched ray stops marching
     float* __restrict__ ev_px = q;
     float* __restrict__ ev_py = q + CQ_CAP;
     float* __restrict__ ev_pz = q + 2 * CQ_CAP;
@@ -251,10 +257,10 @@ __device__ __forceinline__ MarchOut march_compact(const TS& T, const FrameConsts
     const float nd = -fc.density;
     bool live = ray.above;
     int count = 0, cs = 0;                                    // queued samples / steps owning them (uniform)
-    bool latched = false;                                     // saturation skip: this lane's ray is saturated (SAT only)
-    unsigned skipped = 0u;                                    // in-cloud samples of latched rays, counted and not queued (uniform)
+    bool latched = false;                                     // saturation skip: this lane's ray is saturated (SAT && TALLY only: a DEAD ray is `!live`)
+    unsigned skipped = 0u;                                    // in-cloud samples of latched rays, counted and not queued (uniform; TALLY only)
     unsigned* __restrict__ tally = st_base + CQ_STEPS;          // in-cloud samples composited by this wavefront, kept in LDS (round 4: neither a per-lane accumulator register
-    if (lane == 0) tally[0] = 0u;                             // in the march loops nor a scalar one in the SGPR-starved persistent form; one ds_add per flush)
+    if constexpr (TALLY) { if (lane == 0) tally[0] = 0u; }    // in the march loops nor a scalar one in the SGPR-starved persistent form; one ds_add per flush)
     // the two per-ray constants a queued sample carries (step length, phase value) live in LDS, not in registers held across the whole march: the
     // persistent form had spilled `phase` to scratch and re-loaded it, behind a vmcnt(0), at every step with an in-cloud sample (round 4 census)
     float* __restrict__ ray_ss = reinterpret_cast<float*>(tally + 2);
@@ -280,7 +286,7 @@ __device__ __forceinline__ MarchOut march_compact(const TS& T, const FrameConsts
                 have = t > 0.0f;                                                                               // :184
                 below_top = !(hf >= fc.hf_hi);
             }
-            if constexpr (SAT) {
+            if constexpr (SAT && TALLY) {
                 skipped += (unsigned)__popcll(__builtin_amdgcn_ballot_w64(have && latched));
                 have = have && !latched;
             }
@@ -309,7 +315,7 @@ __device__ __forceinline__ MarchOut march_compact(const TS& T, const FrameConsts
         wave_lds_fence();
         const int n = count < 64 ? count : 64;
         unsigned long long carry = 0ull;                     // lanes of the last step whose sample is still queued
-        if (lane == 0) tally[0] += (unsigned)n;
+        if constexpr (TALLY) { if (lane == 0) tally[0] += (unsigned)n; }
         if (lane < n) {
             float Dr, Dg, Db, rq, dt;
             light_march_terms(T, fc, ls, nd, ev_px[lane], ev_py[lane], ev_pz[lane],
@@ -329,7 +335,15 @@ __device__ __forceinline__ MarchOut march_compact(const TS& T, const FrameConsts
             }
             if (s == cs - 1) carry = __builtin_amdgcn_ballot_w64(mine && slot >= n);
         }
-        if constexpr (SAT) {
+        if constexpr (DEAD) {
+            const bool cand = live && alpha >= SAT_ALPHA_MIN;
+            if (fc.sat_skip != 0 && __builtin_amdgcn_ballot_w64(cand) != 0ull) {
+                float B[3];
+                ray_saturation_bound(fc, ray_ph[lane], B);
+                const float L[3] = {Lr, Lg, Lb};
+                if (cand && ray_saturated(fc, Tr, alpha, L, B)) live = false;
+            }
+        } else if constexpr (SAT) {
             const bool cand = !latched && alpha >= SAT_ALPHA_MIN;
             if (fc.sat_skip != 0 && __builtin_amdgcn_ballot_w64(cand) != 0ull) {
                 float B[3];
@@ -361,7 +375,7 @@ __device__ __forceinline__ MarchOut march_compact(const TS& T, const FrameConsts
     }
     wave_lds_fence();
     o.r = acc[128 + lane]; o.g = acc[192 + lane]; o.b = acc[256 + lane]; o.a = sat(acc[64 + lane]); o.t = acc[lane];   // :213-214
-    o.incloud = lane == 0 ? tally[0] + skipped : 0u;
+    if constexpr (TALLY) o.incloud = lane == 0 ? tally[0] + skipped : 0u;
     return o;
 }
 
@@ -573,7 +587,7 @@ __global__ __launch_bounds__(1024) void clouds_kernel_lds(TexSet T, const FrameC
                                // together) 7 waves x 72 VGPRs beat 8 waves x 64 VGPRs + spills: whole frame 1.83 -> 1.80 ms, 1/4 frame 0.49 -> 0.48
 #endif
 // One workgroup's footprint (4 tiles / SEG): `logical` = slab * tiles_x + bx, `rec` = its position in the launch order (the persistent form: its cost-feedback slot).
-template <int VARIANT, int SEG, class TS = TexSet>
+template <int VARIANT, int SEG, class TS = TexSet, bool TALLY = true>
 __device__ __forceinline__ void render_block(TS T, const FrameConsts* __restrict__ fcp, const RenderGeom& G, const uint32_t logical, const uint32_t rec,
                                              uint2* __restrict__ out, unsigned long long* __restrict__ stats, uint32_t* __restrict__ wg_cost, const int tile_of_wave = -1) {
     constexpr int BW = 32 / SEG;                               // workgroup footprint width in pixels
@@ -602,7 +616,7 @@ __device__ __forceinline__ void render_block(TS T, const FrameConsts* __restrict
     } else {
         __shared__ float lds[4][VARIANT == 3 ? CQ_FLOATS : Q_FLOATS];
         const int s0 = (fc.primary_steps * seg) / SEG, s1 = (fc.primary_steps * (seg + 1)) / SEG;
-        if constexpr (VARIANT == 3) o = march_compact<SEG == 1>(T, fc, ray, &lds[wave][0], s0, s1);
+        if constexpr (VARIANT == 3) o = march_compact<SEG == 1, TALLY>(T, fc, ray, &lds[wave][0], s0, s1);
         else o = march_queue(T, fc, ray, &lds[wave][0], s0, s1);
         if constexpr (SEG > 1) {
             __shared__ float comb[4][5][64];
@@ -623,6 +637,7 @@ __device__ __forceinline__ void render_block(TS T, const FrameConsts* __restrict
     if (valid && seg == 0) {
         store_pixel(out, G, gx, gy, lr, o.r, o.g, o.b, o.a);
     }
+    if constexpr (TALLY) {
     if (stats || wg_cost) {
         unsigned ic = o.incloud, ab = (ray.above && seg == 0) ? 1u : 0u;
         for (int off = 32; off > 0; off >>= 1) { ic += __shfl_down(ic, off); ab += __shfl_down(ab, off); }
@@ -631,14 +646,16 @@ __device__ __forceinline__ void render_block(TS T, const FrameConsts* __restrict
             if (wg_cost) atomicAdd(&wg_cost[logical], ic + 16u * ab);   // cost model of the feedback schedule: light marches + live primary marches
         }
     }
+    }
 }
 
-template <int VARIANT, int SEG, class TS = TexSet>
+// TALLY = false (the whole-ray compact kernel only): a launch nobody asked for counts; `stats` and `wg_cost` keep their place in the argument list and are not touched
+template <int VARIANT, int SEG, class TS = TexSet, bool TALLY = true>
 __global__ __launch_bounds__(256, VARIANT == 3 ? CSKY_COMPACT_WAVES : 7) void clouds_kernel(TS T, const FrameConsts* __restrict__ fcp, RenderGeom G, const uint32_t* __restrict__ order,
                                                      uint2* __restrict__ out, unsigned long long* __restrict__ stats, uint32_t* __restrict__ wg_cost) {
     const uint32_t logical = order[blockIdx.x];
     if (logical == 0xffffffffu) return;                        // workgroup-uniform
-    render_block<VARIANT, SEG, TS>(T, fcp, G, logical, blockIdx.x, out, stats, wg_cost);
+    render_block<VARIANT, SEG, TS, TALLY>(T, fcp, G, logical, blockIdx.x, out, stats, wg_cost);
 }
 
 // Persistent form of the whole-ray kernel: the launch is only as large as the chip holds (CUs x resident workgroups) and its
@@ -658,7 +675,7 @@ __global__ __launch_bounds__(256, VARIANT == 3 ? CSKY_COMPACT_WAVES : 7) void cl
 //     wavefront out zeroes them again (a memset node in front of every launch cost 46 us on a busy chip).
 // Used for launches of 12 Ki - 64 Ki wavefronts while two frames are in flight (launch_policy.h has the policy and the
 // numbers; profiles/r02/persistent_launch_ab.txt).
-template <int VARIANT>
+template <int VARIANT, bool TALLY = true>
 __global__ __launch_bounds__(256, VARIANT == 3 ? CSKY_COMPACT_WAVES : 7) void clouds_kernel_persistent(TexSet T, const FrameConsts* __restrict__ fcp, RenderGeom G,
         const uint32_t* __restrict__ order, const uint32_t n_items, uint32_t* __restrict__ heads, uint2* __restrict__ out, unsigned long long* __restrict__ stats,
         uint32_t* __restrict__ wg_cost) {
@@ -711,7 +728,7 @@ __global__ __launch_bounds__(256, VARIANT == 3 ? CSKY_COMPACT_WAVES : 7) void cl
             }
             return;
         }
-        if (logical != 0xffffffffu) render_block<VARIANT, 1>(T, fcp, G, logical, rec, out, stats, wg_cost, tile);
+        if (logical != 0xffffffffu) render_block<VARIANT, 1, TexSet, TALLY>(T, fcp, G, logical, rec, out, stats, wg_cost, tile);
     }
 }
 
@@ -828,22 +845,27 @@ int cloud_variant_count() { return (int)(sizeof(kVariantNames) / sizeof(kVariant
 const char* cloud_variant_name(int v) { return (v >= 0 && v < cloud_variant_count()) ? kVariantNames[v] : nullptr; }
 
 hipError_t launch_clouds(int variant, int seg, const TexSet& t, const FrameConsts* d_fc, const RenderGeom& g, const uint32_t* d_order, int grid,
-                         uint2* d_out, unsigned long long* d_stats, uint32_t* d_wg_cost, hipStream_t s, uint32_t* d_heads, int resident, const TexSet32* t32) {
+                         uint2* d_out, unsigned long long* d_stats, uint32_t* d_wg_cost, hipStream_t s, uint32_t* d_heads, int resident, const TexSet32* t32, bool census_lean) {
     if (grid <= 0) return hipSuccess;
+    // the in-cloud count has a reader only when the launch was given somewhere to put it: without one the whole-ray compact kernel runs in the form whose
+    // latched rays stop marching (march_compact, TALLY = false).  census_lean: that form WITH a stats buffer, which only the census build's counters write.
+    const bool tally = (d_stats != nullptr || d_wg_cost != nullptr) && !census_lean;
     if (t32) {                                                 // exact fp32-coefficient cells: the compact whole-ray kernel on the other texture-set type
         if (variant != 3 || seg != 1) return hipErrorInvalidValue;
         clouds_kernel<3, 1, TexSet32><<<grid, 256, 0, s>>>(*t32, d_fc, g, d_order, d_out, d_stats, d_wg_cost);
         return hipGetLastError();
     }
     if (d_heads && variant == 3 && seg == 1) {                 // persistent form, see clouds_kernel_persistent
-        clouds_kernel_persistent<3><<<grid < resident ? grid : resident, 256, 0, s>>>(t, d_fc, g, d_order, (uint32_t)grid, d_heads, d_out, d_stats, d_wg_cost);
+        if (tally) clouds_kernel_persistent<3, true><<<grid < resident ? grid : resident, 256, 0, s>>>(t, d_fc, g, d_order, (uint32_t)grid, d_heads, d_out, d_stats, d_wg_cost);
+        else clouds_kernel_persistent<3, false><<<grid < resident ? grid : resident, 256, 0, s>>>(t, d_fc, g, d_order, (uint32_t)grid, d_heads, d_out, d_stats, d_wg_cost);
         return hipGetLastError();
     }
     if (variant == 0 && seg == 1) clouds_kernel<0, 1><<<grid, 256, 0, s>>>(t, d_fc, g, d_order, d_out, d_stats, d_wg_cost);
     else if (variant == 1 && seg == 1) clouds_kernel<1, 1><<<grid, 256, 0, s>>>(t, d_fc, g, d_order, d_out, d_stats, d_wg_cost);
     else if (variant == 1 && seg == 2) clouds_kernel<1, 2><<<grid, 256, 0, s>>>(t, d_fc, g, d_order, d_out, d_stats, d_wg_cost);
     else if (variant == 1 && seg == 4) clouds_kernel<1, 4><<<grid, 256, 0, s>>>(t, d_fc, g, d_order, d_out, d_stats, d_wg_cost);
-    else if (variant == 3 && seg == 1) clouds_kernel<3, 1><<<grid, 256, 0, s>>>(t, d_fc, g, d_order, d_out, d_stats, d_wg_cost);
+    else if (variant == 3 && seg == 1 && tally) clouds_kernel<3, 1, TexSet, true><<<grid, 256, 0, s>>>(t, d_fc, g, d_order, d_out, d_stats, d_wg_cost);
+    else if (variant == 3 && seg == 1) clouds_kernel<3, 1, TexSet, false><<<grid, 256, 0, s>>>(t, d_fc, g, d_order, d_out, d_stats, d_wg_cost);
     else if (variant == 3 && seg == 2) clouds_kernel<3, 2><<<grid, 256, 0, s>>>(t, d_fc, g, d_order, d_out, d_stats, d_wg_cost);
     else if (variant == 3 && seg == 4) clouds_kernel<3, 4><<<grid, 256, 0, s>>>(t, d_fc, g, d_order, d_out, d_stats, d_wg_cost);
     else if ((variant == 1 || variant == 3) && seg == 5) {                      // 5 = 4 interleaved segments, one tile per workgroup, 76 KB of LDS

@@ -171,7 +171,7 @@ int clouds_dev(csky_ctx* c, const csky_cloud_params* p, int tile_w, const csky_b
     // second stream at equal or lowest priority to back-fill the tail: one frame at a time 2.00 -> 2.00-2.05 ms, frames identical.  The tail is the last wavefronts'
     // serial chains, not idle slots; the next frame fills it.)
     {   // a failed persistent launch may leave the slot's pop counters armed: re-zero them so that the next launch on this slot starts clean
-        const hipError_t le = launch_clouds(pl.variant, pl.seg, texset(c), c->d_fc, g, order, grid, d_out, d_stats, cost, s, heads, c->resident_wgs, t32p);
+        const hipError_t le = launch_clouds(pl.variant, pl.seg, texset(c), c->d_fc, g, order, grid, d_out, d_stats, cost, s, heads, c->resident_wgs, t32p, c->census_lean);
         if (le != hipSuccess) { if (heads) (void)hipMemsetAsync(heads, 0, 16 * sizeof(uint32_t), s); return fail(c, CSKY_ERR_HIP, "cloud kernel launch failed: %s", hipGetErrorString(le)); }
     }
     if (kt) HIPCHK(c, hipEventRecord(kt[1], s));

@@ -82,6 +82,7 @@ struct csky_ctx {
     uint8_t* d_rad_io = nullptr; size_t rad_io_cap = 0;                    // host forms: uploaded inputs + the requested output layers
     hipEvent_t ev_rad = nullptr;                                           // the transmittance LUT (prologue stream) -> layer 0 (caller's stream)
     csky_cloud_stats last_stats = {0, 0, 0};
+    bool census_lean = false;                                  // csky_census_clouds unless CSKY_CENSUS_TALLY=1: count the blocks of the kernel form that keeps no in-cloud tally (kernels.h launch_clouds)
     // asynchronous host form (csky_submit_clouds / csky_collect): a ring of pinned host frames + device frames on rotating internal streams
     struct HostSlot { hipStream_t s = nullptr; hipEvent_t done = nullptr; uint2* d = nullptr; void* h = nullptr; size_t px = 0; long long ticket = -1; int w = 0, hh = 0; bool busy = false; };
     HostSlot hring[HOST_RING]; int hslots = 2; long long next_ticket = 0;

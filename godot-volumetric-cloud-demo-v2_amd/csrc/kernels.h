@@ -49,12 +49,14 @@ hipError_t launch_bake32(const uint8_t* d_large_chain, const uint8_t* d_small_ch
 
 // ------------------------------------------------------------------------------------------------ cloud_kernels.hip
 // clouds.glsl main() over the rows described by `g`.  d_stats (may be null): [0] += in-cloud samples,
-// [1] += rays above the horizon.
+// [1] += rays above the horizon.  With neither d_stats nor d_wg_cost the whole-ray compact kernel (variant 3, seg 1, fp16-pair cells) runs without its
+// in-cloud tally and stops marching a ray once its stored pixel is final (cloud_kernels.hip march_compact, TALLY = false); the frame is the same.
+// census_lean: launch that form although d_stats is given (csky_census_clouds: the census build's block counters are the buffer's only writers then).
 // seg = ray segments per ray (1, 2 or 4; variant 1 only): a workgroup covers 4/seg tiles of 8x8 pixels.
 // d_order[grid]: physical workgroup -> workgroup-footprint id (0xffffffff = idle), see clouds_launch.cpp::clouds_dev.
 hipError_t launch_clouds(int variant, int seg, const TexSet& t, const FrameConsts* d_fc, const RenderGeom& g, const uint32_t* d_order, int grid,
                          uint2* d_out, unsigned long long* d_stats, uint32_t* d_wg_cost, hipStream_t s, uint32_t* d_heads = nullptr, int resident = 0,
-                         const TexSet32* t32 = nullptr);   // t32: march on the exact fp32-coefficient cells (variant 3, seg 1 only)
+                         const TexSet32* t32 = nullptr, bool census_lean = false);   // t32: march on the exact fp32-coefficient cells (variant 3, seg 1 only)
 // resident 256-thread workgroups per CU of the "compact" kernel (its launch bound): the size of a persistent launch
 int cloud_resident_workgroups_per_cu();
 int cloud_variant_count();

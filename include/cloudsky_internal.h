@@ -16,7 +16,9 @@ extern "C" {
 /* ---- measurement ---------------------------------------------------------------------------------
  * Times `iters` back-to-back launches of the cloud kernel alone with HIP events on the context's stream
  * (after `warmup` untimed launches) and returns the mean per-launch milliseconds.  Also fills the
- * sample counters of one launch (the kernel's own tallies). */
+ * sample counters of one launch (the kernel's own tallies).  The counters come from the FIRST, untimed launch, which is given the stats
+ * buffer; the warm-up and timed launches are given none, like csky_render_clouds_device, and so run the kernel form that keeps no in-cloud
+ * tally and stops marching a ray whose stored pixel is final.  The counts are exact (the full march's); the time is the headline path's. */
 int csky_time_clouds(csky_ctx* ctx, const csky_cloud_params* p, int tile_w, const csky_bands* bands, int warmup,
                      int iters, float* mean_ms, csky_cloud_stats* stats);
 int csky_get_cloud_stats(csky_ctx* ctx, csky_cloud_stats* stats); /* tallies of the last stats-enabled launch */

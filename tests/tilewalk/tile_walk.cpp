@@ -1,0 +1,246 @@
+// tile_walk.cpp -- TEST TOOL ONLY.  A CPU emulation of the compact march (cloud_kernels.hip march_compact, whole rays, fp16-pair cells) on the kernel
+// cores (cloud_core.h, compiled for the host): per 8x8-pixel tile, 64 rays in lock step exactly as one wavefront runs them --
+//   A. one primary sample per live lane and step; the lanes whose sample is in cloud append it to the tile's queue in lane order, the step records its
+//      lane mask and base slot; every 4th step the march ends if no lane is below the top of the height window;
+//   B. as soon as 64 samples are queued (or the march has ended) the first min(count, 64) get their light march and shade_terms;
+//   C. the recorded steps are replayed in order and the owners composite the evaluated samples; the saturation test (cloud_core.h ray_saturated) runs
+//      once, after the replay, on the state the replay left; samples not evaluated move to the front with the part of the last step that owns them.
+// Two forms, as the kernel's TALLY template parameter selects them:
+//   tally = 1  a latched lane keeps taking its primary samples; an in-cloud one is counted, not queued (the launch delivers the in-cloud count);
+//   tally = 0  a latched lane is dead: no further primary sample, `false` to the below-the-top ballot.
+// Against the plain walk of every ray (all samples, one ray at a time) it reports light-marched samples, wave-steps, lane-steps per stage of
+// sample_density (CSKY_TRACE_STAGES) and the rays whose four stored halfs differ -- which must be none.
+// alpha_min >= 0 is the MUTATION CONTROL: that alpha threshold in place of SAT_ALPHA_MIN (and the colour bound scaled by b_scale).
+#include <cstdint>
+#include <cstring>
+#include <thread>
+#include <vector>
+#define CSKY_TRACE_STAGES 1
+#include "../../godot-volumetric-cloud-demo-v2_amd/csrc/cloud_core.h"
+#include "../../godot-volumetric-cloud-demo-v2_amd/csrc/bake.h"
+namespace csky { thread_local int csky_stage = 0; }
+
+using namespace csky;
+
+static size_t mip_offset(int n, int level, int ch) {
+    size_t off = 0;
+    for (int l = 0; l < level; l++) { size_t m = (size_t)(n >> l); off += m * m * m * (size_t)ch; }
+    return off;
+}
+
+// ray_saturated with another alpha threshold and a scaled bound (alpha_min < 0: the product's predicate itself)
+static bool saturated(const FrameConsts& fc, float T, float alpha, const float L[3], const float B[3], float alpha_min, float b_scale) {
+    if (alpha_min < 0.0f) return ray_saturated(fc, T, alpha, L, B);
+    bool s = alpha >= alpha_min;
+    for (int c = 0; c < 3; c++) {
+        const float hi = L[c] + (B[c] * b_scale * T * fc.sat_kT + L[c] * fc.sat_kL);
+        s = s && L[c] >= 6.103515625e-5f && hi < 65504.0f && f2h(hi) == f2h(L[c]);
+    }
+    return s;
+}
+
+// out[] of tile_walk(), one block per march
+enum { PLAIN = 0, TALLY1 = 8, TALLY0 = 16, N_OUT = 24 };
+// block layout: 0 light-marched samples, 1 in-cloud count delivered (light-marched + counted behind the latch), 2 wave-steps, 3 lane-steps inside the
+// height window (weather tap), 4 reaching the shape tap, 5 reaching the detail tap, 6 rays whose stored halfs differ from the plain walk, 7 rays latched
+struct Tally { double v[N_OUT] = {0}; double rays = 0; };
+
+struct Sample { float px, py, pz, t, hf; int owner; };
+struct Step { uint64_t mask; int base; };
+struct Terms { float Dr, Dg, Db, rq, dt; };
+
+// the light march of one queued sample and the state-independent half of its shading (cloud_kernels.hip light_march_terms)
+static Terms light_terms(const TexSet& T, const FrameConsts& fc, const Sample& e, float ss, float phase) {
+    const float nd = -fc.density;
+    float lx = e.px, ly = e.py, lz = e.pz, cd = 0.0f;
+    for (int j = 0; j < fc.light_steps; j++) {
+        advance(lx, ly, lz, fc.linc[j][0], fc.linc[j][1], fc.linc[j][2]);
+        const float lhf = height_fraction(length3_shell(lx, ly, lz));
+        cd += sample_density(T, fc, lx, ly, lz, lhf, fc.wpos_x, fc.wpos_y, j > 2 ? j - 2 : 0, j);
+    }
+    lx = e.px; ly = e.py; lz = e.pz;
+    advance(lx, ly, lz, fc.ldist[0], fc.ldist[1], fc.ldist[2]);
+    const float lhf = height_fraction(length3_shell(lx, ly, lz));
+    const float ld = sample_density(T, fc, lx, ly, lz, lhf, 0.0f, 0.0f, 3, 5);
+    cd += fast_pow(ld, (1.0f - lhf) * 0.8f + 0.5f);
+    Terms r;
+    r.dt = fast_exp(nd * e.t * ss);
+    shade_terms(fc, phase, e.t, e.hf, r.dt, cd, r.Dr, r.Dg, r.Db, r.rq);
+    return r;
+}
+
+static void count_stage(double* v) {
+    const int st = csky_stage;                                  // 0 outside the window, 1 weather tap only, 2 + shape tap, 3 + detail tap
+    if (st >= 1) v[3]++;
+    if (st >= 2) v[4]++;
+    if (st >= 3) v[5]++;
+}
+
+struct Pixel { uint16_t h[4]; };
+static Pixel stored(float r, float g, float b, float alpha) { return Pixel{{f2h(r), f2h(g), f2h(b), f2h(sat(alpha))}}; }
+
+// the plain walk of one ray: every sample, cloud_core.h march() with the stage counts
+static Pixel plain_ray(const TexSet& T, const FrameConsts& fc, const Ray& ray, float phase, double* v) {
+    float Tr = 1.0f, alpha = 0.0f, Lr = 0.0f, Lg = 0.0f, Lb = 0.0f;
+    float px = ray.px, py = ray.py, pz = ray.pz;
+    for (int i = 0; i < fc.primary_steps; i++) {
+        advance(px, py, pz, ray.sx, ray.sy, ray.sz);
+        const float hf = height_fraction(length3_shell(px, py, pz));
+        const float t = sample_density(T, fc, px, py, pz, hf, fc.wpos_x, fc.wpos_y, 0, 0);
+        count_stage(v);
+        if (!(t > 0.0f)) continue;
+        v[0]++; v[1]++;
+        const Sample e{px, py, pz, t, hf, 0};
+        const Terms q = light_terms(T, fc, e, ray.ss, phase);
+        composite_sample(q.dt, q.rq, q.Dr, q.Dg, q.Db, Tr, alpha, Lr, Lg, Lb);
+    }
+    return stored(Lr, Lg, Lb, alpha);
+}
+
+// one tile through march_compact; ref[lane]: the plain walk's stored pixel
+static void compact_tile(const TexSet& T, const FrameConsts& fc, const Ray rays[64], const float phase[64], const bool valid[64], bool tally, float alpha_min,
+                         float b_scale, const Pixel ref[64], double* v) {
+    bool live[64], latched[64];
+    float px[64], py[64], pz[64], Tr[64], alpha[64], L[64][3];
+    bool any = false;
+    for (int l = 0; l < 64; l++) {
+        live[l] = rays[l].above; latched[l] = false; any = any || live[l];
+        px[l] = rays[l].px; py[l] = rays[l].py; pz[l] = rays[l].pz;
+        Tr[l] = 1.0f; alpha[l] = 0.0f; L[l][0] = L[l][1] = L[l][2] = 0.0f;
+    }
+    const float amin = alpha_min < 0.0f ? SAT_ALPHA_MIN : alpha_min;
+    std::vector<Sample> q; q.reserve(128);
+    std::vector<Step> steps; steps.reserve(66);
+    std::vector<Terms> terms(64);
+    double marched = 0, skipped = 0;                             // samples light-marched / in-cloud samples of latched rays, counted and not queued
+    if (any) {
+        int end = fc.primary_steps;
+        for (int i = 0;;) {
+            if (i < end) {                                                   // ---- A
+                uint64_t m = 0; bool below_top = false;
+                Sample cand[64];
+                for (int l = 0; l < 64; l++) {
+                    if (!live[l]) continue;
+                    advance(px[l], py[l], pz[l], rays[l].sx, rays[l].sy, rays[l].sz);
+                    const float hf = height_fraction(length3_shell(px[l], py[l], pz[l]));
+                    const float t = sample_density(T, fc, px[l], py[l], pz[l], hf, fc.wpos_x, fc.wpos_y, 0, 0);
+                    count_stage(v);
+                    bool have = t > 0.0f;
+                    below_top = below_top || !(hf >= fc.hf_hi);
+                    if (tally && have && latched[l]) { skipped++; have = false; }
+                    if (have) { m |= 1ull << l; cand[l] = Sample{px[l], py[l], pz[l], t, hf, l}; }
+                }
+                v[2]++;
+                if ((i & 3) == 3 && !below_top) end = i + 1;
+                if (m) {
+                    steps.push_back(Step{m, (int)q.size()});
+                    for (int l = 0; l < 64; l++) if ((m >> l) & 1) q.push_back(cand[l]);
+                }
+                i++;
+            }
+            const bool last = i >= end;
+            const int count = (int)q.size();
+            if (count == 0) { if (last) break; continue; }
+            if (count < 64 && !last) continue;
+            const int n = count < 64 ? count : 64;                           // ---- B
+            marched += n;
+            for (int k = 0; k < n; k++) terms[k] = light_terms(T, fc, q[k], rays[q[k].owner].ss, phase[q[k].owner]);
+            uint64_t carry = 0;                                              // ---- C
+            for (size_t s = 0; s < steps.size(); s++) {
+                int slot = steps[s].base;
+                for (int l = 0; l < 64; l++) {
+                    if (!((steps[s].mask >> l) & 1)) continue;
+                    if (slot < n) {
+                        const Terms& e = terms[slot];
+                        composite_sample(e.dt, e.rq, e.Dr, e.Dg, e.Db, Tr[l], alpha[l], L[l][0], L[l][1], L[l][2]);
+                    } else if (s + 1 == steps.size()) carry |= 1ull << l;
+                    slot++;
+                }
+            }
+            if (fc.sat_skip) {
+                for (int l = 0; l < 64; l++) {
+                    const bool open = tally ? !latched[l] : live[l];
+                    if (!(open && alpha[l] >= amin)) continue;
+                    float B[3];
+                    ray_saturation_bound(fc, phase[l], B);
+                    if (saturated(fc, Tr[l], alpha[l], L[l], B, alpha_min, b_scale)) {
+                        v[7]++;
+                        if (tally) latched[l] = true; else live[l] = false;
+                    }
+                }
+            }
+            q.erase(q.begin(), q.begin() + n);
+            steps.clear();
+            if (!q.empty()) steps.push_back(Step{carry, 0});
+            if (last && q.empty()) break;
+        }
+    }
+    v[0] += marched; v[1] += marched + skipped;                             // (tally = 0 delivers no count: v[1] is then what it marched)
+    for (int l = 0; l < 64; l++) {
+        if (!valid[l] || !rays[l].above) continue;
+        const Pixel p = stored(L[l][0], L[l][1], L[l][2], alpha[l]);
+        if (memcmp(&p, &ref[l], sizeof p) != 0) v[6]++;
+    }
+}
+
+static void walk_tiles(const TexSet& T, const FrameConsts& fc, int w, int h, int tile0, int tile1, float alpha_min, float b_scale, Tally& out) {
+    const int tiles_x = (w + 7) / 8;
+    for (int tile = tile0; tile < tile1; tile++) {
+        const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+        Ray rays[64]; float phase[64]; bool valid[64]; Pixel ref[64];
+        for (int l = 0; l < 64; l++) {
+            const int gx = tx * 8 + (l & 7), gy = ty * 8 + (l >> 3);
+            valid[l] = gx < w && gy < h;
+            rays[l] = ray_setup(fc, valid[l] ? gx : 0, valid[l] ? gy : 0);
+            if (!valid[l]) rays[l].above = false;
+            phase[l] = 0.0f;
+            ref[l] = Pixel{{0, 0, 0, 0}};
+            if (!rays[l].above) continue;
+            out.rays++;
+            const float ct = fc.ldir[0] * rays[l].dx + fc.ldir[1] * rays[l].dy + fc.ldir[2] * rays[l].dz;
+            phase[l] = fmaxf(fmaxf(henyey_greenstein(ct, 0.6f), henyey_greenstein(ct, fc.hg_g2)), henyey_greenstein(ct, -0.2f));
+            ref[l] = plain_ray(T, fc, rays[l], phase[l], out.v + PLAIN);
+        }
+        for (int mode = 0; mode < 2; mode++) {
+            double* v = out.v + (mode == 0 ? TALLY1 : TALLY0);
+            compact_tile(T, fc, rays, phase, valid, mode == 0, alpha_min, b_scale, ref, v);
+        }
+    }
+}
+
+extern "C" {
+// out[24]: three blocks of 8 (plain walk, tally = 1, tally = 0; layout above); out_misc[2] = above-horizon rays, fc.sat_skip
+void tile_walk(const uint8_t* large_chain, const uint8_t* small_chain, const uint8_t* weather_rgb8, const float params[28], int primary_steps, int light_steps,
+               const uint16_t* sky_h, int sw, int sh, int w, int h, float alpha_min, float b_scale, int threads, double out[24], double out_misc[2]) {
+    std::vector<uint8_t> lc(large_chain, large_chain + mip_offset(SHAPE_N, SHAPE_LEVELS, 4));
+    std::vector<uint8_t> sc(small_chain, small_chain + mip_offset(DETAIL_N, DETAIL_LEVELS, 3));
+    std::vector<ShapeTexel> shape; std::vector<uint4> detail, weather;
+    uint32_t so[SHAPE_LEVELS], dof[DETAIL_LEVELS];
+    bake_shape(lc, shape, so); bake_detail(sc, detail, dof); bake_weather(weather_rgb8, weather);
+    std::vector<float4> sky((size_t)sw * sh);
+    for (size_t i = 0; i < sky.size(); i++) sky[i] = float4{h2f(sky_h[4 * i]), h2f(sky_h[4 * i + 1]), h2f(sky_h[4 * i + 2]), h2f(sky_h[4 * i + 3])};
+    TexSet T; T.shape = shape.data(); T.detail = detail.data(); T.weather = weather.data(); T.sky = sky.data(); T.sky_w = sw; T.sky_h = sh;
+    T.detail_h = nullptr; T.detail_lds = nullptr;
+    { const uint8_t* t5 = sc.data() + mip_offset(DETAIL_N, 5, 3); T.detail_lod5 = (float)(5 * t5[0] + 2 * t5[1] + t5[2]) * (1.0f / (8.0f * 255.0f)); }
+    int rmin = 255, rmax = 0, bmax = 0;
+    for (size_t i = 0; i < (size_t)WEATHER_N * WEATHER_N; i++) { const int r = weather_rgb8[3 * i], b = weather_rgb8[3 * i + 2]; rmin = r < rmin ? r : rmin; rmax = r > rmax ? r : rmax; bmax = b > bmax ? b : bmax; }
+    CloudParams P; memcpy(&P, params, sizeof P);
+    float hlo, hhi;
+    height_window((double)P.cloud_coverage, rmin / 255.0, rmax / 255.0, bmax / 255.0, hlo, hhi);
+    FrameConsts fc;
+    frame_setup(P, sky.data(), sw, sh, primary_steps, light_steps, 0.0f, hlo, hhi, fc);
+    fc.ct_mode = rmin >= 128 ? 1 : (rmax <= 127 ? 2 : 0);
+    const int nt = threads < 1 ? 1 : threads;
+    const int tiles = ((w + 7) / 8) * ((h + 7) / 8);
+    std::vector<Tally> tl(nt);
+    std::vector<std::thread> th;
+    const int chunk = 16;                                        // interleaved chunks of tiles: the cloudy rows are not one thread's
+    for (int k = 0; k < nt; k++) th.emplace_back([&, k] {
+        for (int t0 = k * chunk; t0 < tiles; t0 += nt * chunk) walk_tiles(T, fc, w, h, t0, t0 + chunk < tiles ? t0 + chunk : tiles, alpha_min, b_scale, tl[k]);
+    });
+    for (auto& t : th) t.join();
+    for (int i = 0; i < N_OUT; i++) out[i] = 0;
+    out_misc[0] = 0; out_misc[1] = fc.sat_skip;
+    for (const Tally& t : tl) { for (int i = 0; i < N_OUT; i++) out[i] += t.v[i]; out_misc[0] += t.rays; }
+}
+}

@@ -59,12 +59,30 @@ def kernels_of(asm_files):
 
 
 def base_name(mangled):
-    """_ZN4csky23frame_setup_taps_kernelILi0EEEv... -> frame_setup_taps_kernel<0>: enough to pair a kernel across a change of its parameters"""
+    """_ZN4csky23frame_setup_taps_kernelILi0EEEv... -> frame_setup_taps_kernel<0>: enough to pair a kernel across a change of its parameters.
+    Template arguments may be integers, class names of the namespace and bools; a trailing `true` is dropped, so that a kernel that gained a
+    bool parameter pairs its <..., true> instantiation with the parent's kernel (<..., false> has no counterpart there)."""
     m = re.match(r"_ZN4csky(\d+)", mangled)
     n = int(m.group(1))
     name, rest = mangled[m.end():m.end() + n], mangled[m.end() + n:]
-    t = re.match(r"I((?:Li\d+E)+)E", rest)
-    return name + ("<%s>" % ",".join(re.findall(r"Li(\d+)E", t.group(1))) if t else "")
+    args = []
+    if rest.startswith("I"):
+        rest = rest[1:]
+        while not rest.startswith("E"):
+            t = re.match(r"Li(\d+)E", rest) or re.match(r"Lb([01])E", rest)
+            if t:
+                args.append(t.group(1) if rest[1] == "i" else ("false", "true")[int(t.group(1))])
+                rest = rest[t.end():]
+                continue
+            t = re.match(r"NS_(\d+)", rest)
+            if not t:
+                return name
+            k = int(t.group(1))
+            args.append(rest[t.end():t.end() + k])
+            rest = rest[t.end() + k + 1:]                      # the name and the E that closes the nested name
+    if args and args[-1] == "true":
+        args.pop()
+    return name + ("<%s>" % ",".join(args) if args else "")
 
 
 def main():

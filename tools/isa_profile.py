@@ -34,7 +34,11 @@ import isa_census as IC  # noqa: E402
 
 CSRC = os.path.join(ROOT, "godot-volumetric-cloud-demo-v2_amd", "csrc")
 LLVM = "/opt/rocm/lib/llvm/bin"
-KERNELS = {"plain": "_ZN4csky13clouds_kernelILi3ELi1ENS_6TexSetE", "persistent": "_ZN4csky24clouds_kernel_persistentILi3E"}
+# "plain" / "persistent": the instantiations the headline path and every timed launch run, without the in-cloud tally and with latched rays stopped
+# (cloud_kernels.hip march_compact, TALLY = false): what csky_census_clouds launches, and what bench.py compares with the hardware counters;
+# "*_tally": the ones a launch with a stats buffer runs, which csky_census_clouds launches with CSKY_CENSUS_TALLY=1 in the environment
+KERNELS = {"plain": "_ZN4csky13clouds_kernelILi3ELi1ENS_6TexSetELb0E", "persistent": "_ZN4csky24clouds_kernel_persistentILi3ELb0E",
+           "plain_tally": "_ZN4csky13clouds_kernelILi3ELi1ENS_6TexSetELb1E", "persistent_tally": "_ZN4csky24clouds_kernel_persistentILi3ELb1E"}
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-fno-slp-vectorize", "--offload-arch=gfx950", "-Wno-unused-function", "-Wno-unknown-pragmas", "-Wno-pass-failed"]
 N_CTR_VGPR = 4                      # 256 block counters per kernel
 CENSUS_BYTE_OFFSET = 16             # the kernel's own two 64-bit tallies come first in the stats buffer
@@ -218,13 +222,13 @@ def census_available():
 
 
 def run_counts(config, quiet=False):
-    """GPU box: counts of one frame of `config` for the plain kernel and (CSKY_PERSISTENT=2) the persistent form."""
+    """GPU box: counts of one frame of `config` for the plain kernel and (CSKY_PERSISTENT=2) the persistent form, each with and without the in-cloud tally."""
     lib = os.path.join(ROOT, "godot-volumetric-cloud-demo-v2_amd", "libcloudsky_census.so")
     static = json.load(open(os.path.join(ROOT, "godot-volumetric-cloud-demo-v2_amd", "libcloudsky_census.json")))
     res = {"config": config, "source_hash": static["source_hash"], "kernels": {}}
     args = argparse.Namespace(config=config)
-    for tag in ("plain", "persistent"):
-        env = dict(os.environ, CSKY_LIBRARY=lib, CSKY_PERSISTENT="2" if tag == "persistent" else "0")
+    for tag in KERNELS:
+        env = dict(os.environ, CSKY_LIBRARY=lib, CSKY_PERSISTENT="2" if tag.startswith("persistent") else "0", CSKY_CENSUS_TALLY="1" if tag.endswith("_tally") else "0")
         code = ("import sys, json, hashlib, numpy as np; sys.path.insert(0, %r); import gvcd_amd\n"
                 "W,H,ps,ls,sun = {'C2':(512,256,64,4,(0,1,0)),'C3':(2048,1024,128,6,(1,1,0)),'C5frame':(4096,2048,128,6,(1,1,0))}[%r]\n"
                 "s=np.asarray(sun,np.float64); s=(s/np.linalg.norm(s)).astype(np.float32)\n"
@@ -239,7 +243,7 @@ def run_counts(config, quiet=False):
             raise SystemExit("census run (%s) failed: %s" % (tag, r.stderr[-1500:]))
         d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
         # the product library's frame of the same workload
-        env2 = dict(os.environ, CSKY_PERSISTENT="2" if tag == "persistent" else "0")
+        env2 = dict(os.environ, CSKY_PERSISTENT="2" if tag.startswith("persistent") else "0")
         env2.pop("CSKY_LIBRARY", None)
         code2 = code.replace("cnt=c.census_clouds(p, W, (8,0,1,H//8), 256)\n", "cnt=[]\n")
         r2 = subprocess.run([sys.executable, "-c", code2], env=env2, capture_output=True, text=True, timeout=300)
