@@ -2,6 +2,8 @@
 // lifecycle, settings, noise upload and bake, LUTs, the cloud entry points, the asynchronous host ring, read-backs and kernel timing.  The launch
 // of the cloud kernel is clouds_launch.cpp; the compositor and the radiance cubemap api_sky.cpp; zero-copy frames api_external.cpp; the
 // multi-device handle api_multi.cpp.
+// GPU resources are held by the owner types of owners.h, as members of csky_ctx (context.h) or as locals of the entry point that needs a scratch
+// buffer: nothing here releases a handle by hand, and an early return leaks nothing.
 // Mirrors the resource ownership of the reference's GDScript drivers: cloud_sky.gd (`_initialize_compute_code`,
 // `_render_process`, `cleanup`), sky_lut.gd (`render_lut`), transmittance_lut.gd (`_initialize_compute_code`).
 // There is no CPU render path here: every render entry point needs a live HIP device.
@@ -42,14 +44,26 @@ constexpr size_t CSKY_STATS_WORDS = 2 + 128;             // [0..1] the kernel's 
 
 int ensure_trans(csky_ctx* c, int w, int h) {
     if (c->d_trans_h && c->tw == w && c->th == h) return CSKY_OK;
-    int rc; if ((rc = dev_alloc(c, &c->d_trans_h, (size_t)w * h * 4))) return rc;
-    if ((rc = dev_alloc(c, &c->d_trans_f, (size_t)w * h))) return rc;
+    int rc; if ((rc = c->d_trans_h.alloc(c, (size_t)w * h * 4))) return rc;
+    if ((rc = c->d_trans_f.alloc(c, (size_t)w * h))) return rc;
     c->tw = w; c->th = h; c->have_trans = false; return CSKY_OK;
 }
-int ensure_frame(csky_ctx* c, size_t px) {
-    if (c->d_frame && c->frame_px >= px) return CSKY_OK;
-    int rc; if ((rc = dev_alloc(c, &c->d_frame, px))) return rc;
-    c->frame_px = px; return CSKY_OK;
+// the stream, events and buffers a context has from the start (csky_create)
+int create_resources(csky_ctx* c) {
+    int rc; if ((rc = bind(c))) return rc;
+    // (The frame prologue runs on `stream` too: context.h.  A HIGH-PRIORITY prologue stream was measured in round 2: whole frames with two frames in
+    // flight 1.78 -> 2.02 ms, one rank's 1/8 share 0.329 -> 0.335 ms: the priority queue breaks the overlap of the two frame streams.)
+    if ((rc = c->stream.create(c, hipStreamNonBlocking)) || (rc = c->ev0.create(c, hipEventDefault)) || (rc = c->ev1.create(c, hipEventDefault))) return rc;
+    if ((rc = c->ev_copy.create(c, hipEventDisableTiming)) || (rc = c->ev_rad.create(c, hipEventDisableTiming))) return rc;
+    for (int k = 0; k < RING; k++) {
+        for (long long& v : c->order_key_ring[k]) v = -1;
+        for (long long& v : c->lpt_key[k]) v = -1;
+        if ((rc = c->ev_setup[k].create(c, hipEventDisableTiming)) || (rc = c->ev_clouds[k].create(c, hipEventDisableTiming)) || (rc = c->fc_ring[k].alloc(c, 1))) return rc;
+    }
+    c->d_fc = c->fc_ring[0];
+    if ((rc = c->d_stats.alloc(c, CSKY_STATS_WORDS)) || (rc = c->d_heads.alloc(c, RING * 16))) return rc;
+    HIPCHK(c, hipMemset(c->d_heads, 0, RING * 16 * sizeof(uint32_t)));   // persistent launches leave them zero
+    return CSKY_OK;
 }
 }  // namespace
 
@@ -68,8 +82,8 @@ int ensure_sky(csky_ctx* c, int w, int h) {
     if (c->d_sky_h && c->sw == w && c->sh == h) return CSKY_OK;
     if (c->stream) HIPCHK(c, hipStreamSynchronize(c->stream));  // a size change is rare: drain the context's stream (every reader of the LUT runs there), rebuild both slots
     for (int k = 0; k < 2; k++) {
-        int rc; if ((rc = dev_alloc(c, &c->sky_h_ring[k], (size_t)w * h * 4))) return rc;
-        if ((rc = dev_alloc(c, &c->sky_f_ring[k], (size_t)w * h))) return rc;
+        int rc; if ((rc = c->sky_h_ring[k].alloc(c, (size_t)w * h * 4))) return rc;
+        if ((rc = c->sky_f_ring[k].alloc(c, (size_t)w * h))) return rc;
     }
     c->sky_cur = 0; c->d_sky_h = c->sky_h_ring[0]; c->d_sky_f = c->sky_f_ring[0];
     c->sw = w; c->sh = h; c->have_sky = false; return CSKY_OK;
@@ -81,21 +95,15 @@ int render_trans_dev(csky_ctx* c, int w, int h, hipStream_t s) {
     c->have_trans = true; return CSKY_OK;
 }
 
-int host_slot_prepare(csky_ctx* c, csky_ctx::HostSlot& hs, size_t px, bool need_device) {
-    if (!hs.s) HIPCHK(c, hipStreamCreateWithFlags(&hs.s, hipStreamNonBlocking));
-    if (!hs.done) HIPCHK(c, hipEventCreateWithFlags(&hs.done, hipEventDisableTiming));
-    if (hs.px < px) {
-        HIPCHK(c, hipStreamSynchronize(hs.s));
-        if (hs.d) { (void)hipFree(hs.d); hs.d = nullptr; }
-        if (hs.h) { (void)hipHostFree(hs.h); hs.h = nullptr; }
-        hs.px = 0;
-        if (need_device) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&hs.d), px * 8));
-        HIPCHK(c, hipHostMalloc(&hs.h, px * 8, hipHostMallocDefault));       // pinned: the device-to-host copy is a real asynchronous DMA
-        hs.px = px;
-    } else if (need_device && !hs.d) {
-        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&hs.d), hs.px * 8));
-    }
-    return CSKY_OK;
+int host_slot_prepare(csky_ctx* c, csky_ctx::HostSlot& hs, size_t px) {
+    int rc;
+    if (!hs.s && (rc = hs.s.create(c, hipStreamNonBlocking))) return rc;
+    if (!hs.done && (rc = hs.done.create(c, hipEventDisableTiming))) return rc;
+    if (hs.h.count() >= px * 8) return CSKY_OK;
+    HIPCHK(c, hipStreamSynchronize(hs.s));                    // the slot's last frame may still be on its way into the buffers
+    hs.d.reset(); hs.h.reset();                                // both go before either comes back: the pinned buffer, allocated last, carries the slot's capacity
+    if ((rc = hs.d.alloc(c, px))) return rc;
+    return hs.h.alloc(c, px * 8);
 }
 
 }  // namespace csky
@@ -125,26 +133,8 @@ int csky_create(csky_ctx** out, int device_id) {
     csky_ctx* c = new (std::nothrow) csky_ctx();
     if (!c) return fail(nullptr, CSKY_ERR_INVALID, "csky_create: out of host memory");
     c->device = device_id;
-    auto bail = [&](const char* what, hipError_t err) { fail(nullptr, CSKY_ERR_HIP, "csky_create: %s failed: %s", what, hipGetErrorString(err)); csky_destroy(c); return CSKY_ERR_HIP; };
-    if ((e = hipSetDevice(device_id)) != hipSuccess) return bail("hipSetDevice", e);
-    if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", e);
-    if ((e = hipEventCreate(&c->ev0)) != hipSuccess) return bail("hipEventCreate", e);
-    if ((e = hipEventCreate(&c->ev1)) != hipSuccess) return bail("hipEventCreate", e);
-    if ((e = hipEventCreateWithFlags(&c->ev_copy, hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
-    if ((e = hipEventCreateWithFlags(&c->ev_rad, hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
-    // (The frame prologue runs on `stream` too: context.h.  A HIGH-PRIORITY prologue stream was measured in round 2: whole frames with two frames in
-    // flight 1.78 -> 2.02 ms, one rank's 1/8 share 0.329 -> 0.335 ms: the priority queue breaks the overlap of the two frame streams.)
-    for (int k = 0; k < RING; k++) {
-        for (long long& v : c->order_key_ring[k]) v = -1;
-        for (long long& v : c->lpt_key[k]) v = -1;
-        if ((e = hipEventCreateWithFlags(&c->ev_setup[k], hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
-        if ((e = hipEventCreateWithFlags(&c->ev_clouds[k], hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
-        if ((e = hipMalloc(reinterpret_cast<void**>(&c->fc_ring[k]), sizeof(FrameConsts))) != hipSuccess) return bail("hipMalloc", e);
-    }
-    c->d_fc = c->fc_ring[0];
-    if ((e = hipMalloc(reinterpret_cast<void**>(&c->d_stats), CSKY_STATS_WORDS * sizeof(unsigned long long))) != hipSuccess) return bail("hipMalloc", e);
-    if ((e = hipMalloc(reinterpret_cast<void**>(&c->d_heads), RING * 16 * sizeof(uint32_t))) != hipSuccess) return bail("hipMalloc", e);
-    if ((e = hipMemset(c->d_heads, 0, RING * 16 * sizeof(uint32_t))) != hipSuccess) return bail("hipMemset", e);   // persistent launches leave them zero
+    // a step that fails leaves its text in the half-built context: hand it to the caller's thread, release what was made
+    if (const int rc = create_resources(c)) { fail(nullptr, rc, "csky_create: %s", c->err); csky_destroy(c); return rc; }
     { int cus = 0; (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_id); c->resident_wgs = (cus > 0 ? cus : 256) * cloud_resident_workgroups_per_cu(); }
     // A/B switch (CSKY_PERSISTENT; the A/B of profiles/r02/persistent_launch_ab.txt): 0 = never, 1 = the policy of clouds_dev (default), 2 = every whole-ray launch
     if (const char* pe = getenv("CSKY_PERSISTENT")) c->persistent = atoi(pe);
@@ -157,27 +147,7 @@ void csky_destroy(csky_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();                              // launches may sit on caller streams too
-    void* ptrs[] = {c->d_shape, c->d_detail, c->d_weather, c->d_trans_h, c->d_trans_f, c->sky_h_ring[0], c->sky_h_ring[1], c->sky_f_ring[0], c->sky_f_ring[1],
-                    c->d_stats, c->d_frame, c->d_composite, c->d_raw_large, c->d_raw_small, c->d_raw_weather, c->d_bake_meta, c->d_detail_h, c->d_wg_cost, c->d_lpt_order, c->d_lpt_hist, c->d_heads, c->d_shape32, c->d_detail32, c->d_weather32,
-                    c->rad.tab, c->rad.src_cones, c->rad.out_cones, c->rad_pf.tab, c->rad_pf.src_cones, c->rad_pf.out_cones, c->d_rad_io};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    for (int k = 0; k < RING; k++) {
-        if (c->fc_ring[k]) (void)hipFree(c->fc_ring[k]);
-        if (c->d_order_ring[k]) (void)hipFree(c->d_order_ring[k]);
-        if (c->ev_setup[k]) (void)hipEventDestroy(c->ev_setup[k]);
-        if (c->ev_clouds[k]) (void)hipEventDestroy(c->ev_clouds[k]);
-    }
-    for (auto& hs : c->hring) {
-        if (hs.d) (void)hipFree(hs.d);
-        if (hs.h) (void)hipHostFree(hs.h);
-        if (hs.done) (void)hipEventDestroy(hs.done);
-        if (hs.s) (void)hipStreamDestroy(hs.s);
-    }
-    hipEvent_t evs[] = {c->ev0, c->ev1, c->ev_copy, c->ev_rad};
-    for (hipEvent_t ev : evs) if (ev) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : c->kt_ev) if (ev) (void)hipEventDestroy(ev);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;                                                  // every member releases what it owns (context.h)
 }
 
 static int set_noise_impl(csky_ctx* c, const uint8_t* large_rgba8, const uint8_t* small_rgb8, const uint8_t* weather_rgb8, bool chains_given) {
@@ -196,14 +166,9 @@ static int set_noise_impl(csky_ctx* c, const uint8_t* large_rgba8, const uint8_t
     if (detail_total != (size_t)DETAIL_CHAIN_TEXELS) return fail(c, CSKY_ERR_INVALID, "internal: detail chain size");
     HIPCHK(c, hipDeviceSynchronize());                        // frames reading the old textures may be in flight on caller streams
     c->have_noise = false; c->win_cov = -1e30f;               // a failure below leaves freed / half-baked textures: no render until a later call succeeds
-    if ((rc = dev_alloc(c, &c->d_raw_large, large_chain))) return rc;
-    if ((rc = dev_alloc(c, &c->d_raw_small, small_chain))) return rc;
-    if ((rc = dev_alloc(c, &c->d_raw_weather, weather_b))) return rc;
-    if ((rc = dev_alloc(c, &c->d_shape, shape_total))) return rc;
-    if ((rc = dev_alloc(c, &c->d_detail, detail_total))) return rc;
-    if ((rc = dev_alloc(c, &c->d_weather, (size_t)WEATHER_N * WEATHER_N))) return rc;
-    if ((rc = dev_alloc(c, &c->d_detail_h, detail_total + 8))) return rc;
-    if (!c->d_bake_meta) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_bake_meta), 32));
+    if ((rc = c->d_raw_large.alloc(c, large_chain)) || (rc = c->d_raw_small.alloc(c, small_chain)) || (rc = c->d_raw_weather.alloc(c, weather_b))) return rc;
+    if ((rc = c->d_shape.alloc(c, shape_total)) || (rc = c->d_detail.alloc(c, detail_total)) || (rc = c->d_weather.alloc(c, (size_t)WEATHER_N * WEATHER_N))) return rc;
+    if ((rc = c->d_detail_h.alloc(c, detail_total + 8)) || (rc = c->d_bake_meta.grow(c, 32))) return rc;
     struct { unsigned long long inexact; int range[3]; int pad; } meta = {0ull, {255, 0, 0}, 0};
     hipStream_t s = c->stream;
     HIPCHK(c, hipMemcpyAsync(c->d_bake_meta, &meta, sizeof meta, hipMemcpyHostToDevice, s));
@@ -215,7 +180,7 @@ static int set_noise_impl(csky_ctx* c, const uint8_t* large_rgba8, const uint8_t
         HIPCHK(c, launch_mip_chain(c->d_raw_small, DETAIL_N, 3, DETAIL_LEVELS, s));
     }
     HIPCHK(c, launch_bake(c->d_raw_large, c->d_raw_small, c->d_raw_weather, c->d_shape, c->d_detail, c->d_detail_h, c->d_weather,
-                          reinterpret_cast<unsigned long long*>(c->d_bake_meta), reinterpret_cast<int*>(c->d_bake_meta + 8), s));
+                          reinterpret_cast<unsigned long long*>(c->d_bake_meta.get()), reinterpret_cast<int*>(c->d_bake_meta + 8), s));
 #ifdef CSKY_BRICK_BOUND
     {   // per 8^3 brick (+1 apron on the high side, REPEAT): bmax = (rmax + 1 - fmin) / (2 - fmin), a hair above (the kernel's rcp is approximate)
         std::vector<float> tab(16 * 16 * 16);
@@ -228,7 +193,7 @@ static int set_noise_impl(csky_ctx* c, const uint8_t* large_rgba8, const uint8_t
             const float r = rm * (1.0f / 255.0f), f = fm * (1.0f / (8.0f * 255.0f));
             tab[((size_t)bz * 16 + by) * 16 + bx] = (r + (1.0f - f)) / (2.0f - f) * 1.000004f;
         }
-        if (!c->d_brick) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_brick), tab.size() * sizeof(float)));
+        if ((rc = c->d_brick.grow(c, tab.size()))) return rc;
         HIPCHK(c, hipMemcpy(c->d_brick, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
     }
 #endif
@@ -245,9 +210,7 @@ static int set_noise_impl(csky_ctx* c, const uint8_t* large_rgba8, const uint8_t
     // them on the rounded fp16 cells and warned)  csky_set_exact_cells(1) asks for them regardless (A/B, tests).
     c->cell32 = c->inexact_coeffs != 0 || c->exact_cells == 1;
     if (c->cell32) {
-        if ((rc = dev_alloc(c, &c->d_shape32, shape_total * 4))) return rc;
-        if ((rc = dev_alloc(c, &c->d_detail32, detail_total * 2))) return rc;
-        if ((rc = dev_alloc(c, &c->d_weather32, (size_t)WEATHER_N * WEATHER_N * 2))) return rc;
+        if ((rc = c->d_shape32.alloc(c, shape_total * 4)) || (rc = c->d_detail32.alloc(c, detail_total * 2)) || (rc = c->d_weather32.alloc(c, (size_t)WEATHER_N * WEATHER_N * 2))) return rc;
         HIPCHK(c, launch_bake32(c->d_raw_large, c->d_raw_small, c->d_raw_weather, c->d_shape32, c->d_detail32, c->d_weather32, s));
         HIPCHK(c, hipStreamSynchronize(s));
         if (c->inexact_coeffs)
@@ -255,9 +218,7 @@ static int set_noise_impl(csky_ctx* c, const uint8_t* large_rgba8, const uint8_t
                      "(twice the bytes per tap; the whole-ray compact kernel)", c->inexact_coeffs);
     } else {
         // textures that fit fp16 again: the ~150 MB of exact cells of an earlier bind are not kept until csky_destroy (nothing is in flight: the device was synchronised above)
-        if (c->d_shape32) { (void)hipFree(c->d_shape32); c->d_shape32 = nullptr; }
-        if (c->d_detail32) { (void)hipFree(c->d_detail32); c->d_detail32 = nullptr; }
-        if (c->d_weather32) { (void)hipFree(c->d_weather32); c->d_weather32 = nullptr; }
+        c->d_shape32.reset(); c->d_detail32.reset(); c->d_weather32.reset();
     }
     c->have_noise = true;
     return CSKY_OK;
@@ -295,14 +256,11 @@ int csky_read_baked_texture(csky_ctx* c, int which, void* out, size_t capacity, 
 int csky_test_sqrt_shell(csky_ctx* c, const float* in, float* out, size_t n) {
     if (!c || !in || !out) return fail(c, CSKY_ERR_INVALID, "csky_test_sqrt_shell: NULL argument");
     int rc; if ((rc = bind(c))) return rc;
-    float* d = nullptr;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&d), 2 * n * sizeof(float) + 16));
-    hipError_t e = hipMemcpyAsync(d, in, n * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = launch_sqrt_shell(d, d + n, n, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d + n, n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
-    if (e != hipSuccess) return fail(c, CSKY_ERR_HIP, "csky_test_sqrt_shell: %s", hipGetErrorString(e));
+    DevBuf<float> d; if ((rc = d.alloc(c, 2 * n + 4))) return rc;
+    HIPCHK(c, hipMemcpyAsync(d, in, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, launch_sqrt_shell(d, d + n, n, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, d + n, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return CSKY_OK;
 }
 
@@ -311,7 +269,7 @@ int csky_census_clouds(csky_ctx* c, const csky_cloud_params* p, int tile_w, cons
     int rc; if ((rc = bind(c))) return rc;
     if ((rc = check_bands(c, bands, tile_w))) return rc;
     const size_t rows = (size_t)bands->n_bands * bands->band_rows;
-    if ((rc = ensure_frame(c, (size_t)tile_w * (rows ? rows : 1)))) return rc;
+    if ((rc = c->d_frame.grow(c, (size_t)tile_w * (rows ? rows : 1)))) return rc;
     HIPCHK(c, hipMemsetAsync(c->d_stats, 0, CSKY_STATS_WORDS * sizeof(unsigned long long), c->stream));
     // the blocks of the form the headline path and the timed launches of csky_time_clouds run (no stats buffer there: no in-cloud tally, latched rays stop
     // marching), which is what the hardware counters of those launches are compared with; CSKY_CENSUS_TALLY=1: the form a stats launch runs
@@ -320,7 +278,7 @@ int csky_census_clouds(csky_ctx* c, const csky_cloud_params* p, int tile_w, cons
     rc = clouds_dev(c, p, tile_w, bands, c->d_frame, (size_t)tile_w * 8, c->stream, c->d_stats, true);
     c->census_lean = false;
     if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(counts, reinterpret_cast<const char*>(c->d_stats) + 16, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(counts, reinterpret_cast<const char*>(c->d_stats.get()) + 16, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return CSKY_OK;
 }
@@ -330,14 +288,11 @@ int csky_build_mips_device(csky_ctx* c, uint8_t* vol, int n, int ch, int levels)
     if (!vol || n < 1 || n > 1024 || (n & (n - 1)) || ch < 1 || ch > 4 || levels < 1 || (n >> (levels - 1)) < 1) return fail(c, CSKY_ERR_INVALID, "csky_build_mips_device: bad arguments");
     int rc; if ((rc = bind(c))) return rc;
     const size_t total = chain_offset(n, levels, ch), l0 = (size_t)n * n * n * ch;
-    uint8_t* d = nullptr;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&d), total));
-    hipError_t e = hipMemcpyAsync(d, vol, l0, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = launch_mip_chain(d, n, ch, levels, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(vol + l0, d + l0, total - l0, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
-    if (e != hipSuccess) return fail(c, CSKY_ERR_HIP, "csky_build_mips_device: %s", hipGetErrorString(e));
+    DevBuf<uint8_t> d; if ((rc = d.alloc(c, total))) return rc;
+    HIPCHK(c, hipMemcpyAsync(d, vol, l0, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, launch_mip_chain(d, n, ch, levels, c->stream));
+    HIPCHK(c, hipMemcpyAsync(vol + l0, d + l0, total - l0, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return CSKY_OK;
 }
 
@@ -346,13 +301,10 @@ int csky_generate_detail_noise_device(csky_ctx* c, uint32_t seed, int n, uint8_t
     if (!out_rgb8 || n < 8 || n > 256 || (n & (n - 1))) return fail(c, CSKY_ERR_INVALID, "csky_generate_detail_noise_device: n must be a power of two in [8, 256]");
     int rc; if ((rc = bind(c))) return rc;
     const size_t bytes = (size_t)n * n * n * 3;
-    uint8_t* d = nullptr;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&d), bytes));
-    hipError_t e = launch_detail_noise(seed, n, d, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out_rgb8, d, bytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
-    if (e != hipSuccess) return fail(c, CSKY_ERR_HIP, "csky_generate_detail_noise_device: %s", hipGetErrorString(e));
+    DevBuf<uint8_t> d; if ((rc = d.alloc(c, bytes))) return rc;
+    HIPCHK(c, launch_detail_noise(seed, n, d, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out_rgb8, d, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return CSKY_OK;
 }
 
@@ -364,16 +316,12 @@ int csky_encode_bc7_quality(csky_ctx* c, const uint8_t* rgba8, int w, int h, int
     int rc; if ((rc = bind(c))) return rc;
     const size_t in_bytes = (size_t)w * h * 4 * (size_t)n_images, out_bytes = (size_t)((w + 3) / 4) * ((h + 3) / 4) * 16 * (size_t)n_images;
     const size_t in_pad = (in_bytes + 15) & ~(size_t)15;        // the blocks follow the texels, 16-byte aligned
-    uint8_t* d = nullptr;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&d), in_pad + out_bytes));
+    DevBuf<uint8_t> d; if ((rc = d.alloc(c, in_pad + out_bytes))) return rc;
     uint8_t* d_out = d + in_pad;
-    hipError_t e = hipSuccess;
-    if (e == hipSuccess) e = hipMemcpyAsync(d, rgba8, in_bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = launch_bc7_encode(d, w, h, n_images, quality, reinterpret_cast<uint4*>(d_out), c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(blocks_out, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
-    if (e != hipSuccess) return fail(c, CSKY_ERR_HIP, "csky_encode_bc7: %s", hipGetErrorString(e));
+    HIPCHK(c, hipMemcpyAsync(d, rgba8, in_bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, launch_bc7_encode(d, w, h, n_images, quality, reinterpret_cast<uint4*>(d_out), c->stream));
+    HIPCHK(c, hipMemcpyAsync(blocks_out, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return CSKY_OK;
 }
 
@@ -551,7 +499,7 @@ int csky_render_clouds(csky_ctx* c, const csky_cloud_params* p, int tile_w, int 
     if (tile_w < 1 || tile_h < 1) return fail(c, CSKY_ERR_INVALID, "csky_render_clouds: empty tile");
     if (out && (pitch < (size_t)tile_w * 8)) return fail(c, CSKY_ERR_INVALID, "csky_render_clouds: row_pitch_bytes < tile_w*8");
     int rc; if ((rc = bind(c))) return rc;
-    if ((rc = ensure_frame(c, (size_t)tile_w * tile_h))) return rc;
+    if ((rc = c->d_frame.grow(c, (size_t)tile_w * tile_h))) return rc;
     csky_bands b = {tile_h, 0, 1, 1};
     HIPCHK(c, hipMemsetAsync(c->d_stats, 0, 16, c->stream));
     if ((rc = clouds_dev(c, p, tile_w, &b, c->d_frame, (size_t)tile_w * 8, c->stream, c->d_stats, true))) return rc;
@@ -580,7 +528,7 @@ int csky_submit_clouds(csky_ctx* c, const csky_cloud_params* p, int tile_w, int 
     csky_ctx::HostSlot& hs = c->hring[c->next_ticket % c->hslots];
     if (hs.busy) return fail(c, CSKY_ERR_STATE, "csky_submit_clouds: %d frames are already in flight (csky_set_host_ring); collect ticket %lld first", c->hslots, (long long)hs.ticket);
     const size_t px = (size_t)tile_w * tile_h;
-    if ((rc = host_slot_prepare(c, hs, px, true))) return rc;
+    if ((rc = host_slot_prepare(c, hs, px))) return rc;
     const csky_bands b = {tile_h, 0, 1, 1};
     if ((rc = clouds_dev(c, p, tile_w, &b, hs.d, (size_t)tile_w * 8, hs.s, nullptr, true))) return rc;
     HIPCHK(c, hipMemcpyAsync(hs.h, hs.d, px * 8, hipMemcpyDeviceToHost, hs.s));
@@ -599,7 +547,7 @@ int csky_collect(csky_ctx* c, int64_t ticket, const uint16_t** frame, size_t* by
     int rc; if ((rc = bind(c))) return rc;
     HIPCHK(c, hipEventSynchronize(hs->done));
     hs->busy = false;
-    *frame = reinterpret_cast<const uint16_t*>(hs->h);
+    *frame = static_cast<const uint16_t*>(static_cast<void*>(hs->h));
     if (bytes) *bytes = (size_t)hs->w * hs->hh * 8;
     return CSKY_OK;
 }
@@ -642,7 +590,7 @@ int csky_set_kernel_timing(csky_ctx* c, int enabled) {
     if (!c) return fail(nullptr, CSKY_ERR_INVALID, "csky_set_kernel_timing: ctx is NULL");
     int rc; if ((rc = bind(c))) return rc;
     c->kt_on = enabled != 0; c->kt_count = 0;
-    if (c->kt_on && c->kt_ev.empty()) {      // the first pool is made HERE, not by the first timed launch: 512 hipEventCreate calls are ~1 ms of host time, 3 % of a 20-frame timed region
+    if (c->kt_on && c->kt_ev.empty()) {      // the first pool is made HERE, not by the first timed launch: creating 512 events is ~1 ms of host time, 3 % of a 20-frame timed region
         if ((rc = grow_timing_pool(c, 512))) { c->kt_on = false; return rc; }
     }
     return CSKY_OK;
@@ -671,7 +619,7 @@ int csky_time_clouds(csky_ctx* c, const csky_cloud_params* p, int tile_w, const 
     int rc; if ((rc = bind(c))) return rc;
     if ((rc = check_bands(c, bands, tile_w))) return rc;
     const size_t rows = (size_t)bands->n_bands * bands->band_rows;
-    if ((rc = ensure_frame(c, (size_t)tile_w * (rows ? rows : 1)))) return rc;
+    if ((rc = c->d_frame.grow(c, (size_t)tile_w * (rows ? rows : 1)))) return rc;
     const size_t pitch = (size_t)tile_w * 8;
     HIPCHK(c, hipMemsetAsync(c->d_stats, 0, 16, c->stream));
     if ((rc = clouds_dev(c, p, tile_w, bands, c->d_frame, pitch, c->stream, c->d_stats, true))) return rc;   // stats launch (+ frame setup)
@@ -701,13 +649,10 @@ int csky_generate_shape_noise_tuned_device(csky_ctx* c, uint32_t seed, int n, co
     }
     int rc; if ((rc = bind(c))) return rc;
     const size_t bytes = (size_t)n * n * n * 4;
-    uint32_t* d = nullptr;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&d), bytes));
-    hipError_t e = launch_shape_noise(seed, n, P, d, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out_rgba8, d, bytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
-    if (e != hipSuccess) return fail(c, CSKY_ERR_HIP, "csky_generate_shape_noise_device: %s", hipGetErrorString(e));
+    DevBuf<uint32_t> d; if ((rc = d.alloc(c, bytes / 4))) return rc;
+    HIPCHK(c, launch_shape_noise(seed, n, P, d, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out_rgba8, d, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return CSKY_OK;
 }
 

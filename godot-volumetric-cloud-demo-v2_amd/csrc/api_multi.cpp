@@ -4,33 +4,38 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <utility>
 #include <vector>
 #include "context.h"
 
 using namespace csky;
 
 constexpr int MULTI_SLOTS = 8;            // frames in flight over all groups (csky_multi_set_frames_in_flight x csky_multi_set_groups)
+// What the handle holds per device.  The owners (owners.h) are released with that device current, after it has been waited for (csky_multi_destroy);
+// the context is destroyed after them.  An empty Dev is safe to destroy, so csky_multi_create may bail at any point.
+struct Dev {
+    csky_ctx* ctx = nullptr;              // csky_destroy'ed by csky_multi_destroy
+    Stream side[RING];                    // [frame in flight]: the march streams of the devices behind the first (whose march runs on the consumer's stream);
+                                          // never the context's own stream: the frame prologue runs there, beside the march (context.h)
+    Event done[MULTI_SLOTS];              // [frame slot]: its march (and staged copy) of that frame has finished
+    DevBuf<uint2> stage[RING];            // [per-device frame slot]: compact band buffer on that device (staged form), in pixels, grow-only
+    Event lut;                            // its rows of the sky LUT have been stored into the first device's LUT (csky_multi_render_sky_lut)
+    // preconditions + instrumentation (round 6): peer access to the first device, and timing events of the LAST frame enqueued (csky_multi_set_timing)
+    Event tm[3];                          // [0] before the march, [1] after it, [2] after the staged copy
+    int peer_ok = 1;                      // 1 = hipDeviceCanAccessPeer(device, first) and it was enabled (1 for the first device itself)
+    int tm_valid = 0;                     // 0 none, 1 march only, 2 march + copy
+};
 struct csky_multi {
-    std::vector<csky_ctx*> ctx;
-    std::vector<hipEvent_t> ev_done[MULTI_SLOTS];   // [frame slot][device]: its march (and staged copy) of that frame has finished
-    hipEvent_t ev_begin[MULTI_SLOTS] = {};          // on the first device: the consumer stream's position when the frame was requested
-    std::vector<hipStream_t> side[RING];            // [frame in flight][device]: the march streams of the devices behind the first (whose march runs on the consumer's stream);
-                                                    // never the context's own stream: the frame prologue runs there, beside the march (context.h)
+    std::vector<Dev> dev;
+    // on the first device:
+    Event ev_begin[MULTI_SLOTS];          // the consumer stream's position when the frame was requested
+    Event ev_lut_begin;                   // on its prologue stream: the readers of the LUT slot about to be rewritten are behind this
+    DevBuf<uint2> d_frame;                // host-buffer form: internal frame, in pixels, grow-only
     int fif = 1, groups = 1;              // frames in flight PER GROUP, frame groups (csky_multi_set_groups)
     unsigned long long frame_no = 0;
     bool staged = false;                  // CSKY_MULTI_STAGED=1 / csky_multi_set_staged: local band buffer + peer copy instead of in-place peer stores
-    std::vector<uint2*> d_stage[RING];    // [per-device frame slot][device]: compact band buffer on that device (staged form)
-    std::vector<size_t> stage_px[RING];
-    uint2* d_frame = nullptr; size_t frame_px = 0;   // host-buffer form: internal frame on the first device
-    std::vector<hipEvent_t> ev_lut;       // [device]: its rows of the sky LUT have been stored into the first device's LUT (csky_multi_render_sky_lut)
-    hipEvent_t ev_lut_begin = nullptr;    // on the first device's prologue stream: the readers of the LUT slot about to be rewritten are behind this
-    // preconditions + instrumentation (round 6): which devices can store into the first device's memory, and -- while csky_multi_set_timing is on --
-    // timing events around every device's march and its staged peer copy of the LAST frame enqueued
-    std::vector<int> peer_ok;             // [device]: 1 = hipDeviceCanAccessPeer(device, first) and it was enabled (1 for the first device itself)
     bool all_peer = true;                 // false: some device has no peer access -> staged copies (the runtime bounces them) + the whole LUT on the first device
     bool timing = false;
-    std::vector<hipEvent_t> tm[3];        // [0] before the march, [1] after it, [2] after the staged copy; [device]
-    std::vector<int> tm_valid;            // [device]: 0 none, 1 march only, 2 march + copy
     char err[512] = {0};
     char warn[512] = {0};
 };
@@ -41,7 +46,7 @@ int mfail(csky_multi* m, int code, const char* fmt, ...) {
     return code;
 }
 int mpass(csky_multi* m, int i, int rc) {      // propagate a per-device error text
-    if (rc) snprintf(m->err, sizeof m->err, "device %d (index %d): %s", m->ctx[i]->device, i, m->ctx[i]->err);
+    if (rc) snprintf(m->err, sizeof m->err, "device %d (index %d): %s", m->dev[i].ctx->device, i, m->dev[i].ctx->err);
     return rc;
 }
 }  // namespace
@@ -58,32 +63,23 @@ int csky_multi_create(csky_multi** out, const int* device_ids, int n) {
         csky_ctx* c = nullptr;
         const int rc = csky_create(&c, device_ids[i]);
         if (rc) { csky_multi_destroy(m); return rc; }           // g_err already holds csky_create's text
-        m->ctx.push_back(c);
+        m->dev.emplace_back().ctx = c;
     }
-    auto bail = [&](int code, const char* what, hipError_t e) { mfail(nullptr, code, "csky_multi_create: %s: %s", what, hipGetErrorString(e)); csky_multi_destroy(m); return code; };
+    // a step that fails leaves its text in the context it was made for: it goes to the caller's thread, and the half-built handle goes
+    auto bail = [&](int rc, const csky_ctx* c) { mfail(nullptr, rc, "csky_multi_create: %s", c->err); csky_multi_destroy(m); return rc; };
     const int d0 = device_ids[0];
-    hipError_t e;
     for (int i = 0; i < n; i++) {
         const int di = device_ids[i];
-        if ((e = hipSetDevice(di)) != hipSuccess) return bail(CSKY_ERR_HIP, "hipSetDevice", e);
-        for (int sl = 0; sl < MULTI_SLOTS; sl++) {
-            hipEvent_t ev = nullptr;
-            if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return bail(CSKY_ERR_HIP, "hipEventCreate", e);
-            m->ev_done[sl].push_back(ev);
-        }
-        for (int k = 0; k < RING; k++) {
-            hipStream_t st = nullptr;
-            if ((e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking)) != hipSuccess) return bail(CSKY_ERR_HIP, "hipStreamCreate", e);
-            m->side[k].push_back(st);
-        }
-        for (int k = 0; k < RING; k++) { m->d_stage[k].push_back(nullptr); m->stage_px[k].push_back(0); }
-        { hipEvent_t ev = nullptr; if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return bail(CSKY_ERR_HIP, "hipEventCreate", e); m->ev_lut.push_back(ev); }
-        for (int k = 0; k < 3; k++) m->tm[k].push_back(nullptr);
-        m->tm_valid.push_back(0);
+        Dev& d = m->dev[i];
+        int rc; if ((rc = bind(d.ctx))) return bail(rc, d.ctx);
+        for (Event& ev : d.done) if ((rc = ev.create(d.ctx, hipEventDisableTiming))) return bail(rc, d.ctx);
+        for (Stream& st : d.side) if ((rc = st.create(d.ctx, hipStreamNonBlocking))) return bail(rc, d.ctx);
+        if ((rc = d.lut.create(d.ctx, hipEventDisableTiming))) return bail(rc, d.ctx);
         int ok = 1;
         if (di != d0) {                                          // the march on device di stores into the frame on d0: xGMI peer access
             int can = 0;
-            if ((e = hipDeviceCanAccessPeer(&can, di, d0)) != hipSuccess) return bail(CSKY_ERR_HIP, "hipDeviceCanAccessPeer", e);
+            hipError_t e = hipDeviceCanAccessPeer(&can, di, d0);
+            if (e != hipSuccess) return bail(fail(d.ctx, CSKY_ERR_HIP, "hipDeviceCanAccessPeer: %s", hipGetErrorString(e)), d.ctx);
             if (can) {
                 e = hipDeviceEnablePeerAccess(d0, 0);
                 if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) can = 0;
@@ -93,7 +89,7 @@ int csky_multi_create(csky_multi** out, const int* device_ids, int n) {
         }
         // test hook: pretend device INDEX i (> 0) has no peer access -- also when it IS the first device's GPU, which is all a single-GPU box can offer
         if (const char* fk = getenv("CSKY_MULTI_FAKE_NO_PEER")) if (i > 0 && atoi(fk) == i) ok = 0;
-        m->peer_ok.push_back(ok);
+        d.peer_ok = ok;
         if (!ok) {
             // No peer access between this device and the first one (no xGMI / PCIe P2P route, IOMMU policy, a container without the devices' links): the
             // in-place form cannot work for it.  Not fatal: the whole handle falls back to the STAGED form -- every device renders into a local band
@@ -109,10 +105,10 @@ int csky_multi_create(csky_multi** out, const int* device_ids, int n) {
         snprintf(m->warn + at, sizeof m->warn - at, ": falling back to staged band copies and a whole sky LUT on the first device (slower than in-place xGMI stores)");
         m->staged = true;
     }
-    if ((e = hipSetDevice(d0)) != hipSuccess) return bail(CSKY_ERR_HIP, "hipSetDevice", e);
-    for (int sl = 0; sl < MULTI_SLOTS; sl++)
-        if ((e = hipEventCreateWithFlags(&m->ev_begin[sl], hipEventDisableTiming)) != hipSuccess) return bail(CSKY_ERR_HIP, "hipEventCreate", e);
-    if ((e = hipEventCreateWithFlags(&m->ev_lut_begin, hipEventDisableTiming)) != hipSuccess) return bail(CSKY_ERR_HIP, "hipEventCreate", e);
+    csky_ctx* const c0 = m->dev[0].ctx;
+    if (const int rc = bind(c0)) return bail(rc, c0);
+    for (Event& ev : m->ev_begin) if (const int rc = ev.create(c0, hipEventDisableTiming)) return bail(rc, c0);
+    if (const int rc = m->ev_lut_begin.create(c0, hipEventDisableTiming)) return bail(rc, c0);
     if (const char* se = getenv("CSKY_MULTI_STAGED")) m->staged = (atoi(se) != 0) || !m->all_peer;   // A/B switch for the driver's 8-GPU node (never off without peer access)
     *out = m;
     return CSKY_OK;
@@ -120,59 +116,57 @@ int csky_multi_create(csky_multi** out, const int* device_ids, int n) {
 
 void csky_multi_destroy(csky_multi* m) {
     if (!m) return;
-    for (size_t i = 0; i < m->ctx.size(); i++) {
-        (void)hipSetDevice(m->ctx[i]->device);
+    for (Dev& d : m->dev) {
+        (void)hipSetDevice(d.ctx->device);
         (void)hipDeviceSynchronize();
-        for (int sl = 0; sl < MULTI_SLOTS; sl++) if (i < m->ev_done[sl].size() && m->ev_done[sl][i]) (void)hipEventDestroy(m->ev_done[sl][i]);
-        for (int k = 0; k < RING; k++) if (i < m->side[k].size() && m->side[k][i]) (void)hipStreamDestroy(m->side[k][i]);
-        for (int k = 0; k < RING; k++) if (i < m->d_stage[k].size() && m->d_stage[k][i]) (void)hipFree(m->d_stage[k][i]);
-        if (i < m->ev_lut.size() && m->ev_lut[i]) (void)hipEventDestroy(m->ev_lut[i]);
-        for (int k = 0; k < 3; k++) if (i < m->tm[k].size() && m->tm[k][i]) (void)hipEventDestroy(m->tm[k][i]);
+        Dev gone(std::move(d));                                 // its events, buffers and streams die here, with the device current; d keeps the context alone
     }
-    if (!m->ctx.empty()) {
-        (void)hipSetDevice(m->ctx[0]->device);
-        for (int sl = 0; sl < MULTI_SLOTS; sl++) if (m->ev_begin[sl]) (void)hipEventDestroy(m->ev_begin[sl]);
-        if (m->ev_lut_begin) (void)hipEventDestroy(m->ev_lut_begin);
-        m->ctx[0]->lut_writers.clear();
-        if (m->d_frame) (void)hipFree(m->d_frame);
+    if (!m->dev.empty()) {
+        csky_ctx* const c0 = m->dev[0].ctx;
+        (void)hipSetDevice(c0->device);
+        for (Event& ev : m->ev_begin) ev.reset();
+        m->ev_lut_begin.reset(); m->d_frame.reset();
+        c0->lut_writers.clear();
     }
-    for (csky_ctx* c : m->ctx) csky_destroy(c);
+    for (Dev& d : m->dev) csky_destroy(d.ctx);
     delete m;
 }
 
-int csky_multi_device_count(const csky_multi* m) { return m ? (int)m->ctx.size() : 0; }
-csky_ctx* csky_multi_ctx(csky_multi* m, int i) { return (m && i >= 0 && i < (int)m->ctx.size()) ? m->ctx[i] : nullptr; }
+int csky_multi_device_count(const csky_multi* m) { return m ? (int)m->dev.size() : 0; }
+csky_ctx* csky_multi_ctx(csky_multi* m, int i) { return (m && i >= 0 && i < (int)m->dev.size()) ? m->dev[i].ctx : nullptr; }
 const char* csky_multi_last_error(const csky_multi* m) { return m ? m->err : g_err; }
 const char* csky_multi_last_warning(const csky_multi* m) { return m ? m->warn : ""; }
 int csky_multi_set_timing(csky_multi* m, int enabled) {
     if (!m) return mfail(nullptr, CSKY_ERR_INVALID, "csky_multi_set_timing: handle is NULL");
     const int rc = csky_multi_sync(m); if (rc) return rc;
     if (enabled)
-        for (size_t i = 0; i < m->ctx.size(); i++) {
-            if ((hipSetDevice(m->ctx[i]->device)) != hipSuccess) return mfail(m, CSKY_ERR_HIP, "csky_multi_set_timing: hipSetDevice failed");
-            for (int k = 0; k < 3; k++) if (!m->tm[k][i] && hipEventCreate(&m->tm[k][i]) != hipSuccess) return mfail(m, CSKY_ERR_HIP, "csky_multi_set_timing: hipEventCreate failed");
+        for (size_t i = 0; i < m->dev.size(); i++) {
+            Dev& d = m->dev[i];
+            if ((hipSetDevice(d.ctx->device)) != hipSuccess) return mfail(m, CSKY_ERR_HIP, "csky_multi_set_timing: hipSetDevice failed");
+            for (Event& ev : d.tm) if (!ev) { const int rc = ev.create(d.ctx, hipEventDefault); if (rc) return mpass(m, (int)i, rc); }
         }
     m->timing = enabled != 0;
-    for (auto& v : m->tm_valid) v = 0;
+    for (Dev& d : m->dev) d.tm_valid = 0;
     return CSKY_OK;
 }
 int csky_multi_get_stats(csky_multi* m, csky_multi_stats* out) {
     if (!m || !out) return mfail(m, CSKY_ERR_INVALID, "csky_multi_get_stats: NULL argument");
     memset(out, 0, sizeof *out);
     const int rc = csky_multi_sync(m); if (rc) return rc;       // the events of the last frame must have completed
-    const int n = (int)m->ctx.size();
+    const int n = (int)m->dev.size();
     out->n_devices = n; out->staged = m->staged ? 1 : 0; out->all_peer = m->all_peer ? 1 : 0; out->groups = m->groups; out->frames_in_flight = m->fif;
     out->timing = m->timing ? 1 : 0;
     for (int i = 0; i < n && i < CSKY_MULTI_STATS_MAX; i++) {
-        out->device_id[i] = m->ctx[i]->device; out->peer_access[i] = m->peer_ok[i];
+        const Dev& d = m->dev[i];
+        out->device_id[i] = d.ctx->device; out->peer_access[i] = d.peer_ok;
         out->march_ms[i] = out->copy_ms[i] = -1.0f;
-        if (m->tm_valid[i] >= 1) {
-            if (hipSetDevice(m->ctx[i]->device) != hipSuccess) return mfail(m, CSKY_ERR_HIP, "csky_multi_get_stats: hipSetDevice failed");
+        if (d.tm_valid >= 1) {
+            if (hipSetDevice(d.ctx->device) != hipSuccess) return mfail(m, CSKY_ERR_HIP, "csky_multi_get_stats: hipSetDevice failed");
             float ms = 0.0f;
             // (the first device's share runs on the CALLER's consumer stream, which csky_multi_sync does not own: wait for the timing events themselves)
-            if (hipEventSynchronize(m->tm[m->tm_valid[i] >= 2 ? 2 : 1][i]) != hipSuccess) return mfail(m, CSKY_ERR_HIP, "csky_multi_get_stats: hipEventSynchronize failed");
-            if (hipEventElapsedTime(&ms, m->tm[0][i], m->tm[1][i]) == hipSuccess) out->march_ms[i] = ms; else (void)hipGetLastError();
-            if (m->tm_valid[i] >= 2) { if (hipEventElapsedTime(&ms, m->tm[1][i], m->tm[2][i]) == hipSuccess) out->copy_ms[i] = ms; else (void)hipGetLastError(); }
+            if (hipEventSynchronize(d.tm[d.tm_valid >= 2 ? 2 : 1]) != hipSuccess) return mfail(m, CSKY_ERR_HIP, "csky_multi_get_stats: hipEventSynchronize failed");
+            if (hipEventElapsedTime(&ms, d.tm[0], d.tm[1]) == hipSuccess) out->march_ms[i] = ms; else (void)hipGetLastError();
+            if (d.tm_valid >= 2) { if (hipEventElapsedTime(&ms, d.tm[1], d.tm[2]) == hipSuccess) out->copy_ms[i] = ms; else (void)hipGetLastError(); }
             else out->copy_ms[i] = 0.0f;                         // in-place form: the stores ARE the march
         }
     }
@@ -181,36 +175,36 @@ int csky_multi_get_stats(csky_multi* m, csky_multi_stats* out) {
 
 int csky_multi_set_noise(csky_multi* m, const uint8_t* large, const uint8_t* small, const uint8_t* weather) {
     if (!m) return mfail(nullptr, CSKY_ERR_INVALID, "csky_multi_set_noise: handle is NULL");
-    for (size_t i = 0; i < m->ctx.size(); i++) { const int rc = csky_set_noise(m->ctx[i], large, small, weather); if (rc) return mpass(m, (int)i, rc); }
+    for (size_t i = 0; i < m->dev.size(); i++) { const int rc = csky_set_noise(m->dev[i].ctx, large, small, weather); if (rc) return mpass(m, (int)i, rc); }
     return CSKY_OK;
 }
 int csky_multi_set_noise_mips(csky_multi* m, const uint8_t* large_chain, const uint8_t* small_chain, const uint8_t* weather) {
     if (!m) return mfail(nullptr, CSKY_ERR_INVALID, "csky_multi_set_noise_mips: handle is NULL");
-    for (size_t i = 0; i < m->ctx.size(); i++) { const int rc = csky_set_noise_mips(m->ctx[i], large_chain, small_chain, weather); if (rc) return mpass(m, (int)i, rc); }
+    for (size_t i = 0; i < m->dev.size(); i++) { const int rc = csky_set_noise_mips(m->dev[i].ctx, large_chain, small_chain, weather); if (rc) return mpass(m, (int)i, rc); }
     return CSKY_OK;
 }
 int csky_multi_set_march(csky_multi* m, int primary_steps, int light_steps) {
     if (!m) return mfail(nullptr, CSKY_ERR_INVALID, "csky_multi_set_march: handle is NULL");
-    for (size_t i = 0; i < m->ctx.size(); i++) { const int rc = csky_set_march(m->ctx[i], primary_steps, light_steps); if (rc) return mpass(m, (int)i, rc); }
+    for (size_t i = 0; i < m->dev.size(); i++) { const int rc = csky_set_march(m->dev[i].ctx, primary_steps, light_steps); if (rc) return mpass(m, (int)i, rc); }
     return CSKY_OK;
 }
 int csky_multi_set_transmittance_mapping(csky_multi* m, int mapping) {
     if (!m) return mfail(nullptr, CSKY_ERR_INVALID, "csky_multi_set_transmittance_mapping: handle is NULL");
     if (mapping != CSKY_TLUT_REFERENCE && mapping != CSKY_TLUT_BRUNETON) return mfail(m, CSKY_ERR_INVALID, "csky_multi_set_transmittance_mapping: CSKY_TLUT_REFERENCE (0) or CSKY_TLUT_BRUNETON (1)");
-    for (size_t i = 0; i < m->ctx.size(); i++) { const int rc = csky_set_transmittance_mapping(m->ctx[i], mapping); if (rc) return mpass(m, (int)i, rc); }
+    for (size_t i = 0; i < m->dev.size(); i++) { const int rc = csky_set_transmittance_mapping(m->dev[i].ctx, mapping); if (rc) return mpass(m, (int)i, rc); }
     return CSKY_OK;
 }
 int csky_multi_set_frames_in_flight(csky_multi* m, int frames) {
     if (!m) return mfail(nullptr, CSKY_ERR_INVALID, "csky_multi_set_frames_in_flight: handle is NULL");
     if (frames < 1 || frames > RING) return mfail(m, CSKY_ERR_INVALID, "csky_multi_set_frames_in_flight: 1 .. 8 per frame group (the per-device rings are eight deep)");
     if (frames * m->groups > MULTI_SLOTS) return mfail(m, CSKY_ERR_INVALID, "csky_multi_set_frames_in_flight: frames x groups must be <= %d", MULTI_SLOTS);
-    for (size_t i = 0; i < m->ctx.size(); i++) { const int rc = csky_set_frames_in_flight(m->ctx[i], frames); if (rc) return mpass(m, (int)i, rc); }
+    for (size_t i = 0; i < m->dev.size(); i++) { const int rc = csky_set_frames_in_flight(m->dev[i].ctx, frames); if (rc) return mpass(m, (int)i, rc); }
     m->fif = frames;
     return CSKY_OK;
 }
 int csky_multi_set_groups(csky_multi* m, int groups) {
     if (!m) return mfail(nullptr, CSKY_ERR_INVALID, "csky_multi_set_groups: handle is NULL");
-    const int n = (int)m->ctx.size();
+    const int n = (int)m->dev.size();
     if (groups < 1 || groups > n || n % groups) return mfail(m, CSKY_ERR_INVALID, "csky_multi_set_groups: the group count must divide the %d devices", n);
     if (groups * m->fif > MULTI_SLOTS) return mfail(m, CSKY_ERR_INVALID, "csky_multi_set_groups: frames in flight x groups must be <= %d", MULTI_SLOTS);
     const int rc = csky_multi_sync(m); if (rc) return rc;       // frames of the old partition may be in flight
@@ -234,32 +228,33 @@ int csky_multi_render_sky_lut(csky_multi* m, const csky_sky_params* p) {
     // (the copy a consumer reads: csky_read_sky_lut / csky_copy_sky_lut_device on csky_multi_ctx(m, 0) wait for every writer).  No device's frame
     // set-up reads that copy: each renders the <= 12 texels it filters itself (frame_setup_taps_kernel), for the sun recorded here -- on EVERY
     // device, whatever the group layout (a caller with a static sun renders the LUT once and then frames on all groups).
-    const int n = (int)m->ctx.size();
-    csky_ctx* c0 = m->ctx[0];
+    const int n = (int)m->dev.size();
+    csky_ctx* c0 = m->dev[0].ctx;
     int rc;
     if (c0->d_sky_h && (c0->sw != w || c0->sh != h))            // a size change re-allocates the first device's LUT slots: no device may still be storing rows into them
-        for (int i = 0; i < n; i++) { if ((rc = bind(m->ctx[i]))) return mpass(m, i, rc); if (hipStreamSynchronize(m->ctx[i]->stream) != hipSuccess) return mfail(m, CSKY_ERR_HIP, "csky_multi_render_sky_lut: hipStreamSynchronize failed"); }
+        for (int i = 0; i < n; i++) { if ((rc = bind(m->dev[i].ctx))) return mpass(m, i, rc); if (hipStreamSynchronize(m->dev[i].ctx->stream) != hipSuccess) return mfail(m, CSKY_ERR_HIP, "csky_multi_render_sky_lut: hipStreamSynchronize failed"); }
     if ((rc = bind(c0))) return mpass(m, 0, rc);
     if ((rc = ensure_sky(c0, w, h))) return mpass(m, 0, rc);
     const int k = (c0->have_sky && c0->sky_in_memory) ? c0->sky_cur ^ 1 : c0->sky_cur;     // the other ring slot, as in csky_render_sky_lut_device
     // the readers of slot k (device copies of the LUT before last) sit on the first device's prologue stream: every writer queues behind them
     if (hipEventRecord(m->ev_lut_begin, c0->stream) != hipSuccess) return mfail(m, CSKY_ERR_HIP, "csky_multi_render_sky_lut: hipEventRecord failed");
     for (int i = 0; i < n; i++) {
-        csky_ctx* c = m->ctx[i];
+        csky_ctx* c = m->dev[i].ctx;
         if ((rc = bind(c))) return mpass(m, i, rc);
         if (!c->have_trans && (rc = render_trans_dev(c, 256, 64, c->stream))) return mpass(m, i, rc);   // transmittance_lut.gd:6 default size
         hipError_t e = i ? hipStreamWaitEvent(c->stream, m->ev_lut_begin, 0) : hipSuccess;
         // rows i, i + n, ... stored into the first device's LUT -- or, when some device cannot reach that memory, every row by the first device itself
         if (e == hipSuccess && (m->all_peer || i == 0))
-            e = launch_sky_lut_rows(w, h, m->all_peer ? i : 0, m->all_peer ? n : 1, p->sun_direction, c->d_trans_f, c->tw, c->th, reinterpret_cast<uint2*>(c0->sky_h_ring[k]), c0->sky_f_ring[k], c->stream, c->tlut);
-        if (e == hipSuccess) e = hipEventRecord(m->ev_lut[i], c->stream);
+            e = launch_sky_lut_rows(w, h, m->all_peer ? i : 0, m->all_peer ? n : 1, p->sun_direction, c->d_trans_f, c->tw, c->th, reinterpret_cast<uint2*>(c0->sky_h_ring[k].get()), c0->sky_f_ring[k], c->stream, c->tlut);
+        if (e == hipSuccess) e = hipEventRecord(m->dev[i].lut, c->stream);
         if (e != hipSuccess) return mfail(m, CSKY_ERR_HIP, "csky_multi_render_sky_lut: device index %d: %s", i, hipGetErrorString(e));
         for (int q = 0; q < 3; q++) c->sky_sun[q] = p->sun_direction[q];
         c->psw = w; c->psh = h; c->sky_partial = true; c->have_sky = true;
         if (i) { c->sky_in_memory = false; c->lut_writers.clear(); }
     }
     c0->sky_cur = k; c0->d_sky_h = c0->sky_h_ring[k]; c0->d_sky_f = c0->sky_f_ring[k]; c0->sky_in_memory = true;
-    c0->lut_writers.assign(m->ev_lut.begin() + 1, m->ev_lut.end());      // (its own rows are on its prologue stream, ahead of any reader)
+    c0->lut_writers.clear();
+    for (int i = 1; i < n; i++) c0->lut_writers.push_back(m->dev[i].lut);   // (its own rows are on its prologue stream, ahead of any reader)
     return CSKY_OK;
 }
 
@@ -268,41 +263,40 @@ int csky_multi_render_clouds_device(csky_multi* m, const csky_cloud_params* p, i
     if (!d_out || !p) return mfail(m, CSKY_ERR_INVALID, "csky_multi_render_clouds_device: NULL argument");
     if (tile_w < 1 || tile_h < 8 || (tile_h & 7)) return mfail(m, CSKY_ERR_INVALID, "csky_multi_render_clouds_device: tile_h must be a positive multiple of 8 (bands are 8 rows)");
     if (pitch % 8 || pitch < (size_t)tile_w * 8) return mfail(m, CSKY_ERR_INVALID, "csky_multi_render_clouds_device: row pitch must be a multiple of 8 and >= tile_w*8");
-    const int n_all = (int)m->ctx.size(), total = tile_h / 8;
+    const int n_all = (int)m->dev.size(), total = tile_h / 8;
     // Frame groups (csky_multi_set_groups): consecutive frames go to the G groups in turn; the n/G devices of a group split the frame's bands.
     // Slot = frame number mod (groups x frames in flight): its events, and on every device of the group the stream / ring position
     // slot / groups of that device's frames in flight.
     const int G = m->groups, per = n_all / G, slots = G * m->fif;
     const int slot = (int)(m->frame_no % (unsigned long long)slots), grp = slot % G, dslot = slot / G;   // (frame_no advances only when the frame was enqueued: a failed call must not shift the slot / group rotation)
-    csky_ctx* c0 = m->ctx[0];
+    csky_ctx* c0 = m->dev[0].ctx;
     int rc; if ((rc = bind(c0))) return mpass(m, 0, rc);
     hipStream_t consumer = hip_stream ? (hipStream_t)hip_stream : c0->stream;
     // no device may store into the frame before the consumer's earlier work on it (reads of the previous frame) is done
     if (hipEventRecord(m->ev_begin[slot], consumer) != hipSuccess) return mfail(m, CSKY_ERR_HIP, "csky_multi_render_clouds_device: hipEventRecord failed");
     for (int k = 0; k < per; k++) {
         const int i = grp * per + k;
-        csky_ctx* c = m->ctx[i];
+        Dev& d = m->dev[i];
+        csky_ctx* c = d.ctx;
         if ((rc = bind(c))) return mpass(m, i, rc);
         const int nb = k < total ? (total - k + per - 1) / per : 0;
         if (nb == 0) continue;
-        hipStream_t s = (i == 0) ? consumer : m->side[dslot][i];
+        hipStream_t s = (i == 0) ? consumer : d.side[dslot];
         if (i != 0 && hipStreamWaitEvent(s, m->ev_begin[slot], 0) != hipSuccess) return mfail(m, CSKY_ERR_HIP, "csky_multi_render_clouds_device: hipStreamWaitEvent failed");
         const csky_bands b = {8, k, per, nb};
-        const bool tmg = m->timing && m->tm[0][i];
-        if (tmg) { m->tm_valid[i] = 0; if (hipEventRecord(m->tm[0][i], s) != hipSuccess) return mfail(m, CSKY_ERR_HIP, "csky_multi_render_clouds_device: hipEventRecord failed"); }
+        const bool tmg = m->timing && d.tm[0];
+        if (tmg) { d.tm_valid = 0; if (hipEventRecord(d.tm[0], s) != hipSuccess) return mfail(m, CSKY_ERR_HIP, "csky_multi_render_clouds_device: hipEventRecord failed"); }
         if (m->staged && i != 0) {
             // Fallback for nodes where fine-grained remote stores from inside the march stall: the device renders its bands into a compact local
             // buffer and one strided peer copy (a band = 8 rows, n bands apart in the frame) moves them over xGMI behind the march.
             const size_t need = (size_t)nb * 8 * tile_w;
-            if (m->stage_px[dslot][i] < need) {
+            if (d.stage[dslot].count() < need) {
                 if (hipStreamSynchronize(s) != hipSuccess) return mfail(m, CSKY_ERR_HIP, "csky_multi_render_clouds_device: hipStreamSynchronize failed");
-                if (m->d_stage[dslot][i]) { (void)hipFree(m->d_stage[dslot][i]); m->d_stage[dslot][i] = nullptr; m->stage_px[dslot][i] = 0; }
-                if (hipMalloc(reinterpret_cast<void**>(&m->d_stage[dslot][i]), need * 8) != hipSuccess) return mfail(m, CSKY_ERR_HIP, "csky_multi_render_clouds_device: hipMalloc of the staging buffer failed");
-                m->stage_px[dslot][i] = need;
+                if ((rc = d.stage[dslot].alloc(c, need))) return mpass(m, i, rc);
             }
-            uint2* st = m->d_stage[dslot][i];
+            uint2* st = d.stage[dslot];
             if ((rc = clouds_dev(c, p, tile_w, &b, st, (size_t)tile_w * 8, s, nullptr, true, /*out_full=*/false))) return mpass(m, i, rc);
-            if (tmg && hipEventRecord(m->tm[1][i], s) == hipSuccess) m->tm_valid[i] = 1;
+            if (tmg && hipEventRecord(d.tm[1], s) == hipSuccess) d.tm_valid = 1;
             const size_t band_bytes = (size_t)8 * tile_w * 8;
             char* dst0 = (char*)d_out + (size_t)k * 8 * pitch;
             hipError_t e;
@@ -313,18 +307,18 @@ int csky_multi_render_clouds_device(csky_multi* m, const csky_cloud_params* p, i
                     e = hipMemcpy2DAsync(dst0 + (size_t)bnd * per * 8 * pitch, pitch, (char*)st + (size_t)bnd * band_bytes, (size_t)tile_w * 8, (size_t)tile_w * 8, 8, hipMemcpyDeviceToDevice, s);
             }
             if (e != hipSuccess) return mfail(m, CSKY_ERR_HIP, "csky_multi_render_clouds_device: peer copy failed: %s", hipGetErrorString(e));
-            if (tmg && m->tm_valid[i] == 1 && hipEventRecord(m->tm[2][i], s) == hipSuccess) m->tm_valid[i] = 2;
+            if (tmg && d.tm_valid == 1 && hipEventRecord(d.tm[2], s) == hipSuccess) d.tm_valid = 2;
         } else {
             if ((rc = clouds_dev(c, p, tile_w, &b, (uint2*)d_out, pitch, s, nullptr, true, /*out_full=*/true))) return mpass(m, i, rc);
-            if (tmg && hipEventRecord(m->tm[1][i], s) == hipSuccess) m->tm_valid[i] = 1;
+            if (tmg && hipEventRecord(d.tm[1], s) == hipSuccess) d.tm_valid = 1;
         }
-        if (i != 0 && hipEventRecord(m->ev_done[slot][i], s) != hipSuccess) return mfail(m, CSKY_ERR_HIP, "csky_multi_render_clouds_device: hipEventRecord failed");
+        if (i != 0 && hipEventRecord(d.done[slot], s) != hipSuccess) return mfail(m, CSKY_ERR_HIP, "csky_multi_render_clouds_device: hipEventRecord failed");
     }
     if ((rc = bind(c0))) return mpass(m, 0, rc);
     for (int k = 0; k < per; k++) {
         const int i = grp * per + k;
         if (i == 0 || k >= total) continue;
-        if (hipStreamWaitEvent(consumer, m->ev_done[slot][i], 0) != hipSuccess) return mfail(m, CSKY_ERR_HIP, "csky_multi_render_clouds_device: hipStreamWaitEvent failed");
+        if (hipStreamWaitEvent(consumer, m->dev[i].done[slot], 0) != hipSuccess) return mfail(m, CSKY_ERR_HIP, "csky_multi_render_clouds_device: hipStreamWaitEvent failed");
     }
     m->frame_no++;
     return CSKY_OK;
@@ -334,14 +328,12 @@ int csky_multi_render_clouds(csky_multi* m, const csky_cloud_params* p, int tile
     if (!m) return mfail(nullptr, CSKY_ERR_INVALID, "csky_multi_render_clouds: handle is NULL");
     if (tile_w < 1 || tile_h < 8 || (tile_h & 7)) return mfail(m, CSKY_ERR_INVALID, "csky_multi_render_clouds: tile_h must be a positive multiple of 8 (bands are 8 rows; the single-device csky_render_clouds takes ragged tiles)");
     if (out && pitch < (size_t)tile_w * 8) return mfail(m, CSKY_ERR_INVALID, "csky_multi_render_clouds: row_pitch_bytes < tile_w*8");
-    csky_ctx* c0 = m->ctx[0];
+    csky_ctx* c0 = m->dev[0].ctx;
     int rc; if ((rc = bind(c0))) return mpass(m, 0, rc);
     const size_t px = (size_t)tile_w * tile_h;
-    if (m->frame_px < px) {
+    if (m->d_frame.count() < px) {
         if (hipStreamSynchronize(c0->stream) != hipSuccess) return mfail(m, CSKY_ERR_HIP, "csky_multi_render_clouds: hipStreamSynchronize failed");
-        if (m->d_frame) { (void)hipFree(m->d_frame); m->d_frame = nullptr; m->frame_px = 0; }
-        if (hipMalloc(reinterpret_cast<void**>(&m->d_frame), px * 8) != hipSuccess) return mfail(m, CSKY_ERR_HIP, "csky_multi_render_clouds: hipMalloc failed");
-        m->frame_px = px;
+        if ((rc = m->d_frame.alloc(c0, px))) return mpass(m, 0, rc);
     }
     if ((rc = csky_multi_render_clouds_device(m, p, tile_w, tile_h, m->d_frame, (size_t)tile_w * 8, nullptr))) return rc;
     if ((rc = bind(c0))) return mpass(m, 0, rc);
@@ -355,7 +347,7 @@ int csky_multi_render_clouds(csky_multi* m, const csky_cloud_params* p, int tile
 int csky_multi_set_host_ring(csky_multi* m, int slots) {
     if (!m) return mfail(nullptr, CSKY_ERR_INVALID, "csky_multi_set_host_ring: handle is NULL");
     if (slots < 1 || slots > HOST_RING || slots > m->groups * RING || slots % m->groups) return mfail(m, CSKY_ERR_INVALID, "csky_multi_set_host_ring: 1 .. 8 frames, a multiple of the group count, at most 8 per group");
-    csky_ctx* c0 = m->ctx[0];
+    csky_ctx* c0 = m->dev[0].ctx;
     for (auto& hs : c0->hring) if (hs.busy) return mfail(m, CSKY_ERR_STATE, "csky_multi_set_host_ring: collect the outstanding tickets first");
     const int rc = csky_multi_set_frames_in_flight(m, slots / m->groups); if (rc) return rc;
     c0->hslots = slots;
@@ -365,13 +357,13 @@ int csky_multi_submit_clouds(csky_multi* m, const csky_cloud_params* p, int tile
     if (!m) return mfail(nullptr, CSKY_ERR_INVALID, "csky_multi_submit_clouds: handle is NULL");
     if (!ticket || !p) return mfail(m, CSKY_ERR_INVALID, "csky_multi_submit_clouds: NULL argument");
     if (tile_w < 1 || tile_h < 8 || (tile_h & 7) || tile_w > 16384 || tile_h > 16384) return mfail(m, CSKY_ERR_INVALID, "csky_multi_submit_clouds: tile_h must be a positive multiple of 8, sizes <= 16384");
-    csky_ctx* c0 = m->ctx[0];
+    csky_ctx* c0 = m->dev[0].ctx;
     if (c0->hslots != m->groups * m->fif) { const int rc = csky_multi_set_host_ring(m, m->groups * m->fif); if (rc) return rc; }
     int rc; if ((rc = bind(c0))) return mpass(m, 0, rc);
     csky_ctx::HostSlot& hs = c0->hring[c0->next_ticket % c0->hslots];
     if (hs.busy) return mfail(m, CSKY_ERR_STATE, "csky_multi_submit_clouds: %d frames are already in flight; collect ticket %lld first", c0->hslots, hs.ticket);
     const size_t px = (size_t)tile_w * tile_h;
-    if ((rc = host_slot_prepare(c0, hs, px, true))) return mpass(m, 0, rc);
+    if ((rc = host_slot_prepare(c0, hs, px))) return mpass(m, 0, rc);
     if ((rc = csky_multi_render_clouds_device(m, p, tile_w, tile_h, hs.d, (size_t)tile_w * 8, hs.s))) return rc;
     if ((rc = bind(c0))) return mpass(m, 0, rc);
     if (hipMemcpyAsync(hs.h, hs.d, px * 8, hipMemcpyDeviceToHost, hs.s) != hipSuccess || hipEventRecord(hs.done, hs.s) != hipSuccess)
@@ -382,15 +374,15 @@ int csky_multi_submit_clouds(csky_multi* m, const csky_cloud_params* p, int tile
 }
 int csky_multi_collect(csky_multi* m, int64_t ticket, const uint16_t** frame, size_t* bytes) {
     if (!m) return mfail(nullptr, CSKY_ERR_INVALID, "csky_multi_collect: handle is NULL");
-    return mpass(m, 0, csky_collect(m->ctx[0], ticket, frame, bytes));
+    return mpass(m, 0, csky_collect(m->dev[0].ctx, ticket, frame, bytes));
 }
 
 int csky_multi_sync(csky_multi* m) {
     if (!m) return mfail(nullptr, CSKY_ERR_INVALID, "csky_multi_sync: handle is NULL");
-    for (size_t i = 0; i < m->ctx.size(); i++) {
-        const int rc = csky_sync(m->ctx[i]); if (rc) return mpass(m, (int)i, rc);
+    for (size_t i = 0; i < m->dev.size(); i++) {
+        const int rc = csky_sync(m->dev[i].ctx); if (rc) return mpass(m, (int)i, rc);
         for (int k = 0; k < RING; k++)                         // the march streams of a device's frames in flight
-            if (hipStreamSynchronize(m->side[k][i]) != hipSuccess) return mfail(m, CSKY_ERR_HIP, "csky_multi_sync: hipStreamSynchronize failed on device index %d", (int)i);
+            if (hipStreamSynchronize(m->dev[i].side[k]) != hipSuccess) return mfail(m, CSKY_ERR_HIP, "csky_multi_sync: hipStreamSynchronize failed on device index %d", (int)i);
     }
     return CSKY_OK;
 }

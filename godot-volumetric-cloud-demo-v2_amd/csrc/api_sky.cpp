@@ -36,11 +36,7 @@ int composite_impl(csky_ctx* c, const csky_composite_params* p, const csky_view*
     if (!c->have_trans && (rc = render_trans_dev(c, 256, 64, c->stream))) return rc;       // source_transmittance, clouds_material.tres
     const size_t cb = (size_t)p->cloud_w * p->cloud_h * 8, sb = (size_t)p->sky_w * p->sky_h * 8, ob = (size_t)p->out_w * p->out_h * 8;
     const size_t need = 2 * cb + 2 * sb + ob;
-    if (c->composite_cap < need) {                            // grow-only scratch: no allocation per call once the sizes have been seen
-        if (c->d_composite) { (void)hipFree(c->d_composite); c->d_composite = nullptr; c->composite_cap = 0; }
-        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_composite), need));
-        c->composite_cap = need;
-    }
+    if ((rc = c->d_composite.grow(c, need))) return rc;       // grow-only scratch: no allocation per call once the sizes have been seen
     uint8_t* d = c->d_composite;
     hipError_t e = hipSuccess;
     auto up = [&](size_t off, const void* src, size_t n) { if (e == hipSuccess) e = hipMemcpyAsync(d + off, src, n, hipMemcpyHostToDevice, c->stream); };
@@ -69,25 +65,19 @@ int rad_args(csky_ctx* c, const char* fn, const csky_radiance_params* rp, int fi
     if (first < 0 || n < 1 || first >= L || n > L - first) return fail(c, CSKY_ERR_INVALID, "%s: layer range [%d, %d + %d) not within [0, %d)", fn, first, first, n, L);
     return CSKY_OK;
 }
-template <class T> int rad_grow(csky_ctx* c, T** p, size_t& cap, size_t n) {
-    if (*p && cap >= n) return CSKY_OK;
-    cap = 0;
-    int rc; if ((rc = dev_alloc(c, p, n))) return rc;
-    cap = n; return CSKY_OK;
-}
 // table storage and the block cones of an (S, Ss) geometry (the cones depend on the geometry alone: rebuilt when it changes)
 int rad_prepare(csky_ctx* c, csky_ctx::RadSet& r, int S, int Ss, hipStream_t s) {
     int rc;
-    if ((rc = rad_grow(c, &r.tab, r.tab_n, (size_t)12 * Ss * Ss))) return rc;
-    if (r.cones_ss != Ss || r.sc_n < (size_t)rad_block_count(Ss)) {
+    if ((rc = r.tab.grow(c, (size_t)12 * Ss * Ss))) return rc;
+    if (r.cones_ss != Ss || r.src_cones.count() < (size_t)rad_block_count(Ss)) {
         r.cones_ss = 0;
-        if ((rc = rad_grow(c, &r.src_cones, r.sc_n, (size_t)rad_block_count(Ss)))) return rc;
+        if ((rc = r.src_cones.grow(c, (size_t)rad_block_count(Ss)))) return rc;
         HIPCHK(c, launch_radiance_cones(Ss, r.src_cones, s));
         r.cones_ss = Ss;
     }
-    if (r.cones_s != S || r.oc_n < (size_t)rad_block_count(S)) {
+    if (r.cones_s != S || r.out_cones.count() < (size_t)rad_block_count(S)) {
         r.cones_s = 0;
-        if ((rc = rad_grow(c, &r.out_cones, r.oc_n, (size_t)rad_block_count(S)))) return rc;
+        if ((rc = r.out_cones.grow(c, (size_t)rad_block_count(S)))) return rc;
         HIPCHK(c, launch_radiance_cones(S, r.out_cones, s));
         r.cones_s = S;
     }
@@ -174,7 +164,7 @@ int csky_render_radiance(csky_ctx* c, const csky_composite_params* p, const csky
     if ((rc = bind(c))) return rc;
     const size_t cb = first_layer == 0 ? (size_t)p->cloud_w * p->cloud_h * 8 : 0, sb = first_layer == 0 ? (size_t)p->sky_w * p->sky_h * 8 : 0;
     const size_t ob = (size_t)n_layers * 6 * S * S * 8;
-    if ((rc = rad_grow(c, &c->d_rad_io, c->rad_io_cap, 2 * cb + 2 * sb + ob))) return rc;
+    if ((rc = c->d_rad_io.grow(c, 2 * cb + 2 * sb + ob))) return rc;
     uint8_t* d = c->d_rad_io;
     hipError_t e = hipSuccess;
     auto up = [&](size_t off, const void* src, size_t nb) { if (e == hipSuccess && nb) e = hipMemcpyAsync(d + off, src, nb, hipMemcpyHostToDevice, c->stream); };
@@ -199,7 +189,7 @@ int csky_prefilter_cube(csky_ctx* c, const uint16_t* cube, int face_size, int la
     if ((rc = bind(c))) return rc;
     const size_t plane = (size_t)6 * S * S, lb = plane * 8;
     const int lo = std::max(first_layer, 1), hi = first_layer + n_layers;
-    if ((rc = rad_grow(c, &c->d_rad_io, c->rad_io_cap, lb * (1 + (size_t)(hi - lo))))) return rc;
+    if ((rc = c->d_rad_io.grow(c, lb * (1 + (size_t)(hi - lo))))) return rc;
     uint8_t* d = c->d_rad_io;
     uint2* d_o = reinterpret_cast<uint2*>(d + lb);
     HIPCHK(c, hipMemcpyAsync(d, cube, lb, hipMemcpyHostToDevice, c->stream));

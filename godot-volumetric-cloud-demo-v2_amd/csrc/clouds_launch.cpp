@@ -37,16 +37,14 @@ int ensure_order(csky_ctx* c, int slot, int mode, int tile_w, int tiles_x, int s
     else grid = ((slabs + 7) >> 3) * tiles_x * 8;
     const long long key[4] = {tile_w, slabs, mode, grid};
     if (c->d_order_ring[slot] && memcmp(key, c->order_key_ring[slot], sizeof key) == 0) return CSKY_OK;
-    if (c->order_cap[slot] < (size_t)grid) {
+    if (c->d_order_ring[slot].count() < (size_t)grid) {
         // growing is rare and costs a device-wide wait (an older launch may still read the old table): grow EVERY slot's table now, so that it
         // happens once, at the first frame of a geometry, and not again at the first use of each of the other ring slots (with rings eight deep
         // and a five-frame warm-up that was three synchronisations inside a timed region)
         HIPCHK(c, hipDeviceSynchronize());
         for (int k = 0; k < RING; k++) {
-            if (c->order_cap[k] >= (size_t)grid) continue;
-            if (c->d_order_ring[k]) { (void)hipFree(c->d_order_ring[k]); c->d_order_ring[k] = nullptr; c->order_cap[k] = 0; }
-            HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_order_ring[k]), (size_t)grid * sizeof(uint32_t)));
-            c->order_cap[k] = (size_t)grid;
+            if (c->d_order_ring[k].count() >= (size_t)grid) continue;
+            int rc; if ((rc = c->d_order_ring[k].alloc(c, (size_t)grid))) return rc;
             for (long long& v : c->order_key_ring[k]) v = -1;
         }
     }
@@ -66,20 +64,14 @@ int check_bands(csky_ctx* c, const csky_bands* b, int tile_w) {
     return CSKY_OK;
 }
 
-// The event pool of csky_set_kernel_timing grows to `want` events.  All or nothing: a hipEventCreate failing part-way used to leave null
-// entries in the pool for later timed launches to record on; now the new events made so far are destroyed and the pool keeps its old size.
+// The event pool of csky_set_kernel_timing grows to `want` events.  All or nothing: an event that cannot be made part-way used to leave
+// null entries in the pool for later timed launches to record on; now the new events made so far go with the resize and the pool keeps its old size.
 int grow_timing_pool(csky_ctx* c, size_t want) {
     const size_t old_n = c->kt_ev.size();
     if (want <= old_n) return CSKY_OK;
-    c->kt_ev.resize(want, nullptr);
-    for (size_t i = old_n; i < want; i++) {
-        const hipError_t e = hipEventCreate(&c->kt_ev[i]);
-        if (e != hipSuccess) {
-            for (size_t j = old_n; j < i; j++) (void)hipEventDestroy(c->kt_ev[j]);
-            c->kt_ev.resize(old_n);
-            return fail(c, CSKY_ERR_HIP, "kernel timing: hipEventCreate: %s", hipGetErrorString(e));
-        }
-    }
+    c->kt_ev.resize(want);
+    for (size_t i = old_n; i < want; i++)
+        if (const int rc = c->kt_ev[i].create(c, hipEventDefault)) { c->kt_ev.resize(old_n); return rc; }
     return CSKY_OK;
 }
 
@@ -127,7 +119,7 @@ int clouds_dev(csky_ctx* c, const csky_cloud_params* p, int tile_w, const csky_b
     uint32_t* const heads = pl.persist ? c->d_heads + slot * 16 : nullptr;
     TexSet32 t32; const TexSet32* t32p = nullptr;
     if (c->cell32) { t32 = texset32(c); t32p = &t32; }
-    hipEvent_t* kt = nullptr;                                    // timing pair of this launch (csky_set_kernel_timing)
+    const Event* kt = nullptr;                                   // timing pair of this launch (csky_set_kernel_timing)
     if (c->kt_on) {
         if ((size_t)c->kt_count * 2 + 2 > c->kt_ev.size()) {    // the pool grows on demand: no launch is ever dropped from the sum
             if ((rc = grow_timing_pool(c, c->kt_ev.empty() ? 512 : c->kt_ev.size() * 2))) return rc;
@@ -145,21 +137,21 @@ int clouds_dev(csky_ctx* c, const csky_cloud_params* p, int tile_w, const csky_b
         // order and sort scratch are per ring slot (= per frame parity, like the frame constants), so two frames in flight on two
         // streams never share them; reuse of a slot is ordered by ev_clouds, recorded below after the sort.
         const size_t need = (size_t)(grid > nblocks ? grid : nblocks);
-        if (c->lpt_cap < need) {
+        if (c->d_lpt_order.count() < RING * need) {
             HIPCHK(c, hipDeviceSynchronize());                   // (re)allocation is rare; frames may be in flight on other streams
-            (void)hipFree(c->d_wg_cost); (void)hipFree(c->d_lpt_order); c->d_wg_cost = c->d_lpt_order = nullptr; c->lpt_cap = 0;
+            c->d_wg_cost.reset(); c->d_lpt_order.reset();        // the order, allocated last, carries the capacity of the pair: a failure on the way leaves it empty
             for (int k = 0; k < RING; k++) c->lpt_valid[k] = false;
-            HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_wg_cost), RING * need * sizeof(uint32_t)));
-            HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_lpt_order), RING * need * sizeof(uint32_t)));
+            if ((rc = c->d_wg_cost.alloc(c, RING * need))) return rc;
             if (!c->d_lpt_hist) {
-                HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_lpt_hist), RING * 2048 * sizeof(uint32_t)));
+                if ((rc = c->d_lpt_hist.alloc(c, RING * 2048))) return rc;
                 HIPCHK(c, hipMemset(c->d_lpt_hist, 0, RING * 2048 * sizeof(uint32_t)));
             }
             HIPCHK(c, hipMemset(c->d_wg_cost, 0, RING * need * sizeof(uint32_t)));       // the sort kernels leave both zeroed afterwards
-            c->lpt_cap = need;
+            if ((rc = c->d_lpt_order.alloc(c, RING * need))) return rc;
         }
-        cost = c->d_wg_cost + (size_t)slot * c->lpt_cap;
-        lorder = c->d_lpt_order + (size_t)slot * c->lpt_cap;
+        const size_t per_slot = c->d_lpt_order.count() / RING;
+        cost = c->d_wg_cost + (size_t)slot * per_slot;
+        lorder = c->d_lpt_order + (size_t)slot * per_slot;
         // the costs belong to one view of one tile: same launch geometry AND same place in the texture (a tile walk never reuses them)
         const long long fkey[11] = {g.tile_w, g.band_rows, g.first_band, g.band_stride, g.n_bands, (long long)cp.texture_size[0], (long long)cp.texture_size[1],
                                     (long long)cp.update_position[0], (long long)cp.update_position[1], pl.mode * 16 + pl.static_mode, pl.seg};

@@ -1,0 +1,222 @@
+// TEST TOOL ONLY: the owner types of csrc/owners.h and the destruction of a real csky_ctx (csrc/context.h), run on the CPU.
+// The HIP entry points the owners use are defined HERE as counting stubs: they hand out distinct fake handles (never dereferenced), refuse a release
+// of a handle that is not live, and log every release in order.  No GPU call is made and the HIP runtime is not linked.
+// Prints one "name value" line per figure and "FAIL: ..." per broken expectation; exit status 1 if any.  tests/test_owners_host.py checks both.
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+#include <set>
+#include <utility>
+#include <vector>
+#include "../../godot-volumetric-cloud-demo-v2_amd/csrc/context.h"
+
+namespace {
+
+enum Kind { DEV, PINNED, EVENT, STREAM, KINDS };
+const char* const kind_name[KINDS] = {"dev", "pinned", "event", "stream"};
+struct Release { Kind kind; void* handle; };
+
+uintptr_t g_next = 0;
+std::set<void*> g_live[KINDS];
+std::vector<Release> g_log;            // every release, in order
+std::vector<Kind> g_calls;             // every acquire (its kind) and release (its kind + KINDS), in order
+long g_made[KINDS] = {}, g_bad_release = 0, g_last_error_calls = 0;
+int g_fail_next_malloc = 0;
+int g_failures = 0;
+
+hipError_t acquire(Kind k, void** out) {
+    g_calls.push_back(k);
+    void* h = reinterpret_cast<void*>(++g_next * 0x1000);
+    g_live[k].insert(h); g_made[k]++;
+    *out = h;
+    return hipSuccess;
+}
+hipError_t release(Kind k, void* h) {
+    g_calls.push_back(static_cast<Kind>(k + KINDS));
+    if (!g_live[k].erase(h)) { g_bad_release++; return hipErrorInvalidValue; }   // never handed out, of another kind, or released before
+    g_log.push_back({k, h});
+    return hipSuccess;
+}
+
+void expect(bool ok, const char* fmt, ...) {
+    if (ok) return;
+    g_failures++;
+    printf("FAIL: ");
+    va_list ap; va_start(ap, fmt); vprintf(fmt, ap); va_end(ap);
+    printf("\n");
+}
+long live_total() { long n = 0; for (auto& s : g_live) n += (long)s.size(); return n; }
+long released(Kind k, size_t from = 0) { long n = 0; for (size_t i = from; i < g_log.size(); i++) n += g_log[i].kind == k; return n; }
+
+}  // namespace
+
+extern "C" {
+hipError_t hipMalloc(void** p, size_t) {
+    if (g_fail_next_malloc) { g_fail_next_malloc = 0; g_calls.push_back(DEV); *p = nullptr; return hipErrorOutOfMemory; }
+    return acquire(DEV, p);
+}
+hipError_t hipFree(void* p) { return release(DEV, p); }
+hipError_t hipHostMalloc(void** p, size_t, unsigned int) { return acquire(PINNED, p); }
+hipError_t hipHostFree(void* p) { return release(PINNED, p); }
+hipError_t hipEventCreate(hipEvent_t* e) { return acquire(EVENT, reinterpret_cast<void**>(e)); }
+hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { return acquire(EVENT, reinterpret_cast<void**>(e)); }
+hipError_t hipEventDestroy(hipEvent_t e) { return release(EVENT, e); }
+hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned int) { return acquire(STREAM, reinterpret_cast<void**>(s)); }
+hipError_t hipStreamDestroy(hipStream_t s) { return release(STREAM, s); }
+hipError_t hipGetLastError(void) { g_last_error_calls++; return hipSuccess; }
+const char* hipGetErrorString(hipError_t e) { return e == hipErrorOutOfMemory ? "out of memory (stub)" : "error (stub)"; }
+}
+
+namespace csky {
+thread_local char g_err[512];
+int fail(csky_ctx* c, int code, const char* fmt, ...) {       // as api.cpp's
+    char* dst = c ? c->err : g_err;
+    va_list ap; va_start(ap, fmt); vsnprintf(dst, 512, fmt, ap); va_end(ap);
+    if (code == CSKY_ERR_HIP) (void)hipGetLastError();
+    return code;
+}
+}  // namespace csky
+
+using namespace csky;
+
+namespace {
+
+// 1. each owner type: one release, none after being moved from (by construction or by assignment), none when empty
+template <class Owner, class Make> void once(Kind k, const char* what, Make make) {
+    const size_t log0 = g_log.size(); const long bad0 = g_bad_release;
+    { Owner empty; }
+    expect(g_log.size() == log0, "%s: an empty owner made a release call", what);
+    {
+        Owner a; make(a);
+        void* const h = *g_live[k].rbegin();
+        Owner b(std::move(a));
+        expect(!a, "%s: still holds its handle after being moved from", what);
+        Owner c; make(c);                                      // c's own handle must go when it is assigned over
+        c = std::move(b);
+        expect(!b, "%s: still holds its handle after being move-assigned from", what);
+        expect(released(k, log0) == 1, "%s: move assignment released %ld handles, not the one it overwrote", what, released(k, log0));
+        expect(g_live[k].count(h) == 1, "%s: the moved handle died on the way", what);
+        c.reset();
+        expect(!c && g_live[k].count(h) == 0, "%s: reset() did not release", what);
+        c.reset();
+    }
+    expect(released(k, log0) == 2 && g_log.size() == log0 + 2, "%s: 2 handles made, %ld released", what, released(k, log0));
+    expect(g_bad_release == bad0, "%s: a handle was released twice", what);
+    printf("owner_%s_made 2\nowner_%s_released %ld\n", kind_name[k], kind_name[k], released(k, log0));
+}
+
+void test_owners(csky_ctx* c) {
+    once<DevBuf<float>>(DEV, "DevBuf", [&](DevBuf<float>& b) { expect(b.alloc(c, 16) == CSKY_OK && b.count() == 16, "DevBuf::alloc"); });
+    once<PinnedBuf>(PINNED, "PinnedBuf", [&](PinnedBuf& b) { expect(b.alloc(c, 64) == CSKY_OK && b.count() == 64, "PinnedBuf::alloc"); });
+    once<Event>(EVENT, "Event", [&](Event& e) { expect(e.create(c, hipEventDisableTiming) == CSKY_OK, "Event::create"); });
+    once<Event>(EVENT, "Event (timing)", [&](Event& e) { expect(e.create(c, hipEventDefault) == CSKY_OK, "Event::create"); });
+    once<Stream>(STREAM, "Stream", [&](Stream& s) { expect(s.create(c, hipStreamNonBlocking) == CSKY_OK, "Stream::create"); });
+
+    // 2. alloc releases the old buffer BEFORE it asks for the new one;  3. grow makes no call when the buffer is large enough
+    {
+        DevBuf<uint2> b;
+        expect(b.grow(c, 100) == CSKY_OK && b.count() == 100, "grow of an empty buffer");
+        uint2* const first = b;
+        size_t calls0 = g_calls.size();
+        expect(b.grow(c, 100) == CSKY_OK && b.grow(c, 1) == CSKY_OK && b.grow(c, 0) == CSKY_OK, "grow within the capacity");
+        expect(g_calls.size() == calls0 && b == first && b.count() == 100, "grow within the capacity made %zu HIP calls", g_calls.size() - calls0);
+        printf("grow_within_capacity_calls %zu\n", g_calls.size() - calls0);
+        calls0 = g_calls.size();
+        expect(b.grow(c, 101) == CSKY_OK && b.count() == 101, "grow beyond the capacity");
+        expect(g_calls.size() == calls0 + 2 && g_calls[calls0] == DEV + KINDS && g_calls[calls0 + 1] == DEV, "grow beyond the capacity: not hipFree then hipMalloc");
+        calls0 = g_calls.size();
+        expect(b.alloc(c, 7) == CSKY_OK && b.count() == 7, "alloc allocates exactly what it is asked for");
+        expect(g_calls.size() == calls0 + 2 && g_calls[calls0] == DEV + KINDS && g_calls[calls0 + 1] == DEV, "alloc: not hipFree then hipMalloc");
+        printf("alloc_order_free_then_malloc %d\n", g_calls[calls0] == DEV + KINDS && g_calls[calls0 + 1] == DEV);
+
+        // 4. a failed hipMalloc: the owner is empty with count 0 (the old buffer is gone: it went first), the context has the text
+        c->err[0] = 0;
+        const long le0 = g_last_error_calls, live0 = (long)g_live[DEV].size();
+        g_fail_next_malloc = 1;
+        const int rc = b.grow(c, 1000);
+        expect(rc == CSKY_ERR_HIP, "failed hipMalloc: return code %d", rc);
+        expect(!b && b.count() == 0, "failed hipMalloc: the owner is not empty");
+        expect((long)g_live[DEV].size() == live0 - 1, "failed hipMalloc: the old buffer was not released");
+        expect(c->err[0] != 0, "failed hipMalloc: no error text in the context");
+        expect(g_last_error_calls == le0 + 1, "failed hipMalloc: the runtime's sticky error was not cleared");
+        printf("failed_malloc_error_text %s\n", c->err);
+    }
+    expect(live_total() == 0, "owner tests: %ld handles left alive", live_total());
+}
+
+// 5. / 6. a real csky_ctx with every owning member populated, then deleted
+void test_context() {
+    const long made0[KINDS] = {g_made[DEV], g_made[PINNED], g_made[EVENT], g_made[STREAM]};
+    const size_t log0 = g_log.size(); const long bad0 = g_bad_release;
+    Event foreign; foreign.create(nullptr, hipEventDisableTiming);      // what csky_multi owns and lut_writers only views
+    csky_ctx* c = new csky_ctx();
+    int rc = 0;
+    // in an order unlike the declaration order on purpose: what dies when is the struct's business
+    for (auto& hs : c->hring) { rc |= hs.h.alloc(c, 4096); rc |= hs.d.alloc(c, 512); rc |= hs.done.create(c, hipEventDisableTiming); rc |= hs.s.create(c, hipStreamNonBlocking); }
+    c->kt_ev.resize(2); for (Event& e : c->kt_ev) rc |= e.create(c, hipEventDefault);
+    { const size_t old_n = c->kt_ev.size(); c->kt_ev.resize(70); for (size_t i = old_n; i < c->kt_ev.size(); i++) rc |= c->kt_ev[i].create(c, hipEventDefault); }   // a grown pool: the vector moved its events
+    for (csky_ctx::RadSet* r : {&c->rad_pf, &c->rad}) { rc |= r->out_cones.alloc(c, 6); rc |= r->src_cones.alloc(c, 6); rc |= r->tab.alloc(c, 12); }
+    rc |= c->d_rad_io.alloc(c, 64); rc |= c->ev_rad.create(c, hipEventDisableTiming); rc |= c->d_composite.alloc(c, 64);
+    rc |= c->d_heads.alloc(c, RING * 16); rc |= c->d_lpt_hist.alloc(c, 8); rc |= c->d_lpt_order.alloc(c, 8); rc |= c->d_wg_cost.alloc(c, 8);
+    for (int k = 0; k < RING; k++) { rc |= c->d_order_ring[k].alloc(c, 8); rc |= c->ev_clouds[k].create(c, hipEventDisableTiming); rc |= c->ev_setup[k].create(c, hipEventDisableTiming); rc |= c->fc_ring[k].alloc(c, 1); }
+    rc |= c->d_frame.alloc(c, 64); rc |= c->d_stats.alloc(c, 130);
+    for (int k = 0; k < 2; k++) { rc |= c->sky_f_ring[k].alloc(c, 8); rc |= c->sky_h_ring[k].alloc(c, 32); }
+    rc |= c->d_trans_f.alloc(c, 8); rc |= c->d_trans_h.alloc(c, 32);
+    rc |= c->d_weather32.alloc(c, 8); rc |= c->d_detail32.alloc(c, 8); rc |= c->d_shape32.alloc(c, 8); rc |= c->d_brick.alloc(c, 8);
+    rc |= c->d_detail_h.alloc(c, 8); rc |= c->d_weather.alloc(c, 8); rc |= c->d_detail.alloc(c, 8); rc |= c->d_shape.alloc(c, 8);
+    rc |= c->d_bake_meta.alloc(c, 32); rc |= c->d_raw_weather.alloc(c, 8); rc |= c->d_raw_small.alloc(c, 8); rc |= c->d_raw_large.alloc(c, 8);
+    rc |= c->ev_copy.create(c, hipEventDisableTiming); rc |= c->ev1.create(c, hipEventDefault); rc |= c->ev0.create(c, hipEventDefault);
+    rc |= c->stream.create(c, hipStreamNonBlocking);
+    // the views: aliases of ring slots and copies of somebody else's events.  None of them may be released by the context.
+    c->d_sky_h = c->sky_h_ring[1]; c->d_sky_f = c->sky_f_ring[1]; c->d_fc = c->fc_ring[3]; c->lut_writers.push_back(foreign);
+    expect(rc == 0, "populating the context failed");
+    void* const main_stream = static_cast<hipStream_t>(c->stream);
+    const long made[KINDS] = {g_made[DEV] - made0[DEV], g_made[PINNED] - made0[PINNED], g_made[EVENT] - made0[EVENT] - 1, g_made[STREAM] - made0[STREAM]};
+    // the owning members of context.h, counted by hand
+    const long want[KINDS] = {12 + 2 + 4 + RING + 2 + RING + 4 + 1 + 6 + 1 + HOST_RING, HOST_RING, 4 + 2 * RING + 70 + HOST_RING, 1 + HOST_RING};
+    for (int k = 0; k < KINDS; k++) expect(made[k] == want[k], "context: %ld %s handles made, %ld expected", made[k], kind_name[k], want[k]);
+
+    delete c;
+
+    for (int k = 0; k < KINDS; k++) {
+        printf("context_%s_made %ld\ncontext_%s_released %ld\n", kind_name[k], made[k], kind_name[k], released((Kind)k, log0));
+        expect(released((Kind)k, log0) == made[k], "context: %ld of %ld %s handles released", released((Kind)k, log0), made[k], kind_name[k]);
+    }
+    expect(g_bad_release == bad0, "context: %ld releases of a handle that was not live (double release)", g_bad_release - bad0);
+    expect(live_total() == 1 && g_live[EVENT].count(static_cast<hipEvent_t>(foreign)) == 1, "context: a viewed event was released, or something is left (%ld live)", live_total());
+    // 6. the context's stream is the last stream destroyed, and after every event
+    size_t last_stream = 0, last_event = 0; void* last_stream_h = nullptr;
+    for (size_t i = log0; i < g_log.size(); i++) {
+        if (g_log[i].kind == STREAM) { last_stream = i; last_stream_h = g_log[i].handle; }
+        if (g_log[i].kind == EVENT) last_event = i;
+    }
+    expect(last_stream_h == main_stream, "context: its stream is not the last stream destroyed");
+    expect(last_stream > last_event, "context: an event was destroyed after the context's stream");
+    printf("context_stream_destroyed_last %d\ncontext_stream_after_every_event %d\n", last_stream_h == main_stream, last_stream > last_event);
+    // a host slot's stream goes after the rest of its slot
+    for (size_t i = log0; i + 1 < g_log.size(); i++)
+        if (g_log[i].kind == STREAM && g_log[i].handle != main_stream && i >= 3)
+            expect(g_log[i - 1].kind == EVENT && g_log[i - 2].kind == DEV && g_log[i - 3].kind == PINNED, "host slot: its stream was not destroyed after its event and buffers");
+}
+
+// 7. an empty context makes no release call
+void test_empty_context() {
+    const size_t calls0 = g_calls.size();
+    delete new csky_ctx();
+    printf("empty_context_calls %zu\n", g_calls.size() - calls0);
+    expect(g_calls.size() == calls0, "an empty context made %zu HIP calls when deleted", g_calls.size() - calls0);
+}
+
+}  // namespace
+
+int main() {
+    {
+        csky_ctx* c = new csky_ctx();
+        test_owners(c);
+        delete c;
+    }
+    test_context();
+    test_empty_context();
+    printf("double_releases %ld\nlive_handles_at_exit %ld\nfailures %d\n", g_bad_release, live_total(), g_failures);
+    return g_failures ? 1 : 0;
+}
