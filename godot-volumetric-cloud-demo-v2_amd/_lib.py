@@ -190,6 +190,8 @@ SYMBOLS = [
     ("csky_build_mips_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     ("csky_read_baked_texture", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("csky_test_sqrt_shell", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    ("csky_test_static_order", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]),
+    ("csky_test_lpt_order", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("csky_census_clouds", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.c_int, C.POINTER(Bands), C.c_void_p, C.c_int]),
     ("csky_mip_offset", C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     ("csky_build_mips", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
@@ -556,6 +558,21 @@ class Context:
         out = np.zeros_like(x)
         self._chk(self._L.csky_test_sqrt_shell(self._h, _ptr(x), _ptr(out), x.size))
         return out
+
+    def test_static_order(self, mode, tiles_x, slabs):
+        """Test hook: the static workgroup order (mode 1, 2 or 5) of a tiles_x x slabs launch as the device writes it; its length is the launch's grid."""
+        grid = C.c_int()
+        self._chk(self._L.csky_test_static_order(self._h, int(mode), int(tiles_x), int(slabs), None, 0, C.byref(grid)))
+        out = np.zeros(grid.value, np.uint32)
+        self._chk(self._L.csky_test_static_order(self._h, int(mode), int(tiles_x), int(slabs), _ptr(out), out.size, C.byref(grid)))
+        return out
+
+    def test_lpt_order(self, cost, shift, rounds=1):
+        """Test hook: the cost-feedback sort, `rounds` times on the same device buffers -> (order of the last round, cost as left, the 2048 scratch words as left)."""
+        cost = np.ascontiguousarray(cost, np.uint32)
+        order, left, scratch = np.zeros(cost.size, np.uint32), np.ones(cost.size, np.uint32), np.ones(2048, np.uint32)
+        self._chk(self._L.csky_test_lpt_order(self._h, _ptr(cost), cost.size, int(shift), int(rounds), _ptr(order), _ptr(left), _ptr(scratch)))
+        return order, left, scratch
 
     def read_baked_texture(self, which):
         """Test hook: the device layouts / mip chains csky_set_noise built, as raw bytes (0 shape, 1 detail, 2 weather, 3 / 4 8-bit chains)."""

@@ -18,6 +18,7 @@
 #include "bake_core.h"
 #include "cloud_core.h"
 #include "lut_core.h"
+#include "order_core.h"
 
 using namespace csky;
 
@@ -260,6 +261,43 @@ int csky_test_sqrt_shell(csky_ctx* c, const float* in, float* out, size_t n) {
     HIPCHK(c, hipMemcpyAsync(d, in, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, launch_sqrt_shell(d, d + n, n, c->stream));
     HIPCHK(c, hipMemcpyAsync(out, d + n, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return CSKY_OK;
+}
+
+int csky_test_static_order(csky_ctx* c, int mode, int tiles_x, int slabs, uint32_t* table, size_t capacity, int* grid_out) {
+    if (!c || !grid_out) return fail(c, CSKY_ERR_INVALID, "csky_test_static_order: NULL argument");
+    if ((mode != 1 && mode != 2 && mode != 5) || tiles_x < 1 || slabs < 1 || (long long)tiles_x * slabs > (1ll << 24))
+        return fail(c, CSKY_ERR_INVALID, "csky_test_static_order: mode 1, 2 or 5, tiles_x and slabs >= 1, at most 2^24 footprints");
+    const int grid = static_order_grid(mode, tiles_x, slabs);            // what ensure_order launches with
+    *grid_out = grid;
+    if (!table) return CSKY_OK;
+    if (capacity < (size_t)grid) return fail(c, CSKY_ERR_INVALID, "csky_test_static_order: table too small (%zu < %d entries)", capacity, grid);
+    int rc; if ((rc = bind(c))) return rc;
+    DevBuf<uint32_t> d; if ((rc = d.alloc(c, (size_t)grid))) return rc;
+    HIPCHK(c, hipMemsetAsync(d, 0x5a, (size_t)grid * sizeof(uint32_t), c->stream));     // neither a footprint nor the idle entry: an entry the kernel leaves out shows
+    HIPCHK(c, launch_static_order(mode, tiles_x, slabs, grid, d, c->stream));
+    HIPCHK(c, hipMemcpyAsync(table, d, (size_t)grid * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return CSKY_OK;
+}
+
+int csky_test_lpt_order(csky_ctx* c, const uint32_t* cost, int n, int shift, int rounds, uint32_t* order_out, uint32_t* cost_out, uint32_t* scratch_out) {
+    if (!c || !cost || !order_out || !cost_out || !scratch_out) return fail(c, CSKY_ERR_INVALID, "csky_test_lpt_order: NULL argument");
+    if (n < 1 || n > (1 << 24) || shift < 0 || shift > 31 || rounds < 1 || rounds > 64)
+        return fail(c, CSKY_ERR_INVALID, "csky_test_lpt_order: n in [1, 2^24], shift in [0, 31], rounds in [1, 64]");
+    int rc; if ((rc = bind(c))) return rc;
+    DevBuf<uint32_t> d_cost, d_order, d_scratch;
+    if ((rc = d_cost.alloc(c, (size_t)n)) || (rc = d_order.alloc(c, (size_t)n)) || (rc = d_scratch.alloc(c, 2 * LPT_BUCKETS))) return rc;
+    HIPCHK(c, hipMemsetAsync(d_scratch, 0, 2 * LPT_BUCKETS * sizeof(uint32_t), c->stream));   // once, like clouds_dev at allocation: the kernels leave the histogram zeroed
+    for (int r = 0; r < rounds; r++) {
+        HIPCHK(c, hipMemcpyAsync(d_cost, cost, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemsetAsync(d_order, 0xff, (size_t)n * sizeof(uint32_t), c->stream));   // an entry this round does not write is not the previous round's
+        HIPCHK(c, launch_lpt_order(d_cost, n, shift, d_scratch, d_order, c->stream));
+    }
+    HIPCHK(c, hipMemcpyAsync(order_out, d_order, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(cost_out, d_cost, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(scratch_out, d_scratch, 2 * LPT_BUCKETS * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return CSKY_OK;
 }

@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #include "kernels.h"
 #include "cloud_core.h"
+#include "order_core.h"
 // FP contraction OFF for the code of this file, like section A of cloud_core.h: what a march adds and multiplies itself (the phase value's dot product,
 // the segments' compositing sums) rounds as written.  Stated here because otherwise the last header decides it, and cloud_core.h ends with contraction on.
 #pragma clang fp contract(off)
@@ -682,7 +683,6 @@ __global__ __launch_bounds__(256, VARIANT == 3 ? CSKY_COMPACT_WAVES : 7) void cl
     unsigned xcc;
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
     xcc &= 7u;                                                 // eight sequences: MI355X has 8 XCDs; a part with fewer just leaves sequences to be stolen, one with more folds two XCDs onto one sequence (both still correct: every entry is popped exactly once)
-    const uint32_t per_xcd = (n_items + 7u) >> 3;
     __shared__ uint32_t ticket, slot_ready[2], slot_reads[2], slot_entry[2], slot_rec[2];
     if (threadIdx.x == 0) { ticket = 0; slot_ready[0] = slot_ready[1] = 0; slot_reads[0] = slot_reads[1] = 0; }
     __syncthreads();
@@ -700,8 +700,8 @@ __global__ __launch_bounds__(256, VARIANT == 3 ? CSKY_COMPACT_WAVES : 7) void cl
                 uint32_t jv = 0;
                 if (lane0) jv = atomicAdd(&heads[y], 1u);
                 const uint32_t j = (uint32_t)__builtin_amdgcn_readfirstlane((int)jv);
-                const uint32_t i = 8u * j + y;
-                if (j < per_xcd && i < n_items) { logical = order[i]; rec = i; break; }
+                uint32_t i;
+                if (persistent_pop_index(j, y, n_items, i)) { logical = order[i]; rec = i; break; }                // order_core.h
             }
             for (;;) {                                         // the slot's previous footprint (f - 2) had three readers
                 const uint32_t r = (uint32_t)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(&slot_reads[sl], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP));
@@ -741,11 +741,7 @@ __global__ __launch_bounds__(256, VARIANT == 3 ? CSKY_COMPACT_WAVES : 7) void cl
 // consecutive blocks land on consecutive XCDs, so each XCD also receives a descending sequence).  Counting sort on 1024 cost
 // buckets; ties are placed in arrival order (the schedule may differ run to run, the frame cannot: every ray's arithmetic is
 // independent of where and when its workgroup runs, tests/test_gpu_parity.py::test_variants_and_schedules_agree).
-constexpr int LPT_BUCKETS = 1024;
-__device__ __forceinline__ int lpt_bucket(uint32_t cost, int shift) {
-    const uint32_t b = cost >> shift;
-    return LPT_BUCKETS - 1 - (int)(b > (uint32_t)(LPT_BUCKETS - 1) ? (uint32_t)(LPT_BUCKETS - 1) : b);   // bucket 0 = heaviest
-}
+// (LPT_BUCKETS and lpt_bucket: order_core.h; bucket 0 = heaviest)
 __global__ __launch_bounds__(256) void lpt_hist_kernel(const uint32_t* __restrict__ cost, int n, int shift, uint32_t* __restrict__ hist) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < n) atomicAdd(&hist[lpt_bucket(cost[i], shift)], 1u);
@@ -785,21 +781,13 @@ hipError_t launch_lpt_order(uint32_t* d_cost, int n, int shift, uint32_t* d_scra
 // ---- static workgroup orders, generated on the device (clouds_launch.cpp::ensure_order) --------------------------------
 // Physical workgroup b runs on XCD b % 8 (observed placement, used for speed only).  A "slab" is one 32 x 8 pixel workgroup
 // footprint (bw x 8 for segmented launches); `grid` entries, 0xffffffff = idle padding.
-//   mode 2: natural order
-//   mode 1: contiguous eighths of the launch per XCD
-//   mode 5: slab ROWS dealt round-robin to the XCDs, every XCD walks its rows left to right: all XCDs see the same mix of
-//           elevations and concurrently running workgroups are neighbours (shared cache lines)
+// The entry of workgroup b in modes 1, 2 and 5 is order_core.h::static_order_entry, which the host tests walk too.
 // Written by a kernel on the launch's own stream: no host table, no pageable copy, no device-wide synchronisation when the
 // geometry changes (a 64-tile walk re-uses the table anyway: these orders depend on the launch geometry only).
 __global__ __launch_bounds__(256) void static_order_kernel(int mode, int tiles_x, int slabs, int grid, uint32_t* __restrict__ out) {
     const int b = blockIdx.x * 256 + threadIdx.x;
     if (b >= grid) return;
-    const int nblocks = tiles_x * slabs;
-    uint32_t l = 0xffffffffu;
-    if (mode == 2) { if (b < nblocks) l = (uint32_t)b; }
-    else if (mode == 1) { const int per = (nblocks + 7) >> 3, v = (b & 7) * per + (b >> 3); if ((b >> 3) < per && v < nblocks) l = (uint32_t)v; }
-    else { const int x = b & 7, j = b >> 3, k = j / tiles_x, bx = j - k * tiles_x, i = 8 * k + x; if (i < slabs) l = (uint32_t)(i * tiles_x + bx); }
-    out[b] = l;
+    out[b] = static_order_entry(mode, tiles_x, slabs, b);
 }
 hipError_t launch_static_order(int mode, int tiles_x, int slabs, int grid, uint32_t* d_order, hipStream_t s) {
     if (grid <= 0) return hipSuccess;

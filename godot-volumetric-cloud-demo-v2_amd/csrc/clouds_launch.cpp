@@ -4,6 +4,7 @@
 #include "context.h"
 #include "bake.h"
 #include "launch_policy.h"
+#include "order_core.h"
 
 namespace csky {
 
@@ -29,13 +30,11 @@ TexSet32 texset32(const csky_ctx* c) {
 // (queue kernel, round 1): 5 (slab rows round-robin over the XCDs) 3.93 ms, 1 (contiguous eighths) 4.80 ms, 2 (natural) 4.92 ms;
 // azimuth-wedge and horizon-first orders (5.3-5.8 / 4.77 ms) were dropped in round 2.  The table depends on the launch geometry
 // only (not on update_position: the reference's tile walk re-uses it) and is written by a kernel on the launch's stream.
-int ensure_order(csky_ctx* c, int slot, int mode, int tile_w, int tiles_x, int slabs, hipStream_t s) {
-    const int nblocks = tiles_x * slabs;
-    int grid;
-    if (mode == 2) grid = nblocks;
-    else if (mode == 1) grid = ((nblocks + 7) >> 3) * 8;
-    else grid = ((slabs + 7) >> 3) * tiles_x * 8;
-    const long long key[4] = {tile_w, slabs, mode, grid};
+int ensure_order(csky_ctx* c, int slot, int mode, int tiles_x, int slabs, hipStream_t s) {
+    const int grid = static_order_grid(mode, tiles_x, slabs);                    // order_core.h
+    // everything the table is a function of.  (Until the launch-order tests the key held tile_w in place of tiles_x: in mode 1 a 33-pixel-wide launch of one slab
+    // has a grid of 8 as whole rays, 2 footprints, and as two segments, 3 footprints, and the second form found the first one's table and left a footprint out.)
+    const long long key[4] = {tiles_x, slabs, mode, grid};
     if (c->d_order_ring[slot] && memcmp(key, c->order_key_ring[slot], sizeof key) == 0) return CSKY_OK;
     if (c->d_order_ring[slot].count() < (size_t)grid) {
         // growing is rare and costs a device-wide wait (an older launch may still read the old table): grow EVERY slot's table now, so that it
@@ -126,7 +125,7 @@ int clouds_dev(csky_ctx* c, const csky_cloud_params* p, int tile_w, const csky_b
         }
         kt = &c->kt_ev[(size_t)c->kt_count * 2]; c->kt_count++;
     }
-    if ((rc = ensure_order(c, slot, pl.static_mode, g.tile_w, tiles_x, slabs, s))) return rc;
+    if ((rc = ensure_order(c, slot, pl.static_mode, tiles_x, slabs, s))) return rc;
     const uint32_t* order = c->d_order_ring[slot];
     int grid = c->order_grid_ring[slot];
     uint32_t* cost = nullptr;                                    // per-workgroup costs this launch records (cost feedback only)
@@ -168,9 +167,7 @@ int clouds_dev(csky_ctx* c, const csky_cloud_params* p, int tile_w, const csky_b
     }
     if (kt) HIPCHK(c, hipEventRecord(kt[1], s));
     if (pl.feedback) {
-        int shift = 0;
-        while ((((long long)256 * (c->primary_steps + 16)) >> shift) >= 1024) shift++;     // largest cost: 4 wavefronts x 64 rays x (steps + 16)
-        HIPCHK(c, launch_lpt_order(cost, nblocks, shift, c->d_lpt_hist + slot * 2048, lorder, s));
+        HIPCHK(c, launch_lpt_order(cost, nblocks, lpt_shift(c->primary_steps), c->d_lpt_hist + slot * 2048, lorder, s));   // order_core.h: the largest cost lands below 1024 buckets
         c->lpt_valid[slot] = true;
     }
     HIPCHK(c, hipEventRecord(c->ev_clouds[slot], s)); c->clouds_pending[slot] = true;

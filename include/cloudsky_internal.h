@@ -72,6 +72,14 @@ int csky_read_baked_texture(csky_ctx* ctx, int which, void* out, size_t capacity
 /* Test hook: the march's range-restricted exact square root (cloud_core.h::sqrt_shell, |p|^2 of sample positions) over an array, so that
  * a test can check it EXHAUSTIVELY against IEEE sqrtf on the range it is used on (all 30 067 floats in [3.597e13, 3.6097e13]). */
 int csky_test_sqrt_shell(csky_ctx* ctx, const float* in, float* out, size_t n);
+/* Test hooks of the launch orders (csrc/order_core.h; tests/test_gpu_launch_order.py compares both with the host's tables and with numpy).
+ * csky_test_static_order: the table of workgroup order `mode` (1, 2 or 5) for a launch of tiles_x x slabs footprints, written by the kernel the
+ * frame path runs, and in *grid its number of entries = the launch's workgroups.  table may be NULL to query the grid; capacity is in entries. */
+int csky_test_static_order(csky_ctx* ctx, int mode, int tiles_x, int slabs, uint32_t* table, size_t capacity, int* grid);
+/* csky_test_lpt_order: the cost-feedback sort over the caller's n costs with bucket shift `shift`, `rounds` times back to back on the same device
+ * buffers, as consecutive frames run it: the costs are uploaded again before every round, the 2 * 1024 words of sort scratch are zeroed once, before
+ * the first round.  Out: the order of the last round (n entries), the cost array as the kernels left it (n), the scratch words as left (2048). */
+int csky_test_lpt_order(csky_ctx* ctx, const uint32_t* cost, int n, int shift, int rounds, uint32_t* order_out, uint32_t* cost_out, uint32_t* scratch_out);
 /* Measurement hook of tools/isa_profile.py: one launch of the cloud kernel over `bands` with the statistics buffer bound, then the first n
  * (<= 256) 32-bit basic-block execution counters behind the kernel's own tallies.  The counters are written only by the CENSUS build of the
  * library (the product assembly with a counter per basic block, made by that tool); the product build leaves them zero. */

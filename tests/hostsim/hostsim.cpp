@@ -13,6 +13,7 @@
 #include "../../godot-volumetric-cloud-demo-v2_amd/csrc/bc7enc_core.h"
 #include "../../godot-volumetric-cloud-demo-v2_amd/csrc/bc7_tables.h"
 #include "../../godot-volumetric-cloud-demo-v2_amd/csrc/launch_policy.h"
+#include "../../godot-volumetric-cloud-demo-v2_amd/csrc/order_core.h"
 
 using namespace csky;
 
@@ -248,5 +249,22 @@ extern "C" {
 void hostsim_plan_launch(int variant, int cell32, int segments, int sched_mode, int frames_in_flight, int persistent, long long waves, int out[7]) {
     const LaunchPlan p = plan_launch({variant, cell32 != 0, segments, sched_mode, frames_in_flight, persistent}, waves);
     out[0] = p.variant; out[1] = p.seg; out[2] = p.mode; out[3] = p.static_mode; out[4] = p.bw; out[5] = p.feedback; out[6] = p.persist;
+}
+}
+
+extern "C" {
+// order_core.h, the index arithmetic of the launch orders (tests/test_launch_order.py)
+int hostsim_static_order_grid(int mode, int tiles_x, int slabs) { return static_order_grid(mode, tiles_x, slabs); }
+// the whole table, entry by entry as static_order_kernel writes it; returns the grid
+int hostsim_static_order(int mode, int tiles_x, int slabs, uint32_t* out, int capacity) {
+    const int grid = static_order_grid(mode, tiles_x, slabs);
+    for (int b = 0; b < grid && b < capacity; b++) out[b] = static_order_entry(mode, tiles_x, slabs, b);
+    return grid;
+}
+void hostsim_lpt_bucket(const uint32_t* cost, int n, int shift, int* out) { for (int i = 0; i < n; i++) out[i] = lpt_bucket(cost[i], shift); }
+int hostsim_lpt_shift(int primary_steps) { return lpt_shift(primary_steps); }
+// pop number j of sequence y for every (j, y), j < n_j: out[j * 8 + y] = the order index, or 0xffffffff when the sequence is empty there
+void hostsim_persistent_pops(uint32_t n_items, uint32_t j0, uint32_t n_j, uint32_t* out) {
+    for (uint32_t j = 0; j < n_j; j++) for (uint32_t y = 0; y < 8; y++) { uint32_t i; out[j * 8 + y] = persistent_pop_index(j0 + j, y, n_items, i) ? i : 0xffffffffu; }
 }
 }

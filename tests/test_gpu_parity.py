@@ -67,6 +67,20 @@ def test_clouds_vs_oracle_default_config(gpu_ctx, oracle, otex, o_skies, sun_nam
     gpu_ctx.set_variant(-1)
 
 
+def _device_frame_into_poison(ctx, p, w, h):
+    """csky_render_clouds_device of the whole w x h frame into a tensor whose every half is 0xFFFF before the launch: uint16 [h, w, 4]"""
+    import torch
+    s = torch.cuda.Stream()
+    out = torch.empty((h, w, 4), dtype=torch.int16, device="cuda")
+    torch.cuda.synchronize()
+    with torch.cuda.stream(s):
+        out.fill_(-1)
+        ctx.render_clouds_device(p, w, (8, 0, 1, h // 8), out.data_ptr(), w * 8, s.cuda_stream)
+        got = out.cpu().numpy().view(np.uint16)
+    torch.cuda.synchronize()
+    return got
+
+
 def test_variants_and_schedules_agree(gpu_ctx, oracle):
     """Every workgroup schedule renders bit-identical frames; the kernel variants (lock-step vs wave-cooperative queue)
     do the same per-ray arithmetic and agree to rounding (the compiler contracts the two bodies differently) with
@@ -83,6 +97,10 @@ def test_variants_and_schedules_agree(gpu_ctx, oracle):
                 imgs[v] = (img, st)
             assert (img.view(np.uint16) == imgs[v][0].view(np.uint16)).all(), (v, sch)
             assert st == imgs[v][1]
+            # the host form marches into the context's frame, which the previous launch left holding the right answer: the device form of the same
+            # launch into a tensor of 0xFFFF halfs (NaNs, filled on the launch's stream) shows a footprint the order leaves out
+            dev = _device_frame_into_poison(gpu_ctx, p, 256, 128)
+            assert (dev == imgs[v][0].view(np.uint16)).all(), (v, sch, int((dev != imgs[v][0].view(np.uint16)).sum()), int((dev == 0xFFFF).sum()))
     ok, info = cloud_close(imgs[1][0], imgs[0][0], frac=0.9999, atol=5e-4, rtol=2e-3)
     assert ok, info
     assert imgs[0][1] == imgs[1][1]
@@ -102,6 +120,10 @@ def test_variants_and_schedules_agree(gpu_ctx, oracle):
             img = gpu_ctx.render_clouds(p)
             ok, info = cloud_close(img, imgs[1][0], frac=0.9999, atol=5e-4, rtol=2e-3)
             assert ok and gpu_ctx.cloud_stats() == imgs[1][1], (seg, sch, info)
+            dev = _device_frame_into_poison(gpu_ctx, p, 256, 128)
+            assert not (dev == 0xFFFF).any(), (seg, sch, int((dev == 0xFFFF).sum()))
+            ok, info = cloud_close(dev.view(np.float16), imgs[1][0], frac=0.9999, atol=5e-4, rtol=2e-3)
+            assert ok, (seg, sch, "device form", info)
     gpu_ctx.set_segments(0)
     gpu_ctx.set_variant(1); gpu_ctx.set_schedule(-1)
     # ray segments (1, 2, 4 wavefronts per ray): identical sample positions and in-cloud counts, re-associated compositing
