@@ -201,6 +201,12 @@ SYMBOLS = [
     ("csky_assets_last_error", C.c_char_p, []),
 ]
 
+# include/cloudsky_lut_hooks.h (which cloudsky_internal.h includes): the switch and the launch counter of the sky LUT's reuse
+LUT_HOOK_SYMBOLS = [
+    ("csky_set_sky_lut_reuse", C.c_int, [C.c_void_p, C.c_int]),
+    ("csky_sky_lut_launches", C.c_int64, [C.c_void_p]),
+]
+
 
 DEFAULT_VARIANT = 3   # include/cloudsky.h CSKY_DEFAULT_VARIANT ("compact"); set_variant(-1) selects it
 ABI_VERSION = 9       # include/cloudsky.h CSKY_ABI_VERSION
@@ -226,7 +232,7 @@ def lib():
         except ImportError:
             pass
         L = C.CDLL(path)
-        for name, res, args in SYMBOLS:
+        for name, res, args in SYMBOLS + LUT_HOOK_SYMBOLS:
             fn = getattr(L, name)  # AttributeError = ABI mismatch, surfaced loudly
             fn.restype = res
             fn.argtypes = args
@@ -325,6 +331,18 @@ class Context:
 
     def transmittance_mapping(self):
         return self._L.csky_get_transmittance_mapping(self._h)
+
+    def set_sky_lut_reuse(self, enabled=True):
+        """True (default): a sky-LUT call for what the context already holds launches nothing (the rows form: one device copy).  False: a launch per
+        call, the A/B switch.  The results are identical."""
+        self._chk(self._L.csky_set_sky_lut_reuse(self._h, int(bool(enabled))))
+
+    def sky_lut_launches(self):
+        """Sky-LUT kernels this context has launched, whole and rows form together."""
+        n = self._L.csky_sky_lut_launches(self._h)
+        if n < 0:
+            self._chk(int(n))
+        return int(n)
 
     def set_early_out(self, eps):
         self._chk(self._L.csky_set_early_out(self._h, float(eps)))

@@ -66,6 +66,52 @@ int create_resources(csky_ctx* c) {
     HIPCHK(c, hipMemset(c->d_heads, 0, RING * 16 * sizeof(uint32_t)));   // persistent launches leave them zero
     return CSKY_OK;
 }
+
+// The cache of csky_render_sky_lut_rows_device (context.h).  Its readers and writers sit on CALLER streams, several of them with frames in flight:
+//   fill -> read   every copy out waits for ev_rows_fill (until the event has been seen complete once)
+//   read -> fill   every copy out records an event of the ring ev_rows_read; a fill waits for all that are pending.  A ring slot that comes round
+//                  while still pending is waited for by its new user first, so the newer record stands for the older one too
+//   fill -> fill   a fill waits for the one before it
+bool event_done(hipEvent_t ev) {
+    if (hipEventQuery(ev) == hipSuccess) return true;
+    (void)hipGetLastError();                                   // hipErrorNotReady is an answer, not a failure to resurface later
+    return false;
+}
+int rows_cache_fill(csky_ctx* c, const void* d_rows, size_t px, hipStream_t s) {
+    int rc;
+    if (!c->ev_rows_fill) {
+        if ((rc = c->ev_rows_fill.create(c, hipEventDisableTiming))) return rc;
+        for (Event& ev : c->ev_rows_read) if ((rc = ev.create(c, hipEventDisableTiming))) return rc;
+    }
+    const bool regrow = c->d_rows_cache.count() < px;
+    for (int k = 0; k < RING; k++) {
+        if (!c->rows_read_pending[k]) continue;
+        if (regrow) HIPCHK(c, hipEventSynchronize(c->ev_rows_read[k]));
+        else if (!event_done(c->ev_rows_read[k])) HIPCHK(c, hipStreamWaitEvent(s, c->ev_rows_read[k], 0));
+        c->rows_read_pending[k] = false;
+    }
+    if (!c->rows_fill_done) {
+        if (regrow) HIPCHK(c, hipEventSynchronize(c->ev_rows_fill));
+        else if (!event_done(c->ev_rows_fill)) HIPCHK(c, hipStreamWaitEvent(s, c->ev_rows_fill, 0));
+    }
+    if (regrow && (rc = c->d_rows_cache.alloc(c, px))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->d_rows_cache, d_rows, px * 8, hipMemcpyDeviceToDevice, s));
+    HIPCHK(c, hipEventRecord(c->ev_rows_fill, s));
+    c->rows_fill_done = false;
+    return CSKY_OK;
+}
+int rows_cache_read(csky_ctx* c, void* d_rows_out, size_t px, hipStream_t s) {
+    if (!c->rows_fill_done) {
+        if (event_done(c->ev_rows_fill)) c->rows_fill_done = true;
+        else HIPCHK(c, hipStreamWaitEvent(s, c->ev_rows_fill, 0));
+    }
+    const int k = c->rows_read_cur;
+    if (c->rows_read_pending[k] && !event_done(c->ev_rows_read[k])) HIPCHK(c, hipStreamWaitEvent(s, c->ev_rows_read[k], 0));
+    HIPCHK(c, hipMemcpyAsync(d_rows_out, c->d_rows_cache, px * 8, hipMemcpyDeviceToDevice, s));
+    HIPCHK(c, hipEventRecord(c->ev_rows_read[k], s));
+    c->rows_read_pending[k] = true; c->rows_read_cur = (k + 1) % RING;
+    return CSKY_OK;
+}
 }  // namespace
 
 namespace csky {
@@ -81,6 +127,7 @@ int fail(csky_ctx* c, int code, const char* fmt, ...) {
 
 int ensure_sky(csky_ctx* c, int w, int h) {
     if (c->d_sky_h && c->sw == w && c->sh == h) return CSKY_OK;
+    sky_lut_touch(c);                                           // whatever the slots held goes
     if (c->stream) HIPCHK(c, hipStreamSynchronize(c->stream));  // a size change is rare: drain the context's stream (every reader of the LUT runs there), rebuild both slots
     for (int k = 0; k < 2; k++) {
         int rc; if ((rc = c->sky_h_ring[k].alloc(c, (size_t)w * h * 4))) return rc;
@@ -91,6 +138,7 @@ int ensure_sky(csky_ctx* c, int w, int h) {
 }
 
 int render_trans_dev(csky_ctx* c, int w, int h, hipStream_t s) {
+    c->trans_gen++; sky_lut_touch(c); c->rows_key.valid = false;   // every LUT rendered through the old table is another table's (sky_lut_reuse.h)
     int rc; if ((rc = ensure_trans(c, w, h))) return rc;
     HIPCHK(c, launch_transmittance(w, h, c->d_trans_h, c->d_trans_f, s, c->tlut));
     c->have_trans = true; return CSKY_OK;
@@ -435,9 +483,17 @@ int csky_set_transmittance_mapping(csky_ctx* c, int mapping) {
     HIPCHK(c, hipDeviceSynchronize());                         // readers of the old table may be in flight, on caller streams too (csky_render_transmittance)
     // everything rendered through the old table goes: the table itself (re-rendered on demand), the sky LUT and the radiance snapshot
     c->tlut = mapping; c->have_trans = false; c->have_sky = false; c->sky_partial = false; c->sky_in_memory = false; c->lut_writers.clear(); c->rad.valid = false;
+    c->trans_gen++; sky_lut_touch(c); c->rows_key.valid = false;
     return CSKY_OK;
 }
 int csky_get_transmittance_mapping(const csky_ctx* c) { return c ? c->tlut : CSKY_ERR_INVALID; }
+int csky_set_sky_lut_reuse(csky_ctx* c, int enabled) {
+    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "csky_set_sky_lut_reuse: ctx is NULL");
+    if (enabled != 0 && enabled != 1) return fail(c, CSKY_ERR_INVALID, "csky_set_sky_lut_reuse: 0 (a launch per call) or 1 (reuse, the default)");
+    c->sky_lut_reuse = enabled != 0; sky_lut_touch(c); c->rows_key.valid = false;
+    return CSKY_OK;
+}
+int64_t csky_sky_lut_launches(const csky_ctx* c) { return c ? (int64_t)c->sky_lut_launches : (int64_t)CSKY_ERR_INVALID; }
 int csky_transmittance_uv(int mapping, int w, int h, float r_km, float mu, float uv[2], int* hits_ground) {
     if (!uv) return fail(nullptr, CSKY_ERR_INVALID, "csky_transmittance_uv: uv is NULL");
     if (mapping == CSKY_TLUT_REFERENCE) {                      // transmittance_from_lut (sky-lut.glsl:137-142); the table stores every ray
@@ -471,6 +527,7 @@ int csky_render_transmittance(csky_ctx* c, const csky_transmittance_params* p, u
     int rc; if ((rc = bind(c))) return rc;
     // sky LUTs in flight read the old transmittance LUT: whole ones and the set-ups' own texels on the prologue stream, a rank's rows
     // (csky_render_sky_lut_rows_device) on CALLER streams; the LUT is rendered once at load (transmittance_lut.gd:15-18), so wait for the device
+    sky_lut_touch(c); c->rows_key.valid = false;
     HIPCHK(c, hipDeviceSynchronize());
     if ((rc = render_trans_dev(c, w, h, c->stream))) return rc;
     if (out) HIPCHK(c, hipMemcpyAsync(out, c->d_trans_h, (size_t)w * h * 8, hipMemcpyDeviceToHost, c->stream));
@@ -487,10 +544,18 @@ int csky_render_sky_lut_device(csky_ctx* c, const csky_sky_params* p, void* hip_
     (void)hip_stream;   // the LUT has no inputs of the caller's: it is rendered on the context's stream and its consumers are ordered by events
     if (!c->have_trans && (rc = render_trans_dev(c, 256, 64, c->stream))) return rc;   // transmittance_lut.gd:6 default size
     if ((rc = ensure_sky(c, w, h))) return rc;
+    // The LUT is a function of the sun, its size and the transmittance table alone, and a host refreshes it every pass whether the sun moved or not
+    // (cloud_sky.gd:187 against sun.gd:17): the same request as the one slot sky_cur was rendered from launches nothing and leaves the ring where
+    // it is.  Every consumer (the frame set-ups, the copies out) runs on `stream`, behind the launch that filled the slot.
+    const SkyLutKey req = sky_lut_key(p->sun_direction, w, h, c->tlut, c->trans_gen);
+    if (sky_lut_whole_hit(c->sky_key, req, sky_lut_state(c))) return CSKY_OK;
+    sky_lut_touch(c);                                                               // (set again below, once the launch went through)
     const int k = (c->have_sky && c->sky_in_memory) ? c->sky_cur ^ 1 : c->sky_cur;  // the other ring slot: frame set-ups still reading the current one are ahead on `stream`
     HIPCHK(c, launch_sky_lut(w, h, p->sun_direction, c->d_trans_f, c->tw, c->th, c->sky_h_ring[k], c->sky_f_ring[k], c->stream, c->tlut));
+    c->sky_lut_launches++;
     c->sky_cur = k; c->d_sky_h = c->sky_h_ring[k]; c->d_sky_f = c->sky_f_ring[k];
     c->have_sky = true; c->sky_partial = false; c->sky_in_memory = true; c->lut_writers.clear();
+    c->sky_key = req;
     return CSKY_OK;
 }
 int csky_render_sky_lut_rows_device(csky_ctx* c, const csky_sky_params* p, int first_row, int row_stride, void* d_rows_out, size_t capacity_bytes, void* hip_stream) {
@@ -510,7 +575,23 @@ int csky_render_sky_lut_rows_device(csky_ctx* c, const csky_sky_params* p, int f
     // (Round 5 measured them on a side stream BESIDE the march that follows, joined behind it: a 1/8 share one frame at a time 0.409 -> 0.460 ms, eight
     // in flight 0.241 -> 0.244: two more cross-stream hops cost more than the rows they take off the critical path; profiles/r05/rows_overlap_ab.txt.)
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    HIPCHK(c, launch_sky_lut_rows(w, h, first_row, row_stride, p->sun_direction, c->d_trans_f, c->tw, c->th, reinterpret_cast<uint2*>(d_rows_out), nullptr, s, c->tlut));
+    // The caller's buffer differs from frame to frame, so the rows of an unchanged request cannot simply stay where they are: the context keeps a
+    // copy of the last rows it rendered, and the same request again is one device copy of them on the caller's stream instead of the kernel.
+    // A request that differs renders into the caller's buffer as ever and leaves its copy behind (a sun that moves every frame pays that copy alone).
+    const size_t px = (size_t)n_rows * w;
+    const SkyLutKey req = sky_lut_key(p->sun_direction, w, h, c->tlut, c->trans_gen, first_row, row_stride);
+    sky_lut_touch(c);                                           // the ring's whole LUT, if any, is no longer what the set-ups use
+    if (px && sky_lut_rows_hit(c->rows_key, req, c->sky_lut_reuse)) {
+        if ((rc = rows_cache_read(c, d_rows_out, px, s))) { c->rows_key.valid = false; return rc; }
+    } else {
+        c->rows_key.valid = false;
+        HIPCHK(c, launch_sky_lut_rows(w, h, first_row, row_stride, p->sun_direction, c->d_trans_f, c->tw, c->th, reinterpret_cast<uint2*>(d_rows_out), nullptr, s, c->tlut));
+        if (px) c->sky_lut_launches++;
+        if (px && c->sky_lut_reuse) {
+            if ((rc = rows_cache_fill(c, d_rows_out, px, s))) return rc;
+            c->rows_key = req;
+        }
+    }
     for (int i = 0; i < 3; i++) c->sky_sun[i] = p->sun_direction[i];
     c->psw = w; c->psh = h; c->sky_partial = true; c->have_sky = true; c->sky_in_memory = false; c->lut_writers.clear();
     return CSKY_OK;

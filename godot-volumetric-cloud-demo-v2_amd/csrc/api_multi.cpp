@@ -30,6 +30,8 @@ struct csky_multi {
     // on the first device:
     Event ev_begin[MULTI_SLOTS];          // the consumer stream's position when the frame was requested
     Event ev_lut_begin;                   // on its prologue stream: the readers of the LUT slot about to be rewritten are behind this
+    SkyLutKey lut_key;                    // what csky_multi_render_sky_lut rendered last (sky_lut_reuse.h), and every device's sky_epoch as that call left it:
+    std::vector<unsigned long long> lut_epoch;   // the same request again, with no device's LUT state touched since, renders nothing
     DevBuf<uint2> d_frame;                // host-buffer form: internal frame, in pixels, grow-only
     int fif = 1, groups = 1;              // frames in flight PER GROUP, frame groups (csky_multi_set_groups)
     unsigned long long frame_no = 0;
@@ -231,6 +233,16 @@ int csky_multi_render_sky_lut(csky_multi* m, const csky_sky_params* p) {
     const int n = (int)m->dev.size();
     csky_ctx* c0 = m->dev[0].ctx;
     int rc;
+    // A static sun (the case above) asks for the LUT the handle rendered last: no device renders its rows again, every device keeps the sun it
+    // recorded, and the first context's lut_writers stay the events of the call that stored the rows.  Anything that touched a device's LUT
+    // state since (a context's own LUT calls, a new transmittance table or mapping) moved its sky_epoch: then the handle renders.
+    if (c0->sky_lut_reuse && sky_lut_same_key(m->lut_key, sky_lut_key(p->sun_direction, w, h, c0->tlut, c0->trans_gen)) && m->lut_epoch.size() == (size_t)n) {
+        bool same = true;
+        for (int i = 0; i < n; i++) same = same && m->dev[i].ctx->sky_epoch == m->lut_epoch[i];
+        if (same) return CSKY_OK;
+    }
+    m->lut_key.valid = false;
+    for (int i = 0; i < n; i++) sky_lut_touch(m->dev[i].ctx);   // (the first context's ring slot is about to hold rows of several devices)
     if (c0->d_sky_h && (c0->sw != w || c0->sh != h))            // a size change re-allocates the first device's LUT slots: no device may still be storing rows into them
         for (int i = 0; i < n; i++) { if ((rc = bind(m->dev[i].ctx))) return mpass(m, i, rc); if (hipStreamSynchronize(m->dev[i].ctx->stream) != hipSuccess) return mfail(m, CSKY_ERR_HIP, "csky_multi_render_sky_lut: hipStreamSynchronize failed"); }
     if ((rc = bind(c0))) return mpass(m, 0, rc);
@@ -244,8 +256,10 @@ int csky_multi_render_sky_lut(csky_multi* m, const csky_sky_params* p) {
         if (!c->have_trans && (rc = render_trans_dev(c, 256, 64, c->stream))) return mpass(m, i, rc);   // transmittance_lut.gd:6 default size
         hipError_t e = i ? hipStreamWaitEvent(c->stream, m->ev_lut_begin, 0) : hipSuccess;
         // rows i, i + n, ... stored into the first device's LUT -- or, when some device cannot reach that memory, every row by the first device itself
-        if (e == hipSuccess && (m->all_peer || i == 0))
+        if (e == hipSuccess && (m->all_peer || i == 0)) {
+            if ((m->all_peer ? i : 0) < h) c->sky_lut_launches++;
             e = launch_sky_lut_rows(w, h, m->all_peer ? i : 0, m->all_peer ? n : 1, p->sun_direction, c->d_trans_f, c->tw, c->th, reinterpret_cast<uint2*>(c0->sky_h_ring[k].get()), c0->sky_f_ring[k], c->stream, c->tlut);
+        }
         if (e == hipSuccess) e = hipEventRecord(m->dev[i].lut, c->stream);
         if (e != hipSuccess) return mfail(m, CSKY_ERR_HIP, "csky_multi_render_sky_lut: device index %d: %s", i, hipGetErrorString(e));
         for (int q = 0; q < 3; q++) c->sky_sun[q] = p->sun_direction[q];
@@ -255,6 +269,9 @@ int csky_multi_render_sky_lut(csky_multi* m, const csky_sky_params* p) {
     c0->sky_cur = k; c0->d_sky_h = c0->sky_h_ring[k]; c0->d_sky_f = c0->sky_f_ring[k]; c0->sky_in_memory = true;
     c0->lut_writers.clear();
     for (int i = 1; i < n; i++) c0->lut_writers.push_back(m->dev[i].lut);   // (its own rows are on its prologue stream, ahead of any reader)
+    m->lut_key = sky_lut_key(p->sun_direction, w, h, c0->tlut, c0->trans_gen);
+    m->lut_epoch.resize(n);
+    for (int i = 0; i < n; i++) m->lut_epoch[i] = m->dev[i].ctx->sky_epoch;
     return CSKY_OK;
 }
 

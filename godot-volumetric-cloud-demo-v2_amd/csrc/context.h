@@ -14,6 +14,7 @@
 #include "../../include/cloudsky_internal.h"
 #include "kernels.h"
 #include "owners.h"
+#include "sky_lut_reuse.h"
 
 // Depth of the per-frame rings (frame constants, launch order, cost feedback, pop counters, events): the number of frames a caller may keep
 // in flight on as many streams (csky_set_frames_in_flight).  The slots rotate over all RING entries whatever that number is.
@@ -58,6 +59,16 @@ struct csky_ctx {
     // csky_multi_render_sky_lut: the whole LUT IS in this context's memory (ring slot sky_cur), written row by row by the devices of the handle;
     // readers of the memory copy wait for those writers first.  (sky_partial stays set: the frame set-ups never read the memory copy.)
     bool sky_in_memory = false; std::vector<hipEvent_t> lut_writers;   // views, not owned: copies of events the csky_multi handle owns
+    // Reuse of a rendered LUT (sky_lut_reuse.h).  sky_key: what ring slot sky_cur was rendered from by csky_render_sky_lut_device; a call with the
+    // same key launches nothing (every consumer is on `stream`, behind the launch that filled the slot).  trans_gen counts what replaces the
+    // transmittance table (render_trans_dev, a mapping change); sky_epoch counts every call that may change this context's LUT state, so that a
+    // csky_multi handle can tell that none happened since its own last render.  sky_lut_launches: LUT kernels launched, whole and rows form.
+    csky::SkyLutKey sky_key; unsigned long long trans_gen = 0, sky_epoch = 0; bool sky_lut_reuse = true; long long sky_lut_launches = 0;
+    // csky_render_sky_lut_rows_device: the compact rows of rows_key, copied behind the kernel that rendered them into a caller's buffer; a call with
+    // the same key copies them out on the caller's stream instead of rendering.  ev_rows_fill: the cache is filled; ev_rows_read: the copies out
+    // (a ring: more than one caller stream reads), which the next fill waits for.  Events and buffer are made by the first fill.
+    csky::SkyLutKey rows_key; csky::DevBuf<uint2> d_rows_cache; csky::Event ev_rows_fill, ev_rows_read[RING];
+    bool rows_fill_done = true, rows_read_pending[RING] = {}; int rows_read_cur = 0;
     csky::DevBuf<csky::FrameConsts> fc_ring[RING]; int fc_cur = 0;
     csky::Event ev_setup[RING], ev_clouds[RING]; bool clouds_pending[RING] = {};
     csky::DevBuf<unsigned long long> d_stats;
@@ -105,6 +116,9 @@ extern thread_local char g_err[512];   // error text of calls without a context 
 inline int bind(csky_ctx* c) { HIPCHK(c, hipSetDevice(c->device)); return CSKY_OK; }
 
 // api.cpp
+// forgets what ring slot sky_cur was rendered from: the caller is about to change it, or the context's LUT state (sky_lut_reuse.h)
+inline void sky_lut_touch(csky_ctx* c) { c->sky_key.valid = false; c->sky_epoch++; }
+inline SkyLutState sky_lut_state(const csky_ctx* c) { SkyLutState s; s.reuse = c->sky_lut_reuse; s.have_sky = c->have_sky; s.sky_in_memory = c->sky_in_memory; s.sky_partial = c->sky_partial; s.no_writers = c->lut_writers.empty(); return s; }
 int ensure_sky(csky_ctx* c, int w, int h);
 int render_trans_dev(csky_ctx* c, int w, int h, hipStream_t s);
 int host_slot_prepare(csky_ctx* c, csky_ctx::HostSlot& hs, size_t px);

@@ -99,4 +99,6 @@ int csky_encode_bc7_quality(csky_ctx* ctx, const uint8_t* rgba8, int w, int h, i
 #ifdef __cplusplus
 }
 #endif
+/* The switch and the launch counter of the sky LUT's reuse: declared in a header of their own, which every user of this one gets with it. */
+#include "cloudsky_lut_hooks.h"
 #endif /* CLOUDSKY_INTERNAL_H */
