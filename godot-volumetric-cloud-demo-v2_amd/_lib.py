@@ -64,6 +64,11 @@ class RadianceParams(C.Structure):
     _fields_ = [("face_size", C.c_int), ("layers", C.c_int), ("source_size", C.c_int)]
 
 
+class ShadowParams(C.Structure):
+    """csky_shadow_params (include/cloudsky.h): the cloud shadow map's size, rectangle of the tangent plane and step count."""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("center", C.c_float * 2), ("extent", C.c_float * 2), ("steps", C.c_int)]
+
+
 class CloudStats(C.Structure):
     _fields_ = [("rays", C.c_uint64), ("primary_samples", C.c_uint64), ("incloud_samples", C.c_uint64)]
 
@@ -142,6 +147,8 @@ SYMBOLS = [
     ("csky_render_radiance", C.c_int, [C.c_void_p, C.POINTER(CompositeParams), C.POINTER(RadianceParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_int, C.c_int, C.c_void_p]),
     ("csky_prefilter_cube", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    ("csky_render_cloud_shadow", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.POINTER(ShadowParams), C.c_void_p]),
+    ("csky_render_cloud_shadow_device", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.POINTER(ShadowParams), C.c_void_p, C.c_size_t, C.c_void_p]),
     ("csky_time_clouds", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.c_int, C.POINTER(Bands), C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(CloudStats)]),
     ("csky_get_cloud_stats", C.c_int, [C.c_void_p, C.POINTER(CloudStats)]),
     ("csky_set_kernel_timing", C.c_int, [C.c_void_p, C.c_int]),
@@ -207,6 +214,11 @@ LUT_HOOK_SYMBOLS = [
     ("csky_sky_lut_launches", C.c_int64, [C.c_void_p]),
 ]
 
+# include/cloudsky_shadow_hooks.h (likewise): the A/B switch of the cloud shadow map's exact end
+SHADOW_HOOK_SYMBOLS = [
+    ("csky_set_shadow_exact_end", C.c_int, [C.c_void_p, C.c_int]),
+]
+
 
 DEFAULT_VARIANT = 3   # include/cloudsky.h CSKY_DEFAULT_VARIANT ("compact"); set_variant(-1) selects it
 ABI_VERSION = 9       # include/cloudsky.h CSKY_ABI_VERSION
@@ -232,7 +244,7 @@ def lib():
         except ImportError:
             pass
         L = C.CDLL(path)
-        for name, res, args in SYMBOLS + LUT_HOOK_SYMBOLS:
+        for name, res, args in SYMBOLS + LUT_HOOK_SYMBOLS + SHADOW_HOOK_SYMBOLS:
             fn = getattr(L, name)  # AttributeError = ABI mismatch, surfaced loudly
             fn.restype = res
             fn.argtypes = args
@@ -420,6 +432,31 @@ class Context:
     def copy_sky_lut_device(self, d_out, stream=None):
         """Async device copy of the sky LUT rendered last (w*h*8 bytes of RGBA16F) into a caller-owned device buffer."""
         self._chk(self._L.csky_copy_sky_lut_device(self._h, C.c_void_p(int(d_out)), C.c_void_p(stream or 0)))
+
+    def render_cloud_shadow(self, params, width, height, center=(0.0, 0.0), extent=(16384.0, 16384.0), steps=64, out=None, stream=None):
+        """The cloud shadow map (csky_render_cloud_shadow*, definition: include/cloudsky.h): the sun's transmittance through the clouds of the
+        push-constant block `params` to width x height ground points of the rectangle `extent` (metres along x, z) around `center`, float16
+        [height, width], row j = z, column i = x.  Host path (out None or a numpy float16 array): blocks, returns numpy.  Device path (out a
+        2-D torch tensor of 2-byte elements on this context's GPU, unit column stride; its row stride is the pitch): asynchronous on `stream`,
+        returns the tensor.  Needs the noise and no LUT."""
+        p = cloud_params(params)
+        sp = ShadowParams(int(width), int(height), (C.c_float * 2)(float(center[0]), float(center[1])), (C.c_float * 2)(float(extent[0]), float(extent[1])), int(steps))
+        if out is not None and hasattr(out, "data_ptr"):
+            if out.dim() != 2 or out.element_size() != 2 or tuple(out.shape) != (int(height), int(width)) or (int(width) > 1 and out.stride(1) != 1):
+                raise ValueError("render_cloud_shadow: out must be a [%d, %d] tensor of 2-byte elements with unit column stride" % (int(height), int(width)))
+            pitch = out.stride(0) * 2 if int(height) > 1 else int(width) * 2
+            self._chk(self._L.csky_render_cloud_shadow_device(self._h, C.byref(p), C.byref(sp), C.c_void_p(int(out.data_ptr())), C.c_size_t(int(pitch)), C.c_void_p(stream or 0)))
+            return out
+        if out is None:
+            out = np.zeros((int(height), int(width)), np.float16)
+        if out.shape != (int(height), int(width)) or out.dtype != np.float16 or not out.flags.c_contiguous:
+            raise ValueError("render_cloud_shadow: out must be a contiguous float16 [%d, %d] array" % (int(height), int(width)))
+        self._chk(self._L.csky_render_cloud_shadow(self._h, C.byref(p), C.byref(sp), _ptr(out)))
+        return out
+
+    def set_shadow_exact_end(self, enabled=True):
+        """A/B switch (cloudsky_internal.h): False makes every texel of the shadow map take all its samples; the maps are byte-identical."""
+        self._chk(self._L.csky_set_shadow_exact_end(self._h, int(bool(enabled))))
 
     def sync(self):
         self._chk(self._L.csky_sync(self._h))

@@ -325,6 +325,23 @@ class CloudSky:
                                         self.blend_amount, self.sun_disk_scale, S, L, Ss, first_layer, n_layers, self.radiance.data_ptr(), stream)
         done()
 
+    def cloud_shadow_map(self, size=512, extent=16384.0, center=(0.0, 0.0), steps=64):
+        """What the clouds of the current frame data do to the ground: the sun's transmittance at size x size (or (w, h)) points of the square
+        (or (x, z) rectangle) of `extent` metres around `center` in the observer's tangent plane, float16 [h, w] (csky_render_cloud_shadow; the
+        definition and the lookup uv = ((x, z) - center) / extent + 0.5: include/cloudsky.h).  A torch CUDA tensor with device_buffers=True.
+        Independent of the sky LUTs and of the blend textures; not called by update_sky()."""
+        w, h = (int(size), int(size)) if np.isscalar(size) else (int(size[0]), int(size[1]))
+        ext = (float(extent), float(extent)) if np.isscalar(extent) else (float(extent[0]), float(extent[1]))
+        pc = self._fill_push_constant()
+        if not self.device_buffers:
+            return self.ctx.render_cloud_shadow(pc, w, h, center, ext, steps)
+        import torch
+        out = torch.empty((h, w), dtype=torch.float16, device=torch.device("cuda", self.ctx.device_id))
+        stream, done = self._march_stream()
+        self.ctx.render_cloud_shadow(pc, w, h, center, ext, steps, out=out, stream=stream)
+        done()
+        return out
+
     # ---- render thread ------------------------------------------------------------------------------------
     def _march_stream(self):
         """(hip stream handle, done()) for one batch of library calls in device-buffer mode.  The work is enqueued on torch's CURRENT

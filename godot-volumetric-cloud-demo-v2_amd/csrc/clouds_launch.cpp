@@ -8,8 +8,6 @@
 
 namespace csky {
 
-namespace {
-
 TexSet texset(const csky_ctx* c) {
     TexSet t;
 #ifdef CSKY_BRICK_BOUND
@@ -25,6 +23,8 @@ TexSet32 texset32(const csky_ctx* c) {
     t.shape32 = c->d_shape32; t.detail32 = c->d_detail32; t.weather32 = c->d_weather32;
     return t;
 }
+
+namespace {
 
 // Static workgroup order for ring slot `slot` (cloud_kernels.hip::static_order_kernel; modes 1, 2, 5).  Measured on the headline frame
 // (queue kernel, round 1): 5 (slab rows round-robin over the XCDs) 3.93 ms, 1 (contiguous eighths) 4.80 ms, 2 (natural) 4.92 ms;
@@ -57,6 +57,16 @@ int ensure_order(csky_ctx* c, int slot, int mode, int tiles_x, int slabs, hipStr
 
 }  // namespace
 
+void exact_rejects(csky_ctx* c, float coverage, float& hf_lo, float& hf_hi, int& ct_mode) {
+    if (c->win_cov != coverage) {                       // height window of the exact reject (bake.h), cached per coverage value
+        height_window((double)coverage, c->w_rmin, c->w_rmax, c->w_bmax, c->win_lo, c->win_hi);
+        c->win_cov = coverage;
+    }
+    hf_lo = c->use_window ? c->win_lo : -1.0f; hf_hi = c->use_window ? c->win_hi : 2.0f;
+    // cloud-type range of the weather map (texel values 0..255): all >= 128 or all <= 127 fixes the branch of the height gradient
+    ct_mode = !c->use_window ? 0 : (c->w_rmin * 255.0 >= 127.5 ? 1 : (c->w_rmax * 255.0 <= 127.5 ? 2 : 0));
+}
+
 int check_bands(csky_ctx* c, const csky_bands* b, int tile_w) {
     if (tile_w < 1 || !b || b->band_rows < 1 || b->n_bands < 0 || b->first_band < 0 || b->band_stride < 1)
         return fail(c, CSKY_ERR_INVALID, "render_clouds: bad tile/bands description");
@@ -85,16 +95,11 @@ int clouds_dev(csky_ctx* c, const csky_cloud_params* p, int tile_w, const csky_b
     if (b->n_bands == 0) return CSKY_OK;
     CloudParams cp; memcpy(&cp, p, sizeof cp);
     if (setup) {
-        if (c->win_cov != cp.cloud_coverage) {          // height window of the exact reject (bake.h), cached per coverage value
-            height_window((double)cp.cloud_coverage, c->w_rmin, c->w_rmax, c->w_bmax, c->win_lo, c->win_hi);
-            c->win_cov = cp.cloud_coverage;
-        }
-        const float lo = c->use_window ? c->win_lo : -1.0f, hi = c->use_window ? c->win_hi : 2.0f;
+        float lo, hi; int ctm;
+        exact_rejects(c, cp.cloud_coverage, lo, hi, ctm);
         // frame set-up on the context's stream (beside the caller's: context.h) into the other constants slot (its last reader, the march two frames ago, must be done)
         const int f = (c->fc_cur + 1) % RING;
         if (c->clouds_pending[f]) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_clouds[f], 0));
-        // cloud-type range of the weather map (texel values 0..255): all >= 128 or all <= 127 fixes the branch of the height gradient
-        const int ctm = !c->use_window ? 0 : (c->w_rmin * 255.0 >= 127.5 ? 1 : (c->w_rmax * 255.0 <= 127.5 ? 2 : 0));
         const SetupArgs sa = {c->primary_steps, c->light_steps, c->early_eps, lo, hi, ctm, c->use_window ? 1 : 0};
         if (c->sky_partial)                              // no LUT in memory: the set-up renders the texels of its three taps (clouds.glsl:163-167) itself
             HIPCHK(c, launch_frame_setup_taps(cp, c->sky_sun, c->d_trans_f, c->tw, c->th, c->psw, c->psh, sa, c->fc_ring[f], c->stream, c->tlut));

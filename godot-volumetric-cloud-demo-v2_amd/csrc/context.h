@@ -1,6 +1,6 @@
 // context.h -- the context of libcloudsky (csky_ctx) and the host helpers its C ABI sources share.  Internal to libcloudsky:
 // api.cpp (lifecycle, textures, LUTs, cloud entry points, host ring), clouds_launch.cpp (the cloud kernel launch), api_sky.cpp (compositor,
-// radiance cubemap), api_external.cpp (zero-copy frames), api_multi.cpp (the multi-device handle).
+// radiance cubemap), api_shadow.cpp (cloud shadow map), api_external.cpp (zero-copy frames), api_multi.cpp (the multi-device handle).
 // Ownership: every device buffer, pinned buffer, event and stream of the context is a member of one of the owner types of owners.h and dies with
 // the context (csky_destroy: bind the device, wait for it, delete).  A buffer's count() is its capacity; raw pointers and raw handles in the
 // struct are views of something owned elsewhere and say so.
@@ -99,6 +99,8 @@ struct csky_ctx {
     csky::DevBuf<uint8_t> d_rad_io;                                        // host forms: uploaded inputs + the requested output layers, grow-only
     csky::Event ev_rad;                                                    // the transmittance LUT (prologue stream) -> layer 0 (caller's stream)
     csky_cloud_stats last_stats = {0, 0, 0};
+    csky::DevBuf<uint16_t> d_shadow;                                       // host form of the cloud shadow map: the map before its copy out, grow-only
+    bool shadow_exact_end = true;                                          // csky_set_shadow_exact_end (shadow_core.h shadow_march)
     bool census_lean = false;                                  // csky_census_clouds unless CSKY_CENSUS_TALLY=1: count the blocks of the kernel form that keeps no in-cloud tally (kernels.h launch_clouds)
     // asynchronous host form (csky_submit_clouds / csky_collect): a ring of pinned host frames + device frames on rotating internal streams
     // (a slot's capacity is h.count(), in bytes; d holds as many pixels of 8 bytes)
@@ -124,6 +126,11 @@ int render_trans_dev(csky_ctx* c, int w, int h, hipStream_t s);
 int host_slot_prepare(csky_ctx* c, csky_ctx::HostSlot& hs, size_t px);
 
 // clouds_launch.cpp
+TexSet texset(const csky_ctx* c);       // the bound textures as the kernels take them: fp16-pair cells, and the exact fp32 cells of a context in that mode
+TexSet32 texset32(const csky_ctx* c);
+// what the exact specialisations of a density sample take for this coverage (csky_set_height_window switches them together): the height window
+// outside which density() is 0 for the bound weather map, and FrameConsts::ct_mode
+void exact_rejects(csky_ctx* c, float coverage, float& hf_lo, float& hf_hi, int& ct_mode);
 int check_bands(csky_ctx* c, const csky_bands* b, int tile_w);
 int grow_timing_pool(csky_ctx* c, size_t want);
 // frame set-up (when `setup`) + the cloud kernel on stream s into d_out.  d_stats: optional device counters.

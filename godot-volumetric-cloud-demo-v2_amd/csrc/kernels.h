@@ -71,6 +71,12 @@ hipError_t launch_interleave_bands(const void* d_gathered, size_t member_stride_
 // test hook: cloud_core.h::sqrt_shell over an array
 hipError_t launch_sqrt_shell(const float* d_in, float* d_out, size_t n, hipStream_t s);
 
+// ------------------------------------------------------------------------------------------------ shadow.hip
+// the cloud shadow map (shadow_core.h): sc.w x sc.h halfs into d_out, row pitch sc.pitch_h halfs.  fc: shadow_frame_consts; both blocks travel as
+// kernel arguments.  t32: march on the exact fp32-coefficient cells.
+struct ShadowConsts;
+hipError_t launch_cloud_shadow(const TexSet& t, const TexSet32* t32, const FrameConsts& fc, const ShadowConsts& sc, uint16_t* d_out, hipStream_t s);
+
 // ------------------------------------------------------------------------------------------------ bc7enc.hip
 // BC7 (BPTC) blocks of n_img images of w x h RGBA8 texels (what compress/mode=2 of the *.import files asks the importer for)
 hipError_t launch_bc7_encode(const uint8_t* d_img, int w, int h, int n_img, int quality, uint4* d_blocks, hipStream_t s);

@@ -43,7 +43,7 @@ extern "C" {
 #define CSKY_ERR_IO (-4)         /* asset file problem                                       */
 #define CSKY_ERR_STATE (-5)      /* e.g. clouds requested before noise / LUTs exist          */
 
-#define CSKY_ABI_VERSION 9  /* 9: csky_set_ / csky_get_ / csky_multi_set_transmittance_mapping, csky_transmittance_uv (CSKY_TLUT_BRUNETON); 8: csky_render_radiance[_device], csky_prefilter_cube (the radiance cubemap); 7: csky_multi_last_warning (csky_multi_create no longer fails without peer access: it falls back to staged copies and says so); 6: the measurement / tuning / test entry points moved to cloudsky_internal.h (same library), csky_generate_shape_noise_tuned[_device]; 5: csky_last_warning (warnings no longer sit in csky_last_error), exact fp32-coefficient texture cells, csky_render_sky_lut_rows_device, csky_interleave_bands_device, csky_encode_bc7, rings eight deep; 4: csky_submit_* / csky_collect, csky_multi_set_groups / _set_staged, csky_composite_view, csky_external_frame_* (incl. _fence / _ready / _wait); 3: csky_set_noise_mips, csky_decode_bc7, csky_load_ctex[3d]; 2: csky_multi_*, device asset builders */
+#define CSKY_ABI_VERSION 9  /* 9 (entry points only added since): csky_render_cloud_shadow[_device] (the cloud shadow map); csky_set_ / csky_get_ / csky_multi_set_transmittance_mapping, csky_transmittance_uv (CSKY_TLUT_BRUNETON); 8: csky_render_radiance[_device], csky_prefilter_cube (the radiance cubemap); 7: csky_multi_last_warning (csky_multi_create no longer fails without peer access: it falls back to staged copies and says so); 6: the measurement / tuning / test entry points moved to cloudsky_internal.h (same library), csky_generate_shape_noise_tuned[_device]; 5: csky_last_warning (warnings no longer sit in csky_last_error), exact fp32-coefficient texture cells, csky_render_sky_lut_rows_device, csky_interleave_bands_device, csky_encode_bc7, rings eight deep; 4: csky_submit_* / csky_collect, csky_multi_set_groups / _set_staged, csky_composite_view, csky_external_frame_* (incl. _fence / _ready / _wait); 3: csky_set_noise_mips, csky_decode_bc7, csky_load_ctex[3d]; 2: csky_multi_*, device asset builders */
 
 typedef struct csky_ctx csky_ctx; /* opaque: owns every device allocation, the HIP stream and events */
 
@@ -305,6 +305,44 @@ int csky_render_radiance(csky_ctx* ctx, const csky_composite_params* sky, const 
  * csky_render_radiance* is left alone); blocks. */
 int csky_prefilter_cube(csky_ctx* ctx, const uint16_t* cube_rgba16f, int face_size, int layers, int source_size, int first_layer, int n_layers,
                         uint16_t* out_rgba16f);
+
+/* ---- cloud shadow map: the sun's transmittance to the ground --------------------------------------
+ * What the clouds of a frame do to the ground under them: a W x H map of R16F texels over a rectangle of the observer's tangent plane, for a host
+ * that lights its scene with sun.gd's DirectionalLight3D under this sky.  World frame of the shader (clouds.glsl:43-45, :223): the observer stands at
+ * (0, Rg, 0), Rg = 6 000 000, Rb = 6 001 500, Rt = 6 004 000 metres.  For texel (i, j), centre (cx, cz), extents (ex, ez), N steps:
+ *     g     = ( cx + ((i + 0.5) / W - 0.5) * ex ,  Rg ,  cz + ((j + 0.5) / H - 0.5) * ez )          the ground point, tangent plane at the observer
+ *     l     = normalize(LIGHT_DIRECTION)                                                            clouds.glsl:150
+ *     start = g + l * intersectSphere(g, l, Rb)        end = g + l * intersectSphere(g, l, Rt)      clouds.glsl:97-105 for a general position
+ *     sd    = length(end - start);  ss = sd / N;  step = l * sd / N                                 as :226-230 with N for 128
+ *     p     = start + step * 0.5;   tau = 0
+ *     N times:  w = texture(weather_noise, p.xz * 0.00006 + 0.5 + weather_pos)                      :174
+ *               tau += density(p, w, 0.0)                                                           :109-137, mip 0
+ *               p += step
+ *     T(i,j) = exp(-density * ss * tau)          stored as one IEEE half, row j, column i
+ * No jitter: the view march's hash() hides banding in a view and would be noise in a map.  T is 1 - alpha as the march itself would report it
+ * looking at the sun from g (each step's dt multiplies into 1 - alpha, :207, :210).  Night: if l.y <= 0 every texel is 0, no direct light reaches
+ * the ground.  The positions are evaluated in fp32 with IEEE sqrt and divide, without contraction, dot products summed left to right, in the
+ * order written (bit-identical on the device and on a host); the taps, density() and the final exp use the march's own cores and the hardware
+ * exp2.  A texel whose exponent has reached 18 stores the half 0 and is not sampled further (exp(-18) < 2^-25): the bytes do not depend on that.
+ * Of the push-constant block only cloud_pos, detailed_pos, weather_pos, LIGHT_DIRECTION, time, density and cloud_coverage are read: pass the block
+ * packed for the frame (cloud_sky.gd:251-289).  Needs the noise (CSKY_ERR_STATE without it) and NO LUT: the map does not depend on the atmosphere.
+ * Lookup in a host shader, for a world position (x, z) in this frame (observer at (0, 0)):
+ *     uv = ((x, z) - center) / extent + 0.5          texel centres at ((i + 0.5) / W, (j + 0.5) / H); sample with linear filtering, clamp to edge
+ * The ground is the tangent plane, not the sphere (33 m above it 20 km from the observer); far enough out (134 km) the plane leaves the cloud
+ * layer's base and the formula above, which is still what is stored, stops describing a shadow. */
+typedef struct {
+    int   width, height;   /* texels, 1..8192 each                                                        */
+    float center[2];       /* x, z of the map's centre, metres, the shader's frame (observer at 0, 0)     */
+    float extent[2];       /* side lengths along x and z, metres; finite, > 0; |center| + extent/2 <= 1e6 */
+    int   steps;           /* N, 1..1024; 0 = 64                                                          */
+} csky_shadow_params;
+/* Blocking host form: out_r16f receives height rows of width halfs, tightly packed.  CSKY_ERR_INVALID: a NULL pointer, a size, step count or
+ * extent out of range, a non-finite float among the fields read. */
+int csky_render_cloud_shadow(csky_ctx* ctx, const csky_cloud_params* p, const csky_shadow_params* sp, uint16_t* out_r16f);
+/* Device form: rows of row_pitch_bytes (even, >= 2 * width) into d_out_r16f, asynchronously on hip_stream (the context's own stream if NULL).
+ * Writes the width x height halfs and nothing else: not the pitch padding. */
+int csky_render_cloud_shadow_device(csky_ctx* ctx, const csky_cloud_params* p, const csky_shadow_params* sp, void* d_out_r16f, size_t row_pitch_bytes,
+                                    void* hip_stream);
 
 /* ---- frames in flight ---------------------------------------------------------------------------- */
 /* Policy hint for the automatic segment / schedule choice: n = 2..8: the caller keeps n frames in flight by rotating n streams

@@ -101,4 +101,6 @@ int csky_encode_bc7_quality(csky_ctx* ctx, const uint8_t* rgba8, int w, int h, i
 #endif
 /* The switch and the launch counter of the sky LUT's reuse: declared in a header of their own, which every user of this one gets with it. */
 #include "cloudsky_lut_hooks.h"
+/* The A/B switch of the cloud shadow map's exact end, likewise. */
+#include "cloudsky_shadow_hooks.h"
 #endif /* CLOUDSKY_INTERNAL_H */

@@ -1,0 +1,55 @@
+// shadow_host.cpp -- TEST TOOL ONLY.  Compiles the cloud shadow map's per-lane code (csrc/shadow_core.h on top of cloud_core.h: what the lanes of
+// shadow.hip run) for the HOST with g++, so that the `-m "not gpu"` suite can check it against the numpy restatement of the definition
+// (tests/shadow_reference.py) without a GPU.  It is NOT part of libcloudsky and is never a render fallback: the product has no CPU path.
+#include <cstdint>
+#include <cstring>
+#include <cmath>
+#include <vector>
+#include "../../godot-volumetric-cloud-demo-v2_amd/csrc/shadow_core.h"
+#include "../../godot-volumetric-cloud-demo-v2_amd/csrc/bake.h"
+
+using namespace csky;
+
+extern "C" {
+
+// mip chains (level 0 first) -> baked fp16-pair layouts -> every texel of the map as shadow_kernel's lanes compute it (a wavefront of one lane).
+// out_h: height rows of width halfs.  exact_end: ShadowConsts::exact_end.  taken (may be NULL): the lane-samples taken, summed over the map.
+// Returns 0, or -1 for a step count out of range.
+int shadow_host_map(const uint8_t* large_chain, const uint8_t* small_chain, const uint8_t* weather_rgb8, const float params[28], int width, int height,
+                    const float center[2], const float extent[2], int steps, int exact_end, int use_window, uint16_t* out_h, uint64_t* taken) {
+    if (steps < 1 || steps > 1024 || width < 1 || height < 1) return -1;
+    std::vector<uint8_t> lc(large_chain, large_chain + csky_mip_offset(SHAPE_N, SHAPE_LEVELS, 4));
+    std::vector<uint8_t> sc_(small_chain, small_chain + csky_mip_offset(DETAIL_N, DETAIL_LEVELS, 3));
+    std::vector<ShapeTexel> shape; std::vector<uint4> detail, weather;
+    uint32_t shape_off[SHAPE_LEVELS], detail_off[DETAIL_LEVELS];
+    bake_shape(lc, shape, shape_off); bake_detail(sc_, detail, detail_off); bake_weather(weather_rgb8, weather);
+    TexSet T;
+    T.shape = shape.data(); T.detail = detail.data(); T.weather = weather.data(); T.sky = nullptr; T.sky_w = 0; T.sky_h = 0;
+    T.detail_h = nullptr; T.detail_lds = nullptr;
+    { const uint8_t* t5 = sc_.data() + csky_mip_offset(DETAIL_N, 5, 3); T.detail_lod5 = (float)(5 * t5[0] + 2 * t5[1] + t5[2]) * (1.0f / (8.0f * 255.0f)); }
+    CloudParams P; memcpy(&P, params, sizeof P);
+    float hlo = -1.0f, hhi = 2.0f; int ctm = 0;
+    if (use_window) {                                        // like api_shadow.cpp: the exact specialisations are switched together
+        int rmin = 255, rmax = 0, bmax = 0;
+        for (size_t i = 0; i < (size_t)WEATHER_N * WEATHER_N; i++) { const int r = weather_rgb8[3 * i], b = weather_rgb8[3 * i + 2]; rmin = r < rmin ? r : rmin; rmax = r > rmax ? r : rmax; bmax = b > bmax ? b : bmax; }
+        height_window((double)P.cloud_coverage, rmin / 255.0, rmax / 255.0, bmax / 255.0, hlo, hhi);
+        ctm = rmin >= 128 ? 1 : (rmax <= 127 ? 2 : 0);
+    }
+    ShadowConsts sc;
+    sc.w = width; sc.h = height; sc.cx = center[0]; sc.cz = center[1]; sc.ex = extent[0]; sc.ez = extent[1];
+    sc.steps = steps; sc.exact_end = exact_end ? 1 : 0; sc.pitch_h = (uint32_t)width;
+    FrameConsts fc;
+    shadow_frame_consts(P, steps, hlo, hhi, ctm, fc);
+    sc.night = fc.ldir[1] > 0.0f ? 0 : 1;
+    unsigned long long n = 0;
+    for (int j = 0; j < height; j++) for (int i = 0; i < width; i++) out_h[(size_t)j * width + i] = shadow_texel(T, fc, sc, i, j, true, &n);
+    if (taken) *taken = n;
+    return 0;
+}
+
+size_t csky_mip_offset(int n, int level, int ch) {  // same definition as assets.cpp (this tool does not link libcloudsky)
+    size_t off = 0;
+    for (int l = 0; l < level; l++) { size_t m = (size_t)(n >> l); off += m * m * m * (size_t)ch; }
+    return off;
+}
+}
