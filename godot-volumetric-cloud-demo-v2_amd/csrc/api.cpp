@@ -1,11 +1,10 @@
 // api.cpp -- the C ABI of libcloudsky (include/cloudsky.h; the measurement / tuning / test entry points: include/cloudsky_internal.h): context
-// lifecycle, settings, noise upload and bake, LUTs, the cloud entry points, the asynchronous host ring, read-backs and kernel timing.  The launch
-// of the cloud kernel is clouds_launch.cpp; the compositor and the radiance cubemap api_sky.cpp; zero-copy frames api_external.cpp; the
-// multi-device handle api_multi.cpp.
+// lifecycle, settings, noise upload and bake, the cloud entry points, the asynchronous host ring, read-backs and kernel timing.  The LUTs are
+// api_lut.cpp; the launch of the cloud kernel clouds_launch.cpp; the compositor and the radiance cubemap api_sky.cpp; the cloud shadow map
+// api_shadow.cpp; zero-copy frames api_external.cpp; the multi-device handle api_multi.cpp.
 // GPU resources are held by the owner types of owners.h, as members of csky_ctx (context.h) or as locals of the entry point that needs a scratch
 // buffer: nothing here releases a handle by hand, and an early return leaks nothing.
-// Mirrors the resource ownership of the reference's GDScript drivers: cloud_sky.gd (`_initialize_compute_code`,
-// `_render_process`, `cleanup`), sky_lut.gd (`render_lut`), transmittance_lut.gd (`_initialize_compute_code`).
+// Mirrors the resource ownership of the reference's GDScript driver cloud_sky.gd (`_initialize_compute_code`, `_render_process`, `cleanup`).
 // There is no CPU render path here: every render entry point needs a live HIP device.
 #include <cstdarg>
 #include <cstdio>
@@ -17,7 +16,6 @@
 #include "context.h"
 #include "bake_core.h"
 #include "cloud_core.h"
-#include "lut_core.h"
 #include "order_core.h"
 
 using namespace csky;
@@ -43,12 +41,6 @@ static_assert(sizeof(csky_cloud_params) == sizeof(CloudParams), "ABI struct mism
 namespace {
 constexpr size_t CSKY_STATS_WORDS = 2 + 128;             // [0..1] the kernel's own tallies; then 256 32-bit basic-block counters of the census build (tools/isa_profile.py; zero in the product build)
 
-int ensure_trans(csky_ctx* c, int w, int h) {
-    if (c->d_trans_h && c->tw == w && c->th == h) return CSKY_OK;
-    int rc; if ((rc = c->d_trans_h.alloc(c, (size_t)w * h * 4))) return rc;
-    if ((rc = c->d_trans_f.alloc(c, (size_t)w * h))) return rc;
-    c->tw = w; c->th = h; c->have_trans = false; return CSKY_OK;
-}
 // the stream, events and buffers a context has from the start (csky_create)
 int create_resources(csky_ctx* c) {
     int rc; if ((rc = bind(c))) return rc;
@@ -67,51 +59,6 @@ int create_resources(csky_ctx* c) {
     return CSKY_OK;
 }
 
-// The cache of csky_render_sky_lut_rows_device (context.h).  Its readers and writers sit on CALLER streams, several of them with frames in flight:
-//   fill -> read   every copy out waits for ev_rows_fill (until the event has been seen complete once)
-//   read -> fill   every copy out records an event of the ring ev_rows_read; a fill waits for all that are pending.  A ring slot that comes round
-//                  while still pending is waited for by its new user first, so the newer record stands for the older one too
-//   fill -> fill   a fill waits for the one before it
-bool event_done(hipEvent_t ev) {
-    if (hipEventQuery(ev) == hipSuccess) return true;
-    (void)hipGetLastError();                                   // hipErrorNotReady is an answer, not a failure to resurface later
-    return false;
-}
-int rows_cache_fill(csky_ctx* c, const void* d_rows, size_t px, hipStream_t s) {
-    int rc;
-    if (!c->ev_rows_fill) {
-        if ((rc = c->ev_rows_fill.create(c, hipEventDisableTiming))) return rc;
-        for (Event& ev : c->ev_rows_read) if ((rc = ev.create(c, hipEventDisableTiming))) return rc;
-    }
-    const bool regrow = c->d_rows_cache.count() < px;
-    for (int k = 0; k < RING; k++) {
-        if (!c->rows_read_pending[k]) continue;
-        if (regrow) HIPCHK(c, hipEventSynchronize(c->ev_rows_read[k]));
-        else if (!event_done(c->ev_rows_read[k])) HIPCHK(c, hipStreamWaitEvent(s, c->ev_rows_read[k], 0));
-        c->rows_read_pending[k] = false;
-    }
-    if (!c->rows_fill_done) {
-        if (regrow) HIPCHK(c, hipEventSynchronize(c->ev_rows_fill));
-        else if (!event_done(c->ev_rows_fill)) HIPCHK(c, hipStreamWaitEvent(s, c->ev_rows_fill, 0));
-    }
-    if (regrow && (rc = c->d_rows_cache.alloc(c, px))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->d_rows_cache, d_rows, px * 8, hipMemcpyDeviceToDevice, s));
-    HIPCHK(c, hipEventRecord(c->ev_rows_fill, s));
-    c->rows_fill_done = false;
-    return CSKY_OK;
-}
-int rows_cache_read(csky_ctx* c, void* d_rows_out, size_t px, hipStream_t s) {
-    if (!c->rows_fill_done) {
-        if (event_done(c->ev_rows_fill)) c->rows_fill_done = true;
-        else HIPCHK(c, hipStreamWaitEvent(s, c->ev_rows_fill, 0));
-    }
-    const int k = c->rows_read_cur;
-    if (c->rows_read_pending[k] && !event_done(c->ev_rows_read[k])) HIPCHK(c, hipStreamWaitEvent(s, c->ev_rows_read[k], 0));
-    HIPCHK(c, hipMemcpyAsync(d_rows_out, c->d_rows_cache, px * 8, hipMemcpyDeviceToDevice, s));
-    HIPCHK(c, hipEventRecord(c->ev_rows_read[k], s));
-    c->rows_read_pending[k] = true; c->rows_read_cur = (k + 1) % RING;
-    return CSKY_OK;
-}
 }  // namespace
 
 namespace csky {
@@ -123,25 +70,6 @@ int fail(csky_ctx* c, int code, const char* fmt, ...) {
     va_list ap; va_start(ap, fmt); vsnprintf(dst, 512, fmt, ap); va_end(ap);
     if (code == CSKY_ERR_HIP) (void)hipGetLastError();       // the runtime's last-error slot is sticky: a failed call must not resurface as the "launch error" of a later kernel
     return code;
-}
-
-int ensure_sky(csky_ctx* c, int w, int h) {
-    if (c->d_sky_h && c->sw == w && c->sh == h) return CSKY_OK;
-    sky_lut_touch(c);                                           // whatever the slots held goes
-    if (c->stream) HIPCHK(c, hipStreamSynchronize(c->stream));  // a size change is rare: drain the context's stream (every reader of the LUT runs there), rebuild both slots
-    for (int k = 0; k < 2; k++) {
-        int rc; if ((rc = c->sky_h_ring[k].alloc(c, (size_t)w * h * 4))) return rc;
-        if ((rc = c->sky_f_ring[k].alloc(c, (size_t)w * h))) return rc;
-    }
-    c->sky_cur = 0; c->d_sky_h = c->sky_h_ring[0]; c->d_sky_f = c->sky_f_ring[0];
-    c->sw = w; c->sh = h; c->have_sky = false; return CSKY_OK;
-}
-
-int render_trans_dev(csky_ctx* c, int w, int h, hipStream_t s) {
-    c->trans_gen++; sky_lut_touch(c); c->rows_key.valid = false;   // every LUT rendered through the old table is another table's (sky_lut_reuse.h)
-    int rc; if ((rc = ensure_trans(c, w, h))) return rc;
-    HIPCHK(c, launch_transmittance(w, h, c->d_trans_h, c->d_trans_f, s, c->tlut));
-    c->have_trans = true; return CSKY_OK;
 }
 
 int host_slot_prepare(csky_ctx* c, csky_ctx::HostSlot& hs, size_t px) {
@@ -475,132 +403,12 @@ int csky_set_height_window(csky_ctx* c, int enabled) {
     if (!c) return fail(nullptr, CSKY_ERR_INVALID, "csky_set_height_window: ctx is NULL");
     c->use_window = enabled != 0; return CSKY_OK;
 }
-int csky_set_transmittance_mapping(csky_ctx* c, int mapping) {
-    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "csky_set_transmittance_mapping: ctx is NULL");
-    if (mapping != CSKY_TLUT_REFERENCE && mapping != CSKY_TLUT_BRUNETON) return fail(c, CSKY_ERR_INVALID, "csky_set_transmittance_mapping: CSKY_TLUT_REFERENCE (0) or CSKY_TLUT_BRUNETON (1)");
-    if (mapping == c->tlut) return CSKY_OK;
-    int rc; if ((rc = bind(c))) return rc;
-    HIPCHK(c, hipDeviceSynchronize());                         // readers of the old table may be in flight, on caller streams too (csky_render_transmittance)
-    // everything rendered through the old table goes: the table itself (re-rendered on demand), the sky LUT and the radiance snapshot
-    c->tlut = mapping; c->have_trans = false; c->have_sky = false; c->sky_partial = false; c->sky_in_memory = false; c->lut_writers.clear(); c->rad.valid = false;
-    c->trans_gen++; sky_lut_touch(c); c->rows_key.valid = false;
-    return CSKY_OK;
-}
-int csky_get_transmittance_mapping(const csky_ctx* c) { return c ? c->tlut : CSKY_ERR_INVALID; }
-int csky_set_sky_lut_reuse(csky_ctx* c, int enabled) {
-    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "csky_set_sky_lut_reuse: ctx is NULL");
-    if (enabled != 0 && enabled != 1) return fail(c, CSKY_ERR_INVALID, "csky_set_sky_lut_reuse: 0 (a launch per call) or 1 (reuse, the default)");
-    c->sky_lut_reuse = enabled != 0; sky_lut_touch(c); c->rows_key.valid = false;
-    return CSKY_OK;
-}
-int64_t csky_sky_lut_launches(const csky_ctx* c) { return c ? (int64_t)c->sky_lut_launches : (int64_t)CSKY_ERR_INVALID; }
-int csky_transmittance_uv(int mapping, int w, int h, float r_km, float mu, float uv[2], int* hits_ground) {
-    if (!uv) return fail(nullptr, CSKY_ERR_INVALID, "csky_transmittance_uv: uv is NULL");
-    if (mapping == CSKY_TLUT_REFERENCE) {                      // transmittance_from_lut (sky-lut.glsl:137-142); the table stores every ray
-        if (w < 1 || h < 1) return fail(nullptr, CSKY_ERR_INVALID, "csky_transmittance_uv: empty table");
-        uv[0] = sat(mu * 0.5f + 0.5f); uv[1] = sat((r_km - EARTH_RADIUS) / ATMOSPHERE_THICKNESS);
-        if (hits_ground) *hits_ground = 0;
-        return CSKY_OK;
-    }
-    if (mapping != CSKY_TLUT_BRUNETON) return fail(nullptr, CSKY_ERR_INVALID, "csky_transmittance_uv: CSKY_TLUT_REFERENCE (0) or CSKY_TLUT_BRUNETON (1)");
-    if (w < 2 || h < 2) return fail(nullptr, CSKY_ERR_INVALID, "csky_transmittance_uv: CSKY_TLUT_BRUNETON needs a table of at least 2 x 2");
-    const bool hit = tlut_uv(w, h, r_km, mu, uv[0], uv[1]);
-    if (hits_ground) *hits_ground = hit ? 1 : 0;
-    return CSKY_OK;
-}
 int csky_variant_count(void) { return cloud_variant_count(); }
 const char* csky_variant_name(int v) { return cloud_variant_name(v); }
 
 int csky_sync(csky_ctx* c) {
     if (!c) return fail(nullptr, CSKY_ERR_INVALID, "csky_sync: ctx is NULL");
     int rc; if ((rc = bind(c))) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return CSKY_OK;
-}
-
-int csky_render_transmittance(csky_ctx* c, const csky_transmittance_params* p, uint16_t* out) {
-    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "csky_render_transmittance: ctx is NULL");
-    if (!p) return fail(c, CSKY_ERR_INVALID, "csky_render_transmittance: params is NULL");
-    const int w = (int)p->texture_size[0], h = (int)p->texture_size[1];
-    if (w < 1 || h < 1 || w > 8192 || h > 8192) return fail(c, CSKY_ERR_INVALID, "csky_render_transmittance: texture_size out of range");
-    if (c->tlut == CSKY_TLUT_BRUNETON && (w < 2 || h < 2)) return fail(c, CSKY_ERR_INVALID, "csky_render_transmittance: CSKY_TLUT_BRUNETON needs a table of at least 2 x 2 (texel centres sit on the ends of both ranges)");
-    int rc; if ((rc = bind(c))) return rc;
-    // sky LUTs in flight read the old transmittance LUT: whole ones and the set-ups' own texels on the prologue stream, a rank's rows
-    // (csky_render_sky_lut_rows_device) on CALLER streams; the LUT is rendered once at load (transmittance_lut.gd:15-18), so wait for the device
-    sky_lut_touch(c); c->rows_key.valid = false;
-    HIPCHK(c, hipDeviceSynchronize());
-    if ((rc = render_trans_dev(c, w, h, c->stream))) return rc;
-    if (out) HIPCHK(c, hipMemcpyAsync(out, c->d_trans_h, (size_t)w * h * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return CSKY_OK;
-}
-
-int csky_render_sky_lut_device(csky_ctx* c, const csky_sky_params* p, void* hip_stream) {
-    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "csky_render_sky_lut: ctx is NULL");
-    if (!p) return fail(c, CSKY_ERR_INVALID, "csky_render_sky_lut: params is NULL");
-    const int w = (int)p->texture_size[0], h = (int)p->texture_size[1];
-    if (w < 1 || h < 1 || w > 8192 || h > 8192) return fail(c, CSKY_ERR_INVALID, "csky_render_sky_lut: texture_size out of range");
-    int rc; if ((rc = bind(c))) return rc;
-    (void)hip_stream;   // the LUT has no inputs of the caller's: it is rendered on the context's stream and its consumers are ordered by events
-    if (!c->have_trans && (rc = render_trans_dev(c, 256, 64, c->stream))) return rc;   // transmittance_lut.gd:6 default size
-    if ((rc = ensure_sky(c, w, h))) return rc;
-    // The LUT is a function of the sun, its size and the transmittance table alone, and a host refreshes it every pass whether the sun moved or not
-    // (cloud_sky.gd:187 against sun.gd:17): the same request as the one slot sky_cur was rendered from launches nothing and leaves the ring where
-    // it is.  Every consumer (the frame set-ups, the copies out) runs on `stream`, behind the launch that filled the slot.
-    const SkyLutKey req = sky_lut_key(p->sun_direction, w, h, c->tlut, c->trans_gen);
-    if (sky_lut_whole_hit(c->sky_key, req, sky_lut_state(c))) return CSKY_OK;
-    sky_lut_touch(c);                                                               // (set again below, once the launch went through)
-    const int k = (c->have_sky && c->sky_in_memory) ? c->sky_cur ^ 1 : c->sky_cur;  // the other ring slot: frame set-ups still reading the current one are ahead on `stream`
-    HIPCHK(c, launch_sky_lut(w, h, p->sun_direction, c->d_trans_f, c->tw, c->th, c->sky_h_ring[k], c->sky_f_ring[k], c->stream, c->tlut));
-    c->sky_lut_launches++;
-    c->sky_cur = k; c->d_sky_h = c->sky_h_ring[k]; c->d_sky_f = c->sky_f_ring[k];
-    c->have_sky = true; c->sky_partial = false; c->sky_in_memory = true; c->lut_writers.clear();
-    c->sky_key = req;
-    return CSKY_OK;
-}
-int csky_render_sky_lut_rows_device(csky_ctx* c, const csky_sky_params* p, int first_row, int row_stride, void* d_rows_out, size_t capacity_bytes, void* hip_stream) {
-    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "csky_render_sky_lut_rows_device: ctx is NULL");
-    if (!p || !d_rows_out) return fail(c, CSKY_ERR_INVALID, "csky_render_sky_lut_rows_device: NULL argument");
-    const int w = (int)p->texture_size[0], h = (int)p->texture_size[1];
-    if (w < 1 || h < 1 || w > 8192 || h > 8192) return fail(c, CSKY_ERR_INVALID, "csky_render_sky_lut_rows_device: texture_size out of range");
-    if (first_row < 0 || row_stride < 1 || first_row >= row_stride) return fail(c, CSKY_ERR_INVALID, "csky_render_sky_lut_rows_device: need 0 <= first_row < row_stride");
-    const int n_rows = first_row < h ? (h - first_row + row_stride - 1) / row_stride : 0;
-    if (capacity_bytes < (size_t)n_rows * w * 8) return fail(c, CSKY_ERR_INVALID, "csky_render_sky_lut_rows_device: %zu bytes given, %d rows of %d bytes needed", capacity_bytes, n_rows, w * 8);
-    int rc; if ((rc = bind(c))) return rc;
-    if (!c->have_trans) {                                       // (rendered on the context's stream: the caller's stream reads it)
-        if ((rc = render_trans_dev(c, 256, 64, c->stream))) return rc;
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    // the rows have no consumer inside the library: they are rendered on the CALLER's stream, in order with the bands they travel with.
-    // (Round 5 measured them on a side stream BESIDE the march that follows, joined behind it: a 1/8 share one frame at a time 0.409 -> 0.460 ms, eight
-    // in flight 0.241 -> 0.244: two more cross-stream hops cost more than the rows they take off the critical path; profiles/r05/rows_overlap_ab.txt.)
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    // The caller's buffer differs from frame to frame, so the rows of an unchanged request cannot simply stay where they are: the context keeps a
-    // copy of the last rows it rendered, and the same request again is one device copy of them on the caller's stream instead of the kernel.
-    // A request that differs renders into the caller's buffer as ever and leaves its copy behind (a sun that moves every frame pays that copy alone).
-    const size_t px = (size_t)n_rows * w;
-    const SkyLutKey req = sky_lut_key(p->sun_direction, w, h, c->tlut, c->trans_gen, first_row, row_stride);
-    sky_lut_touch(c);                                           // the ring's whole LUT, if any, is no longer what the set-ups use
-    if (px && sky_lut_rows_hit(c->rows_key, req, c->sky_lut_reuse)) {
-        if ((rc = rows_cache_read(c, d_rows_out, px, s))) { c->rows_key.valid = false; return rc; }
-    } else {
-        c->rows_key.valid = false;
-        HIPCHK(c, launch_sky_lut_rows(w, h, first_row, row_stride, p->sun_direction, c->d_trans_f, c->tw, c->th, reinterpret_cast<uint2*>(d_rows_out), nullptr, s, c->tlut));
-        if (px) c->sky_lut_launches++;
-        if (px && c->sky_lut_reuse) {
-            if ((rc = rows_cache_fill(c, d_rows_out, px, s))) return rc;
-            c->rows_key = req;
-        }
-    }
-    for (int i = 0; i < 3; i++) c->sky_sun[i] = p->sun_direction[i];
-    c->psw = w; c->psh = h; c->sky_partial = true; c->have_sky = true; c->sky_in_memory = false; c->lut_writers.clear();
-    return CSKY_OK;
-}
-
-int csky_render_sky_lut(csky_ctx* c, const csky_sky_params* p, uint16_t* out) {
-    int rc = csky_render_sky_lut_device(c, p, nullptr);
-    if (rc) return rc;
-    if (out) HIPCHK(c, hipMemcpyAsync(out, c->d_sky_h, (size_t)c->sw * c->sh * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return CSKY_OK;
 }
@@ -683,28 +491,6 @@ int csky_poll(csky_ctx* c, int64_t ticket) {
     return fail(c, CSKY_ERR_STATE, "csky_poll: ticket %lld is not outstanding", (long long)ticket);
 }
 
-int csky_read_transmittance(csky_ctx* c, uint16_t* out, int* w, int* h) {
-    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "csky_read_transmittance: ctx is NULL");
-    if (!c->have_trans) return fail(c, CSKY_ERR_STATE, "csky_read_transmittance: LUT not rendered yet");
-    int rc; if ((rc = bind(c))) return rc;
-    if (w) *w = c->tw; if (h) *h = c->th;
-    if (out) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipMemcpy(out, c->d_trans_h, (size_t)c->tw * c->th * 8, hipMemcpyDeviceToHost)); }
-    return CSKY_OK;
-}
-int csky_read_sky_lut(csky_ctx* c, uint16_t* out, int* w, int* h) {
-    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "csky_read_sky_lut: ctx is NULL");
-    if (!c->have_sky) return fail(c, CSKY_ERR_STATE, "csky_read_sky_lut: LUT not rendered yet");
-    if (!c->sky_in_memory) return fail(c, CSKY_ERR_STATE, "csky_read_sky_lut: the last LUT went to the caller as rows (csky_render_sky_lut_rows_device), this context holds none");
-    int rc; if ((rc = bind(c))) return rc;
-    if (w) *w = c->sw; if (h) *h = c->sh;
-    if (out) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        for (hipEvent_t ev : c->lut_writers) HIPCHK(c, hipEventSynchronize(ev));       // rows written by the other devices of a csky_multi handle
-        HIPCHK(c, hipMemcpy(out, c->d_sky_h, (size_t)c->sw * c->sh * 8, hipMemcpyDeviceToHost));
-    }
-    return CSKY_OK;
-}
-
 int csky_set_kernel_timing(csky_ctx* c, int enabled) {
     if (!c) return fail(nullptr, CSKY_ERR_INVALID, "csky_set_kernel_timing: ctx is NULL");
     int rc; if ((rc = bind(c))) return rc;
@@ -778,23 +564,6 @@ int csky_generate_shape_noise_tuned_device(csky_ctx* c, uint32_t seed, int n, co
 int csky_get_cloud_stats(csky_ctx* c, csky_cloud_stats* stats) {
     if (!c || !stats) return fail(c, CSKY_ERR_INVALID, "csky_get_cloud_stats: NULL argument");
     *stats = c->last_stats; return CSKY_OK;
-}
-
-
-int csky_copy_sky_lut_device(csky_ctx* c, void* d_out, void* hip_stream) {
-    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "csky_copy_sky_lut_device: ctx is NULL");
-    if (!d_out) return fail(c, CSKY_ERR_INVALID, "csky_copy_sky_lut_device: d_out is NULL");
-    if (!c->have_sky) return fail(c, CSKY_ERR_STATE, "csky_copy_sky_lut_device: LUT not rendered yet");
-    if (!c->sky_in_memory) return fail(c, CSKY_ERR_STATE, "csky_copy_sky_lut_device: the last LUT went to the caller as rows (csky_render_sky_lut_rows_device), this context holds none");
-    int rc; if ((rc = bind(c))) return rc;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    // the copy runs on the context's stream right behind the LUT's render (a later render goes to the other ring slot and, like every
-    // writer of a slot, is queued behind this reader on the same stream); the caller's stream then waits for it
-    for (hipEvent_t ev : c->lut_writers) HIPCHK(c, hipStreamWaitEvent(c->stream, ev, 0));   // rows written by the other devices of a csky_multi handle
-    HIPCHK(c, hipMemcpyAsync(d_out, c->d_sky_h, (size_t)c->sw * c->sh * 8, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipEventRecord(c->ev_copy, c->stream));
-    HIPCHK(c, hipStreamWaitEvent(s, c->ev_copy, 0));
-    return CSKY_OK;
 }
 
 int csky_interleave_bands_device(csky_ctx* c, const void* d_gathered, size_t member_stride_bytes, int members, size_t band_bytes, int total_bands, void* d_frame, void* hip_stream) {

@@ -30,7 +30,7 @@ struct csky_multi {
     // on the first device:
     Event ev_begin[MULTI_SLOTS];          // the consumer stream's position when the frame was requested
     Event ev_lut_begin;                   // on its prologue stream: the readers of the LUT slot about to be rewritten are behind this
-    SkyLutKey lut_key;                    // what csky_multi_render_sky_lut rendered last (sky_lut_reuse.h), and every device's sky_epoch as that call left it:
+    SkyLutKey lut_key;                    // what csky_multi_render_sky_lut rendered last (sky_lut_reuse.h), and every device's LUT epoch as that call left it:
     std::vector<unsigned long long> lut_epoch;   // the same request again, with no device's LUT state touched since, renders nothing
     DevBuf<uint2> d_frame;                // host-buffer form: internal frame, in pixels, grow-only
     int fif = 1, groups = 1;              // frames in flight PER GROUP, frame groups (csky_multi_set_groups)
@@ -128,7 +128,7 @@ void csky_multi_destroy(csky_multi* m) {
         (void)hipSetDevice(c0->device);
         for (Event& ev : m->ev_begin) ev.reset();
         m->ev_lut_begin.reset(); m->d_frame.reset();
-        c0->lut_writers.clear();
+        c0->lut.writers.clear();
     }
     for (Dev& d : m->dev) csky_destroy(d.ctx);
     delete m;
@@ -223,8 +223,8 @@ int csky_multi_set_staged(csky_multi* m, int staged) {
 int csky_multi_render_sky_lut(csky_multi* m, const csky_sky_params* p) {
     if (!m) return mfail(nullptr, CSKY_ERR_INVALID, "csky_multi_render_sky_lut: handle is NULL");
     if (!p) return mfail(m, CSKY_ERR_INVALID, "csky_multi_render_sky_lut: params is NULL");
-    const int w = (int)p->texture_size[0], h = (int)p->texture_size[1];
-    if (w < 1 || h < 1 || w > 8192 || h > 8192) return mfail(m, CSKY_ERR_INVALID, "csky_multi_render_sky_lut: texture_size out of range");
+    int w, h, rc;
+    if ((rc = lut_size(nullptr, "csky_multi_render_sky_lut", p->texture_size, w, h))) return mfail(m, rc, "%s", g_err);
     // sky_lut.gd:43-52 renders the LUT once per frame (cloud_sky.gd:187); n devices rendering n whole copies would each spend 33 us of a chip on it,
     // 12 % of a 1/8 frame share.  Device i renders rows i, i + n, ... and stores them, like its bands, straight into the LUT on the first device
     // (the copy a consumer reads: csky_read_sky_lut / csky_copy_sky_lut_device on csky_multi_ctx(m, 0) wait for every writer).  No device's frame
@@ -232,46 +232,42 @@ int csky_multi_render_sky_lut(csky_multi* m, const csky_sky_params* p) {
     // device, whatever the group layout (a caller with a static sun renders the LUT once and then frames on all groups).
     const int n = (int)m->dev.size();
     csky_ctx* c0 = m->dev[0].ctx;
-    int rc;
     // A static sun (the case above) asks for the LUT the handle rendered last: no device renders its rows again, every device keeps the sun it
-    // recorded, and the first context's lut_writers stay the events of the call that stored the rows.  Anything that touched a device's LUT
-    // state since (a context's own LUT calls, a new transmittance table or mapping) moved its sky_epoch: then the handle renders.
-    if (c0->sky_lut_reuse && sky_lut_same_key(m->lut_key, sky_lut_key(p->sun_direction, w, h, c0->tlut, c0->trans_gen)) && m->lut_epoch.size() == (size_t)n) {
+    // recorded, and the first context's writers stay the events of the call that stored the rows.  Anything that touched a device's LUT
+    // state since (a context's own LUT calls, a new transmittance table or mapping) moved its epoch: then the handle renders.
+    if (c0->lut.st.reuse && sky_lut_same_key(m->lut_key, sky_lut_key(p->sun_direction, w, h, c0->tlut, c0->lut.st.trans_gen)) && m->lut_epoch.size() == (size_t)n) {
         bool same = true;
-        for (int i = 0; i < n; i++) same = same && m->dev[i].ctx->sky_epoch == m->lut_epoch[i];
+        for (int i = 0; i < n; i++) same = same && m->dev[i].ctx->lut.st.epoch == m->lut_epoch[i];
         if (same) return CSKY_OK;
     }
     m->lut_key.valid = false;
-    for (int i = 0; i < n; i++) sky_lut_touch(m->dev[i].ctx);   // (the first context's ring slot is about to hold rows of several devices)
-    if (c0->d_sky_h && (c0->sw != w || c0->sh != h))            // a size change re-allocates the first device's LUT slots: no device may still be storing rows into them
+    for (int i = 0; i < n; i++) m->dev[i].ctx->lut.st.touch();   // (the first context's ring slot is about to hold rows of several devices)
+    if (c0->lut.aw && (c0->lut.aw != w || c0->lut.ah != h))   // a size change re-allocates the first device's LUT slots: no device may still be storing rows into them
         for (int i = 0; i < n; i++) { if ((rc = bind(m->dev[i].ctx))) return mpass(m, i, rc); if (hipStreamSynchronize(m->dev[i].ctx->stream) != hipSuccess) return mfail(m, CSKY_ERR_HIP, "csky_multi_render_sky_lut: hipStreamSynchronize failed"); }
     if ((rc = bind(c0))) return mpass(m, 0, rc);
     if ((rc = ensure_sky(c0, w, h))) return mpass(m, 0, rc);
-    const int k = (c0->have_sky && c0->sky_in_memory) ? c0->sky_cur ^ 1 : c0->sky_cur;     // the other ring slot, as in csky_render_sky_lut_device
+    const int k = c0->lut.render_slot();
     // the readers of slot k (device copies of the LUT before last) sit on the first device's prologue stream: every writer queues behind them
     if (hipEventRecord(m->ev_lut_begin, c0->stream) != hipSuccess) return mfail(m, CSKY_ERR_HIP, "csky_multi_render_sky_lut: hipEventRecord failed");
     for (int i = 0; i < n; i++) {
         csky_ctx* c = m->dev[i].ctx;
         if ((rc = bind(c))) return mpass(m, i, rc);
-        if (!c->have_trans && (rc = render_trans_dev(c, 256, 64, c->stream))) return mpass(m, i, rc);   // transmittance_lut.gd:6 default size
+        if ((rc = ensure_default_trans(c))) return mpass(m, i, rc);
         hipError_t e = i ? hipStreamWaitEvent(c->stream, m->ev_lut_begin, 0) : hipSuccess;
         // rows i, i + n, ... stored into the first device's LUT -- or, when some device cannot reach that memory, every row by the first device itself
         if (e == hipSuccess && (m->all_peer || i == 0)) {
-            if ((m->all_peer ? i : 0) < h) c->sky_lut_launches++;
-            e = launch_sky_lut_rows(w, h, m->all_peer ? i : 0, m->all_peer ? n : 1, p->sun_direction, c->d_trans_f, c->tw, c->th, reinterpret_cast<uint2*>(c0->sky_h_ring[k].get()), c0->sky_f_ring[k], c->stream, c->tlut);
+            if ((m->all_peer ? i : 0) < h) c->lut.launches++;
+            e = launch_sky_lut_rows(w, h, m->all_peer ? i : 0, m->all_peer ? n : 1, p->sun_direction, c->d_trans_f, c->tw, c->th, reinterpret_cast<uint2*>(c0->lut.ring_h[k].get()), c0->lut.ring_f[k], c->stream, c->tlut);
         }
         if (e == hipSuccess) e = hipEventRecord(m->dev[i].lut, c->stream);
         if (e != hipSuccess) return mfail(m, CSKY_ERR_HIP, "csky_multi_render_sky_lut: device index %d: %s", i, hipGetErrorString(e));
-        for (int q = 0; q < 3; q++) c->sky_sun[q] = p->sun_direction[q];
-        c->psw = w; c->psh = h; c->sky_partial = true; c->have_sky = true;
-        if (i) { c->sky_in_memory = false; c->lut_writers.clear(); }
+        if (i) { c->lut.st.became_rows(p->sun_direction, w, h); c->lut.writers.clear(); }
     }
-    c0->sky_cur = k; c0->d_sky_h = c0->sky_h_ring[k]; c0->d_sky_f = c0->sky_f_ring[k]; c0->sky_in_memory = true;
-    c0->lut_writers.clear();
-    for (int i = 1; i < n; i++) c0->lut_writers.push_back(m->dev[i].lut);   // (its own rows are on its prologue stream, ahead of any reader)
-    m->lut_key = sky_lut_key(p->sun_direction, w, h, c0->tlut, c0->trans_gen);
+    c0->lut.publish(k); c0->lut.st.became_shared(p->sun_direction, w, h);
+    for (int i = 1; i < n; i++) c0->lut.writers.push_back(m->dev[i].lut);   // (its own rows are on its prologue stream, ahead of any reader)
+    m->lut_key = sky_lut_key(p->sun_direction, w, h, c0->tlut, c0->lut.st.trans_gen);
     m->lut_epoch.resize(n);
-    for (int i = 0; i < n; i++) m->lut_epoch[i] = m->dev[i].ctx->sky_epoch;
+    for (int i = 0; i < n; i++) m->lut_epoch[i] = m->dev[i].ctx->lut.st.epoch;
     return CSKY_OK;
 }
 

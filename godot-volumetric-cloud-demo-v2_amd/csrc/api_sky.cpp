@@ -33,7 +33,7 @@ int composite_impl(csky_ctx* c, const csky_composite_params* p, const csky_view*
     if (p->out_w < 1 || p->out_h < 1 || p->cloud_w < 1 || p->cloud_h < 1 || p->sky_w < 1 || p->sky_h < 1 || p->out_w > 16384 || p->out_h > 16384)
         return fail(c, CSKY_ERR_INVALID, "csky_composite_sky: bad image size");
     int rc; if ((rc = bind(c))) return rc;
-    if (!c->have_trans && (rc = render_trans_dev(c, 256, 64, c->stream))) return rc;       // source_transmittance, clouds_material.tres
+    if ((rc = ensure_default_trans(c))) return rc;            // source_transmittance, clouds_material.tres
     const size_t cb = (size_t)p->cloud_w * p->cloud_h * 8, sb = (size_t)p->sky_w * p->sky_h * 8, ob = (size_t)p->out_w * p->out_h * 8;
     const size_t need = 2 * cb + 2 * sb + ob;
     if ((rc = c->d_composite.grow(c, need))) return rc;       // grow-only scratch: no allocation per call once the sizes have been seen
@@ -98,7 +98,7 @@ int radiance_dev(csky_ctx* c, const char* fn, const csky_composite_params* p, in
     int rc;
     const size_t plane = (size_t)6 * S * S;
     if (first == 0) {
-        if (!c->have_trans && (rc = render_trans_dev(c, 256, 64, c->stream))) return rc;   // source_transmittance, clouds_material.tres
+        if ((rc = ensure_default_trans(c))) return rc;                                    // source_transmittance, clouds_material.tres
         HIPCHK(c, hipEventRecord(c->ev_rad, c->stream));                                  // the LUT may have been rendered there
         HIPCHK(c, hipStreamWaitEvent(s, c->ev_rad, 0));
         c->rad.valid = false;

@@ -13,7 +13,7 @@ TexSet texset(const csky_ctx* c) {
 #ifdef CSKY_BRICK_BOUND
     t.brick = c->d_brick;
 #endif
-    t.shape = c->d_shape; t.detail = c->d_detail; t.weather = c->d_weather; t.sky = c->d_sky_f; t.sky_w = c->sw; t.sky_h = c->sh; t.detail_lod5 = c->detail_lod5; t.detail_h = c->d_detail_h; t.detail_lds = nullptr;
+    t.shape = c->d_shape; t.detail = c->d_detail; t.weather = c->d_weather; t.sky = c->lut.cur_f(); t.sky_w = c->lut.aw; t.sky_h = c->lut.ah; t.detail_lod5 = c->detail_lod5; t.detail_h = c->d_detail_h; t.detail_lds = nullptr;
     return t;
 }
 
@@ -88,7 +88,7 @@ int clouds_dev(csky_ctx* c, const csky_cloud_params* p, int tile_w, const csky_b
                unsigned long long* d_stats, bool setup, bool out_full) {
     if (!p) return fail(c, CSKY_ERR_INVALID, "render_clouds: params is NULL");
     if (!c->have_noise) return fail(c, CSKY_ERR_STATE, "render_clouds: csky_set_noise has not been called");
-    if (!c->have_sky) return fail(c, CSKY_ERR_STATE, "render_clouds: no sky LUT yet (call csky_render_sky_lut first; cloud_sky.gd:187,242)");
+    if (c->lut.st.holds == SkyLutHolds::None) return fail(c, CSKY_ERR_STATE, "render_clouds: no sky LUT yet (call csky_render_sky_lut first; cloud_sky.gd:187,242)");
     if (!(p->texture_size[0] >= 1.0f) || !(p->texture_size[1] >= 1.0f)) return fail(c, CSKY_ERR_INVALID, "render_clouds: texture_size must be >= 1");
     int rc; if ((rc = check_bands(c, b, tile_w))) return rc;
     if (pitch_bytes % 8 || pitch_bytes < (size_t)tile_w * 8) return fail(c, CSKY_ERR_INVALID, "render_clouds: row pitch must be a multiple of 8 and >= tile_w*8");
@@ -101,10 +101,11 @@ int clouds_dev(csky_ctx* c, const csky_cloud_params* p, int tile_w, const csky_b
         const int f = (c->fc_cur + 1) % RING;
         if (c->clouds_pending[f]) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_clouds[f], 0));
         const SetupArgs sa = {c->primary_steps, c->light_steps, c->early_eps, lo, hi, ctm, c->use_window ? 1 : 0};
-        if (c->sky_partial)                              // no LUT in memory: the set-up renders the texels of its three taps (clouds.glsl:163-167) itself
-            HIPCHK(c, launch_frame_setup_taps(cp, c->sky_sun, c->d_trans_f, c->tw, c->th, c->psw, c->psh, sa, c->fc_ring[f], c->stream, c->tlut));
+        const SkyLut& l = c->lut;
+        if (l.st.own_taps())                             // the set-up renders the texels of its three taps (clouds.glsl:163-167) itself
+            HIPCHK(c, launch_frame_setup_taps(cp, l.st.sun, c->d_trans_f, c->tw, c->th, l.st.w, l.st.h, sa, c->fc_ring[f], c->stream, c->tlut));
         else
-            HIPCHK(c, launch_frame_setup(cp, c->d_sky_f, c->sw, c->sh, sa, c->fc_ring[f], c->stream));
+            HIPCHK(c, launch_frame_setup(cp, l.cur_f(), l.aw, l.ah, sa, c->fc_ring[f], c->stream));
         HIPCHK(c, hipEventRecord(c->ev_setup[f], c->stream));
         c->fc_cur = f; c->d_fc = c->fc_ring[f];
         // (Round 5 bounded what folding the set-up INTO the march launch could return by simply not waiting here -- legal in a timing run with constant

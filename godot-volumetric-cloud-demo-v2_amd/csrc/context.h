@@ -1,6 +1,7 @@
 // context.h -- the context of libcloudsky (csky_ctx) and the host helpers its C ABI sources share.  Internal to libcloudsky:
-// api.cpp (lifecycle, textures, LUTs, cloud entry points, host ring), clouds_launch.cpp (the cloud kernel launch), api_sky.cpp (compositor,
-// radiance cubemap), api_shadow.cpp (cloud shadow map), api_external.cpp (zero-copy frames), api_multi.cpp (the multi-device handle).
+// api.cpp (lifecycle, textures, cloud entry points, host ring), api_lut.cpp (the transmittance and sky LUTs), clouds_launch.cpp (the cloud kernel
+// launch), api_sky.cpp (compositor, radiance cubemap), api_shadow.cpp (cloud shadow map), api_external.cpp (zero-copy frames), api_multi.cpp (the
+// multi-device handle).
 // Ownership: every device buffer, pinned buffer, event and stream of the context is a member of one of the owner types of owners.h and dies with
 // the context (csky_destroy: bind the device, wait for it, delete).  A buffer's count() is its capacity; raw pointers and raw handles in the
 // struct are views of something owned elsewhere and say so.
@@ -20,6 +21,49 @@
 // in flight on as many streams (csky_set_frames_in_flight).  The slots rotate over all RING entries whatever that number is.
 constexpr int RING = 8;
 constexpr int HOST_RING = 8;   // pinned host frames of the asynchronous host form (a single context uses up to RING of them, csky_multi up to groups x frames in flight)
+
+namespace csky {
+
+// The context's sky LUT: what it holds (sky_lut_reuse.h: the state and its transitions) and the memory it holds it in.
+// The ring is two slots deep: the sky LUT and the frame set-up of frame k+1 run on the context's stream beside the march of frame k, and every
+// reader of the LUT runs on that stream too, so a render goes to the slot the readers ahead of it are not using (csky_ctx, frame prologue pipeline).
+// Two sizes, because no reader can do with one: aw x ah is what both slots are allocated for, which is the size of the whole LUT in memory (Whole,
+// Shared: ensure_sky comes before every launch into a slot); st.w x st.h is the size of the LUT a Rows or Shared context renders its own taps for.
+// The rows form allocates nothing, so a Rows context's ring may still be sized for an earlier whole LUT of another size.
+struct SkyLut {
+    SkyLutHeld st;
+    DevBuf<uint16_t> ring_h[2]; DevBuf<float4> ring_f[2];   // RGBA16F image + float4 copy of the rounded values
+    int cur = 0;                                             // the slot readers use
+    int aw = 0, ah = 0;                                      // 0 x 0: not allocated (ensure_sky)
+    // Shared: the other devices' rows of the slot have been stored (csky_multi_render_sky_lut); readers of the memory copy wait for them first.
+    // Empty in every other state.
+    std::vector<hipEvent_t> writers;                         // views, not owned: copies of events the csky_multi handle owns
+    long long launches = 0;                                  // LUT kernels launched, whole and rows form (csky_sky_lut_launches)
+
+    uint16_t* cur_h() const { return ring_h[cur]; }
+    float4* cur_f() const { return ring_f[cur]; }
+    // the slot to render into: the other one while readers may be using the current one (they are ahead on the context's stream)
+    int render_slot() const { return st.in_memory() ? cur ^ 1 : cur; }
+    // slot k has been rendered into: readers use it from here on.  (The caller names what it holds: st.became_whole / st.became_shared.)
+    void publish(int k) { cur = k; writers.clear(); }
+    void drop() { st.drop(); writers.clear(); }
+};
+
+// csky_render_sky_lut_rows_device: the compact rows of st.rows_key, copied behind the kernel that rendered them into a caller's buffer; a call with
+// the same key copies them out on the caller's stream instead of rendering.  Events and buffer are made by the first fill.
+// Its readers and writers sit on CALLER streams, several of them with frames in flight:
+//   fill -> read   every copy out waits for ev_fill (until the event has been seen complete once)
+//   read -> fill   every copy out records an event of the ring ev_read; a fill waits for all that are pending.  A ring slot that comes round
+//                  while still pending is waited for by its new user first, so the newer record stands for the older one too
+//   fill -> fill   a fill waits for the one before it
+struct RowsCache {
+    DevBuf<uint2> d; Event ev_fill, ev_read[RING];
+    bool fill_done = true, read_pending[RING] = {}; int read_cur = 0;
+    int fill(csky_ctx* c, const void* d_rows, size_t px, hipStream_t s);     // api_lut.cpp
+    int read(csky_ctx* c, void* d_rows_out, size_t px, hipStream_t s);
+};
+
+}  // namespace csky
 
 struct csky_ctx {
     int device = 0;
@@ -43,7 +87,6 @@ struct csky_ctx {
     // LUTs: RGBA16F image + float4 copy of the rounded values
     csky::DevBuf<uint16_t> d_trans_h; csky::DevBuf<float4> d_trans_f; int tw = 0, th = 0; bool have_trans = false;
     int tlut = CSKY_TLUT_REFERENCE;                   // the transmittance LUT's parametrization (csky_set_transmittance_mapping, tlut_core.h): its writer and every reader get it
-    uint16_t* d_sky_h = nullptr; float4* d_sky_f = nullptr; int sw = 0, sh = 0; bool have_sky = false;   // views, not owned: = ring slot sky_cur
     csky::FrameConsts* d_fc = nullptr;                                                                    // view, not owned: = ring slot fc_cur
     // Frame prologue pipeline.  The sky LUT and the frame set-up of frame k+1 are small dependent kernels; enqueued behind the
     // cloud kernel of frame k they cost their run time plus two launch gaps per frame (6 % of one GPU's 1/8-frame share).  They
@@ -52,23 +95,8 @@ struct csky_ctx {
     // three-deep texture rings for the same reason, sky_lut.gd:143-146), so they overlap the march of the previous frame; events order
     // set-up -> clouds (ev_setup) and clouds -> the next writer of that slot (ev_clouds).  All sky-LUT readers run on `stream`.
     // A march that itself runs on `stream` (NULL hip_stream, the blocking host forms) has its prologue in line with it: nothing overlaps there.
-    csky::DevBuf<uint16_t> sky_h_ring[2]; csky::DevBuf<float4> sky_f_ring[2]; int sky_cur = 0;
-    // csky_render_sky_lut_rows_device: the LUT of sun sky_sun exists only as the rows the caller's buffer received (one rank of an N-way frame
-    // split); the texels this context's frame set-up filters are rendered by the set-up kernel itself (clouds_dev)
-    bool sky_partial = false; float sky_sun[3] = {0, 1, 0}; int psw = 0, psh = 0;
-    // csky_multi_render_sky_lut: the whole LUT IS in this context's memory (ring slot sky_cur), written row by row by the devices of the handle;
-    // readers of the memory copy wait for those writers first.  (sky_partial stays set: the frame set-ups never read the memory copy.)
-    bool sky_in_memory = false; std::vector<hipEvent_t> lut_writers;   // views, not owned: copies of events the csky_multi handle owns
-    // Reuse of a rendered LUT (sky_lut_reuse.h).  sky_key: what ring slot sky_cur was rendered from by csky_render_sky_lut_device; a call with the
-    // same key launches nothing (every consumer is on `stream`, behind the launch that filled the slot).  trans_gen counts what replaces the
-    // transmittance table (render_trans_dev, a mapping change); sky_epoch counts every call that may change this context's LUT state, so that a
-    // csky_multi handle can tell that none happened since its own last render.  sky_lut_launches: LUT kernels launched, whole and rows form.
-    csky::SkyLutKey sky_key; unsigned long long trans_gen = 0, sky_epoch = 0; bool sky_lut_reuse = true; long long sky_lut_launches = 0;
-    // csky_render_sky_lut_rows_device: the compact rows of rows_key, copied behind the kernel that rendered them into a caller's buffer; a call with
-    // the same key copies them out on the caller's stream instead of rendering.  ev_rows_fill: the cache is filled; ev_rows_read: the copies out
-    // (a ring: more than one caller stream reads), which the next fill waits for.  Events and buffer are made by the first fill.
-    csky::SkyLutKey rows_key; csky::DevBuf<uint2> d_rows_cache; csky::Event ev_rows_fill, ev_rows_read[RING];
-    bool rows_fill_done = true, rows_read_pending[RING] = {}; int rows_read_cur = 0;
+    csky::SkyLut lut;
+    csky::RowsCache rows_cache;
     csky::DevBuf<csky::FrameConsts> fc_ring[RING]; int fc_cur = 0;
     csky::Event ev_setup[RING], ev_clouds[RING]; bool clouds_pending[RING] = {};
     csky::DevBuf<unsigned long long> d_stats;
@@ -118,12 +146,16 @@ extern thread_local char g_err[512];   // error text of calls without a context 
 inline int bind(csky_ctx* c) { HIPCHK(c, hipSetDevice(c->device)); return CSKY_OK; }
 
 // api.cpp
-// forgets what ring slot sky_cur was rendered from: the caller is about to change it, or the context's LUT state (sky_lut_reuse.h)
-inline void sky_lut_touch(csky_ctx* c) { c->sky_key.valid = false; c->sky_epoch++; }
-inline SkyLutState sky_lut_state(const csky_ctx* c) { SkyLutState s; s.reuse = c->sky_lut_reuse; s.have_sky = c->have_sky; s.sky_in_memory = c->sky_in_memory; s.sky_partial = c->sky_partial; s.no_writers = c->lut_writers.empty(); return s; }
+int host_slot_prepare(csky_ctx* c, csky_ctx::HostSlot& hs, size_t px);
+
+// api_lut.cpp
+inline SkyLutState sky_lut_state(const csky_ctx* c) { return sky_lut_state(c->lut.st, c->lut.writers.empty()); }
+// both ring slots at w x h.  A size change drops what the context holds first, so a failed allocation leaves a context that holds nothing
 int ensure_sky(csky_ctx* c, int w, int h);
 int render_trans_dev(csky_ctx* c, int w, int h, hipStream_t s);
-int host_slot_prepare(csky_ctx* c, csky_ctx::HostSlot& hs, size_t px);
+int ensure_default_trans(csky_ctx* c);   // the table at its default size (transmittance_lut.gd:6) on the context's stream, unless the context has one
+// a LUT request's texture_size as integers; `fn` is the entry point the error text names.  The text goes where fail() puts it: c, or g_err without one
+int lut_size(csky_ctx* c, const char* fn, const float texture_size[2], int& w, int& h);
 
 // clouds_launch.cpp
 TexSet texset(const csky_ctx* c);       // the bound textures as the kernels take them: fp16-pair cells, and the exact fp32 cells of a context in that mode

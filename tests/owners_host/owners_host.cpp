@@ -148,7 +148,7 @@ void test_owners(csky_ctx* c) {
 void test_context() {
     const long made0[KINDS] = {g_made[DEV], g_made[PINNED], g_made[EVENT], g_made[STREAM]};
     const size_t log0 = g_log.size(); const long bad0 = g_bad_release;
-    Event foreign; foreign.create(nullptr, hipEventDisableTiming);      // what csky_multi owns and lut_writers only views
+    Event foreign; foreign.create(nullptr, hipEventDisableTiming);      // what csky_multi owns and lut.writers only views
     csky_ctx* c = new csky_ctx();
     int rc = 0;
     // in an order unlike the declaration order on purpose: what dies when is the struct's business
@@ -160,7 +160,7 @@ void test_context() {
     rc |= c->d_heads.alloc(c, RING * 16); rc |= c->d_lpt_hist.alloc(c, 8); rc |= c->d_lpt_order.alloc(c, 8); rc |= c->d_wg_cost.alloc(c, 8);
     for (int k = 0; k < RING; k++) { rc |= c->d_order_ring[k].alloc(c, 8); rc |= c->ev_clouds[k].create(c, hipEventDisableTiming); rc |= c->ev_setup[k].create(c, hipEventDisableTiming); rc |= c->fc_ring[k].alloc(c, 1); }
     rc |= c->d_frame.alloc(c, 64); rc |= c->d_stats.alloc(c, 130);
-    for (int k = 0; k < 2; k++) { rc |= c->sky_f_ring[k].alloc(c, 8); rc |= c->sky_h_ring[k].alloc(c, 32); }
+    for (int k = 0; k < 2; k++) { rc |= c->lut.ring_f[k].alloc(c, 8); rc |= c->lut.ring_h[k].alloc(c, 32); }
     rc |= c->d_trans_f.alloc(c, 8); rc |= c->d_trans_h.alloc(c, 32);
     rc |= c->d_weather32.alloc(c, 8); rc |= c->d_detail32.alloc(c, 8); rc |= c->d_shape32.alloc(c, 8); rc |= c->d_brick.alloc(c, 8);
     rc |= c->d_detail_h.alloc(c, 8); rc |= c->d_weather.alloc(c, 8); rc |= c->d_detail.alloc(c, 8); rc |= c->d_shape.alloc(c, 8);
@@ -168,7 +168,7 @@ void test_context() {
     rc |= c->ev_copy.create(c, hipEventDisableTiming); rc |= c->ev1.create(c, hipEventDefault); rc |= c->ev0.create(c, hipEventDefault);
     rc |= c->stream.create(c, hipStreamNonBlocking);
     // the views: aliases of ring slots and copies of somebody else's events.  None of them may be released by the context.
-    c->d_sky_h = c->sky_h_ring[1]; c->d_sky_f = c->sky_f_ring[1]; c->d_fc = c->fc_ring[3]; c->lut_writers.push_back(foreign);
+    c->d_fc = c->fc_ring[3]; c->lut.writers.push_back(foreign);
     expect(rc == 0, "populating the context failed");
     void* const main_stream = static_cast<hipStream_t>(c->stream);
     const long made[KINDS] = {g_made[DEV] - made0[DEV], g_made[PINNED] - made0[PINNED], g_made[EVENT] - made0[EVENT] - 1, g_made[STREAM] - made0[STREAM]};
