@@ -48,14 +48,10 @@ int create_resources(csky_ctx* c) {
     // flight 1.78 -> 2.02 ms, one rank's 1/8 share 0.329 -> 0.335 ms: the priority queue breaks the overlap of the two frame streams.)
     if ((rc = c->stream.create(c, hipStreamNonBlocking)) || (rc = c->ev0.create(c, hipEventDefault)) || (rc = c->ev1.create(c, hipEventDefault))) return rc;
     if ((rc = c->ev_copy.create(c, hipEventDisableTiming)) || (rc = c->ev_rad.create(c, hipEventDisableTiming))) return rc;
-    for (int k = 0; k < RING; k++) {
-        for (long long& v : c->order_key_ring[k]) v = -1;
-        for (long long& v : c->lpt_key[k]) v = -1;
-        if ((rc = c->ev_setup[k].create(c, hipEventDisableTiming)) || (rc = c->ev_clouds[k].create(c, hipEventDisableTiming)) || (rc = c->fc_ring[k].alloc(c, 1))) return rc;
-    }
-    c->d_fc = c->fc_ring[0];
-    if ((rc = c->d_stats.alloc(c, CSKY_STATS_WORDS)) || (rc = c->d_heads.alloc(c, RING * 16))) return rc;
-    HIPCHK(c, hipMemset(c->d_heads, 0, RING * 16 * sizeof(uint32_t)));   // persistent launches leave them zero
+    for (FrameSlot& k : c->ring.slot)
+        if ((rc = k.ev_setup.create(c, hipEventDisableTiming)) || (rc = k.ev_clouds.create(c, hipEventDisableTiming)) || (rc = k.fc.alloc(c, 1))) return rc;
+    if ((rc = c->d_stats.alloc(c, CSKY_STATS_WORDS)) || (rc = c->ring.d_heads.alloc(c, RING * 16))) return rc;
+    HIPCHK(c, hipMemset(c->ring.d_heads, 0, RING * 16 * sizeof(uint32_t)));   // persistent launches leave them zero
     return CSKY_OK;
 }
 
@@ -494,9 +490,9 @@ int csky_poll(csky_ctx* c, int64_t ticket) {
 int csky_set_kernel_timing(csky_ctx* c, int enabled) {
     if (!c) return fail(nullptr, CSKY_ERR_INVALID, "csky_set_kernel_timing: ctx is NULL");
     int rc; if ((rc = bind(c))) return rc;
-    c->kt_on = enabled != 0; c->kt_count = 0;
-    if (c->kt_on && c->kt_ev.empty()) {      // the first pool is made HERE, not by the first timed launch: creating 512 events is ~1 ms of host time, 3 % of a 20-frame timed region
-        if ((rc = grow_timing_pool(c, 512))) { c->kt_on = false; return rc; }
+    c->kt.on = enabled != 0; c->kt.count = 0;
+    if (c->kt.on && c->kt.ev.empty()) {      // the first pool is made HERE, not by the first timed launch: creating 512 events is ~1 ms of host time, 3 % of a 20-frame timed region
+        if ((rc = c->kt.grow(c, 512))) { c->kt.on = false; return rc; }
     }
     return CSKY_OK;
 }
@@ -504,16 +500,7 @@ int csky_set_kernel_timing(csky_ctx* c, int enabled) {
 int csky_get_kernel_ms(csky_ctx* c, float* total_ms, int* launches) {
     if (!c || !total_ms || !launches) return fail(c, CSKY_ERR_INVALID, "csky_get_kernel_ms: NULL argument");
     int rc; if ((rc = bind(c))) return rc;
-    const int n = c->kt_count;                                 // every launch since the last call (the pool grows on demand)
-    float sum = 0.0f;
-    for (int i = 0; i < n; i++) {
-        HIPCHK(c, hipEventSynchronize(c->kt_ev[(size_t)i * 2 + 1]));
-        float ms = 0.0f;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->kt_ev[(size_t)i * 2], c->kt_ev[(size_t)i * 2 + 1]));
-        sum += ms;
-    }
-    *total_ms = sum; *launches = n; c->kt_count = 0;
-    return CSKY_OK;
+    return c->kt.read_out(c, total_ms, launches);              // every launch since the last call (the pool grows on demand)
 }
 
 // The stats launch delivers the exact counts (the tally form of the kernel); the warm-up and timed launches pass no stats buffer and take the form

@@ -5,6 +5,8 @@
 // Ownership: every device buffer, pinned buffer, event and stream of the context is a member of one of the owner types of owners.h and dies with
 // the context (csky_destroy: bind the device, wait for it, delete).  A buffer's count() is its capacity; raw pointers and raw handles in the
 // struct are views of something owned elsewhere and say so.
+// The per-frame ring is one member (FrameRing, below): each of its RING slots owns its frame constants, its two events and its order table, and the
+// ring hands out slot k's share of the four allocations the slots share.  What a slot remembers about its cached orders is frame_ring.h's.
 // Member order: `stream` is declared before everything recorded on it or ordered by it, and HostSlot::s before the rest of its slot; members die
 // in reverse order, so a stream is destroyed after the events and buffers that were used on it.  Keep new members below it.
 #pragma once
@@ -15,6 +17,7 @@
 #include "../../include/cloudsky_internal.h"
 #include "kernels.h"
 #include "owners.h"
+#include "frame_ring.h"
 #include "sky_lut_reuse.h"
 
 // Depth of the per-frame rings (frame constants, launch order, cost feedback, pop counters, events): the number of frames a caller may keep
@@ -63,6 +66,123 @@ struct RowsCache {
     int read(csky_ctx* c, void* d_rows_out, size_t px, hipStream_t s);
 };
 
+// One frame in flight: what the set-up kernel writes for it, the events that order it, and the workgroup orders cached for it.  The slots rotate
+// (= frame parity), so two frames in flight with different geometries never share a table, costs or pop counters.
+struct FrameSlot {
+    DevBuf<FrameConsts> fc;                // written by the frame set-up on the context's stream, read by the march
+    Event ev_setup, ev_clouds;             // set-up -> march; march (and its feedback sort) -> the next writer of this slot
+    bool pending = false;                  // ev_clouds has been recorded at least once: the next user of the slot waits for it.  Never cleared
+    DevBuf<uint32_t> order;                // static workgroup order (physical workgroup -> slab), written on the device, cached per launch geometry
+    OrderTableState order_st;
+    FeedbackState feedback;                // cost-feedback schedule (mode 7): per-workgroup costs of the last launch -> heaviest-first order of the next one
+};
+
+// The per-frame ring.  Frame prologue pipeline: the sky LUT and the frame set-up of frame k+1 are small dependent kernels; enqueued behind the cloud
+// kernel of frame k they cost their run time plus two launch gaps per frame (6 % of one GPU's 1/8-frame share).  They run on the context's own
+// stream instead, beside the caller's, into the next slot of a ring (the sky LUT two deep: every reader of it runs on that stream; the frame
+// constants RING deep: the marches of up to RING frames in flight read them) (the reference keeps three-deep texture rings for the same reason,
+// sky_lut.gd:143-146), so they overlap the march of the previous frame; events order set-up -> clouds (ev_setup) and clouds -> the next writer of
+// that slot (ev_clouds).  A march that itself runs on the context's stream (NULL hip_stream, the blocking host forms) has its prologue in line
+// with it: nothing overlaps there.
+struct FrameRing {
+    FrameSlot slot[RING]; int cur = 0;     // cur: the slot of the last set-up, which a launch without set-up uses again
+    // shared by the slots, RING equal shares each: costs and feedback orders of capacity() workgroups per slot, 2048 words of sort scratch,
+    // 16 words of pop counters of the persistent launch form (8 per XCD + the exit counter; zero between launches)
+    DevBuf<uint32_t> d_cost, d_feedback_order, d_sort_scratch, d_heads;
+
+    FrameConsts* fc() const { return slot[cur].fc; }
+    size_t capacity() const { return d_feedback_order.count() / RING; }
+    uint32_t* cost(int k) const { return d_cost + (size_t)k * capacity(); }
+    uint32_t* feedback_order(int k) const { return d_feedback_order + (size_t)k * capacity(); }
+    uint32_t* sort_scratch(int k) const { return d_sort_scratch + k * 2048; }
+    uint32_t* heads(int k) const { return d_heads + k * 16; }
+
+    // Prologue, first half: the slot the next set-up writes.  Its last reader, the march RING frames ago, must be done before `ctx_stream` writes it.
+    int next_slot(csky_ctx* c, hipStream_t ctx_stream, int& f) {
+        f = (cur + 1) % RING;
+        if (slot[f].pending) HIPCHK(c, hipStreamWaitEvent(ctx_stream, slot[f].ev_clouds, 0));
+        return CSKY_OK;
+    }
+    // Prologue, second half: the set-up of slot f was enqueued on ctx_stream.  The slot is current and the launch stream s waits for it.
+    // (Round 5 bounded what folding the set-up INTO the march launch could return by simply not waiting here -- legal in a timing run with constant
+    // parameters: whole frame one at a time 2.014 -> 2.000 ms, a 1/8 share 0.408 -> 0.404, eight in flight 0.224 -> 0.227: the prologue of frame k + 1
+    // already runs under the march of frame k; profiles/r05/rows_overlap_ab.txt.)
+    int setup_enqueued(csky_ctx* c, int f, hipStream_t ctx_stream, hipStream_t s) {
+        HIPCHK(c, hipEventRecord(slot[f].ev_setup, ctx_stream));
+        cur = f;
+        HIPCHK(c, hipStreamWaitEvent(s, slot[f].ev_setup, 0));
+        return CSKY_OK;
+    }
+    // Every order table grows to `grid` entries.  Growing is rare and costs a device-wide wait (an older launch may still read the old table): grow
+    // EVERY slot's table now, so that it happens once, at the first frame of a geometry, and not again at the first use of each of the other ring
+    // slots (with rings eight deep and a five-frame warm-up that was three synchronisations inside a timed region).  A table that is large enough
+    // keeps its memory and its key.
+    int grow_order_tables(csky_ctx* c, size_t grid) {
+        HIPCHK(c, hipDeviceSynchronize());
+        for (FrameSlot& k : slot) {
+            if (k.order.count() >= grid) continue;
+            if (const int rc = k.order.alloc(c, grid)) return rc;
+            k.order_st.forget();
+        }
+        return CSKY_OK;
+    }
+    // Room for the feedback of `need` workgroups per slot.  (Re)allocation is rare; frames may be in flight on other streams.  The order, allocated
+    // last, carries the capacity of the pair: a failure on the way leaves it empty.  The sort kernels leave costs and scratch zeroed afterwards.
+    int reserve_feedback(csky_ctx* c, size_t need) {
+        if (d_feedback_order.count() >= RING * need) return CSKY_OK;
+        HIPCHK(c, hipDeviceSynchronize());
+        d_cost.reset(); d_feedback_order.reset();
+        for (FrameSlot& k : slot) k.feedback.forget();
+        int rc; if ((rc = d_cost.alloc(c, RING * need))) return rc;
+        if (!d_sort_scratch) {
+            if ((rc = d_sort_scratch.alloc(c, RING * 2048))) return rc;
+            HIPCHK(c, hipMemset(d_sort_scratch, 0, RING * 2048 * sizeof(uint32_t)));
+        }
+        HIPCHK(c, hipMemset(d_cost, 0, RING * need * sizeof(uint32_t)));
+        return d_feedback_order.alloc(c, RING * need);
+    }
+    // Finish: the march of slot k (and the sort behind it) was enqueued on s.
+    int march_enqueued(csky_ctx* c, int k, hipStream_t s) {
+        HIPCHK(c, hipEventRecord(slot[k].ev_clouds, s));
+        slot[k].pending = true;
+        return CSKY_OK;
+    }
+};
+
+// Optional per-launch timing of the cloud kernel (csky_set_kernel_timing): HIP event pairs recorded around the launch on ITS stream.
+struct TimingPool {
+    bool on = false; std::vector<Event> ev; int count = 0;   // count: launches timed since the last read-out, two events each
+    // The pool grows to `want` events.  All or nothing: an event that cannot be made part-way used to leave null entries in the pool for
+    // later timed launches to record on; now the new events made so far go with the resize and the pool keeps its old size.
+    int grow(csky_ctx* c, size_t want) {
+        const size_t old_n = ev.size();
+        if (want <= old_n) return CSKY_OK;
+        ev.resize(want);
+        for (size_t i = old_n; i < want; i++)
+            if (const int rc = ev[i].create(c, hipEventDefault)) { ev.resize(old_n); return rc; }
+        return CSKY_OK;
+    }
+    // the event pair of the next timed launch.  The pool doubles on demand: no launch is ever dropped from the sum
+    int next_pair(csky_ctx* c, const Event*& pair) {
+        if ((size_t)count * 2 + 2 > ev.size())
+            if (const int rc = grow(c, ev.empty() ? 512 : ev.size() * 2)) return rc;
+        pair = &ev[(size_t)count * 2]; count++;
+        return CSKY_OK;
+    }
+    // the summed time of every launch since the last read-out, which it waits for
+    int read_out(csky_ctx* c, float* total_ms, int* launches) {
+        float sum = 0.0f;
+        for (int i = 0; i < count; i++) {
+            HIPCHK(c, hipEventSynchronize(ev[(size_t)i * 2 + 1]));
+            float ms = 0.0f;
+            HIPCHK(c, hipEventElapsedTime(&ms, ev[(size_t)i * 2], ev[(size_t)i * 2 + 1]));
+            sum += ms;
+        }
+        *total_ms = sum; *launches = count; count = 0;
+        return CSKY_OK;
+    }
+};
+
 }  // namespace csky
 
 struct csky_ctx {
@@ -87,18 +207,10 @@ struct csky_ctx {
     // LUTs: RGBA16F image + float4 copy of the rounded values
     csky::DevBuf<uint16_t> d_trans_h; csky::DevBuf<float4> d_trans_f; int tw = 0, th = 0; bool have_trans = false;
     int tlut = CSKY_TLUT_REFERENCE;                   // the transmittance LUT's parametrization (csky_set_transmittance_mapping, tlut_core.h): its writer and every reader get it
-    csky::FrameConsts* d_fc = nullptr;                                                                    // view, not owned: = ring slot fc_cur
-    // Frame prologue pipeline.  The sky LUT and the frame set-up of frame k+1 are small dependent kernels; enqueued behind the
-    // cloud kernel of frame k they cost their run time plus two launch gaps per frame (6 % of one GPU's 1/8-frame share).  They
-    // run on the context's own stream (`stream`, above) instead, beside the caller's, into the next slot of a ring (the sky LUT two deep: every
-    // reader of it runs on `stream`; the frame constants RING deep: the marches of up to RING frames in flight read them) (the reference keeps
-    // three-deep texture rings for the same reason, sky_lut.gd:143-146), so they overlap the march of the previous frame; events order
-    // set-up -> clouds (ev_setup) and clouds -> the next writer of that slot (ev_clouds).  All sky-LUT readers run on `stream`.
-    // A march that itself runs on `stream` (NULL hip_stream, the blocking host forms) has its prologue in line with it: nothing overlaps there.
+    // The frame prologue pipeline (FrameRing, above) runs on `stream`, and so do all sky-LUT readers.
     csky::SkyLut lut;
     csky::RowsCache rows_cache;
-    csky::DevBuf<csky::FrameConsts> fc_ring[RING]; int fc_cur = 0;
-    csky::Event ev_setup[RING], ev_clouds[RING]; bool clouds_pending[RING] = {};
+    csky::FrameRing ring;
     csky::DevBuf<unsigned long long> d_stats;
     csky::DevBuf<uint2> d_frame;                     // internal frame for the host-buffer form / timing, in pixels, grow-only
     int primary_steps = 128, light_steps = 6;        // clouds.glsl:228, :186
@@ -108,16 +220,8 @@ struct csky_ctx {
     int segments = 0;                                 // ray segments per ray: 0 = auto, 1, 2, 4
     int frames_in_flight = 1;                         // csky_set_frames_in_flight: the caller alternates that many streams
     int frames_overlapping = 1;                       // how many of them the hardware queues in effect can keep apart: the launch policy's hint (clouds_dev)
-    // static workgroup order (physical workgroup -> slab), written on the device, one table per ring slot (= frame parity, so two
-    // frames in flight with different geometries never share one), cached per launch geometry
-    csky::DevBuf<uint32_t> d_order_ring[RING]; int order_grid_ring[RING] = {};
-    long long order_key_ring[RING][4];     // csky_create fills them with -1
-    // cost-feedback schedule (mode 7): per-workgroup costs of the last launch -> heaviest-first order of the next one
-    csky::DevBuf<uint32_t> d_wg_cost, d_lpt_order, d_lpt_hist;   // costs and order: RING slots of count() / RING workgroups each (clouds_dev)
-    csky::DevBuf<uint32_t> d_heads; int persistent = 1; int resident_wgs = 0;   // persistent launches: 2 ring slots x (8 per-XCD pop counters + exit counter)
-    bool lpt_valid[RING] = {}; long long lpt_key[RING][11];   // csky_create fills the keys with -1
-    // optional per-launch timing of the cloud kernel (csky_set_kernel_timing): HIP event pairs recorded around the launch on ITS stream
-    bool kt_on = false; std::vector<csky::Event> kt_ev; int kt_count = 0;   // the event pool grows on demand (clouds_dev)
+    int persistent = 1; int resident_wgs = 0;         // the persistent launch form: allowed; workgroups resident at once
+    csky::TimingPool kt;                              // csky_set_kernel_timing
     csky::DevBuf<uint8_t> d_composite;                                     // grow-only scratch of csky_composite_sky
     // radiance cubemap (csky_render_radiance*, csky_prefilter_cube): source-record table and block cones, grow-only.  `rad` is the snapshot
     // of the last layer-0 call, which later calls filter from; csky_prefilter_cube works in `rad_pf` and leaves the snapshot alone
@@ -164,7 +268,6 @@ TexSet32 texset32(const csky_ctx* c);
 // outside which density() is 0 for the bound weather map, and FrameConsts::ct_mode
 void exact_rejects(csky_ctx* c, float coverage, float& hf_lo, float& hf_hi, int& ct_mode);
 int check_bands(csky_ctx* c, const csky_bands* b, int tile_w);
-int grow_timing_pool(csky_ctx* c, size_t want);
 // frame set-up (when `setup`) + the cloud kernel on stream s into d_out.  d_stats: optional device counters.
 int clouds_dev(csky_ctx* c, const csky_cloud_params* p, int tile_w, const csky_bands* b, uint2* d_out, size_t pitch_bytes, hipStream_t s,
                unsigned long long* d_stats, bool setup, bool out_full = false);

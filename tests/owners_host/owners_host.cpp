@@ -1,6 +1,8 @@
 // TEST TOOL ONLY: the owner types of csrc/owners.h and the destruction of a real csky_ctx (csrc/context.h), run on the CPU.
 // The HIP entry points the owners use are defined HERE as counting stubs: they hand out distinct fake handles (never dereferenced), refuse a release
 // of a handle that is not live, and log every release in order.  No GPU call is made and the HIP runtime is not linked.
+// Two pieces of the frame ring's and the timing pool's own code (context.h) run over the same stubs: the growth of the order tables and a pool growth
+// that fails part-way.
 // Prints one "name value" line per figure and "FAIL: ..." per broken expectation; exit status 1 if any.  tests/test_owners_host.py checks both.
 #include <cstdarg>
 #include <cstdint>
@@ -12,7 +14,8 @@
 
 namespace {
 
-enum Kind { DEV, PINNED, EVENT, STREAM, KINDS };
+enum Kind { DEV, PINNED, EVENT, STREAM, KINDS };                     // in g_calls a release is its kind + KINDS
+const Kind DEVICE_SYNC = static_cast<Kind>(2 * KINDS);                // hipDeviceSynchronize: an entry of g_calls ONLY, no kind -- never an index of the arrays below
 const char* const kind_name[KINDS] = {"dev", "pinned", "event", "stream"};
 struct Release { Kind kind; void* handle; };
 
@@ -22,6 +25,9 @@ std::vector<Release> g_log;            // every release, in order
 std::vector<Kind> g_calls;             // every acquire (its kind) and release (its kind + KINDS), in order
 long g_made[KINDS] = {}, g_bad_release = 0, g_last_error_calls = 0;
 int g_fail_next_malloc = 0;
+int g_fail_event_in = 0;                 // n > 0: the n-th event creation from here on fails
+std::vector<size_t> g_malloc_bytes;    // of every hipMalloc that succeeded, in order
+long g_device_syncs = 0;
 int g_failures = 0;
 
 hipError_t acquire(Kind k, void** out) {
@@ -51,14 +57,19 @@ long released(Kind k, size_t from = 0) { long n = 0; for (size_t i = from; i < g
 }  // namespace
 
 extern "C" {
-hipError_t hipMalloc(void** p, size_t) {
+hipError_t hipMalloc(void** p, size_t bytes) {
     if (g_fail_next_malloc) { g_fail_next_malloc = 0; g_calls.push_back(DEV); *p = nullptr; return hipErrorOutOfMemory; }
+    g_malloc_bytes.push_back(bytes);
     return acquire(DEV, p);
 }
+hipError_t hipDeviceSynchronize(void) { g_calls.push_back(DEVICE_SYNC); g_device_syncs++; return hipSuccess; }
 hipError_t hipFree(void* p) { return release(DEV, p); }
 hipError_t hipHostMalloc(void** p, size_t, unsigned int) { return acquire(PINNED, p); }
 hipError_t hipHostFree(void* p) { return release(PINNED, p); }
-hipError_t hipEventCreate(hipEvent_t* e) { return acquire(EVENT, reinterpret_cast<void**>(e)); }
+hipError_t hipEventCreate(hipEvent_t* e) {
+    if (g_fail_event_in && --g_fail_event_in == 0) { g_calls.push_back(EVENT); *e = nullptr; return hipErrorOutOfMemory; }
+    return acquire(EVENT, reinterpret_cast<void**>(e));
+}
 hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { return acquire(EVENT, reinterpret_cast<void**>(e)); }
 hipError_t hipEventDestroy(hipEvent_t e) { return release(EVENT, e); }
 hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned int) { return acquire(STREAM, reinterpret_cast<void**>(s)); }
@@ -153,12 +164,13 @@ void test_context() {
     int rc = 0;
     // in an order unlike the declaration order on purpose: what dies when is the struct's business
     for (auto& hs : c->hring) { rc |= hs.h.alloc(c, 4096); rc |= hs.d.alloc(c, 512); rc |= hs.done.create(c, hipEventDisableTiming); rc |= hs.s.create(c, hipStreamNonBlocking); }
-    c->kt_ev.resize(2); for (Event& e : c->kt_ev) rc |= e.create(c, hipEventDefault);
-    { const size_t old_n = c->kt_ev.size(); c->kt_ev.resize(70); for (size_t i = old_n; i < c->kt_ev.size(); i++) rc |= c->kt_ev[i].create(c, hipEventDefault); }   // a grown pool: the vector moved its events
+    c->kt.ev.resize(2); for (Event& e : c->kt.ev) rc |= e.create(c, hipEventDefault);
+    rc |= c->kt.grow(c, 70);   // a grown pool: the vector moved its events
+    expect(c->kt.ev.size() == 70, "the timing pool did not grow to 70 events");
     for (csky_ctx::RadSet* r : {&c->rad_pf, &c->rad}) { rc |= r->out_cones.alloc(c, 6); rc |= r->src_cones.alloc(c, 6); rc |= r->tab.alloc(c, 12); }
     rc |= c->d_rad_io.alloc(c, 64); rc |= c->ev_rad.create(c, hipEventDisableTiming); rc |= c->d_composite.alloc(c, 64);
-    rc |= c->d_heads.alloc(c, RING * 16); rc |= c->d_lpt_hist.alloc(c, 8); rc |= c->d_lpt_order.alloc(c, 8); rc |= c->d_wg_cost.alloc(c, 8);
-    for (int k = 0; k < RING; k++) { rc |= c->d_order_ring[k].alloc(c, 8); rc |= c->ev_clouds[k].create(c, hipEventDisableTiming); rc |= c->ev_setup[k].create(c, hipEventDisableTiming); rc |= c->fc_ring[k].alloc(c, 1); }
+    rc |= c->ring.d_heads.alloc(c, RING * 16); rc |= c->ring.d_sort_scratch.alloc(c, 8); rc |= c->ring.d_feedback_order.alloc(c, 8); rc |= c->ring.d_cost.alloc(c, 8);
+    for (FrameSlot& k : c->ring.slot) { rc |= k.order.alloc(c, 8); rc |= k.ev_clouds.create(c, hipEventDisableTiming); rc |= k.ev_setup.create(c, hipEventDisableTiming); rc |= k.fc.alloc(c, 1); }
     rc |= c->d_frame.alloc(c, 64); rc |= c->d_stats.alloc(c, 130);
     for (int k = 0; k < 2; k++) { rc |= c->lut.ring_f[k].alloc(c, 8); rc |= c->lut.ring_h[k].alloc(c, 32); }
     rc |= c->d_trans_f.alloc(c, 8); rc |= c->d_trans_h.alloc(c, 32);
@@ -167,8 +179,9 @@ void test_context() {
     rc |= c->d_bake_meta.alloc(c, 32); rc |= c->d_raw_weather.alloc(c, 8); rc |= c->d_raw_small.alloc(c, 8); rc |= c->d_raw_large.alloc(c, 8);
     rc |= c->ev_copy.create(c, hipEventDisableTiming); rc |= c->ev1.create(c, hipEventDefault); rc |= c->ev0.create(c, hipEventDefault);
     rc |= c->stream.create(c, hipStreamNonBlocking);
-    // the views: aliases of ring slots and copies of somebody else's events.  None of them may be released by the context.
-    c->d_fc = c->fc_ring[3]; c->lut.writers.push_back(foreign);
+    // the views: copies of somebody else's events.  None of them may be released by the context.
+    c->ring.cur = 3; c->lut.writers.push_back(foreign);
+    expect(c->ring.fc() == c->ring.slot[3].fc.get(), "the ring's frame constants are not the current slot's");
     expect(rc == 0, "populating the context failed");
     void* const main_stream = static_cast<hipStream_t>(c->stream);
     const long made[KINDS] = {g_made[DEV] - made0[DEV], g_made[PINNED] - made0[PINNED], g_made[EVENT] - made0[EVENT] - 1, g_made[STREAM] - made0[STREAM]};
@@ -207,6 +220,72 @@ void test_empty_context() {
     expect(g_calls.size() == calls0, "an empty context made %zu HIP calls when deleted", g_calls.size() - calls0);
 }
 
+// 8. the order tables grow together (FrameRing::grow_order_tables): one device-wide wait, then every table that is too small is re-allocated at exactly
+// the grid asked for, its free before its malloc, and forgets its key; a table that is large enough keeps its memory and its key
+void test_order_table_growth() {
+    csky_ctx* c = new csky_ctx();
+    FrameRing& r = c->ring;
+    const size_t caps[RING] = {8, 8, 64, 8, 8, 8, 8, 8};
+    int rc = 0;
+    for (int k = 0; k < RING; k++) { rc |= r.slot[k].order.alloc(c, caps[k]); r.slot[k].order_st.written(order_key(k + 1, 1, 1, 8)); }
+    expect(rc == 0, "order-table growth: populating the ring failed");
+    uint32_t* const large = r.slot[2].order;
+    const size_t calls0 = g_calls.size(), mallocs0 = g_malloc_bytes.size(); const long syncs0 = g_device_syncs;
+    expect(r.grow_order_tables(c, 32) == CSKY_OK, "order-table growth failed");
+    const size_t ncalls = g_calls.size() - calls0;
+    bool order_ok = ncalls == 15 && g_calls[calls0] == DEVICE_SYNC;
+    for (size_t i = 1; order_ok && i < ncalls; i += 2) order_ok = g_calls[calls0 + i] == DEV + KINDS && g_calls[calls0 + i + 1] == DEV;
+    expect(order_ok, "order-table growth: not one device-wide wait followed by seven times hipFree then hipMalloc (%zu calls)", ncalls);
+    long of_32 = 0, forgotten = 0;
+    for (size_t i = mallocs0; i < g_malloc_bytes.size(); i++) of_32 += g_malloc_bytes[i] == 32 * sizeof(uint32_t);
+    for (int k = 0; k < RING; k++) {
+        forgotten += !r.slot[k].order_st.key.valid;
+        if (k != 2) expect(r.slot[k].order.count() == 32 && !r.slot[k].order_st.key.valid, "order-table growth: slot %d is not a 32-entry table without a key", k);
+    }
+    const bool kept = r.slot[2].order == large && r.slot[2].order.count() == 64 && r.slot[2].order_st.hit(true, order_key(3, 1, 1, 8));
+    expect(kept, "order-table growth: the 64-entry table lost its memory or its key");
+    expect(of_32 == 7 && g_malloc_bytes.size() - mallocs0 == 7 && forgotten == 7, "order-table growth: %ld allocations of 32 entries, %ld keys forgotten", of_32, forgotten);
+    printf("order_growth_device_syncs %ld\norder_growth_calls_in_order %d\norder_growth_allocations_of_32 %ld\norder_growth_keys_forgotten %ld\norder_growth_large_table_kept %d\n",
+           g_device_syncs - syncs0, order_ok, of_32, forgotten, kept);
+    // a second growth to a size every table has: the wait, and nothing else
+    const size_t calls1 = g_calls.size();
+    expect(r.grow_order_tables(c, 32) == CSKY_OK && g_calls.size() == calls1 + 1, "order-table growth within every table's capacity allocated something");
+    delete c;
+    expect(live_total() == 0, "order-table growth: %ld handles left alive", live_total());
+}
+
+// 9. the timing pool (TimingPool): a growth that cannot make one of its events returns the error, keeps the old size and releases the events it had made;
+// the pool of a timed launch starts at 512 events and doubles when the next pair does not fit
+void test_timing_pool() {
+    csky_ctx* c = new csky_ctx();
+    TimingPool& p = c->kt;
+    expect(p.grow(c, 4) == CSKY_OK && p.ev.size() == 4, "timing pool: growth to 4 events");
+    const long made0 = g_made[EVENT], live0 = (long)g_live[EVENT].size(); const size_t log0 = g_log.size();
+    c->err[0] = 0;
+    g_fail_event_in = 3;
+    const int rc = p.grow(c, 10);
+    expect(rc == CSKY_ERR_HIP && g_fail_event_in == 0, "timing pool: a failed growth returned %d", rc);
+    expect(p.ev.size() == 4 && p.ev[0] && p.ev[3], "timing pool: a failed growth left %zu events", p.ev.size());
+    expect(g_made[EVENT] - made0 == 2 && released(EVENT, log0) == 2 && (long)g_live[EVENT].size() == live0, "timing pool: a failed growth made %ld events and released %ld",
+           g_made[EVENT] - made0, released(EVENT, log0));
+    printf("pool_growth_failure_is_error %d\npool_growth_failure_size %zu\npool_growth_failure_events_made %ld\npool_growth_failure_events_released %ld\npool_growth_failure_error_text %s\n",
+           rc == CSKY_ERR_HIP, p.ev.size(), g_made[EVENT] - made0, released(EVENT, log0), c->err);
+    expect(p.grow(c, 10) == CSKY_OK && p.ev.size() == 10, "timing pool: the growth after a failed one");
+    delete c;
+
+    c = new csky_ctx();
+    TimingPool& q = c->kt;
+    const Event* pair = nullptr; size_t after_256 = 0;
+    for (int i = 0; i < 257; i++) {
+        expect(q.next_pair(c, pair) == CSKY_OK && pair == &q.ev[(size_t)i * 2] && pair[0] && pair[1], "timing pool: pair %d", i);
+        if (i == 255) after_256 = q.ev.size();
+    }
+    expect(after_256 == 512 && q.ev.size() == 1024 && q.count == 257, "timing pool: %zu events after 256 pairs, %zu after 257", after_256, q.ev.size());
+    printf("pool_events_after_256_pairs %zu\npool_events_after_257_pairs %zu\n", after_256, q.ev.size());
+    delete c;
+    expect(live_total() == 0, "timing pool: %ld handles left alive", live_total());
+}
+
 }  // namespace
 
 int main() {
@@ -217,6 +296,8 @@ int main() {
     }
     test_context();
     test_empty_context();
+    test_order_table_growth();
+    test_timing_pool();
     printf("double_releases %ld\nlive_handles_at_exit %ld\nfailures %d\n", g_bad_release, live_total(), g_failures);
     return g_failures ? 1 : 0;
 }

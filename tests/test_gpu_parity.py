@@ -521,6 +521,31 @@ def test_frames_in_flight_are_independent(pkg, gpu_ctx, oracle):
         gpu_ctx.set_march(128, 6)
 
 
+def test_kernel_timing_counts_every_launch_past_its_first_pool(gpu_ctx, oracle):
+    """The event pool of the kernel timing starts at 512 events, 256 launches, and doubles when a pair does not fit: 300 timed launches of an 8 x 8 tile
+    on one stream are all in the sum, and a read-out empties the count."""
+    import math
+
+    import torch
+    sun = (1, 1, 0)
+    gpu_ctx.set_march(16, 2)
+    try:
+        gpu_ctx.render_sky_lut(norm(sun), 200, 100)
+        p = oracle.default_params(64, 32, sun)
+        out = torch.zeros((8, 8, 4), dtype=torch.int16, device="cuda")
+        stream = torch.cuda.Stream()
+        gpu_ctx.set_kernel_timing(True)
+        for _ in range(300):
+            gpu_ctx.render_clouds_device(p, 8, (8, 0, 1, 1), out.data_ptr(), 8 * 8, stream.cuda_stream)
+        ms, n = gpu_ctx.kernel_ms()
+        assert n == 300 and math.isfinite(ms) and ms > 0.0, (n, ms)
+        assert gpu_ctx.kernel_ms()[1] == 0
+        torch.cuda.synchronize()
+    finally:
+        gpu_ctx.set_kernel_timing(False)
+        gpu_ctx.set_march(128, 6)
+
+
 def test_stratus_only_weather_map(pkg, noise, oracle, o_trans):
     """Cloud-type channel below 0.5 everywhere: the 'all low' frame-wide specialisation of the height gradient (ct_mode 2) vs the
     oracle, and bit-identical to the general form (csky_set_height_window(0) switches the exact specialisations off)."""

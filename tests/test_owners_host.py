@@ -76,3 +76,29 @@ def test_the_context_stream_dies_last(report):
 def test_an_empty_context_releases_nothing(report):
     _, _, figures = report
     assert int(one(figures, "empty_context_calls")) == 0
+
+
+def test_order_tables_grow_together_after_one_device_wide_wait(report):
+    _, _, figures = report
+    # tables of 8, 8, 64, 8, 8, 8, 8, 8 entries, every key recorded, grown to 32 by the ring's own code (context.h FrameRing::grow_order_tables)
+    assert int(one(figures, "order_growth_device_syncs")) == 1
+    assert int(one(figures, "order_growth_calls_in_order")) == 1           # the wait first, then seven times hipFree before hipMalloc
+    assert int(one(figures, "order_growth_allocations_of_32")) == 7
+    assert int(one(figures, "order_growth_keys_forgotten")) == 7
+    assert int(one(figures, "order_growth_large_table_kept")) == 1         # the 64-entry table keeps its memory and its key
+
+
+def test_a_failed_growth_of_the_timing_pool_is_all_or_nothing(report):
+    _, _, figures = report
+    # a pool of 4 events grown to 10 by the pool's own grow, the third new event refused
+    assert int(one(figures, "pool_growth_failure_is_error")) == 1
+    assert int(one(figures, "pool_growth_failure_size")) == 4
+    assert int(one(figures, "pool_growth_failure_events_made")) == 2
+    assert int(one(figures, "pool_growth_failure_events_released")) == 2
+    assert "hipEventCreate" in one(figures, "pool_growth_failure_error_text")
+
+
+def test_the_timing_pool_starts_at_512_events_and_doubles(report):
+    _, _, figures = report
+    assert int(one(figures, "pool_events_after_256_pairs")) == 512
+    assert int(one(figures, "pool_events_after_257_pairs")) == 1024
