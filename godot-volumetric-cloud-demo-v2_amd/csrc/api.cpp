@@ -123,100 +123,95 @@ void csky_destroy(csky_ctx* c) {
     delete c;                                                  // every member releases what it owns (context.h)
 }
 
-static int set_noise_impl(csky_ctx* c, const uint8_t* large_rgba8, const uint8_t* small_rgb8, const uint8_t* weather_rgb8, bool chains_given) {
+#ifdef CSKY_BRICK_BOUND
+static int upload_brick_bounds(csky_ctx* c, const uint8_t* large_rgba8) {
+    // per 8^3 brick (+1 apron on the high side, REPEAT): bmax = (rmax + 1 - fmin) / (2 - fmin), a hair above (the kernel's rcp is approximate)
+    std::vector<float> tab(16 * 16 * 16);
+    for (int bz = 0; bz < 16; bz++) for (int by = 0; by < 16; by++) for (int bx = 0; bx < 16; bx++) {
+        int rm = 0, fm = 1 << 30;
+        for (int z = bz * 8; z <= bz * 8 + 8; z++) for (int y = by * 8; y <= by * 8 + 8; y++) for (int x = bx * 8; x <= bx * 8 + 8; x++) {
+            const uint8_t* tx = large_rgba8 + ((((size_t)(z & 127) * 128 + (y & 127)) * 128 + (x & 127)) * 4);
+            rm = std::max(rm, (int)tx[0]); fm = std::min(fm, 5 * tx[1] + 2 * tx[2] + tx[3]);
+        }
+        const float r = rm * (1.0f / 255.0f), f = fm * (1.0f / (8.0f * 255.0f));
+        tab[((size_t)bz * 16 + by) * 16 + bx] = (r + (1.0f - f)) / (2.0f - f) * 1.000004f;
+    }
+    if (const int rc = c->noise.d_brick.grow(c, tab.size())) return rc;
+    HIPCHK(c, hipMemcpy(c->noise.d_brick, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+    return CSKY_OK;
+}
+#endif
+
+// The steps of a bind and what each leaves the context knowing: NoiseHeld (noise_set.h), which also has every size used here.
+static int set_noise(csky_ctx* c, const uint8_t* large_rgba8, const uint8_t* small_rgb8, const uint8_t* weather_rgb8, bool chains_given) {
     if (!c) return fail(nullptr, CSKY_ERR_INVALID, "csky_set_noise: ctx is NULL");
     if (!large_rgba8 || !small_rgb8 || !weather_rgb8) return fail(c, CSKY_ERR_INVALID, "csky_set_noise: NULL texture pointer");
     int rc; if ((rc = bind(c))) return rc;
+    // the kernels' level offsets (cloud_core.h: closed forms shared with device code, not constexpr) are those of the chains as allocated and baked
+    for (int l = 0; l < SHAPE_LEVELS; l++) if (chain_texels(SHAPE_N, l) != shape_level_offset(l)) return fail(c, CSKY_ERR_INVALID, "internal: shape mip offset mismatch");
+    for (int l = 0; l < DETAIL_LEVELS; l++) if (chain_texels(DETAIL_N, l) != detail_level_offset(l)) return fail(c, CSKY_ERR_INVALID, "internal: detail mip offset mismatch");
+    HIPCHK(c, hipDeviceSynchronize());                        // frames reading the old textures may be in flight on caller streams
+    NoiseSet& n = c->noise;
+    n.st.begin_rebind();                                      // a failure below leaves freed / half-baked textures: no render until a later call reaches ready()
+    if ((rc = n.d_raw_large.alloc(c, RAW_SHAPE_CHAIN)) || (rc = n.d_raw_small.alloc(c, RAW_DETAIL_CHAIN)) || (rc = n.d_raw_weather.alloc(c, RAW_WEATHER))) return rc;
+    if ((rc = n.d_shape.alloc(c, SHAPE_CELLS)) || (rc = n.d_detail.alloc(c, DETAIL_CELLS)) || (rc = n.d_weather.alloc(c, WEATHER_CELLS))) return rc;
+    if ((rc = n.d_detail_h.alloc(c, DETAIL_H_HALFS)) || (rc = n.d_bake_meta.grow(c, 32))) return rc;
     // The level-0 textures go to the device as they are (9.2 MB); mip chains (mipmaps/generate=true, perlworlnoise.tga.import:24,
     // worlnoise.bmp.import:24) and the device layouts are built there (bake_kernels.hip::launch_mip_chain / launch_bake).
-    const size_t large_l0 = (size_t)SHAPE_N * SHAPE_N * SHAPE_N * 4, small_l0 = (size_t)DETAIL_N * DETAIL_N * DETAIL_N * 3, weather_b = (size_t)WEATHER_N * WEATHER_N * 3;
-    const size_t large_chain = chain_offset(SHAPE_N, SHAPE_LEVELS, 4), small_chain = chain_offset(DETAIL_N, DETAIL_LEVELS, 3);
-    size_t shape_total = 0, detail_total = 0;
-    for (int l = 0; l < SHAPE_LEVELS; l++) { c->shape_off[l] = (uint32_t)shape_total; const size_t n = SHAPE_N >> l; shape_total += n * n * n; }
-    for (int l = 0; l < DETAIL_LEVELS; l++) { c->detail_off[l] = (uint32_t)detail_total; const size_t n = DETAIL_N >> l; detail_total += n * n * n; }
-    for (int l = 0; l < SHAPE_LEVELS; l++) if (c->shape_off[l] != shape_level_offset(l)) return fail(c, CSKY_ERR_INVALID, "internal: shape mip offset mismatch");
-    for (int l = 0; l < DETAIL_LEVELS; l++) if (c->detail_off[l] != detail_level_offset(l)) return fail(c, CSKY_ERR_INVALID, "internal: detail mip offset mismatch");
-    if (detail_total != (size_t)DETAIL_CHAIN_TEXELS) return fail(c, CSKY_ERR_INVALID, "internal: detail chain size");
-    HIPCHK(c, hipDeviceSynchronize());                        // frames reading the old textures may be in flight on caller streams
-    c->have_noise = false; c->win_cov = -1e30f;               // a failure below leaves freed / half-baked textures: no render until a later call succeeds
-    if ((rc = c->d_raw_large.alloc(c, large_chain)) || (rc = c->d_raw_small.alloc(c, small_chain)) || (rc = c->d_raw_weather.alloc(c, weather_b))) return rc;
-    if ((rc = c->d_shape.alloc(c, shape_total)) || (rc = c->d_detail.alloc(c, detail_total)) || (rc = c->d_weather.alloc(c, (size_t)WEATHER_N * WEATHER_N))) return rc;
-    if ((rc = c->d_detail_h.alloc(c, detail_total + 8)) || (rc = c->d_bake_meta.grow(c, 32))) return rc;
-    struct { unsigned long long inexact; int range[3]; int pad; } meta = {0ull, {255, 0, 0}, 0};
+    struct { unsigned long long inexact; int range[3]; int pad; } meta = {0ull, {255, 0, 0}, 0};   // the bake's counters: min R, max R, max B of the weather map
     hipStream_t s = c->stream;
-    HIPCHK(c, hipMemcpyAsync(c->d_bake_meta, &meta, sizeof meta, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(c->d_raw_large, large_rgba8, chains_given ? large_chain : large_l0, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(c->d_raw_small, small_rgb8, chains_given ? small_chain : small_l0, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(c->d_raw_weather, weather_rgb8, weather_b, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(n.d_bake_meta, &meta, sizeof meta, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(n.d_raw_large, large_rgba8, chains_given ? RAW_SHAPE_CHAIN : RAW_SHAPE_L0, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(n.d_raw_small, small_rgb8, chains_given ? RAW_DETAIL_CHAIN : RAW_DETAIL_L0, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(n.d_raw_weather, weather_rgb8, RAW_WEATHER, hipMemcpyHostToDevice, s));
     if (!chains_given) {                                      // csky_set_noise_mips: the caller's chains (e.g. the importer's own, csky_load_ctex3d) are used as they are
-        HIPCHK(c, launch_mip_chain(c->d_raw_large, SHAPE_N, 4, SHAPE_LEVELS, s));
-        HIPCHK(c, launch_mip_chain(c->d_raw_small, DETAIL_N, 3, DETAIL_LEVELS, s));
+        HIPCHK(c, launch_mip_chain(n.d_raw_large, SHAPE_N, 4, SHAPE_LEVELS, s));
+        HIPCHK(c, launch_mip_chain(n.d_raw_small, DETAIL_N, 3, DETAIL_LEVELS, s));
     }
-    HIPCHK(c, launch_bake(c->d_raw_large, c->d_raw_small, c->d_raw_weather, c->d_shape, c->d_detail, c->d_detail_h, c->d_weather,
-                          reinterpret_cast<unsigned long long*>(c->d_bake_meta.get()), reinterpret_cast<int*>(c->d_bake_meta + 8), s));
+    HIPCHK(c, launch_bake(n.d_raw_large, n.d_raw_small, n.d_raw_weather, n.d_shape, n.d_detail, n.d_detail_h, n.d_weather,
+                          reinterpret_cast<unsigned long long*>(n.d_bake_meta.get()), reinterpret_cast<int*>(n.d_bake_meta + 8), s));
 #ifdef CSKY_BRICK_BOUND
-    {   // per 8^3 brick (+1 apron on the high side, REPEAT): bmax = (rmax + 1 - fmin) / (2 - fmin), a hair above (the kernel's rcp is approximate)
-        std::vector<float> tab(16 * 16 * 16);
-        for (int bz = 0; bz < 16; bz++) for (int by = 0; by < 16; by++) for (int bx = 0; bx < 16; bx++) {
-            int rm = 0, fm = 1 << 30;
-            for (int z = bz * 8; z <= bz * 8 + 8; z++) for (int y = by * 8; y <= by * 8 + 8; y++) for (int x = bx * 8; x <= bx * 8 + 8; x++) {
-                const uint8_t* tx = large_rgba8 + ((((size_t)(z & 127) * 128 + (y & 127)) * 128 + (x & 127)) * 4);
-                rm = std::max(rm, (int)tx[0]); fm = std::min(fm, 5 * tx[1] + 2 * tx[2] + tx[3]);
-            }
-            const float r = rm * (1.0f / 255.0f), f = fm * (1.0f / (8.0f * 255.0f));
-            tab[((size_t)bz * 16 + by) * 16 + bx] = (r + (1.0f - f)) / (2.0f - f) * 1.000004f;
-        }
-        if ((rc = c->d_brick.grow(c, tab.size()))) return rc;
-        HIPCHK(c, hipMemcpy(c->d_brick, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
+    if ((rc = upload_brick_bounds(c, large_rgba8))) return rc;
 #endif
-    uint8_t t5[3] = {0, 0, 0};                                // detail LOD 5 is one texel: every tap at that level returns it (cloud_core.h::detail_tap)
-    HIPCHK(c, hipMemcpyAsync(&meta, c->d_bake_meta, sizeof meta, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(t5, c->d_raw_small + chain_offset(DETAIL_N, 5, 3), 3, hipMemcpyDeviceToHost, s));
+    uint8_t t5[3] = {0, 0, 0};
+    HIPCHK(c, hipMemcpyAsync(&meta, n.d_bake_meta, sizeof meta, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(t5, n.d_raw_small + RAW_DETAIL_LOD5, 3, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
-    c->inexact_coeffs = meta.inexact;
-    c->detail_lod5 = (float)(5 * t5[0] + 2 * t5[1] + t5[2]) * (1.0f / (8.0f * 255.0f));
-    c->w_rmin = meta.range[0] / 255.0; c->w_rmax = meta.range[1] / 255.0; c->w_bmax = meta.range[2] / 255.0; c->win_cov = -1e30f;   // channel ranges for the height-window reject
     c->warn[0] = 0;
-    // Textures whose cells do not fit fp16 (white noise, checkerboards: csky_noise_inexact_coeffs() > 0) are marched on EXACT cells: the same
-    // polynomial with fp32 coefficients (bake_core.h), twice the bytes per tap, the compact whole-ray kernel on TexSet32.  (Rounds 1-3 marched
-    // them on the rounded fp16 cells and warned)  csky_set_exact_cells(1) asks for them regardless (A/B, tests).
-    c->cell32 = c->inexact_coeffs != 0 || c->exact_cells == 1;
-    if (c->cell32) {
-        if ((rc = c->d_shape32.alloc(c, shape_total * 4)) || (rc = c->d_detail32.alloc(c, detail_total * 2)) || (rc = c->d_weather32.alloc(c, (size_t)WEATHER_N * WEATHER_N * 2))) return rc;
-        HIPCHK(c, launch_bake32(c->d_raw_large, c->d_raw_small, c->d_raw_weather, c->d_shape32, c->d_detail32, c->d_weather32, s));
+    if (n.st.bound(meta.inexact, WeatherRange{meta.range[0], meta.range[1], meta.range[2]}, detail_lod5_value(t5))) {
+        if ((rc = n.d_shape32.alloc(c, SHAPE32_F4)) || (rc = n.d_detail32.alloc(c, DETAIL32_F4)) || (rc = n.d_weather32.alloc(c, WEATHER32_F4))) return rc;
+        HIPCHK(c, launch_bake32(n.d_raw_large, n.d_raw_small, n.d_raw_weather, n.d_shape32, n.d_detail32, n.d_weather32, s));
         HIPCHK(c, hipStreamSynchronize(s));
-        if (c->inexact_coeffs)
+        if (n.st.inexact())   // (rounds 1-3 marched such textures on the rounded fp16 cells and warned)
             snprintf(c->warn, sizeof c->warn, "csky_set_noise: %llu finite-difference coefficients of these textures do not fit fp16: marching on exact fp32 cells "
-                     "(twice the bytes per tap; the whole-ray compact kernel)", c->inexact_coeffs);
+                     "(twice the bytes per tap; the whole-ray compact kernel)", n.st.inexact());
     } else {
         // textures that fit fp16 again: the ~150 MB of exact cells of an earlier bind are not kept until csky_destroy (nothing is in flight: the device was synchronised above)
-        c->d_shape32.reset(); c->d_detail32.reset(); c->d_weather32.reset();
+        n.d_shape32.reset(); n.d_detail32.reset(); n.d_weather32.reset();
     }
-    c->have_noise = true;
+    n.st.ready();
     return CSKY_OK;
 }
 
 int csky_set_noise(csky_ctx* c, const uint8_t* large_rgba8, const uint8_t* small_rgb8, const uint8_t* weather_rgb8) {
-    return set_noise_impl(c, large_rgba8, small_rgb8, weather_rgb8, false);
+    return set_noise(c, large_rgba8, small_rgb8, weather_rgb8, false);
 }
 int csky_set_noise_mips(csky_ctx* c, const uint8_t* large_chain_rgba8, const uint8_t* small_chain_rgb8, const uint8_t* weather_rgb8) {
-    return set_noise_impl(c, large_chain_rgba8, small_chain_rgb8, weather_rgb8, true);
+    return set_noise(c, large_chain_rgba8, small_chain_rgb8, weather_rgb8, true);
 }
 
 int csky_read_baked_texture(csky_ctx* c, int which, void* out, size_t capacity, size_t* bytes) {
     if (!c || !bytes) return fail(c, CSKY_ERR_INVALID, "csky_read_baked_texture: NULL argument");
-    if (!c->have_noise) return fail(c, CSKY_ERR_STATE, "csky_read_baked_texture: csky_set_noise has not been called");
+    if (!c->noise.st.have()) return fail(c, CSKY_ERR_STATE, "csky_read_baked_texture: csky_set_noise has not been called");
     int rc; if ((rc = bind(c))) return rc;
-    size_t shape_total = 0;
-    for (int l = 0; l < SHAPE_LEVELS; l++) { const size_t n = SHAPE_N >> l; shape_total += n * n * n; }
+    const NoiseSet& ns = c->noise;
     const void* src = nullptr; size_t n = 0;
     switch (which) {
-        case 0: src = c->d_shape; n = shape_total * sizeof(ShapeTexel); break;
-        case 1: src = c->d_detail; n = (size_t)DETAIL_CHAIN_TEXELS * sizeof(uint4); break;
-        case 2: src = c->d_weather; n = (size_t)WEATHER_N * WEATHER_N * sizeof(uint4); break;
-        case 3: src = c->d_raw_large; n = chain_offset(SHAPE_N, SHAPE_LEVELS, 4); break;
-        case 4: src = c->d_raw_small; n = chain_offset(DETAIL_N, DETAIL_LEVELS, 3); break;
+        case 0: src = ns.d_shape; n = SHAPE_CELLS * sizeof(ShapeTexel); break;
+        case 1: src = ns.d_detail; n = DETAIL_CELLS * sizeof(uint4); break;
+        case 2: src = ns.d_weather; n = WEATHER_CELLS * sizeof(uint4); break;
+        case 3: src = ns.d_raw_large; n = RAW_SHAPE_CHAIN; break;
+        case 4: src = ns.d_raw_small; n = RAW_DETAIL_CHAIN; break;
         default: return fail(c, CSKY_ERR_INVALID, "csky_read_baked_texture: which must be 0..4");
     }
     *bytes = n;
@@ -337,8 +332,8 @@ int csky_encode_bc7_quality(csky_ctx* c, const uint8_t* rgba8, int w, int h, int
 
 int csky_noise_inexact_coeffs(csky_ctx* c, uint64_t* n) {
     if (!c || !n) return CSKY_ERR_INVALID;
-    if (!c->have_noise) return fail(c, CSKY_ERR_STATE, "csky_noise_inexact_coeffs: csky_set_noise has not been called");
-    *n = (uint64_t)c->inexact_coeffs;
+    if (!c->noise.st.have()) return fail(c, CSKY_ERR_STATE, "csky_noise_inexact_coeffs: csky_set_noise has not been called");
+    *n = (uint64_t)c->noise.st.inexact();
     return CSKY_OK;
 }
 
@@ -393,7 +388,7 @@ int csky_set_segments(csky_ctx* c, int segments) {
 int csky_set_exact_cells(csky_ctx* c, int mode) {
     if (!c) return fail(nullptr, CSKY_ERR_INVALID, "csky_set_exact_cells: ctx is NULL");
     if (mode != 0 && mode != 1) return fail(c, CSKY_ERR_INVALID, "csky_set_exact_cells: 0 (only when a coefficient does not fit fp16) or 1 (always)");
-    c->exact_cells = mode; return CSKY_OK;                     // takes effect at the next csky_set_noise*
+    c->noise.st.request_exact(mode); return CSKY_OK;           // takes effect at the next csky_set_noise*
 }
 int csky_set_height_window(csky_ctx* c, int enabled) {
     if (!c) return fail(nullptr, CSKY_ERR_INVALID, "csky_set_height_window: ctx is NULL");

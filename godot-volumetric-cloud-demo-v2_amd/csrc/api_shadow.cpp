@@ -24,23 +24,22 @@ int shadow_check(csky_ctx* c, const char* fn, const csky_cloud_params* p, const 
                           cp.LIGHT_DIRECTION[0], cp.LIGHT_DIRECTION[1], cp.LIGHT_DIRECTION[2], cp.time, cp.density, cp.cloud_coverage};
     for (float v : read) if (!std::isfinite(v)) return fail(c, CSKY_ERR_INVALID, "%s: a push-constant field the shadow map reads is not finite", fn);
     if (pitch_bytes < (size_t)sp->width * 2 || pitch_bytes % 2) return fail(c, CSKY_ERR_INVALID, "%s: row pitch must be even and >= 2 * width", fn);
-    if (!c->have_noise) return fail(c, CSKY_ERR_STATE, "%s: csky_set_noise has not been called", fn);
+    if (!c->noise.st.have()) return fail(c, CSKY_ERR_STATE, "%s: csky_set_noise has not been called", fn);
     return CSKY_OK;
 }
 
 // The launch on stream s, for arguments shadow_check has passed.
 int shadow_launch(csky_ctx* c, const char* fn, const csky_cloud_params* p, const csky_shadow_params* sp, uint16_t* d_out, size_t pitch_bytes, hipStream_t s) {
     CloudParams cp; memcpy(&cp, p, sizeof cp);
-    float lo, hi; int ctm;
-    exact_rejects(c, cp.cloud_coverage, lo, hi, ctm);   // the height window and the cloud-type branch, as the cloud march gets them
+    const ExactRejects rej = c->noise.st.rejects(cp.cloud_coverage, c->use_window);   // the height window and the cloud-type branch, as the cloud march gets them
     ShadowConsts sc;
     sc.w = sp->width; sc.h = sp->height; sc.cx = sp->center[0]; sc.cz = sp->center[1]; sc.ex = sp->extent[0]; sc.ez = sp->extent[1];
     sc.steps = sp->steps == 0 ? 64 : sp->steps; sc.exact_end = c->shadow_exact_end ? 1 : 0; sc.pitch_h = (uint32_t)(pitch_bytes / 2);
     FrameConsts fc;
-    shadow_frame_consts(cp, sc.steps, lo, hi, ctm, fc);
+    shadow_frame_consts(cp, sc.steps, rej.hf_lo, rej.hf_hi, rej.ct_mode, fc);
     sc.night = fc.ldir[1] > 0.0f ? 0 : 1;               // l.y <= 0; a zero LIGHT_DIRECTION (no direction: l is NaN) counts as night too
     TexSet32 t32; const TexSet32* t32p = nullptr;
-    if (c->cell32) { t32 = texset32(c); t32p = &t32; }
+    if (c->noise.st.cell32()) { t32 = texset32(c); t32p = &t32; }
     const hipError_t e = launch_cloud_shadow(texset(c), t32p, fc, sc, d_out, s);
     if (e != hipSuccess) return fail(c, CSKY_ERR_HIP, "%s: kernel launch failed: %s", fn, hipGetErrorString(e));
     return CSKY_OK;

@@ -4,25 +4,25 @@
 // (FrameRing); when a cached order may be used is frame_ring.h's.
 #include <cstring>
 #include "context.h"
-#include "bake.h"
 #include "launch_policy.h"
 #include "order_core.h"
 
 namespace csky {
 
 TexSet texset(const csky_ctx* c) {
+    const NoiseSet& n = c->noise;
     TexSet t;
 #ifdef CSKY_BRICK_BOUND
-    t.brick = c->d_brick;
+    t.brick = n.d_brick;
 #endif
-    t.shape = c->d_shape; t.detail = c->d_detail; t.weather = c->d_weather; t.sky = c->lut.cur_f(); t.sky_w = c->lut.aw; t.sky_h = c->lut.ah; t.detail_lod5 = c->detail_lod5; t.detail_h = c->d_detail_h; t.detail_lds = nullptr;
+    t.shape = n.d_shape; t.detail = n.d_detail; t.weather = n.d_weather; t.sky = c->lut.cur_f(); t.sky_w = c->lut.aw; t.sky_h = c->lut.ah; t.detail_lod5 = n.st.detail_lod5(); t.detail_h = n.d_detail_h; t.detail_lds = nullptr;
     return t;
 }
 
 TexSet32 texset32(const csky_ctx* c) {
     TexSet32 t;
     static_cast<TexSet&>(t) = texset(c);
-    t.shape32 = c->d_shape32; t.detail32 = c->d_detail32; t.weather32 = c->d_weather32;
+    t.shape32 = c->noise.d_shape32; t.detail32 = c->noise.d_detail32; t.weather32 = c->noise.d_weather32;
     return t;
 }
 
@@ -47,10 +47,9 @@ int ensure_order(csky_ctx* c, int slot, int mode, int tiles_x, int slabs, hipStr
 
 // Frame set-up on the context's stream (beside the caller's: context.h) into the next slot of the ring; the launch stream s waits for it.
 int frame_setup(csky_ctx* c, const CloudParams& cp, hipStream_t s) {
-    float lo, hi; int ctm;
-    exact_rejects(c, cp.cloud_coverage, lo, hi, ctm);
+    const ExactRejects rej = c->noise.st.rejects(cp.cloud_coverage, c->use_window);
     int f, rc; if ((rc = c->ring.next_slot(c, c->stream, f))) return rc;
-    const SetupArgs sa = {c->primary_steps, c->light_steps, c->early_eps, lo, hi, ctm, c->use_window ? 1 : 0};
+    const SetupArgs sa = {c->primary_steps, c->light_steps, c->early_eps, rej.hf_lo, rej.hf_hi, rej.ct_mode, c->use_window ? 1 : 0};
     const SkyLut& l = c->lut;
     if (l.st.own_taps())                             // the set-up renders the texels of its three taps (clouds.glsl:163-167) itself
         HIPCHK(c, launch_frame_setup_taps(cp, l.st.sun, c->d_trans_f, c->tw, c->th, l.st.w, l.st.h, sa, c->ring.slot[f].fc, c->stream, c->tlut));
@@ -61,16 +60,6 @@ int frame_setup(csky_ctx* c, const CloudParams& cp, hipStream_t s) {
 
 }  // namespace
 
-void exact_rejects(csky_ctx* c, float coverage, float& hf_lo, float& hf_hi, int& ct_mode) {
-    if (c->win_cov != coverage) {                       // height window of the exact reject (bake.h), cached per coverage value
-        height_window((double)coverage, c->w_rmin, c->w_rmax, c->w_bmax, c->win_lo, c->win_hi);
-        c->win_cov = coverage;
-    }
-    hf_lo = c->use_window ? c->win_lo : -1.0f; hf_hi = c->use_window ? c->win_hi : 2.0f;
-    // cloud-type range of the weather map (texel values 0..255): all >= 128 or all <= 127 fixes the branch of the height gradient
-    ct_mode = !c->use_window ? 0 : (c->w_rmin * 255.0 >= 127.5 ? 1 : (c->w_rmax * 255.0 <= 127.5 ? 2 : 0));
-}
-
 int check_bands(csky_ctx* c, const csky_bands* b, int tile_w) {
     if (tile_w < 1 || !b || b->band_rows < 1 || b->n_bands < 0 || b->first_band < 0 || b->band_stride < 1)
         return fail(c, CSKY_ERR_INVALID, "render_clouds: bad tile/bands description");
@@ -80,7 +69,7 @@ int check_bands(csky_ctx* c, const csky_bands* b, int tile_w) {
 int clouds_dev(csky_ctx* c, const csky_cloud_params* p, int tile_w, const csky_bands* b, uint2* d_out, size_t pitch_bytes, hipStream_t s,
                unsigned long long* d_stats, bool setup, bool out_full) {
     if (!p) return fail(c, CSKY_ERR_INVALID, "render_clouds: params is NULL");
-    if (!c->have_noise) return fail(c, CSKY_ERR_STATE, "render_clouds: csky_set_noise has not been called");
+    if (!c->noise.st.have()) return fail(c, CSKY_ERR_STATE, "render_clouds: csky_set_noise has not been called");
     if (c->lut.st.holds == SkyLutHolds::None) return fail(c, CSKY_ERR_STATE, "render_clouds: no sky LUT yet (call csky_render_sky_lut first; cloud_sky.gd:187,242)");
     if (!(p->texture_size[0] >= 1.0f) || !(p->texture_size[1] >= 1.0f)) return fail(c, CSKY_ERR_INVALID, "render_clouds: texture_size must be >= 1");
     int rc; if ((rc = check_bands(c, b, tile_w))) return rc;
@@ -93,13 +82,13 @@ int clouds_dev(csky_ctx* c, const csky_cloud_params* p, int tile_w, const csky_b
     const long long waves = ((long long)(tile_w + 7) / 8) * (((long long)b->n_bands * b->band_rows + 7) / 8);
     // the policy is told how many frames CAN overlap (csky_set_frames_in_flight): where the hardware queues cannot keep the frames' streams apart the launches
     // run one after the other, and the forms chosen for overlapping launches (the persistent one above all) are the slower ones alone
-    const LaunchPlan pl = plan_launch({c->variant, c->cell32, c->segments, c->sched_mode, c->frames_overlapping, c->persistent}, waves);
+    const LaunchPlan pl = plan_launch({c->variant, c->noise.st.cell32(), c->segments, c->sched_mode, c->frames_overlapping, c->persistent}, waves);
     const int tiles_x = (g.tile_w + pl.bw - 1) / pl.bw, slabs = (g.n_bands * g.band_rows + 7) >> 3, nblocks = tiles_x * slabs;
     FrameRing& ring = c->ring;
     const int slot = ring.cur;                                   // without set-up (the warm-up and timed launches of csky_time_clouds): the current slot again
     uint32_t* const heads = pl.persist ? ring.heads(slot) : nullptr;
     TexSet32 t32; const TexSet32* t32p = nullptr;
-    if (c->cell32) { t32 = texset32(c); t32p = &t32; }
+    if (c->noise.st.cell32()) { t32 = texset32(c); t32p = &t32; }
     // timing pair of this launch (csky_set_kernel_timing).  Taken BEFORE the order table on purpose: next_pair may create events and may fail, and
     // either after ensure_order would change the order of the HIP calls a launch makes
     const Event* kt = nullptr;

@@ -18,6 +18,7 @@
 #include "kernels.h"
 #include "owners.h"
 #include "frame_ring.h"
+#include "noise_set.h"
 #include "sky_lut_reuse.h"
 
 // Depth of the per-frame rings (frame constants, launch order, cost feedback, pop counters, events): the number of frames a caller may keep
@@ -50,6 +51,17 @@ struct SkyLut {
     // slot k has been rendered into: readers use it from here on.  (The caller names what it holds: st.became_whole / st.became_shared.)
     void publish(int k) { cur = k; writers.clear(); }
     void drop() { st.drop(); writers.clear(); }
+};
+
+// The bound noise set (csky_set_noise*; cloud_sky.gd:298-341): what the context knows about it (noise_set.h: the state, its steps and every size)
+// and the memory it is held in.
+struct NoiseSet {
+    NoiseHeld st;
+    DevBuf<uint8_t> d_raw_large, d_raw_small, d_raw_weather, d_bake_meta;   // 8-bit mip chains (inputs of the device bake) and the bake's counters
+    DevBuf<ShapeTexel> d_shape; DevBuf<uint4> d_detail, d_weather; DevBuf<uint16_t> d_detail_h;   // fp16-pair cells
+    DevBuf<float> d_brick;                                                  // CSKY_BRICK_BOUND experiment build only
+    // exact cells (bake_core.h): fp32-coefficient layouts, held while st.cell32()
+    DevBuf<float4> d_shape32, d_detail32, d_weather32;
 };
 
 // csky_render_sky_lut_rows_device: the compact rows of st.rows_key, copied behind the kernel that rendered them into a caller's buffer; a call with
@@ -194,16 +206,8 @@ struct csky_ctx {
     // after the other (profiles/r11/queue_overlap_ab.txt); with one, the four queues go round.
     csky::Stream stream;
     csky::Event ev0, ev1, ev_copy;
-    // noise set (cloud_sky.gd:298-341)
-    csky::DevBuf<uint8_t> d_raw_large, d_raw_small, d_raw_weather, d_bake_meta;   // 8-bit mip chains (inputs of the device bake)
-    csky::DevBuf<csky::ShapeTexel> d_shape; unsigned long long inexact_coeffs = 0; csky::DevBuf<uint4> d_detail, d_weather; csky::DevBuf<uint16_t> d_detail_h; bool have_noise = false;
-    csky::DevBuf<float> d_brick;                                            // CSKY_BRICK_BOUND experiment build only
-    // exact cells (bake_core.h): fp32-coefficient layouts, built when a coefficient of the bound textures does not fit fp16 (or exact_cells == 1)
-    csky::DevBuf<float4> d_shape32, d_detail32, d_weather32; bool cell32 = false; int exact_cells = 0;
-    uint32_t shape_off[csky::SHAPE_LEVELS] = {}, detail_off[csky::DETAIL_LEVELS] = {};
-    float detail_lod5 = 0.0f;
-    double w_rmin = 0.0, w_rmax = 1.0, w_bmax = 1.0;   // range of the weather map's cloud-type / coverage channels
-    float win_cov = -1e30f, win_lo = -1.0f, win_hi = 2.0f; bool use_window = true;
+    csky::NoiseSet noise;
+    bool use_window = true;                           // csky_set_height_window: the exact rejects of a density sample (noise_set.h)
     // LUTs: RGBA16F image + float4 copy of the rounded values
     csky::DevBuf<uint16_t> d_trans_h; csky::DevBuf<float4> d_trans_f; int tw = 0, th = 0; bool have_trans = false;
     int tlut = CSKY_TLUT_REFERENCE;                   // the transmittance LUT's parametrization (csky_set_transmittance_mapping, tlut_core.h): its writer and every reader get it
@@ -264,9 +268,6 @@ int lut_size(csky_ctx* c, const char* fn, const float texture_size[2], int& w, i
 // clouds_launch.cpp
 TexSet texset(const csky_ctx* c);       // the bound textures as the kernels take them: fp16-pair cells, and the exact fp32 cells of a context in that mode
 TexSet32 texset32(const csky_ctx* c);
-// what the exact specialisations of a density sample take for this coverage (csky_set_height_window switches them together): the height window
-// outside which density() is 0 for the bound weather map, and FrameConsts::ct_mode
-void exact_rejects(csky_ctx* c, float coverage, float& hf_lo, float& hf_hi, int& ct_mode);
 int check_bands(csky_ctx* c, const csky_bands* b, int tile_w);
 // frame set-up (when `setup`) + the cloud kernel on stream s into d_out.  d_stats: optional device counters.
 int clouds_dev(csky_ctx* c, const csky_cloud_params* p, int tile_w, const csky_bands* b, uint2* d_out, size_t pitch_bytes, hipStream_t s,

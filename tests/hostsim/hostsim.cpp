@@ -8,7 +8,7 @@
 #include <vector>
 #include "../../godot-volumetric-cloud-demo-v2_amd/csrc/cloud_core.h"
 #include "../../godot-volumetric-cloud-demo-v2_amd/csrc/lut_core.h"
-#include "../../godot-volumetric-cloud-demo-v2_amd/csrc/bake.h"
+#include "../../godot-volumetric-cloud-demo-v2_amd/csrc/noise_set.h"
 #include "../../godot-volumetric-cloud-demo-v2_amd/csrc/composite_core.h"
 #include "../../godot-volumetric-cloud-demo-v2_amd/csrc/bc7enc_core.h"
 #include "../../godot-volumetric-cloud-demo-v2_amd/csrc/bc7_tables.h"
@@ -45,11 +45,11 @@ void hostsim_sky(int w, int h, const float sun[3], const uint16_t* trans_h, int 
 // mip chains (level 0 first) -> baked layouts -> march every pixel of the band set, like clouds_kernel does.
 // number of fp16-inexact polynomial-cell coefficients of a texture set (bake.h), and the shape cell rank this build uses
 unsigned long long hostsim_inexact_coeffs(const uint8_t* large_chain, const uint8_t* small_chain, const uint8_t* weather_rgb8) {
-    std::vector<uint8_t> lc(large_chain, large_chain + csky_mip_offset(SHAPE_N, SHAPE_LEVELS, 4));
-    std::vector<uint8_t> sc(small_chain, small_chain + csky_mip_offset(DETAIL_N, DETAIL_LEVELS, 3));
+    std::vector<uint8_t> lc(large_chain, large_chain + RAW_SHAPE_CHAIN);
+    std::vector<uint8_t> sc(small_chain, small_chain + RAW_DETAIL_CHAIN);
     std::vector<ShapeTexel> shape; std::vector<uint4> detail, weather;
-    uint32_t so[SHAPE_LEVELS], dof[DETAIL_LEVELS];
     unsigned long long n = 0;
+    uint32_t so[SHAPE_LEVELS], dof[DETAIL_LEVELS];
     bake_shape(lc, shape, so, &n); bake_detail(sc, detail, dof, &n); bake_weather(weather_rgb8, weather, &n);
     return n;
 }
@@ -57,11 +57,11 @@ int hostsim_shape_poly() { return CSKY_SHAPE_POLY; }
 // the HOST bake of the three device layouts (bake.h), for the byte comparison with what csky_set_noise bakes on the GPU.
 // which: 0 shape, 1 detail, 2 weather.  Returns the byte count; out may be NULL to query it.
 size_t hostsim_bake(const uint8_t* large_chain, const uint8_t* small_chain, const uint8_t* weather_rgb8, int which, uint8_t* out) {
-    std::vector<uint8_t> lc(large_chain, large_chain + csky_mip_offset(SHAPE_N, SHAPE_LEVELS, 4));
-    std::vector<uint8_t> sc(small_chain, small_chain + csky_mip_offset(DETAIL_N, DETAIL_LEVELS, 3));
+    std::vector<uint8_t> lc(large_chain, large_chain + RAW_SHAPE_CHAIN);
+    std::vector<uint8_t> sc(small_chain, small_chain + RAW_DETAIL_CHAIN);
     std::vector<ShapeTexel> shape; std::vector<uint4> detail, weather;
-    uint32_t so[SHAPE_LEVELS], dof[DETAIL_LEVELS];
     const void* src; size_t n;
+    uint32_t so[SHAPE_LEVELS], dof[DETAIL_LEVELS];
     if (which == 0) { bake_shape(lc, shape, so); src = shape.data(); n = shape.size() * sizeof(ShapeTexel); }
     else if (which == 1) { bake_detail(sc, detail, dof); src = detail.data(); n = detail.size() * sizeof(uint4); }
     else { bake_weather(weather_rgb8, weather); src = weather.data(); n = weather.size() * sizeof(uint4); }
@@ -72,33 +72,24 @@ size_t hostsim_bake(const uint8_t* large_chain, const uint8_t* small_chain, cons
 void hostsim_clouds(const uint8_t* large_chain, const uint8_t* small_chain, const uint8_t* weather_rgb8, const float params[28],
                     int primary_steps, int light_steps, float early_eps, const uint16_t* sky_h, int sw, int sh, int tile_w,
                     int band_rows, int first_band, int band_stride, int n_bands, uint16_t* out_h, uint64_t* incloud, int use_window, float* window_out, int use_lds_path) {
-    std::vector<uint8_t> lc(large_chain, large_chain + csky_mip_offset(SHAPE_N, SHAPE_LEVELS, 4));
-    std::vector<uint8_t> sc(small_chain, small_chain + csky_mip_offset(DETAIL_N, DETAIL_LEVELS, 3));
+    std::vector<uint8_t> lc(large_chain, large_chain + RAW_SHAPE_CHAIN);
+    std::vector<uint8_t> sc(small_chain, small_chain + RAW_DETAIL_CHAIN);
     std::vector<ShapeTexel> shape; std::vector<uint4> detail, weather;
     TexSet T;
-    uint32_t shape_off[SHAPE_LEVELS], detail_off[DETAIL_LEVELS];
-    bake_shape(lc, shape, shape_off); bake_detail(sc, detail, detail_off); bake_weather(weather_rgb8, weather);
+    uint32_t so[SHAPE_LEVELS], dof[DETAIL_LEVELS];
+    bake_shape(lc, shape, so); bake_detail(sc, detail, dof); bake_weather(weather_rgb8, weather);
     std::vector<float4> sky = widen(sky_h, sw, sh);
     T.shape = shape.data(); T.detail = detail.data(); T.weather = weather.data(); T.sky = sky.data(); T.sky_w = sw; T.sky_h = sh;
     std::vector<uint16_t> detail_h;
     bake_detail_unpacked(sc, detail_h);
     T.detail_h = detail_h.data(); T.detail_lds = use_lds_path ? detail_h.data() : nullptr;
-    { const uint8_t* t5 = sc.data() + csky_mip_offset(DETAIL_N, 5, 3); T.detail_lod5 = (float)(5 * t5[0] + 2 * t5[1] + t5[2]) * (1.0f / (8.0f * 255.0f)); }
+    T.detail_lod5 = detail_lod5_value(sc.data() + RAW_DETAIL_LOD5);
     CloudParams P; memcpy(&P, params, sizeof P);
     FrameConsts fc;
-    float hlo = -1.0f, hhi = 2.0f;
-    if (use_window) {
-        int rmin = 255, rmax = 0, bmax = 0;
-        for (size_t i = 0; i < (size_t)WEATHER_N * WEATHER_N; i++) { const int r = weather_rgb8[3 * i], b = weather_rgb8[3 * i + 2]; rmin = r < rmin ? r : rmin; rmax = r > rmax ? r : rmax; bmax = b > bmax ? b : bmax; }
-        height_window((double)P.cloud_coverage, rmin / 255.0, rmax / 255.0, bmax / 255.0, hlo, hhi);
-    }
-    if (window_out) { window_out[0] = hlo; window_out[1] = hhi; }
-    frame_setup(P, sky.data(), sw, sh, primary_steps, light_steps, early_eps, hlo, hhi, fc);
-    if (use_window) {                                        // like api.cpp: the exact specialisations are switched together
-        int rmin = 255, rmax = 0;
-        for (size_t i = 0; i < (size_t)WEATHER_N * WEATHER_N; i++) { const int r = weather_rgb8[3 * i]; rmin = r < rmin ? r : rmin; rmax = r > rmax ? r : rmax; }
-        fc.ct_mode = rmin >= 128 ? 1 : (rmax <= 127 ? 2 : 0);
-    }
+    const ExactRejects rej = exact_rejects(weather_range(weather_rgb8), P.cloud_coverage, use_window != 0);   // like api.cpp: the exact specialisations are switched together
+    if (window_out) { window_out[0] = rej.hf_lo; window_out[1] = rej.hf_hi; }
+    frame_setup(P, sky.data(), sw, sh, primary_steps, light_steps, early_eps, rej.hf_lo, rej.hf_hi, fc);
+    fc.ct_mode = rej.ct_mode;
     uint64_t ic = 0;
     const int rows = n_bands * band_rows;
     for (int lr = 0; lr < rows; lr++) {
@@ -151,15 +142,15 @@ void hostsim_march_monotonic(const float params[28], int primary_steps, int W, i
 // out[2*i] = lazy, out[2*i+1] = eager.  pos = 3 floats per point, lods = {shape, detail} per point.
 void hostsim_density_forms(const uint8_t* large_chain, const uint8_t* small_chain, const uint8_t* weather_rgb8, const float params[28],
                            const uint16_t* sky_h, int sw, int sh, int n, const float* pos, const int* lods, float* out) {
-    std::vector<uint8_t> lc(large_chain, large_chain + csky_mip_offset(SHAPE_N, SHAPE_LEVELS, 4));
-    std::vector<uint8_t> sc(small_chain, small_chain + csky_mip_offset(DETAIL_N, DETAIL_LEVELS, 3));
+    std::vector<uint8_t> lc(large_chain, large_chain + RAW_SHAPE_CHAIN);
+    std::vector<uint8_t> sc(small_chain, small_chain + RAW_DETAIL_CHAIN);
     std::vector<ShapeTexel> shape; std::vector<uint4> detail, weather;
     uint32_t so[SHAPE_LEVELS], dof[DETAIL_LEVELS];
     bake_shape(lc, shape, so); bake_detail(sc, detail, dof); bake_weather(weather_rgb8, weather);
     std::vector<float4> sky = widen(sky_h, sw, sh);
     TexSet T; T.shape = shape.data(); T.detail = detail.data(); T.weather = weather.data(); T.sky = sky.data(); T.sky_w = sw; T.sky_h = sh;
     T.detail_h = nullptr; T.detail_lds = nullptr;
-    { const uint8_t* t5 = sc.data() + csky_mip_offset(DETAIL_N, 5, 3); T.detail_lod5 = (float)(5 * t5[0] + 2 * t5[1] + t5[2]) * (1.0f / (8.0f * 255.0f)); }
+    T.detail_lod5 = detail_lod5_value(sc.data() + RAW_DETAIL_LOD5);
     CloudParams P; memcpy(&P, params, sizeof P);
     FrameConsts fc;
     frame_setup(P, sky.data(), sw, sh, 128, 6, 0.0f, -1.0f, 2.0f, fc);
@@ -185,11 +176,6 @@ void hostsim_composite(int out_w, int out_h, const uint16_t* cf, const uint16_t*
     }
 }
 
-size_t csky_mip_offset(int n, int level, int ch) {  // same definition as assets.cpp (this tool does not link libcloudsky)
-    size_t off = 0;
-    for (int l = 0; l < level; l++) { size_t m = (size_t)(n >> l); off += m * m * m * (size_t)ch; }
-    return off;
-}
 }
 
 extern "C" {

@@ -174,9 +174,9 @@ void test_context() {
     rc |= c->d_frame.alloc(c, 64); rc |= c->d_stats.alloc(c, 130);
     for (int k = 0; k < 2; k++) { rc |= c->lut.ring_f[k].alloc(c, 8); rc |= c->lut.ring_h[k].alloc(c, 32); }
     rc |= c->d_trans_f.alloc(c, 8); rc |= c->d_trans_h.alloc(c, 32);
-    rc |= c->d_weather32.alloc(c, 8); rc |= c->d_detail32.alloc(c, 8); rc |= c->d_shape32.alloc(c, 8); rc |= c->d_brick.alloc(c, 8);
-    rc |= c->d_detail_h.alloc(c, 8); rc |= c->d_weather.alloc(c, 8); rc |= c->d_detail.alloc(c, 8); rc |= c->d_shape.alloc(c, 8);
-    rc |= c->d_bake_meta.alloc(c, 32); rc |= c->d_raw_weather.alloc(c, 8); rc |= c->d_raw_small.alloc(c, 8); rc |= c->d_raw_large.alloc(c, 8);
+    rc |= c->noise.d_weather32.alloc(c, 8); rc |= c->noise.d_detail32.alloc(c, 8); rc |= c->noise.d_shape32.alloc(c, 8); rc |= c->noise.d_brick.alloc(c, 8);
+    rc |= c->noise.d_detail_h.alloc(c, 8); rc |= c->noise.d_weather.alloc(c, 8); rc |= c->noise.d_detail.alloc(c, 8); rc |= c->noise.d_shape.alloc(c, 8);
+    rc |= c->noise.d_bake_meta.alloc(c, 32); rc |= c->noise.d_raw_weather.alloc(c, 8); rc |= c->noise.d_raw_small.alloc(c, 8); rc |= c->noise.d_raw_large.alloc(c, 8);
     rc |= c->ev_copy.create(c, hipEventDisableTiming); rc |= c->ev1.create(c, hipEventDefault); rc |= c->ev0.create(c, hipEventDefault);
     rc |= c->stream.create(c, hipStreamNonBlocking);
     // the views: copies of somebody else's events.  None of them may be released by the context.
