@@ -69,6 +69,17 @@ class ShadowParams(C.Structure):
     _fields_ = [("width", C.c_int), ("height", C.c_int), ("center", C.c_float * 2), ("extent", C.c_float * 2), ("steps", C.c_int)]
 
 
+class AerialParams(C.Structure):
+    """csky_aerial_params (include/cloudsky.h): the aerial-perspective volume's sizes, reach, screen aspect and sun."""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("depth", C.c_int), ("steps_per_slice", C.c_int), ("far_km", C.c_float), ("aspect", C.c_float),
+                ("sun_direction", C.c_float * 3)]
+
+
+class View(C.Structure):
+    """csky_view (include/cloudsky.h): the camera's basis, column-major, and its vertical field of view."""
+    _fields_ = [("basis", C.c_float * 9), ("fov_y_degrees", C.c_float)]
+
+
 class CloudStats(C.Structure):
     _fields_ = [("rays", C.c_uint64), ("primary_samples", C.c_uint64), ("incloud_samples", C.c_uint64)]
 
@@ -149,6 +160,8 @@ SYMBOLS = [
     ("csky_prefilter_cube", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     ("csky_render_cloud_shadow", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.POINTER(ShadowParams), C.c_void_p]),
     ("csky_render_cloud_shadow_device", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.POINTER(ShadowParams), C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("csky_render_aerial_perspective", C.c_int, [C.c_void_p, C.POINTER(AerialParams), C.POINTER(View), C.c_void_p]),
+    ("csky_render_aerial_perspective_device", C.c_int, [C.c_void_p, C.POINTER(AerialParams), C.POINTER(View), C.c_void_p, C.c_void_p]),
     ("csky_time_clouds", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.c_int, C.POINTER(Bands), C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(CloudStats)]),
     ("csky_get_cloud_stats", C.c_int, [C.c_void_p, C.POINTER(CloudStats)]),
     ("csky_set_kernel_timing", C.c_int, [C.c_void_p, C.c_int]),
@@ -452,6 +465,30 @@ class Context:
         if out.shape != (int(height), int(width)) or out.dtype != np.float16 or not out.flags.c_contiguous:
             raise ValueError("render_cloud_shadow: out must be a contiguous float16 [%d, %d] array" % (int(height), int(width)))
         self._chk(self._L.csky_render_cloud_shadow(self._h, C.byref(p), C.byref(sp), _ptr(out)))
+        return out
+
+    def render_aerial_perspective(self, sun, width=32, height=32, depth=32, far_km=32.0, steps_per_slice=2, view=None, aspect=0.0, out=None, stream=None):
+        """The aerial-perspective volume (csky_render_aerial_perspective*, definition: include/cloudsky.h): in-scattered light (rgb, the sky LUT's
+        units) and transmittance (a) of the atmosphere in front of geometry, float16 [depth, height, width, 4]; slice k is the state at distance
+        (k + 1) * far_km / depth along the column's ray.  view: None = the equirectangular panorama over the whole sphere, or (basis 3x3 with the
+        camera's right / up / back axes as columns, fov_y_degrees) with `aspect` the screen's width / height (0 = width / height).  Host path (out
+        None or a numpy float16 array): blocks, returns numpy.  Device path (out a contiguous torch tensor of 2-byte elements on this context's
+        GPU): asynchronous on `stream`, written in place, returns the tensor.  Needs the transmittance LUT and nothing else."""
+        shape = (int(depth), int(height), int(width), 4)
+        p = AerialParams(shape[2], shape[1], shape[0], int(steps_per_slice), float(far_km), float(aspect), (C.c_float * 3)(*[float(x) for x in sun]))
+        v = None
+        if view is not None:
+            v = C.byref(View((C.c_float * 9)(*[float(x) for x in np.asarray(view[0], np.float32).T.reshape(-1)]), float(view[1])))   # column-major basis
+        if out is not None and hasattr(out, "data_ptr"):
+            if tuple(out.shape) != shape or out.element_size() != 2 or not out.is_contiguous():
+                raise ValueError("render_aerial_perspective: out must be a contiguous %s tensor of 2-byte elements" % (shape,))
+            self._chk(self._L.csky_render_aerial_perspective_device(self._h, C.byref(p), v, C.c_void_p(int(out.data_ptr())), C.c_void_p(stream or 0)))
+            return out
+        if out is None:
+            out = np.zeros(shape, np.float16)
+        if out.shape != shape or out.dtype != np.float16 or not out.flags.c_contiguous:
+            raise ValueError("render_aerial_perspective: out must be a contiguous float16 %s array" % (shape,))
+        self._chk(self._L.csky_render_aerial_perspective(self._h, C.byref(p), v, _ptr(out)))
         return out
 
     def set_shadow_exact_end(self, enabled=True):

@@ -342,6 +342,22 @@ class CloudSky:
         done()
         return out
 
+    def aerial_perspective(self, width=32, height=32, depth=32, far_km=32.0, steps_per_slice=2, view=None):
+        """What the atmosphere does in front of the scene's geometry under the current sun (the one update_sky() hands the sky LUT): in-scattered
+        light and transmittance per view direction and depth slice, float16 [depth, height, width, 4] (csky_render_aerial_perspective; the
+        definition and the host's lookup: include/cloudsky.h).  view: None = the panorama over the whole sphere, which depends on
+        the sun alone; or (basis, fov_y_degrees) as sky_view takes them, the aspect ratio being width / height.  A torch CUDA tensor with
+        device_buffers=True.  Independent of the noise, the sky LUTs and the blend textures; not called by update_sky()."""
+        sun = self.frame_data.LIGHT_DIRECTION
+        if not self.device_buffers:
+            return self.ctx.render_aerial_perspective(sun, width, height, depth, far_km, steps_per_slice, view)
+        import torch
+        out = torch.empty((int(depth), int(height), int(width), 4), dtype=torch.float16, device=torch.device("cuda", self.ctx.device_id))
+        stream, done = self._march_stream()
+        self.ctx.render_aerial_perspective(sun, width, height, depth, far_km, steps_per_slice, view, out=out, stream=stream)
+        done()
+        return out
+
     # ---- render thread ------------------------------------------------------------------------------------
     def _march_stream(self):
         """(hip stream handle, done()) for one batch of library calls in device-buffer mode.  The work is enqueued on torch's CURRENT

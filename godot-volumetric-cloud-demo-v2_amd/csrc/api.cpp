@@ -47,7 +47,8 @@ int create_resources(csky_ctx* c) {
     // (The frame prologue runs on `stream` too: context.h.  A HIGH-PRIORITY prologue stream was measured in round 2: whole frames with two frames in
     // flight 1.78 -> 2.02 ms, one rank's 1/8 share 0.329 -> 0.335 ms: the priority queue breaks the overlap of the two frame streams.)
     if ((rc = c->stream.create(c, hipStreamNonBlocking)) || (rc = c->ev0.create(c, hipEventDefault)) || (rc = c->ev1.create(c, hipEventDefault))) return rc;
-    if ((rc = c->ev_copy.create(c, hipEventDisableTiming)) || (rc = c->ev_rad.create(c, hipEventDisableTiming))) return rc;
+    if ((rc = c->ev_copy.create(c, hipEventDisableTiming)) || (rc = c->ev_rad.create(c, hipEventDisableTiming)) ||
+        (rc = c->ev_aerial.create(c, hipEventDisableTiming))) return rc;
     for (FrameSlot& k : c->ring.slot)
         if ((rc = k.ev_setup.create(c, hipEventDisableTiming)) || (rc = k.ev_clouds.create(c, hipEventDisableTiming)) || (rc = k.fc.alloc(c, 1))) return rc;
     if ((rc = c->d_stats.alloc(c, CSKY_STATS_WORDS)) || (rc = c->ring.d_heads.alloc(c, RING * 16))) return rc;

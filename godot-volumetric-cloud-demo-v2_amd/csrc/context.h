@@ -1,6 +1,6 @@
 // context.h -- the context of libcloudsky (csky_ctx) and the host helpers its C ABI sources share.  Internal to libcloudsky:
 // api.cpp (lifecycle, textures, cloud entry points, host ring), api_lut.cpp (the transmittance and sky LUTs), clouds_launch.cpp (the cloud kernel
-// launch), api_sky.cpp (compositor, radiance cubemap), api_shadow.cpp (cloud shadow map), api_external.cpp (zero-copy frames), api_multi.cpp (the
+// launch), api_sky.cpp (compositor, radiance cubemap), api_shadow.cpp (cloud shadow map), api_aerial.cpp (aerial-perspective volume), api_external.cpp (zero-copy frames), api_multi.cpp (the
 // multi-device handle).
 // Ownership: every device buffer, pinned buffer, event and stream of the context is a member of one of the owner types of owners.h and dies with
 // the context (csky_destroy: bind the device, wait for it, delete).  A buffer's count() is its capacity; raw pointers and raw handles in the
@@ -237,6 +237,8 @@ struct csky_ctx {
     csky_cloud_stats last_stats = {0, 0, 0};
     csky::DevBuf<uint16_t> d_shadow;                                       // host form of the cloud shadow map: the map before its copy out, grow-only
     bool shadow_exact_end = true;                                          // csky_set_shadow_exact_end (shadow_core.h shadow_march)
+    csky::DevBuf<uint2> d_aerial;                                          // host form of the aerial-perspective volume: the volume before its copy out, grow-only
+    csky::Event ev_aerial;                                                 // the transmittance LUT (the context's stream) -> the volume (caller's stream)
     bool census_lean = false;                                  // csky_census_clouds unless CSKY_CENSUS_TALLY=1: count the blocks of the kernel form that keeps no in-cloud tally (kernels.h launch_clouds)
     // asynchronous host form (csky_submit_clouds / csky_collect): a ring of pinned host frames + device frames on rotating internal streams
     // (a slot's capacity is h.count(), in bytes; d holds as many pixels of 8 bytes)

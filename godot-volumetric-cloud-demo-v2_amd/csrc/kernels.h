@@ -77,6 +77,11 @@ hipError_t launch_sqrt_shell(const float* d_in, float* d_out, size_t n, hipStrea
 struct ShadowConsts;
 hipError_t launch_cloud_shadow(const TexSet& t, const TexSet32* t32, const FrameConsts& fc, const ShadowConsts& sc, uint16_t* d_out, hipStream_t s);
 
+// ------------------------------------------------------------------------------------------------ aerial.hip
+// the aerial-perspective volume (aerial_core.h): g.d slices of g.h x g.w RGBA16F texels into d_out, tightly packed; g travels as a kernel argument
+struct AerialGeom;
+hipError_t launch_aerial(const AerialGeom& g, const float4* d_trans, int tw, int th, uint2* d_out, hipStream_t s, int tlut = 0);
+
 // ------------------------------------------------------------------------------------------------ bc7enc.hip
 // BC7 (BPTC) blocks of n_img images of w x h RGBA8 texels (what compress/mode=2 of the *.import files asks the importer for)
 hipError_t launch_bc7_encode(const uint8_t* d_img, int w, int h, int n_img, int quality, uint4* d_blocks, hipStream_t s);

@@ -344,6 +344,52 @@ int csky_render_cloud_shadow(csky_ctx* ctx, const csky_cloud_params* p, const cs
 int csky_render_cloud_shadow_device(csky_ctx* ctx, const csky_cloud_params* p, const csky_shadow_params* sp, void* d_out_r16f, size_t row_pitch_bytes,
                                     void* hip_stream);
 
+/* ---- aerial-perspective volume: in-scattering in front of geometry --------------------------------
+ * What the air between the eye and the scene's geometry does: a W x H x D volume of RGBA16F texels, in-scattered light (rgb) and transmittance (a)
+ * per view direction and depth slice, for every opaque and transparent surface of a host's scene to tap (Hillaire's fourth table).  It is the
+ * integral the sky LUT holds (sky-lut.glsl:219-276 compute_inscattering) stopped at a finite distance, by the sky LUT's own per-step code.
+ * Inputs: the context's transmittance table and its mapping; a sun direction s, used as given (like csky_sky_params.sun_direction, not normalised);
+ * the sizes W, H, D and S steps per slice; far_km; a view.
+ * Column (i, j) -> EYEDIR e, exactly as the compositor does it: with a csky_view, the perspective camera of csky_composite_view (basis columns,
+ * fov_y_degrees; the aspect ratio is `aspect`, 0 = W / H); with view == NULL, the equirectangular panorama of csky_composite_sky over the whole
+ * sphere (u = (i+.5)/W -> azimuth (2u-1) pi, v = (j+.5)/H -> elevation (0.5-v) pi, e = (cos el cos az, sin el, cos el sin az)).  The observer of the
+ * atmosphere model never moves, so the panorama form depends on the sun alone: a host renders it per sun change, not per frame.
+ * The column's ray in the LUT's frame, by the compositor's convention (clouds.gdshader:34-45 against sky-lut.glsl:221-223,286-297):
+ *     ray_dir = (-e.x, -e.z, e.y)      ray_origin = (0, 0, 6371.5)      sun_dir = (-s.x, -s.z, s.y)
+ *     t_stop  = ground_dist < 0 ? atmos_dist : ground_dist                         (sky-lut.glsl:299-309)
+ *     n = D * S;   dt = far_km / (float)n
+ *     L = 0, Tr = 1
+ *     for i in 0..n-1:   t = (i + 0.5) * dt
+ *         if t >= t_stop: this step is skipped (L and Tr unchanged)
+ *         else:           the body of sky-lut.glsl:235-272, unchanged
+ *         after step i = (k+1) * S - 1:   slice k of the column = ( M * L   (sky-lut.glsl:207-217),
+ *                                                                   a = (((Tr.x + Tr.y) + Tr.z) + Tr.w) * 0.25 )
+ * Output: D x H x W texels of RGBA16F, tightly packed [slice][row][col].  rgb is in the sky LUT's units (a host divides by 50 exactly as
+ * clouds.gdshader:44 does).  Slice k holds the state at distance (k + 1) * far_km / D ALONG THE RAY: radial distance, not view-space z.  Columns
+ * past the ground or the top of the atmosphere keep the value they had at the stop.
+ * Host lookup: a surface at distance t along column direction (u, v) samples w = t / far_km - 0.5 / D with linear filtering and clamp to edge; for
+ * t below the first slice it scales rgb by t * D / far_km and mixes a towards 1 by the same weight; composited = surface * a + rgb / 50
+ * (INTEGRATION.md has the shader).
+ * Tie to the reference: a column whose ray_dir floats are those of a sky-LUT texel, with far_km that texel's t_d and D * S = 30, has that texel's
+ * rgb in its last slice, bit for bit (dt is the same expression and no midpoint reaches t_stop).
+ * Ranges: W, H in 1..512, D in 1..256, S in 1..16, far_km finite in (0, 2000], fov_y_degrees in (0, 180), aspect >= 0; every float read must be
+ * finite (CSKY_ERR_INVALID otherwise).  Zero fields take the defaults 32 x 32 x 32, S = 2, far_km = 32.  Needs the transmittance table
+ * (csky_render_transmittance; CSKY_ERR_STATE without it, and after a change of its mapping until it is rendered again) and nothing else: no noise,
+ * no sky LUT, no cloud frame; it changes none of them. */
+typedef struct {
+    int   width, height, depth;   /* W, H in 1..512, D in 1..256; 0 = 32                                   */
+    int   steps_per_slice;        /* S, 1..16; 0 = 2                                                       */
+    float far_km;                 /* distance of the last slice along the ray, (0, 2000]; 0 = 32           */
+    float aspect;                 /* with a view: the screen's width / height; 0 = W / H.  Unused without  */
+    float sun_direction[3];       /* towards the sun, as csky_sky_params.sun_direction                     */
+} csky_aerial_params;
+/* Blocking host form: out_rgba16f receives D * H * W * 4 halfs. */
+int csky_render_aerial_perspective(csky_ctx* ctx, const csky_aerial_params* params, const csky_view* view_or_NULL, uint16_t* out_rgba16f);
+/* Device form: asynchronous on hip_stream (the context's own stream if NULL), ordered behind what the context's stream has done to the
+ * transmittance table.  Writes the D * H * W texels and nothing else. */
+int csky_render_aerial_perspective_device(csky_ctx* ctx, const csky_aerial_params* params, const csky_view* view_or_NULL, void* d_out_rgba16f,
+                                          void* hip_stream);
+
 /* ---- frames in flight ---------------------------------------------------------------------------- */
 /* Policy hint for the automatic segment / schedule choice: n = 2..8: the caller keeps n frames in flight by rotating n streams
  * between consecutive csky_render_*_device calls (always safe: per-frame state lives in eight-deep rings ordered by events); the
