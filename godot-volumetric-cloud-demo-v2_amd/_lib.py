@@ -32,6 +32,18 @@ def transmittance_uv(r_km, mu, mapping=TLUT_BRUNETON, w=256, h=64):
     return float(uv[0]), float(uv[1]), bool(hit.value)
 
 
+def aerial_shadow_rect(sun, far_km=32.0):
+    """csky_aerial_shadow_rect (host only, no GPU): the rectangle (center, extent), two (x, z) pairs in metres, that a cloud shadow map must cover
+    for an aerial-perspective volume of reach far_km under the sun `sun`.  Raises CloudSkyError (CSKY_ERR_INVALID) when the sun is not above the
+    horizon, or so low that the rectangle leaves the range of csky_shadow_params."""
+    p = AerialParams(0, 0, 0, 0, float(far_km), 0.0, (C.c_float * 3)(*[float(x) for x in sun]))
+    center, extent = (C.c_float * 2)(), (C.c_float * 2)()
+    rc = lib().csky_aerial_shadow_rect(C.byref(p), center, extent)
+    if rc != OK:
+        raise CloudSkyError(rc, (lib().csky_last_error(None) or b"").decode())
+    return (float(center[0]), float(center[1])), (float(extent[0]), float(extent[1]))
+
+
 class CloudSkyError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("libcloudsky error %d: %s" % (code, msg))
@@ -162,6 +174,10 @@ SYMBOLS = [
     ("csky_render_cloud_shadow_device", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.POINTER(ShadowParams), C.c_void_p, C.c_size_t, C.c_void_p]),
     ("csky_render_aerial_perspective", C.c_int, [C.c_void_p, C.POINTER(AerialParams), C.POINTER(View), C.c_void_p]),
     ("csky_render_aerial_perspective_device", C.c_int, [C.c_void_p, C.POINTER(AerialParams), C.POINTER(View), C.c_void_p, C.c_void_p]),
+    ("csky_render_aerial_perspective_shadowed", C.c_int, [C.c_void_p, C.POINTER(AerialParams), C.POINTER(View), C.POINTER(ShadowParams), C.c_void_p, C.c_void_p]),
+    ("csky_render_aerial_perspective_shadowed_device", C.c_int, [C.c_void_p, C.POINTER(AerialParams), C.POINTER(View), C.POINTER(ShadowParams), C.c_void_p, C.c_size_t,
+                                                                 C.c_void_p, C.c_void_p]),
+    ("csky_aerial_shadow_rect", C.c_int, [C.POINTER(AerialParams), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     ("csky_time_clouds", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.c_int, C.POINTER(Bands), C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(CloudStats)]),
     ("csky_get_cloud_stats", C.c_int, [C.c_void_p, C.POINTER(CloudStats)]),
     ("csky_set_kernel_timing", C.c_int, [C.c_void_p, C.c_int]),
@@ -489,6 +505,45 @@ class Context:
         if out.shape != shape or out.dtype != np.float16 or not out.flags.c_contiguous:
             raise ValueError("render_aerial_perspective: out must be a contiguous float16 %s array" % (shape,))
         self._chk(self._L.csky_render_aerial_perspective(self._h, C.byref(p), v, _ptr(out)))
+        return out
+
+    def render_aerial_perspective_shadowed(self, sun, shadow, center, extent, width=32, height=32, depth=32, far_km=32.0, steps_per_slice=2, view=None, aspect=0.0,
+                                           out=None, stream=None):
+        """The aerial-perspective volume with a cloud shadow map inside it: light shafts (csky_render_aerial_perspective_shadowed*, definition:
+        include/cloudsky.h).  `shadow` is the map render_cloud_shadow made for the rectangle `extent` around `center` (metres along x, z) under the
+        same sun; the other arguments and the result are render_aerial_perspective's.  Host path (shadow a numpy float16 [h, w] array; out None or a
+        numpy float16 array): blocks, returns numpy.  Device path (shadow a 2-D torch tensor of 2-byte elements on this context's GPU with unit
+        column stride, whose row stride gives the pitch; out a contiguous torch tensor of 2-byte elements or None): asynchronous on `stream`, on
+        which the map is read; returns the tensor.  Needs the transmittance LUT and nothing else."""
+        shape = (int(depth), int(height), int(width), 4)
+        p = AerialParams(shape[2], shape[1], shape[0], int(steps_per_slice), float(far_km), float(aspect), (C.c_float * 3)(*[float(x) for x in sun]))
+        v = None
+        if view is not None:
+            v = C.byref(View((C.c_float * 9)(*[float(x) for x in np.asarray(view[0], np.float32).T.reshape(-1)]), float(view[1])))   # column-major basis
+        if hasattr(shadow, "data_ptr"):
+            if shadow.dim() != 2 or shadow.element_size() != 2 or (shadow.shape[1] > 1 and shadow.stride(1) != 1):
+                raise ValueError("render_aerial_perspective_shadowed: shadow must be a 2-D tensor of 2-byte elements with unit column stride")
+            mh, mw = int(shadow.shape[0]), int(shadow.shape[1])
+            pitch = shadow.stride(0) * 2 if mh > 1 else mw * 2
+            sp = ShadowParams(mw, mh, (C.c_float * 2)(float(center[0]), float(center[1])), (C.c_float * 2)(float(extent[0]), float(extent[1])), 0)
+            if out is None:
+                import torch
+                out = torch.empty(shape, dtype=torch.float16, device=shadow.device)
+            if not hasattr(out, "data_ptr") or tuple(out.shape) != shape or out.element_size() != 2 or not out.is_contiguous():
+                raise ValueError("render_aerial_perspective_shadowed: with a device map, out must be a contiguous %s tensor of 2-byte elements" % (shape,))
+            self._chk(self._L.csky_render_aerial_perspective_shadowed_device(self._h, C.byref(p), v, C.byref(sp), C.c_void_p(int(shadow.data_ptr())), C.c_size_t(int(pitch)),
+                                                                             C.c_void_p(int(out.data_ptr())), C.c_void_p(stream or 0)))
+            return out
+        shadow = np.asarray(shadow)
+        if shadow.ndim != 2 or shadow.dtype != np.float16:
+            raise ValueError("render_aerial_perspective_shadowed: shadow must be a float16 [h, w] array (or a 2-D torch tensor on the GPU)")
+        shadow = np.ascontiguousarray(shadow)
+        sp = ShadowParams(int(shadow.shape[1]), int(shadow.shape[0]), (C.c_float * 2)(float(center[0]), float(center[1])), (C.c_float * 2)(float(extent[0]), float(extent[1])), 0)
+        if out is None:
+            out = np.zeros(shape, np.float16)
+        if not isinstance(out, np.ndarray) or out.shape != shape or out.dtype != np.float16 or not out.flags.c_contiguous:
+            raise ValueError("render_aerial_perspective_shadowed: with a host map, out must be a contiguous float16 %s array" % (shape,))
+        self._chk(self._L.csky_render_aerial_perspective_shadowed(self._h, C.byref(p), v, C.byref(sp), _ptr(shadow), _ptr(out)))
         return out
 
     def set_shadow_exact_end(self, enabled=True):

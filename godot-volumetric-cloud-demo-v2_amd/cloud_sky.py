@@ -17,6 +17,7 @@ import numpy as np
 from . import assets as _assets
 from . import tiling as _tiling
 from ._lib import Context
+from ._lib import aerial_shadow_rect as _aerial_shadow_rect
 from .sky_lut import SkyLut
 from .transmittance_lut import TransmittanceLut
 
@@ -342,13 +343,20 @@ class CloudSky:
         done()
         return out
 
-    def aerial_perspective(self, width=32, height=32, depth=32, far_km=32.0, steps_per_slice=2, view=None):
+    def aerial_perspective(self, width=32, height=32, depth=32, far_km=32.0, steps_per_slice=2, view=None, cloud_shadows=False, shadow_size=256):
         """What the atmosphere does in front of the scene's geometry under the current sun (the one update_sky() hands the sky LUT): in-scattered
         light and transmittance per view direction and depth slice, float16 [depth, height, width, 4] (csky_render_aerial_perspective; the
         definition and the host's lookup: include/cloudsky.h).  view: None = the panorama over the whole sphere, which depends on
         the sun alone; or (basis, fov_y_degrees) as sky_view takes them, the aspect ratio being width / height.  A torch CUDA tensor with
-        device_buffers=True.  Independent of the noise, the sky LUTs and the blend textures; not called by update_sky()."""
+        device_buffers=True.  Independent of the noise, the sky LUTs and the blend textures; not called by update_sky().
+        cloud_shadows=True: light shafts.  The clouds of the current frame data shadow the volume's direct sun
+        (csky_render_aerial_perspective_shadowed): a shadow_size x shadow_size (or (w, h)) cloud shadow map is rendered over the rectangle
+        aerial_shadow_rect gives for far_km and the sun, and the volume taps it; with device_buffers=True both run back to back on the march
+        stream, without a host hop.  A sun at or below the horizon casts no shafts: the plain volume is rendered.  A sun so low that the rectangle
+        leaves the shadow map's range (within a quarter of a degree of the horizon at 32 km) raises CloudSkyError, as aerial_shadow_rect does."""
         sun = self.frame_data.LIGHT_DIRECTION
+        if cloud_shadows and float(np.float32(sun[1])) > 0.0:
+            return self._aerial_perspective_shadowed(sun, width, height, depth, far_km, steps_per_slice, view, shadow_size)
         if not self.device_buffers:
             return self.ctx.render_aerial_perspective(sun, width, height, depth, far_km, steps_per_slice, view)
         import torch
@@ -356,6 +364,23 @@ class CloudSky:
         stream, done = self._march_stream()
         self.ctx.render_aerial_perspective(sun, width, height, depth, far_km, steps_per_slice, view, out=out, stream=stream)
         done()
+        return out
+
+    def _aerial_perspective_shadowed(self, sun, width, height, depth, far_km, steps_per_slice, view, shadow_size):
+        mw, mh = (int(shadow_size), int(shadow_size)) if np.isscalar(shadow_size) else (int(shadow_size[0]), int(shadow_size[1]))
+        center, extent = _aerial_shadow_rect(sun, far_km)
+        pc = self._fill_push_constant()
+        if not self.device_buffers:
+            shadow = self.ctx.render_cloud_shadow(pc, mw, mh, center, extent)
+            return self.ctx.render_aerial_perspective_shadowed(sun, shadow, center, extent, width, height, depth, far_km, steps_per_slice, view)
+        import torch
+        dev = torch.device("cuda", self.ctx.device_id)
+        shadow = torch.empty((mh, mw), dtype=torch.float16, device=dev)
+        out = torch.empty((int(depth), int(height), int(width), 4), dtype=torch.float16, device=dev)
+        stream, done = self._march_stream()
+        self.ctx.render_cloud_shadow(pc, mw, mh, center, extent, out=shadow, stream=stream)          # the volume reads the map on the same stream
+        self.ctx.render_aerial_perspective_shadowed(sun, shadow, center, extent, width, height, depth, far_km, steps_per_slice, view, out=out, stream=stream)
+        done()                                           # torch's stream is behind both launches: the map's memory may be reused on it from here
         return out
 
     # ---- render thread ------------------------------------------------------------------------------------

@@ -1,9 +1,12 @@
-// api_aerial.cpp -- the aerial-perspective volume's C ABI (csky_render_aerial_perspective / _device; aerial_core.h, aerial.hip).
+// api_aerial.cpp -- the aerial-perspective volume's C ABI (csky_render_aerial_perspective / _device; aerial_core.h, aerial.hip), and
+// the same volume with a cloud shadow map inside it (csky_render_aerial_perspective_shadowed / _device, csky_aerial_shadow_rect; shafts_core.h,
+// shafts.hip).
 // The call reads the context's transmittance table and nothing else of it: no noise, no sky LUT, no cloud frame, no slot of any ring (geometry and sun
 // travel as kernel arguments), no stream of its own.
 #include <cmath>
 #include "context.h"
 #include "aerial_core.h"
+#include "shafts_core.h"
 
 using namespace csky;
 
@@ -47,6 +50,35 @@ int aerial_launch(csky_ctx* c, const char* fn, const AerialGeom& g, uint2* d_out
     return CSKY_OK;
 }
 
+// The shadowed forms' own arguments: the map's geometry (of sp only width, height, center and extent are read) and its pitch; m gets everything
+// but the pointer and the sun.
+int shafts_check(csky_ctx* c, const char* fn, const csky_shadow_params* sp, const void* map, size_t pitch_bytes, ShaftsMap& m) {
+    if (!sp) return fail(c, CSKY_ERR_INVALID, "%s: the shadow map's params are NULL", fn);
+    if (!map) return fail(c, CSKY_ERR_INVALID, "%s: the shadow map is NULL", fn);
+    if (sp->width < 1 || sp->width > 8192 || sp->height < 1 || sp->height > 8192) return fail(c, CSKY_ERR_INVALID, "%s: the shadow map's width and height must be in [1, 8192]", fn);
+    for (int k = 0; k < 2; k++)
+        if (!std::isfinite(sp->center[k]) || !std::isfinite(sp->extent[k]) || !(sp->extent[k] > 0.0f))
+            return fail(c, CSKY_ERR_INVALID, "%s: the shadow map's center and extent must be finite, extent > 0", fn);
+    if (pitch_bytes < (size_t)sp->width * 2 || pitch_bytes % 2) return fail(c, CSKY_ERR_INVALID, "%s: the shadow map's row pitch must be even and >= 2 * width", fn);
+    m.texels = nullptr; m.pitch_h = (uint32_t)(pitch_bytes / 2); m.w = sp->width; m.h = sp->height;
+    m.cx = sp->center[0]; m.cz = sp->center[1]; m.ex = sp->extent[0]; m.ez = sp->extent[1];
+    m.lx = m.ly = m.lz = 0.0f;
+    return CSKY_OK;
+}
+
+// The shadowed launch on stream s, behind whatever the context's stream has done to the table; the map is read on s.  g.sun, which aerial_check
+// has found finite, gives the map its sun.
+int shafts_launch(csky_ctx* c, const char* fn, const AerialGeom& g, ShaftsMap m, uint2* d_out, hipStream_t s) {
+    float l[3];
+    shafts_sun(g.sun, l);
+    m.lx = l[0]; m.ly = l[1]; m.lz = l[2];
+    HIPCHK(c, hipEventRecord(c->ev_aerial, c->stream));
+    HIPCHK(c, hipStreamWaitEvent(s, c->ev_aerial, 0));
+    const hipError_t e = launch_shafts(g, m, c->d_trans_f, c->tw, c->th, d_out, s, c->tlut);
+    if (e != hipSuccess) return fail(c, CSKY_ERR_HIP, "%s: kernel launch failed: %s", fn, hipGetErrorString(e));
+    return CSKY_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -71,6 +103,48 @@ int csky_render_aerial_perspective(csky_ctx* c, const csky_aerial_params* ap, co
     if ((rc = aerial_launch(c, fn, g, c->d_aerial, c->stream))) return rc;
     HIPCHK(c, hipMemcpyAsync(out, c->d_aerial, n * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return CSKY_OK;
+}
+
+int csky_render_aerial_perspective_shadowed_device(csky_ctx* c, const csky_aerial_params* ap, const csky_view* view, const csky_shadow_params* sp,
+                                                   const void* d_map, size_t pitch, void* d_out, void* hip_stream) {
+    const char* fn = "csky_render_aerial_perspective_shadowed_device";
+    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "%s: ctx is NULL", fn);
+    if (!d_out) return fail(c, CSKY_ERR_INVALID, "%s: d_out is NULL", fn);
+    AerialGeom g; ShaftsMap m;
+    int rc; if ((rc = shafts_check(c, fn, sp, d_map, pitch, m)) || (rc = aerial_check(c, fn, ap, view, g)) || (rc = bind(c))) return rc;
+    m.texels = static_cast<const uint16_t*>(d_map);
+    return shafts_launch(c, fn, g, m, static_cast<uint2*>(d_out), hip_stream ? (hipStream_t)hip_stream : (hipStream_t)c->stream);
+}
+
+int csky_render_aerial_perspective_shadowed(csky_ctx* c, const csky_aerial_params* ap, const csky_view* view, const csky_shadow_params* sp,
+                                            const uint16_t* map, uint16_t* out) {
+    const char* fn = "csky_render_aerial_perspective_shadowed";
+    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "%s: ctx is NULL", fn);
+    if (!out) return fail(c, CSKY_ERR_INVALID, "%s: out is NULL", fn);
+    AerialGeom g; ShaftsMap m;
+    int rc; if ((rc = shafts_check(c, fn, sp, map, sp ? (size_t)sp->width * 2 : 0, m)) || (rc = aerial_check(c, fn, ap, view, g)) || (rc = bind(c))) return rc;
+    const size_t n = (size_t)g.d * g.h * g.w, nm = (size_t)m.w * m.h;
+    if ((rc = c->d_aerial.grow(c, n)) || (rc = c->d_shafts_map.grow(c, nm))) return rc;   // nothing of an earlier call is in flight: this form blocks
+    HIPCHK(c, hipMemcpyAsync(c->d_shafts_map, map, nm * 2, hipMemcpyHostToDevice, c->stream));
+    m.texels = c->d_shafts_map;
+    if ((rc = shafts_launch(c, fn, g, m, c->d_aerial, c->stream))) return rc;
+    HIPCHK(c, hipMemcpyAsync(out, c->d_aerial, n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return CSKY_OK;
+}
+
+int csky_aerial_shadow_rect(const csky_aerial_params* ap, float center[2], float extent[2]) {
+    const char* fn = "csky_aerial_shadow_rect";
+    if (!ap || !center || !extent) return fail(nullptr, CSKY_ERR_INVALID, "%s: NULL argument", fn);
+    const float far_km = ap->far_km == 0.0f ? 32.0f : ap->far_km;
+    if (!std::isfinite(far_km) || !(far_km > 0.0f) || !(far_km <= 2000.0f)) return fail(nullptr, CSKY_ERR_INVALID, "%s: far_km must be finite and in (0, 2000], or 0 for 32", fn);
+    for (int k = 0; k < 3; k++) if (!std::isfinite(ap->sun_direction[k])) return fail(nullptr, CSKY_ERR_INVALID, "%s: sun_direction is not finite", fn);
+    float ce[2], ex[2];
+    if (!shafts_rect(ap->sun_direction, far_km * 1000.0f, ce, ex)) return fail(nullptr, CSKY_ERR_INVALID, "%s: the sun is not above the horizon: no shadow map applies", fn);
+    for (int k = 0; k < 2; k++)
+        if (!(std::fabs(ce[k]) + 0.5f * ex[k] <= 1.0e6f)) return fail(nullptr, CSKY_ERR_INVALID, "%s: the sun is too low: the rectangle leaves the 1e6 m range of csky_shadow_params", fn);
+    for (int k = 0; k < 2; k++) { center[k] = ce[k]; extent[k] = ex[k]; }
     return CSKY_OK;
 }
 

@@ -82,6 +82,11 @@ hipError_t launch_cloud_shadow(const TexSet& t, const TexSet32* t32, const Frame
 struct AerialGeom;
 hipError_t launch_aerial(const AerialGeom& g, const float4* d_trans, int tw, int th, uint2* d_out, hipStream_t s, int tlut = 0);
 
+// ------------------------------------------------------------------------------------------------ shafts.hip
+// the same volume with the cloud shadow map m inside it (shafts_core.h): m.texels is a device pointer, read on s; g and m travel as kernel arguments
+struct ShaftsMap;
+hipError_t launch_shafts(const AerialGeom& g, const ShaftsMap& m, const float4* d_trans, int tw, int th, uint2* d_out, hipStream_t s, int tlut = 0);
+
 // ------------------------------------------------------------------------------------------------ bc7enc.hip
 // BC7 (BPTC) blocks of n_img images of w x h RGBA8 texels (what compress/mode=2 of the *.import files asks the importer for)
 hipError_t launch_bc7_encode(const uint8_t* d_img, int w, int h, int n_img, int quality, uint4* d_blocks, hipStream_t s);

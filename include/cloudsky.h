@@ -390,6 +390,55 @@ int csky_render_aerial_perspective(csky_ctx* ctx, const csky_aerial_params* para
 int csky_render_aerial_perspective_device(csky_ctx* ctx, const csky_aerial_params* params, const csky_view* view_or_NULL, void* d_out_rgba16f,
                                           void* hip_stream);
 
+/* ---- light shafts: the cloud shadow map inside the aerial-perspective volume ---------------------
+ * The volume above lights every step of every column with the full sun.  Under a broken cloud deck the haze in front of a shadowed hillside is
+ * then as bright as the haze in a sun patch.  These forms take a cloud shadow map (csky_render_cloud_shadow*, above) and multiply the direct sun
+ * of every step by what the clouds between the step and the sun let through: crepuscular rays.
+ * As in csky_render_aerial_perspective: the columns, the rays, n = D * S, dt, the skip rule, the slice texel, the output layout, the defaults and
+ * ranges; the transmittance table is required (CSKY_ERR_STATE without it); no noise, sky LUT or frame is needed and none is changed.
+ * One thing changes, inside a taken step; everything else of the step is sky-lut.glsl:235-272 as before:
+ *     t_sun' = t_sun * s          (all four wavelengths; t_sun: sky-lut.glsl:254)
+ * The multiple-scattering term, the step's transmittance and therefore Tr are untouched: alpha does not depend on the map.
+ * Of sp only width (W), height (H), center (cx, cz) and extent (ex, ez) are read; steps is ignored.  The factor s of a step:
+ *     ll = sqrt((sx*sx + sy*sy) + sz*sz);   l = sun_direction / ll            once per call, fp32
+ *     if !(l.y > 0):  s = 1 for every step, the map is not read                the planet's own shadow is the transmittance table's business
+ *     (x, y, z), dist, altitude: the step's own (sky-lut.glsl:236-240), km, the LUT's frame
+ *     h  = altitude * 1000                                                    metres above the atmosphere model's ground; the observer is at 500
+ *     wx = -x * 1000,   wz = -y * 1000                                        the inverse of ray_dir = (-e.x, -e.z, e.y)
+ *     if h >= 4000:  s = 1, no tap                                            Rt - Rg: above the cloud layer
+ *     k  = h / l.y;   gx = wx - l.x * k,   gz = wz - l.z * k                  to the ground along the sun
+ *     u  = (gx - cx) / ex + 0.5,   v = (gz - cz) / ez + 0.5                   the shadow map's documented lookup
+ *     fx = u * W - 0.5,            fy = v * H - 0.5
+ *     if !(fx >= -1 && fx < W && fy >= -1 && fy < H):  s = 1                  also NaN and inf; before any conversion to int
+ *     i0 = floor(fx), ax = fx - i0;   j0 = floor(fy), ay = fy - j0
+ *     tap(i, j) = inside the map ? the half as a float : 1.0                  outside the map the sky is clear
+ *     lerp(a, b, w) = a + (b - a) * w
+ *     m  = lerp(lerp(tap(i0, j0), tap(i0+1, j0), ax), lerp(tap(i0, j0+1), tap(i0+1, j0+1), ax), ay)
+ *     w  = clamp((h - 1500) / 2500, 0, 1);   s = m + (1 - m) * w              below the layer's base s is m; it fades to clear at the top
+ * All in fp32 without contraction, in the order written.  A map of equal texels filters to that value exactly.
+ * Approximations: the map's tangent plane stands in for the sphere.  The cloud march's observer stands on the ground (clouds.glsl:223) while the
+ * atmosphere's stands 0.5 km up (sky-lut.glsl:61-62): that inconsistency is the reference's, and the volume takes the atmosphere's altitude.
+ * Inside the layer the whole-layer map over-shadows, hence the blend.  The host must pass the sun the map was rendered with.
+ * Consequences: a map of all 1.0, and a sun with l.y <= 0 (or a zero vector), give the bytes of csky_render_aerial_perspective; the alpha bytes
+ * are those of csky_render_aerial_perspective for any map.
+ * CSKY_ERR_INVALID, besides those of csky_render_aerial_perspective: a NULL sp, map or out pointer; width or height outside 1..8192; a non-finite
+ * center; a non-finite or non-positive extent; a pitch that is odd or below 2 * width. */
+/* Blocking host form: shadow_r16f holds sp->height rows of sp->width halfs, tightly packed; out_rgba16f receives D * H * W * 4 halfs. */
+int csky_render_aerial_perspective_shadowed(csky_ctx* ctx, const csky_aerial_params* params, const csky_view* view_or_NULL, const csky_shadow_params* sp,
+                                            const uint16_t* shadow_r16f, uint16_t* out_rgba16f);
+/* Device form: asynchronous on hip_stream (the context's own stream if NULL), ordered behind what the context's stream has done to the
+ * transmittance table.  The map, rows of shadow_row_pitch_bytes, is read on that stream: a map rendered on it by csky_render_cloud_shadow_device
+ * just before needs no further ordering.  Reads the width x height halfs, not the pitch padding; writes the D * H * W texels and nothing else. */
+int csky_render_aerial_perspective_shadowed_device(csky_ctx* ctx, const csky_aerial_params* params, const csky_view* view_or_NULL,
+                                                   const csky_shadow_params* sp, const void* d_shadow_r16f, size_t shadow_row_pitch_bytes,
+                                                   void* d_out_rgba16f, void* hip_stream);
+/* Host only, no context: the rectangle a shadow map must cover for the volume of `params` (of which far_km, 0 = 32, and sun_direction are read).
+ * With far_m = far_km * 1000, l as above and k = 4000 / l.y:
+ *     shift = (-l.x * k, -l.z * k);   center = shift / 2;   extent = 2 * far_m + |shift|      per axis
+ * Every projected (gx, gz) of a step with h < 4000 lies inside it.  CSKY_ERR_INVALID: !(l.y > 0), or |center| + extent / 2 > 1e6 on an axis (the
+ * range of csky_shadow_params: the sun is too low), a NULL pointer, a non-finite sun or a far_km out of range. */
+int csky_aerial_shadow_rect(const csky_aerial_params* params, float center[2], float extent[2]);
+
 /* ---- frames in flight ---------------------------------------------------------------------------- */
 /* Policy hint for the automatic segment / schedule choice: n = 2..8: the caller keeps n frames in flight by rotating n streams
  * between consecutive csky_render_*_device calls (always safe: per-frame state lives in eight-deep rings ordered by events); the
