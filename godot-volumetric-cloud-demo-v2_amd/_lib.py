@@ -87,6 +87,16 @@ class AerialParams(C.Structure):
                 ("sun_direction", C.c_float * 3)]
 
 
+class DepthParams(C.Structure):
+    """csky_depth_params (include/cloudsky.h): the cloud depth frame's size and step count."""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("steps", C.c_int)]
+
+
+class CloudAerialParams(C.Structure):
+    """csky_cloud_aerial_params (include/cloudsky.h): the size of the cloud frame and its depth frame, the step count and the sun."""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("steps", C.c_int), ("sun_direction", C.c_float * 3)]
+
+
 class View(C.Structure):
     """csky_view (include/cloudsky.h): the camera's basis, column-major, and its vertical field of view."""
     _fields_ = [("basis", C.c_float * 9), ("fov_y_degrees", C.c_float)]
@@ -178,6 +188,10 @@ SYMBOLS = [
     ("csky_render_aerial_perspective_shadowed_device", C.c_int, [C.c_void_p, C.POINTER(AerialParams), C.POINTER(View), C.POINTER(ShadowParams), C.c_void_p, C.c_size_t,
                                                                  C.c_void_p, C.c_void_p]),
     ("csky_aerial_shadow_rect", C.c_int, [C.POINTER(AerialParams), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    ("csky_render_cloud_depth", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.POINTER(DepthParams), C.c_void_p]),
+    ("csky_render_cloud_depth_device", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.POINTER(DepthParams), C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("csky_apply_cloud_aerial", C.c_int, [C.c_void_p, C.POINTER(CloudAerialParams), C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("csky_apply_cloud_aerial_device", C.c_int, [C.c_void_p, C.POINTER(CloudAerialParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("csky_time_clouds", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.c_int, C.POINTER(Bands), C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(CloudStats)]),
     ("csky_get_cloud_stats", C.c_int, [C.c_void_p, C.POINTER(CloudStats)]),
     ("csky_set_kernel_timing", C.c_int, [C.c_void_p, C.c_int]),
@@ -544,6 +558,58 @@ class Context:
         if not isinstance(out, np.ndarray) or out.shape != shape or out.dtype != np.float16 or not out.flags.c_contiguous:
             raise ValueError("render_aerial_perspective_shadowed: with a host map, out must be a contiguous float16 %s array" % (shape,))
         self._chk(self._L.csky_render_aerial_perspective_shadowed(self._h, C.byref(p), v, C.byref(sp), _ptr(shadow), _ptr(out)))
+        return out
+
+    def render_cloud_depth(self, params, width, height, steps=0, out=None, stream=None):
+        """The cloud depth frame (csky_render_cloud_depth*, definition: include/cloudsky.h): for the rays of a width x height hemisphere frame
+        of the push-constant block `params`, the cloud's mean, first and last distance from the observer in km and the frame's alpha, float16
+        [height, width, 4].  steps 0 = the context's primary step count.  Host path (out None or a numpy float16 array): blocks, returns numpy.
+        Device path (out a [height, width, 4] torch tensor of 2-byte elements on this context's GPU whose texels are contiguous; its row stride
+        is the pitch): asynchronous on `stream`, written in place, returns the tensor.  Needs the noise and no LUT."""
+        p = cloud_params(params)
+        shape = (int(height), int(width), 4)
+        dp = DepthParams(shape[1], shape[0], int(steps))
+        if out is not None and hasattr(out, "data_ptr"):
+            if out.dim() != 3 or out.element_size() != 2 or tuple(out.shape) != shape or out.stride(2) != 1 or (shape[1] > 1 and out.stride(1) != 4):
+                raise ValueError("render_cloud_depth: out must be a %s tensor of 2-byte elements with contiguous texels" % (shape,))
+            pitch = out.stride(0) * 2 if shape[0] > 1 else shape[1] * 8
+            self._chk(self._L.csky_render_cloud_depth_device(self._h, C.byref(p), C.byref(dp), C.c_void_p(int(out.data_ptr())), C.c_size_t(int(pitch)), C.c_void_p(stream or 0)))
+            return out
+        if out is None:
+            out = np.zeros(shape, np.float16)
+        if out.shape != shape or out.dtype != np.float16 or not out.flags.c_contiguous:
+            raise ValueError("render_cloud_depth: out must be a contiguous float16 %s array" % (shape,))
+        self._chk(self._L.csky_render_cloud_depth(self._h, C.byref(p), C.byref(dp), _ptr(out)))
+        return out
+
+    def apply_cloud_aerial(self, sun, cloud, depth, steps=16, out=None, stream=None):
+        """The air in front of a cloud frame (csky_apply_cloud_aerial*, definition: include/cloudsky.h): `cloud` a hemisphere frame and `depth`
+        its depth frame (render_cloud_depth), both float16 [h, w, 4]; the result is the frame with the atmosphere's extinction and in-scattering
+        over each pixel's mean cloud distance under the sun `sun` (used as given), its alpha unchanged.  Host path (numpy arrays): blocks,
+        returns numpy.  Device path (contiguous torch tensors of 2-byte elements on this context's GPU): asynchronous on `stream`, returns
+        `out`, a new tensor unless given; out may be `cloud`.  Needs the transmittance LUT and nothing else."""
+        shape = tuple(int(x) for x in cloud.shape)
+        if len(shape) != 3 or shape[2] != 4 or tuple(int(x) for x in depth.shape) != shape:
+            raise ValueError("apply_cloud_aerial: cloud and depth must be [h, w, 4] images of one size")
+        p = CloudAerialParams(shape[1], shape[0], int(steps), (C.c_float * 3)(*[float(x) for x in sun]))
+        if hasattr(cloud, "data_ptr"):
+            if out is None:
+                import torch
+                out = torch.empty(shape, dtype=torch.float16, device=cloud.device)
+            for t in (cloud, depth, out):
+                if not hasattr(t, "data_ptr") or tuple(t.shape) != shape or t.element_size() != 2 or not t.is_contiguous():
+                    raise ValueError("apply_cloud_aerial: with a device frame, cloud, depth and out must be contiguous %s tensors of 2-byte elements" % (shape,))
+            self._chk(self._L.csky_apply_cloud_aerial_device(self._h, C.byref(p), C.c_void_p(int(cloud.data_ptr())), C.c_void_p(int(depth.data_ptr())),
+                                                             C.c_void_p(int(out.data_ptr())), C.c_void_p(stream or 0)))
+            return out
+        cloud, depth = np.ascontiguousarray(cloud), np.ascontiguousarray(depth)
+        if cloud.dtype != np.float16 or depth.dtype != np.float16:
+            raise ValueError("apply_cloud_aerial: cloud and depth must be float16 arrays (or torch tensors on the GPU)")
+        if out is None:
+            out = np.zeros(shape, np.float16)
+        if out.shape != shape or out.dtype != np.float16 or not out.flags.c_contiguous:
+            raise ValueError("apply_cloud_aerial: out must be a contiguous float16 %s array" % (shape,))
+        self._chk(self._L.csky_apply_cloud_aerial(self._h, C.byref(p), _ptr(cloud), _ptr(depth), _ptr(out)))
         return out
 
     def set_shadow_exact_end(self, enabled=True):

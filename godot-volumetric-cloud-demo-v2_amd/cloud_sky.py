@@ -383,6 +383,62 @@ class CloudSky:
         done()                                           # torch's stream is behind both launches: the map's memory may be reused on it from here
         return out
 
+    def cloud_depth(self):
+        """Where along each ray of the hemisphere frame the clouds of the current frame data sit: the mean, first and last distance from the
+        observer in km and the frame's alpha, float16 [h, w, 4] at the frame's size and the context's step count, so that the samples are the
+        frame's (csky_render_cloud_depth; the definition: include/cloudsky.h).  A torch CUDA tensor with device_buffers=True.  Independent of
+        the sky LUTs and of the blend textures; not called by update_sky()."""
+        W, H = self._texture_size
+        pc = self._fill_push_constant()
+        if not self.device_buffers:
+            return self.ctx.render_cloud_depth(pc, W, H)
+        import torch
+        out = torch.empty((H, W, 4), dtype=torch.float16, device=torch.device("cuda", self.ctx.device_id))
+        stream, done = self._march_stream()
+        self.ctx.render_cloud_depth(pc, W, H, out=out, stream=stream)
+        done()
+        return out
+
+    def aerial_clouds(self, frame=None, steps=16):
+        """The current frame (or `frame`, a float16 [h, w, 4] image at the frame's size) with the air in front of its clouds under the current
+        sun: the depth frame of the current frame data places every pixel's cloud, and the atmosphere's extinction and in-scattering over that
+        distance are applied (csky_render_cloud_depth + csky_apply_cloud_aerial; the definition: include/cloudsky.h).  A new image, alpha
+        unchanged; a host binds it in place of the frame.  With device_buffers=True both kernels run back to back on the march
+        stream, without a host hop.  A sun at or under the horizon still applies the extinction.  Not called by update_sky().
+        `frame` may be a numpy array or a torch tensor on either side: it is moved to where this object keeps its frames (the GPU with
+        device_buffers=True, the host without), and the result is of that kind.  With frames_to_update > 1 the current frame is a texture that
+        update_sky() refreshes tile by tile, while the depth frame describes the current frame data as a whole: call this once per finished
+        pass (`self.frame == self.frames_to_update`), on the texture the pass completed, as INTEGRATION.md tells a C host."""
+        self.flush()
+        if frame is None:
+            frame = self.last_frame
+        if frame is None:
+            raise RuntimeError("aerial_clouds: no frame yet (call update_sky() first)")
+        W, H = self._texture_size
+        is_tensor = hasattr(frame, "data_ptr")
+        if not is_tensor and not isinstance(frame, np.ndarray):
+            raise ValueError("aerial_clouds: frame must be a numpy float16 array or a torch float16 tensor, not %s" % type(frame).__name__)
+        if tuple(int(x) for x in frame.shape) != (H, W, 4) or str(frame.dtype).split(".")[-1] != "float16":
+            raise ValueError("aerial_clouds: frame must be a float16 [%d, %d, 4] image, the size of the hemisphere frame" % (H, W))
+        sun = self.frame_data.LIGHT_DIRECTION
+        pc = self._fill_push_constant()
+        if not self.device_buffers:
+            if is_tensor:
+                frame = frame.cpu().numpy()
+            return self.ctx.apply_cloud_aerial(sun, frame, self.ctx.render_cloud_depth(pc, W, H), steps)
+        import torch
+        dev = torch.device("cuda", self.ctx.device_id)
+        if not is_tensor:
+            frame = torch.from_numpy(np.ascontiguousarray(frame))
+        frame = frame.to(dev).contiguous()
+        depth = torch.empty((H, W, 4), dtype=torch.float16, device=dev)
+        out = torch.empty((H, W, 4), dtype=torch.float16, device=dev)
+        stream, done = self._march_stream()
+        self.ctx.render_cloud_depth(pc, W, H, out=depth, stream=stream)            # the apply step reads the depth frame on the same stream
+        self.ctx.apply_cloud_aerial(sun, frame, depth, steps, out=out, stream=stream)
+        done()                                           # torch's stream is behind both launches: the depth frame's memory may be reused on it from here
+        return out
+
     # ---- render thread ------------------------------------------------------------------------------------
     def _march_stream(self):
         """(hip stream handle, done()) for one batch of library calls in device-buffer mode.  The work is enqueued on torch's CURRENT

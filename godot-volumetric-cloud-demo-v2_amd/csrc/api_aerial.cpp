@@ -1,12 +1,14 @@
 // api_aerial.cpp -- the aerial-perspective volume's C ABI (csky_render_aerial_perspective / _device; aerial_core.h, aerial.hip), and
 // the same volume with a cloud shadow map inside it (csky_render_aerial_perspective_shadowed / _device, csky_aerial_shadow_rect; shafts_core.h,
-// shafts.hip).
+// shafts.hip), and the air in front of a cloud frame (csky_apply_cloud_aerial / _device; cloud_aerial_core.h, cloud_aerial.hip;
+// DESIGN.md §16), which reads the caller's two images besides.
 // The call reads the context's transmittance table and nothing else of it: no noise, no sky LUT, no cloud frame, no slot of any ring (geometry and sun
 // travel as kernel arguments), no stream of its own.
 #include <cmath>
 #include "context.h"
 #include "aerial_core.h"
 #include "shafts_core.h"
+#include "cloud_aerial_core.h"
 
 using namespace csky;
 
@@ -79,9 +81,59 @@ int shafts_launch(csky_ctx* c, const char* fn, const AerialGeom& g, ShaftsMap m,
     return CSKY_OK;
 }
 
+// csky_apply_cloud_aerial*: the argument and state checks of both forms, and the kernel's argument block with the default filled in.
+int cloud_aerial_check(csky_ctx* c, const char* fn, const csky_cloud_aerial_params* ap, CloudAerialGeom& g) {
+    if (!ap) return fail(c, CSKY_ERR_INVALID, "%s: params is NULL", fn);
+    if (ap->width < 1 || ap->width > 8192 || ap->height < 1 || ap->height > 8192) return fail(c, CSKY_ERR_INVALID, "%s: width and height must be in [1, 8192]", fn);
+    if (ap->steps < 0 || ap->steps > 64) return fail(c, CSKY_ERR_INVALID, "%s: steps must be in [1, 64], or 0 for 16", fn);
+    g.w = ap->width; g.h = ap->height; g.n = ap->steps ? ap->steps : 16;
+    for (int k = 0; k < 3; k++) {
+        if (!std::isfinite(ap->sun_direction[k])) return fail(c, CSKY_ERR_INVALID, "%s: sun_direction is not finite", fn);
+        g.sun[k] = ap->sun_direction[k];
+    }
+    if (!c->have_trans) return fail(c, CSKY_ERR_STATE, "%s: the transmittance LUT has not been rendered (csky_render_transmittance)", fn);
+    return CSKY_OK;
+}
+
+// The launch on stream s, behind whatever the context's stream has done to the table; both images are read on s.
+int cloud_aerial_launch(csky_ctx* c, const char* fn, const CloudAerialGeom& g, const uint2* d_cloud, const uint2* d_depth, uint2* d_out, hipStream_t s) {
+    HIPCHK(c, hipEventRecord(c->ev_aerial, c->stream));
+    HIPCHK(c, hipStreamWaitEvent(s, c->ev_aerial, 0));
+    const hipError_t e = launch_cloud_aerial(g, c->d_trans_f, c->tw, c->th, d_cloud, d_depth, d_out, s, c->tlut);
+    if (e != hipSuccess) return fail(c, CSKY_ERR_HIP, "%s: kernel launch failed: %s", fn, hipGetErrorString(e));
+    return CSKY_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int csky_apply_cloud_aerial_device(csky_ctx* c, const csky_cloud_aerial_params* ap, const void* d_cloud, const void* d_depth, void* d_out, void* hip_stream) {
+    const char* fn = "csky_apply_cloud_aerial_device";
+    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "%s: ctx is NULL", fn);
+    if (!d_cloud || !d_depth || !d_out) return fail(c, CSKY_ERR_INVALID, "%s: d_cloud, d_depth or d_out is NULL", fn);
+    CloudAerialGeom g;
+    int rc; if ((rc = cloud_aerial_check(c, fn, ap, g)) || (rc = bind(c))) return rc;
+    return cloud_aerial_launch(c, fn, g, static_cast<const uint2*>(d_cloud), static_cast<const uint2*>(d_depth), static_cast<uint2*>(d_out),
+                               hip_stream ? (hipStream_t)hip_stream : (hipStream_t)c->stream);
+}
+
+int csky_apply_cloud_aerial(csky_ctx* c, const csky_cloud_aerial_params* ap, const uint16_t* cloud, const uint16_t* depth, uint16_t* out) {
+    const char* fn = "csky_apply_cloud_aerial";
+    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "%s: ctx is NULL", fn);
+    if (!cloud || !depth || !out) return fail(c, CSKY_ERR_INVALID, "%s: cloud, depth or out is NULL", fn);
+    CloudAerialGeom g;
+    int rc; if ((rc = cloud_aerial_check(c, fn, ap, g)) || (rc = bind(c))) return rc;
+    const size_t n = (size_t)g.w * g.h;
+    if ((rc = c->d_cloud_aerial.grow(c, 2 * n))) return rc;     // nothing of an earlier call is in flight: this form blocks
+    uint2* d_cloud = c->d_cloud_aerial; uint2* d_depth = d_cloud + n;
+    HIPCHK(c, hipMemcpyAsync(d_cloud, cloud, n * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_depth, depth, n * 8, hipMemcpyHostToDevice, c->stream));
+    if ((rc = cloud_aerial_launch(c, fn, g, d_cloud, d_depth, d_cloud, c->stream))) return rc;
+    HIPCHK(c, hipMemcpyAsync(out, d_cloud, n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return CSKY_OK;
+}
 
 int csky_render_aerial_perspective_device(csky_ctx* c, const csky_aerial_params* ap, const csky_view* view, void* d_out, void* hip_stream) {
     const char* fn = "csky_render_aerial_perspective_device";

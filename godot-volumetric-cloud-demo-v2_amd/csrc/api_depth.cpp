@@ -1,0 +1,66 @@
+// api_depth.cpp -- the cloud depth frame's C ABI (csky_render_cloud_depth / _device; depth_core.h, depth.hip).
+// The call reads the bound noise and the push-constant block and nothing else: no LUT, no slot of the cloud frames' constants ring (both constant
+// blocks of a launch are computed here and travel as kernel arguments), no stream of its own.
+#include <cmath>
+#include <cstring>
+#include "context.h"
+#include "depth_core.h"
+
+using namespace csky;
+
+namespace {
+
+// The argument and state checks of both forms.  fn: the entry point's name for the error text.
+int depth_check(csky_ctx* c, const char* fn, const csky_cloud_params* p, const csky_depth_params* dp, size_t pitch_bytes) {
+    if (!p || !dp) return fail(c, CSKY_ERR_INVALID, "%s: NULL argument", fn);
+    if (dp->width < 1 || dp->width > 8192 || dp->height < 1 || dp->height > 8192) return fail(c, CSKY_ERR_INVALID, "%s: width and height must be in [1, 8192]", fn);
+    if (dp->steps < 0 || dp->steps > 1024) return fail(c, CSKY_ERR_INVALID, "%s: steps must be in [1, 1024], or 0 for the context's primary step count", fn);
+    CloudParams cp; memcpy(&cp, p, sizeof cp);
+    const float read[] = {cp.cloud_pos[0], cp.cloud_pos[1], cp.detailed_pos[0], cp.detailed_pos[1], cp.weather_pos[0], cp.weather_pos[1], cp.time, cp.density, cp.cloud_coverage};
+    for (float v : read) if (!std::isfinite(v)) return fail(c, CSKY_ERR_INVALID, "%s: a push-constant field the depth frame reads is not finite", fn);
+    if (pitch_bytes < (size_t)dp->width * 8 || pitch_bytes % 8) return fail(c, CSKY_ERR_INVALID, "%s: row pitch must be a multiple of 8 and >= 8 * width", fn);
+    if (!c->noise.st.have()) return fail(c, CSKY_ERR_STATE, "%s: csky_set_noise has not been called", fn);
+    return CSKY_OK;
+}
+
+// The launch on stream s, for arguments depth_check has passed.
+int depth_launch(csky_ctx* c, const char* fn, const csky_cloud_params* p, const csky_depth_params* dp, uint2* d_out, size_t pitch_bytes, hipStream_t s) {
+    CloudParams cp; memcpy(&cp, p, sizeof cp);
+    const ExactRejects rej = c->noise.st.rejects(cp.cloud_coverage, c->use_window);   // the height window and the cloud-type branch, as the cloud march gets them
+    DepthConsts dc;
+    dc.w = dp->width; dc.h = dp->height; dc.steps = dp->steps == 0 ? c->primary_steps : dp->steps; dc.pitch_px = (uint32_t)(pitch_bytes / 8);
+    FrameConsts fc;
+    depth_frame_consts(cp, dc.w, dc.h, dc.steps, rej.hf_lo, rej.hf_hi, rej.ct_mode, fc);
+    TexSet32 t32; const TexSet32* t32p = nullptr;
+    if (c->noise.st.cell32()) { t32 = texset32(c); t32p = &t32; }
+    const hipError_t e = launch_cloud_depth(texset(c), t32p, fc, dc, d_out, s);
+    if (e != hipSuccess) return fail(c, CSKY_ERR_HIP, "%s: kernel launch failed: %s", fn, hipGetErrorString(e));
+    return CSKY_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int csky_render_cloud_depth_device(csky_ctx* c, const csky_cloud_params* p, const csky_depth_params* dp, void* d_out, size_t pitch, void* hip_stream) {
+    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "csky_render_cloud_depth_device: ctx is NULL");
+    if (!d_out) return fail(c, CSKY_ERR_INVALID, "csky_render_cloud_depth_device: d_out is NULL");
+    const char* fn = "csky_render_cloud_depth_device";
+    int rc; if ((rc = depth_check(c, fn, p, dp, pitch)) || (rc = bind(c))) return rc;
+    return depth_launch(c, fn, p, dp, static_cast<uint2*>(d_out), pitch, hip_stream ? (hipStream_t)hip_stream : (hipStream_t)c->stream);
+}
+
+int csky_render_cloud_depth(csky_ctx* c, const csky_cloud_params* p, const csky_depth_params* dp, uint16_t* out) {
+    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "csky_render_cloud_depth: ctx is NULL");
+    const char* fn = "csky_render_cloud_depth";
+    if (!out) return fail(c, CSKY_ERR_INVALID, "%s: out is NULL", fn);
+    int rc; if ((rc = depth_check(c, fn, p, dp, dp ? (size_t)dp->width * 8 : 0)) || (rc = bind(c))) return rc;
+    const size_t n = (size_t)dp->width * dp->height;
+    if ((rc = c->d_depth.grow(c, n))) return rc;               // nothing of an earlier call is in flight: this form blocks
+    if ((rc = depth_launch(c, fn, p, dp, c->d_depth, (size_t)dp->width * 8, c->stream))) return rc;
+    HIPCHK(c, hipMemcpyAsync(out, c->d_depth, n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return CSKY_OK;
+}
+
+}  // extern "C"

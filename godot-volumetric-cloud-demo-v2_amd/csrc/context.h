@@ -240,6 +240,8 @@ struct csky_ctx {
     csky::DevBuf<uint2> d_aerial;                                          // host form of the aerial-perspective volume: the volume before its copy out, grow-only
     csky::Event ev_aerial;                                                 // the transmittance LUT (the context's stream) -> the volume (caller's stream)
     csky::DevBuf<uint16_t> d_shafts_map;                                   // host form of the shadowed volume: the caller's shadow map, uploaded, grow-only
+    csky::DevBuf<uint2> d_depth;                                           // host form of the cloud depth frame: the frame before its copy out, grow-only
+    csky::DevBuf<uint2> d_cloud_aerial;                                    // host form of csky_apply_cloud_aerial: the cloud frame (corrected in place), then the depth frame, grow-only
     bool census_lean = false;                                  // csky_census_clouds unless CSKY_CENSUS_TALLY=1: count the blocks of the kernel form that keeps no in-cloud tally (kernels.h launch_clouds)
     // asynchronous host form (csky_submit_clouds / csky_collect): a ring of pinned host frames + device frames on rotating internal streams
     // (a slot's capacity is h.count(), in bytes; d holds as many pixels of 8 bytes)

@@ -87,6 +87,19 @@ hipError_t launch_aerial(const AerialGeom& g, const float4* d_trans, int tw, int
 struct ShaftsMap;
 hipError_t launch_shafts(const AerialGeom& g, const ShaftsMap& m, const float4* d_trans, int tw, int th, uint2* d_out, hipStream_t s, int tlut = 0);
 
+// ------------------------------------------------------------------------------------------------ depth.hip
+// the cloud depth frame (depth_core.h): dc.w x dc.h RGBA16F texels into d_out, row pitch dc.pitch_px pixels.  fc: depth_frame_consts; both blocks
+// travel as kernel arguments.  t32: march on the exact fp32-coefficient cells.
+struct DepthConsts;
+hipError_t launch_cloud_depth(const TexSet& t, const TexSet32* t32, const FrameConsts& fc, const DepthConsts& dc, uint2* d_out, hipStream_t s);
+
+// ------------------------------------------------------------------------------------------------ cloud_aerial.hip
+// the air in front of a cloud frame (cloud_aerial_core.h): g.w x g.h RGBA16F texels of d_cloud, placed by d_depth, into d_out, all tightly packed;
+// d_out may be d_cloud.  g travels as a kernel argument
+struct CloudAerialGeom;
+hipError_t launch_cloud_aerial(const CloudAerialGeom& g, const float4* d_trans, int tw, int th, const uint2* d_cloud, const uint2* d_depth, uint2* d_out,
+                               hipStream_t s, int tlut = 0);
+
 // ------------------------------------------------------------------------------------------------ bc7enc.hip
 // BC7 (BPTC) blocks of n_img images of w x h RGBA8 texels (what compress/mode=2 of the *.import files asks the importer for)
 hipError_t launch_bc7_encode(const uint8_t* d_img, int w, int h, int n_img, int quality, uint4* d_blocks, hipStream_t s);

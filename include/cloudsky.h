@@ -439,6 +439,81 @@ int csky_render_aerial_perspective_shadowed_device(csky_ctx* ctx, const csky_aer
  * range of csky_shadow_params: the sun is too low), a NULL pointer, a non-finite sun or a far_km out of range. */
 int csky_aerial_shadow_rect(const csky_aerial_params* params, float center[2], float extent[2]);
 
+/* ---- cloud depth frame: where along each ray the cloud sits --------------------------------------
+ * A hemisphere frame holds (L, alpha) integrated along each ray and nothing about where along the ray the cloud sits.  This call renders, for the
+ * rays of a W x H frame, the distance of the cloud from the observer: for a host to order its own geometry against the clouds, and for
+ * csky_apply_cloud_aerial below.  It is the frame's primary march without its light march.  For pixel (i, j), N steps:
+ *     ray      the frame's own: clouds.glsl:258-262, :248-256, :218-231, :143-145 with texture_size = (W, H), update_position = 0 and N for 128;
+ *              hash() is 0 in fp32, so p starts at the shell entry
+ *     t0     = intersectSphere(camPos, dir, Rb)                                  the distance of the shell entry, the float the ray set-up computes
+ *     T = 1, alpha = 0, sw = 0, swd = 0, front = back = unset, p = start
+ *     for k in 0..N-1:
+ *         p += step                                                              :173
+ *         t  = density(p, texture(weather_noise, p.xz * 0.00006 + 0.5 + weather_pos), 0.0)     :174-177
+ *         if t > 0:                                                              :184
+ *             dt = exp(-density * t * ss)                                        :178
+ *             s  = t0 + (float)(k + 1) * ss                                      metres from the observer; fp32, no contraction
+ *             w  = T * (1 - dt);   sw += w;   swd += w * s
+ *             alpha += (1 - dt) * (1 - alpha);   T *= dt                         :207, :210
+ *             if front is unset: front = s
+ *             back = s
+ *     texel  = dir.y <= 0, or !(sw > 0):  (0, 0, 0, 0)
+ *              else:  mean = clamp(swd / sw, front, back)
+ *                     ( mean / 1000, front / 1000, back / 1000, saturate(alpha) )         four halfs: km, km, km, the frame's alpha
+ * mean is the distance of the samples weighted by what each adds to alpha; front and back are the first and the last in-cloud sample.  Distances
+ * are along the ray, not view-space z.  The positions, t0, s, w, sw, swd and the texel are evaluated in fp32 without contraction, in the order
+ * written; the taps, density() and exp use the march's own cores and the hardware exp2, so alpha is the frame's within an fp16 ulp.  The light
+ * march is not run, and a ray that has become opaque is not cut short: back needs the whole ray.
+ * Of the push-constant block only cloud_pos, detailed_pos, weather_pos, time, density and cloud_coverage are read; texture_size and
+ * update_position are not: the call renders the whole W x H frame.  Pass the frame's own size and step count and the samples are the frame's.
+ * Needs the noise (CSKY_ERR_STATE without it) and NO LUT.  csky_set_height_window and csky_set_exact_cells act as on the cloud march.
+ * Output: RGBA16F, row j, column i.  A host compares a fragment's distance along the pixel's ray (km) with g (front) and b (back). */
+typedef struct {
+    int width, height;     /* pixels, 1..8192 each                                                        */
+    int steps;             /* N, 1..1024; 0 = the context's primary step count (csky_set_march)           */
+} csky_depth_params;
+/* Blocking host form: out_rgba16f receives height rows of width texels, tightly packed.  CSKY_ERR_INVALID: a NULL pointer, a size or step count
+ * out of range, a non-finite float among the fields read. */
+int csky_render_cloud_depth(csky_ctx* ctx, const csky_cloud_params* p, const csky_depth_params* dp, uint16_t* out_rgba16f);
+/* Device form: rows of row_pitch_bytes (a multiple of 8, >= 8 * width) into d_out_rgba16f, asynchronously on hip_stream (the context's own stream
+ * if NULL).  Writes the width x height texels and nothing else: not the pitch padding. */
+int csky_render_cloud_depth_device(csky_ctx* ctx, const csky_cloud_params* p, const csky_depth_params* dp, void* d_out_rgba16f, size_t row_pitch_bytes,
+                                   void* hip_stream);
+
+/* ---- aerial perspective on a cloud frame ---------------------------------------------------------
+ * The reference composites a cloud 2 km overhead and one 60 km out by the same formula and hides the far ones behind a fade
+ * (clouds.gdshader:115).  This call puts the air in front of the clouds of a frame: per pixel the extinction and the in-scattering of the
+ * aerial-perspective volume above over the distance the depth frame holds.  Inputs: a cloud frame and a depth frame of the same W x H, both
+ * RGBA16F, tightly packed; the context's transmittance table and its mapping; a sun direction, used as given (NOT normalised here: like
+ * csky_aerial_params.sun_direction, a sun that is not a unit vector gives phase terms that mean nothing, NaN among them); n steps.
+ * For pixel (i, j), c the cloud texel and z the depth texel:
+ *     if c.a (the half) == 0, or !(z.r > 0):   out = c, byte for byte
+ *     e   = the pixel's normalised direction: clouds.glsl:258-262, :248-256 for a W x H frame, update_position 0
+ *     the column of csky_render_aerial_perspective along e with D = 1, S = n, far_km = (float)z.r:
+ *           ray_origin (0, 0, 6371.5), dt = far_km / (float)n, the skip rule, the step body, L and Tr after the n steps
+ *     C   = M * L;   tr = (((Tr.x + Tr.y) + Tr.z) + Tr.w) * 0.25                that column's one slice, before its rounding to halfs
+ *     out.rgb = half( c.rgb * tr + c.a * (C.rgb / 50) )                         fp32, no contraction, this order;   out.a = c.a's bytes
+ * The distance is the stored half, so the call is a function of its two images; out may be the cloud frame itself (not the depth frame).  A
+ * sun at or under the horizon still applies the extinction.
+ * Approximations: the whole cloud along a ray is placed at its mean distance, and light scattered into the ray inside the cloud is not
+ * attenuated separately from light behind it.  As in the shadowed volume the cloud march's observer stands on the ground while the
+ * atmosphere's stands 0.5 km up: the inconsistency is the reference's.
+ * Ranges: W, H in 1..8192, n in 1..64 (0 = 16), a finite sun (CSKY_ERR_INVALID otherwise, and for a NULL pointer).  Needs the transmittance
+ * table (CSKY_ERR_STATE without it, and after a change of its mapping until it is rendered again) and nothing else; it changes no state. */
+typedef struct {
+    int   width, height;          /* W, H in 1..8192: the size of both images                               */
+    int   steps;                  /* n, 1..64; 0 = 16                                                      */
+    float sun_direction[3];       /* towards the sun, as csky_aerial_params.sun_direction                  */
+} csky_cloud_aerial_params;
+/* Blocking host form: three images of height * width * 4 halfs. */
+int csky_apply_cloud_aerial(csky_ctx* ctx, const csky_cloud_aerial_params* params, const uint16_t* cloud_rgba16f, const uint16_t* depth_rgba16f,
+                            uint16_t* out_rgba16f);
+/* Device form: asynchronous on hip_stream (the context's own stream if NULL), ordered behind what the context's stream has done to the
+ * transmittance table.  Both images are read on that stream: frames rendered on it just before need no further ordering.  Writes the
+ * width x height texels of d_out and nothing else. */
+int csky_apply_cloud_aerial_device(csky_ctx* ctx, const csky_cloud_aerial_params* params, const void* d_cloud_rgba16f, const void* d_depth_rgba16f,
+                                   void* d_out_rgba16f, void* hip_stream);
+
 /* ---- frames in flight ---------------------------------------------------------------------------- */
 /* Policy hint for the automatic segment / schedule choice: n = 2..8: the caller keeps n frames in flight by rotating n streams
  * between consecutive csky_render_*_device calls (always safe: per-frame state lives in eight-deep rings ordered by events); the
