@@ -192,6 +192,11 @@ SYMBOLS = [
     ("csky_render_cloud_depth_device", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.POINTER(DepthParams), C.c_void_p, C.c_size_t, C.c_void_p]),
     ("csky_apply_cloud_aerial", C.c_int, [C.c_void_p, C.POINTER(CloudAerialParams), C.c_void_p, C.c_void_p, C.c_void_p]),
     ("csky_apply_cloud_aerial_device", C.c_int, [C.c_void_p, C.POINTER(CloudAerialParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("csky_render_clouds_dirs", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    ("csky_render_clouds_dirs_device", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("csky_render_clouds_view", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.POINTER(View), C.c_int, C.c_int, C.c_void_p]),
+    ("csky_render_clouds_view_device", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.POINTER(View), C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("csky_composite_view_frames", C.c_int, [C.c_void_p, C.POINTER(CompositeParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("csky_time_clouds", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.c_int, C.POINTER(Bands), C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(CloudStats)]),
     ("csky_get_cloud_stats", C.c_int, [C.c_void_p, C.POINTER(CloudStats)]),
     ("csky_set_kernel_timing", C.c_int, [C.c_void_p, C.c_int]),
@@ -612,6 +617,65 @@ class Context:
         self._chk(self._L.csky_apply_cloud_aerial(self._h, C.byref(p), _ptr(cloud), _ptr(depth), _ptr(out)))
         return out
 
+    def _rays_out(self, name, shape, out):
+        """(device?, out, pitch) for the image of a rays call: a [h, w, 4] torch tensor of 2-byte elements with contiguous texels, or a numpy array."""
+        if out is not None and hasattr(out, "data_ptr"):
+            if out.dim() != 3 or out.element_size() != 2 or tuple(out.shape) != shape or out.stride(2) != 1 or (shape[1] > 1 and out.stride(1) != 4):
+                raise ValueError("%s: out must be a %s tensor of 2-byte elements with contiguous texels" % (name, shape))
+            return True, out, (out.stride(0) * 2 if shape[0] > 1 else shape[1] * 8)
+        if out is None:
+            out = np.zeros(shape, np.float16)
+        if out.shape != shape or out.dtype != np.float16 or not out.flags.c_contiguous:
+            raise ValueError("%s: out must be a contiguous float16 %s array" % (name, shape))
+        return False, out, shape[1] * 8
+
+    def render_clouds_dirs(self, params, dirs, out=None, stream=None):
+        """The direct cloud march over caller-given rays (csky_render_clouds_dirs*, definition: include/cloudsky.h): `dirs` is [h, w, 3] float32, a
+        direction per pixel, used as given; the result is what the hemisphere frame stores for that ray, float16 [h, w, 4].  A direction at or
+        under the horizon, or whose squared length is outside [0.99, 1.01], gives a zero texel.  texture_size and update_position of `params`
+        are not read.  Host path (dirs a numpy array; out None or a numpy float16 array): blocks, returns numpy.  Device path (dirs a contiguous
+        float32 torch tensor on this context's GPU; out a [h, w, 4] tensor of 2-byte elements whose texels are contiguous, its row stride the
+        pitch, or None for a new one): asynchronous on `stream`, returns the tensor.  Needs the noise and a sky LUT."""
+        p = cloud_params(params)
+        if len(dirs.shape) != 3 or int(dirs.shape[2]) != 3:
+            raise ValueError("render_clouds_dirs: dirs must be a [h, w, 3] float32 array (or torch tensor on the GPU)")
+        shape = (int(dirs.shape[0]), int(dirs.shape[1]), 4)
+        if hasattr(dirs, "data_ptr"):
+            import torch
+            if dirs.dtype != torch.float32 or not dirs.is_contiguous():
+                raise ValueError("render_clouds_dirs: a device dirs must be a contiguous float32 tensor")
+            if out is None:
+                out = torch.empty(shape, dtype=torch.float16, device=dirs.device)
+            dev, out, pitch = self._rays_out("render_clouds_dirs", shape, out)
+            if not dev:
+                raise ValueError("render_clouds_dirs: with device dirs, out must be a torch tensor")
+            self._chk(self._L.csky_render_clouds_dirs_device(self._h, C.byref(p), shape[1], shape[0], C.c_void_p(int(dirs.data_ptr())), C.c_void_p(int(out.data_ptr())),
+                                                             C.c_size_t(int(pitch)), C.c_void_p(stream or 0)))
+            return out
+        d = np.ascontiguousarray(dirs, np.float32)
+        dev, out, _ = self._rays_out("render_clouds_dirs", shape, out)
+        if dev:
+            raise ValueError("render_clouds_dirs: with host dirs, out must be a numpy array")
+        self._chk(self._L.csky_render_clouds_dirs(self._h, C.byref(p), shape[1], shape[0], _ptr(d), _ptr(out)))
+        return out
+
+    def render_clouds_view(self, params, basis, fov_y_degrees, width, height, out=None, stream=None):
+        """The direct cloud march of a camera view (csky_render_clouds_view*, definition: include/cloudsky.h): the ray of every SCREEN pixel of a
+        width x height perspective camera, the EYEDIR composite_view uses (basis: 3x3, columns = the camera's right / up / back axes), marched as
+        the hemisphere frame's rays are; float16 [height, width, 4], zero under the horizon.  Host path (out None or a numpy float16 array):
+        blocks, returns numpy.  Device path (out a [height, width, 4] torch tensor of 2-byte elements on this context's GPU whose texels are
+        contiguous; its row stride is the pitch): asynchronous on `stream`, written in place, returns the tensor.  Needs the noise and a sky LUT."""
+        p = cloud_params(params)
+        shape = (int(height), int(width), 4)
+        v = View((C.c_float * 9)(*[float(x) for x in np.asarray(basis, np.float32).T.reshape(-1)]), float(fov_y_degrees))   # column-major basis
+        dev, out, pitch = self._rays_out("render_clouds_view", shape, out)
+        if dev:
+            self._chk(self._L.csky_render_clouds_view_device(self._h, C.byref(p), C.byref(v), shape[1], shape[0], C.c_void_p(int(out.data_ptr())), C.c_size_t(int(pitch)),
+                                                             C.c_void_p(stream or 0)))
+        else:
+            self._chk(self._L.csky_render_clouds_view(self._h, C.byref(p), C.byref(v), shape[1], shape[0], _ptr(out)))
+        return out
+
     def set_shadow_exact_end(self, enabled=True):
         """A/B switch (cloudsky_internal.h): False makes every texel of the shadow map take all its samples; the maps are byte-identical."""
         self._chk(self._L.csky_set_shadow_exact_end(self._h, int(bool(enabled))))
@@ -697,6 +761,19 @@ class Context:
         v = (C.c_float * 10)(*([float(x) for x in np.asarray(basis, np.float32).T.reshape(-1)] + [float(fov_y_degrees)]))   # column-major basis, then the fov
         out = np.zeros((out_h, out_w, 4), np.uint16)
         self._chk(self._L.csky_composite_view(self._h, C.byref(p), C.cast(v, C.c_void_p), _ptr(a[0]), _ptr(a[1]), _ptr(a[2]), _ptr(a[3]), _ptr(out)))
+        return out.view(np.float16)
+
+    def composite_view_frames(self, cloud_from, cloud_to, sky_from, sky_to, light_dir, basis, fov_y_degrees, blend_amount=0.0, sun_disk_scale=2.0):
+        """composite_view with cloud_from / cloud_to being VIEW frames of the same camera (render_clouds_view), float16 [out_h, out_w, 4]: each
+        screen pixel reads its own cloud texel instead of tapping a hemisphere frame (csky_composite_view_frames)."""
+        a = [np.ascontiguousarray(x).view(np.uint16) for x in (cloud_from, cloud_to, sky_from, sky_to)]
+        out_h, out_w = a[0].shape[0], a[0].shape[1]
+        p = CompositeParams(out_w, out_h, a[0].shape[1], a[0].shape[0], a[2].shape[1], a[2].shape[0], float(blend_amount), float(sun_disk_scale))
+        for k in range(3):
+            p.light_direction[k] = float(light_dir[k])
+        v = (C.c_float * 10)(*([float(x) for x in np.asarray(basis, np.float32).T.reshape(-1)] + [float(fov_y_degrees)]))   # column-major basis, then the fov
+        out = np.zeros((out_h, out_w, 4), np.uint16)
+        self._chk(self._L.csky_composite_view_frames(self._h, C.byref(p), C.cast(v, C.c_void_p), _ptr(a[0]), _ptr(a[1]), _ptr(a[2]), _ptr(a[3]), _ptr(out)))
         return out.view(np.float16)
 
     def render_radiance(self, cloud_from, cloud_to, sky_from, sky_to, light_dir, blend_amount=0.0, sun_disk_scale=2.0, face_size=64, layers=8, source_size=0,

@@ -265,12 +265,33 @@ class CloudSky:
         sf, st = (host(t) for t in self.sky_lut.back_texture)   # sky_blend_from/to_texture = the two OLDER ring copies (cloud_sky.gd:147-148)
         return self.ctx.composite_sky(bf, bt, sf, st, self.frame_data.LIGHT_DIRECTION, self.blend_amount, self.sun_disk_scale, out_w, out_h)
 
-    def sky_view(self, basis, fov_y_degrees=75.0, out_w=1152, out_h=648):
+    def cloud_view(self, basis, fov_y_degrees=75.0, out_w=1152, out_h=648):
+        """The clouds of the current frame data marched along the rays of a perspective camera's SCREEN pixels instead of the hemisphere frame's
+        (csky_render_clouds_view; the definition: include/cloudsky.h): float16 [out_h, out_w, 4], what the hemisphere frame would store for each
+        ray, at the camera's own angular resolution; zero under the horizon.  The block _fill_push_constant() packs, the context's step counts.
+        basis as sky_view takes it.  A torch CUDA tensor with device_buffers=True.  Not called by update_sky()."""
+        pc = self._fill_push_constant()
+        if not self.device_buffers:
+            return self.ctx.render_clouds_view(pc, basis, fov_y_degrees, out_w, out_h)
+        import torch
+        out = torch.empty((int(out_h), int(out_w), 4), dtype=torch.float16, device=torch.device("cuda", self.ctx.device_id))
+        stream, done = self._march_stream()
+        self.ctx.render_clouds_view(pc, basis, fov_y_degrees, out_w, out_h, out=out, stream=stream)
+        done()
+        return out
+
+    def sky_view(self, basis, fov_y_degrees=75.0, out_w=1152, out_h=648, direct=False):
         """The same through a perspective camera: one EYEDIR per SCREEN pixel, the way the engine evaluates clouds.gdshader
-        (csky_composite_view).  basis: 3x3, columns = the camera's right / up / back axes (Camera3D.global_transform.basis)."""
+        (csky_composite_view).  basis: 3x3, columns = the camera's right / up / back axes (Camera3D.global_transform.basis).
+        direct=True: the clouds are marched for this very view (cloud_view) instead of tapped from the hemisphere frames, and composited with
+        csky_composite_view_frames; both cloud images are that one frame, so blend_amount has no effect on the clouds."""
         def host(t):
             return t.cpu().numpy() if hasattr(t, "cpu") else t
         self.flush()
+        if direct:
+            cv = host(self.cloud_view(basis, fov_y_degrees, out_w, out_h))
+            sf, st = (host(t) for t in self.sky_lut.back_texture)
+            return self.ctx.composite_view_frames(cv, cv, sf, st, self.frame_data.LIGHT_DIRECTION, basis, fov_y_degrees, self.blend_amount, self.sun_disk_scale)
         bf, bt = host(self.textures[self.texture_to_blend_from]), host(self.textures[self.texture_to_blend_to])
         sf, st = (host(t) for t in self.sky_lut.back_texture)
         return self.ctx.composite_view(bf, bt, sf, st, self.frame_data.LIGHT_DIRECTION, basis, fov_y_degrees, self.blend_amount, self.sun_disk_scale, out_w, out_h)

@@ -7,6 +7,7 @@
 #include <cstring>
 #include "context.h"
 #include "radiance_core.h"
+#include "rays_core.h"
 
 using namespace csky;
 
@@ -22,16 +23,18 @@ CompositeArgs composite_args(const csky_ctx* c, const csky_composite_params* p, 
     a.blend_amount = p->blend_amount; a.sun_disk_scale = p->sun_disk_scale;
     a.sun[0] = p->light_direction[0]; a.sun[1] = p->light_direction[1]; a.sun[2] = p->light_direction[2];
     a.out_w = p->out_w; a.out_h = p->out_h;
-    a.view_mode = 0; a.tan_half_fov_y = 1.0f; a.aspect = 1.0f;
+    a.view_mode = 0; a.tan_half_fov_y = 1.0f; a.aspect = 1.0f; a.cloud_mode = 0;
     for (int k = 0; k < 9; k++) a.cam[k] = (k % 4 == 0) ? 1.0f : 0.0f;
     return a;
 }
 int composite_impl(csky_ctx* c, const csky_composite_params* p, const csky_view* view, const uint16_t* cloud_from, const uint16_t* cloud_to,
-                   const uint16_t* sky_from, const uint16_t* sky_to, uint16_t* out) {
+                   const uint16_t* sky_from, const uint16_t* sky_to, uint16_t* out, int cloud_mode = 0) {
     if (!c) return fail(nullptr, CSKY_ERR_INVALID, "csky_composite_sky: ctx is NULL");
     if (!p || !cloud_from || !cloud_to || !sky_from || !sky_to || !out) return fail(c, CSKY_ERR_INVALID, "csky_composite_sky: NULL argument");
     if (p->out_w < 1 || p->out_h < 1 || p->cloud_w < 1 || p->cloud_h < 1 || p->sky_w < 1 || p->sky_h < 1 || p->out_w > 16384 || p->out_h > 16384)
         return fail(c, CSKY_ERR_INVALID, "csky_composite_sky: bad image size");
+    if (cloud_mode == 1 && (p->cloud_w != p->out_w || p->cloud_h != p->out_h))
+        return fail(c, CSKY_ERR_INVALID, "csky_composite_view_frames: cloud_w x cloud_h must equal out_w x out_h (the cloud images are view frames)");
     int rc; if ((rc = bind(c))) return rc;
     if ((rc = ensure_default_trans(c))) return rc;            // source_transmittance, clouds_material.tres
     const size_t cb = (size_t)p->cloud_w * p->cloud_h * 8, sb = (size_t)p->sky_w * p->sky_h * 8, ob = (size_t)p->out_w * p->out_h * 8;
@@ -43,10 +46,8 @@ int composite_impl(csky_ctx* c, const csky_composite_params* p, const csky_view*
     up(0, cloud_from, cb); up(cb, cloud_to, cb); up(2 * cb, sky_from, sb); up(2 * cb + sb, sky_to, sb);
     CompositeArgs a = composite_args(c, p, d, d + cb, d + 2 * cb, d + 2 * cb + sb);
     if (view) {
-        a.view_mode = 1;
-        for (int k = 0; k < 9; k++) a.cam[k] = view->basis[k];
-        a.tan_half_fov_y = tanf(view->fov_y_degrees * 0.5f * 3.14159265358979323846f / 180.0f);
-        a.aspect = (float)p->out_w / (float)p->out_h;
+        composite_view_args(a, view->basis, view->fov_y_degrees, p->out_w, p->out_h);   // rays_core.h: the view march's projection is this one
+        a.cloud_mode = cloud_mode;
     }
     if (e == hipSuccess) e = launch_composite(a, reinterpret_cast<uint2*>(d + 2 * cb + 2 * sb), c->stream, c->tlut);
     if (e == hipSuccess) e = hipMemcpyAsync(out, d + 2 * cb + 2 * sb, ob, hipMemcpyDeviceToHost, c->stream);
@@ -138,6 +139,12 @@ int csky_composite_view(csky_ctx* c, const csky_composite_params* p, const csky_
     if (!view) return fail(c, CSKY_ERR_INVALID, "csky_composite_view: view is NULL");
     if (!(view->fov_y_degrees > 0.0f && view->fov_y_degrees < 180.0f)) return fail(c, CSKY_ERR_INVALID, "csky_composite_view: fov_y_degrees must be in (0, 180)");
     return composite_impl(c, p, view, cloud_from, cloud_to, sky_from, sky_to, out);
+}
+int csky_composite_view_frames(csky_ctx* c, const csky_composite_params* p, const csky_view* view, const uint16_t* cloud_from, const uint16_t* cloud_to,
+                               const uint16_t* sky_from, const uint16_t* sky_to, uint16_t* out) {
+    if (!view) return fail(c, CSKY_ERR_INVALID, "csky_composite_view_frames: view is NULL");
+    if (!(view->fov_y_degrees > 0.0f && view->fov_y_degrees < 180.0f)) return fail(c, CSKY_ERR_INVALID, "csky_composite_view_frames: fov_y_degrees must be in (0, 180)");
+    return composite_impl(c, p, view, cloud_from, cloud_to, sky_from, sky_to, out, 1);
 }
 
 int csky_render_radiance_device(csky_ctx* c, const csky_composite_params* p, const csky_radiance_params* rp, const void* d_cloud_from, const void* d_cloud_to,

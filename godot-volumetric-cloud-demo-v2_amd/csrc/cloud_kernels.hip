@@ -874,3 +874,54 @@ hipError_t launch_clouds(int variant, int seg, const TexSet& t, const FrameConst
 }
 
 }  // namespace csky
+
+// ---- the direct march: caller-given rays ------------------------------------------------------------------------
+// clouds.glsl sky(dir) for the directions of a W x H image the caller describes (a buffer of directions, or a camera view) instead of the
+// hemi-octahedral grid's: render_block's whole-ray form with another front end.  One pixel per lane, an 8x8 tile per wavefront, four tiles side by
+// side per workgroup (32 x 8 pixels), march_compact<true, false> (whole rays, no tally: nobody reads a count here) on the frame constants the cloud
+// frame's own set-up kernel wrote.  A plain launch in natural order: workgroup b is footprint b, row-major.  Lanes outside the image and lanes whose
+// direction fails rays_core.h rays_accept do not march (`above = false`): they take no sample and compute no texture address; the latter store zeros.
+#include "rays_core.h"
+#pragma clang fp contract(off)   // (rays_core.h ends with contraction on, like cloud_core.h)
+
+namespace csky {
+
+// SRC 0: directions from `dirs` ([H][W][3] floats, tightly packed); 1: the view of G (composite_eyedir, view_mode 1)
+template <int SRC, class TS>
+__global__ __launch_bounds__(256, CSKY_COMPACT_WAVES) void clouds_rays_kernel(TS T, const FrameConsts* __restrict__ fcp, RaysGeom G, const float* __restrict__ dirs,
+                                                                              uint2* __restrict__ out) {
+    __shared__ float lds[4][CQ_FLOATS];
+    const int tiles_x = (G.w + 31) >> 5;
+    const int slab = (int)blockIdx.x / tiles_x, bx = (int)blockIdx.x - slab * tiles_x;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int gx = bx * 32 + wave * 8 + (lane & 7);
+    const int gy = slab * 8 + (lane >> 3);
+    const bool valid = gx < G.w && gy < G.h;
+    const FrameConsts& fc = *fcp;
+    T.detail_lds = nullptr;                                    // compile-time constant here: the LDS tap path folds away
+    float ex = 0.0f, ey = 0.0f, ez = 0.0f;                     // (0, 0, 0) fails rays_accept
+    if constexpr (SRC == 0) {
+        if (valid) { const float* __restrict__ d = dirs + ((size_t)gy * (size_t)G.w + (size_t)gx) * 3; ex = d[0]; ey = d[1]; ez = d[2]; }
+    } else {
+        rays_view_dir(G, valid ? gx : 0, valid ? gy : 0, ex, ey, ez);
+    }
+    Ray ray = rays_ray(fc, ex, ey, ez);
+    if (!valid) ray.above = false;
+    const MarchOut o = march_compact<true, false>(T, fc, ray, &lds[wave][0], 0, fc.primary_steps);
+    if (valid) out[(size_t)gy * G.pitch_px + gx] = pack_half4(f2h(o.r), f2h(o.g), f2h(o.b), f2h(o.a));   // store_pixel's packing
+}
+
+hipError_t launch_clouds_rays(const TexSet& t, const TexSet32* t32, const FrameConsts* d_fc, const RaysGeom& g, const float* d_dirs, uint2* d_out, hipStream_t s) {
+    if (g.w < 1 || g.h < 1 || g.w > 8192 || g.h > 8192 || g.pitch_px < (uint32_t)g.w) return hipErrorInvalidValue;
+    const unsigned grid = (unsigned)(((g.w + 31) >> 5) * ((g.h + 7) >> 3));
+    if (t32) {
+        if (d_dirs) clouds_rays_kernel<0, TexSet32><<<grid, 256, 0, s>>>(*t32, d_fc, g, d_dirs, d_out);
+        else clouds_rays_kernel<1, TexSet32><<<grid, 256, 0, s>>>(*t32, d_fc, g, d_dirs, d_out);
+    } else {
+        if (d_dirs) clouds_rays_kernel<0, TexSet><<<grid, 256, 0, s>>>(t, d_fc, g, d_dirs, d_out);
+        else clouds_rays_kernel<1, TexSet><<<grid, 256, 0, s>>>(t, d_fc, g, d_dirs, d_out);
+    }
+    return hipGetLastError();
+}
+
+}  // namespace csky

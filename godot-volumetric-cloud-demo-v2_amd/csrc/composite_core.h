@@ -26,6 +26,9 @@ struct CompositeArgs {
     int view_mode;
     float cam[9];                                                       // column-major: cam[0..2] = basis.x, [3..5] = basis.y, [6..8] = basis.z
     float tan_half_fov_y, aspect;
+    // where `clouds` of G:112 comes from: 0 = cloud_from / cloud_to are hemi-octahedral hemisphere frames tapped at the encoded direction (G:106-112);
+    // 1 = they are out_w x out_h view frames (cw x ch = out_w x out_h) of the same view, read at the output pixel itself
+    int cloud_mode;
 };
 
 struct C3 { float x, y, z; };
@@ -87,22 +90,30 @@ CSKY_HD void composite_eyedir(const CompositeArgs& A, int i, int j, float& ex, f
 template <int TLUT = TLUT_REFERENCE> CSKY_HD C3 composite_pixel(const CompositeArgs& A, int i, int j) {
     float ex, ey, ez;
     composite_eyedir(A, i, j, ex, ey, ez);                                               // EYEDIR
-    // G:106-110: clamp below the horizon, hemi-octahedral encode of norm.xzy
-    float nx = ex, ny = fmaxf(0.0f, ey), nz = ez;
-    const float nl = sqrtf(nx * nx + ny * ny + nz * nz);
-    nx = nx / nl; ny = ny / nl; nz = nz / nl;
-    float ox = nx, oy = nz, oz = ny;                                                     // e = norm.xzy
-    const float dsum = fabsf(ox) + fabsf(oy) + fabsf(oz);                                // G:23
-    ox = ox / dsum; oy = oy / dsum; oz = oz / dsum;
-    if (!(oz >= 0.0f)) {                                                                 // G:24 (dead: norm.y >= 0)
-        const float sx = ox >= 0.0f ? 1.0f : -1.0f, sy = oy >= 0.0f ? 1.0f : -1.0f;
-        const float wx = (1.0f - fabsf(oy)) * sx, wy = (1.0f - fabsf(ox)) * sy;
-        ox = wx; oy = wy;
+    C4 bf, bt;
+    if (A.cloud_mode == 1) {
+        // view frames: the texel of this very pixel, marched along EYEDIR (cloudsky.h csky_composite_view_frames)
+        const uint16_t *f = A.cloud_from + ((size_t)j * A.cw + i) * 4, *t = A.cloud_to + ((size_t)j * A.cw + i) * 4;
+        bf.x = h2f(f[0]); bf.y = h2f(f[1]); bf.z = h2f(f[2]); bf.w = h2f(f[3]);
+        bt.x = h2f(t[0]); bt.y = h2f(t[1]); bt.z = h2f(t[2]); bt.w = h2f(t[3]);
+    } else {
+        // G:106-110: clamp below the horizon, hemi-octahedral encode of norm.xzy
+        float nx = ex, ny = fmaxf(0.0f, ey), nz = ez;
+        const float nl = sqrtf(nx * nx + ny * ny + nz * nz);
+        nx = nx / nl; ny = ny / nl; nz = nz / nl;
+        float ox = nx, oy = nz, oz = ny;                                                     // e = norm.xzy
+        const float dsum = fabsf(ox) + fabsf(oy) + fabsf(oz);                                // G:23
+        ox = ox / dsum; oy = oy / dsum; oz = oz / dsum;
+        if (!(oz >= 0.0f)) {                                                                 // G:24 (dead: norm.y >= 0)
+            const float sx = ox >= 0.0f ? 1.0f : -1.0f, sy = oy >= 0.0f ? 1.0f : -1.0f;
+            const float wx = (1.0f - fabsf(oy)) * sx, wy = (1.0f - fabsf(ox)) * sy;
+            ox = wx; oy = wy;
+        }
+        float uvy = oy * 0.5f + 0.5f;                                                        // G:27-29
+        const float uvx = ox * 0.5f + uvy;
+        uvy = ox * -0.5f + uvy;
+        bf = tap_half_clamp(A.cloud_from, A.cw, A.ch, uvx, uvy); bt = tap_half_clamp(A.cloud_to, A.cw, A.ch, uvx, uvy);   // G:111-112
     }
-    float uvy = oy * 0.5f + 0.5f;                                                        // G:27-29
-    const float uvx = ox * 0.5f + uvy;
-    uvy = ox * -0.5f + uvy;
-    const C4 bf = tap_half_clamp(A.cloud_from, A.cw, A.ch, uvx, uvy), bt = tap_half_clamp(A.cloud_to, A.cw, A.ch, uvx, uvy);   // G:111-112
     const float cr = mixf(bf.x, bt.x, A.blend_amount), cg = mixf(bf.y, bt.y, A.blend_amount), cb = mixf(bf.z, bt.z, A.blend_amount),
                 ca = mixf(bf.w, bt.w, A.blend_amount);                                   // G:113
     // get_atmo(EYEDIR), G:87-103

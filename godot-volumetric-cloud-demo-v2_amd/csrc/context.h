@@ -1,6 +1,6 @@
 // context.h -- the context of libcloudsky (csky_ctx) and the host helpers its C ABI sources share.  Internal to libcloudsky:
 // api.cpp (lifecycle, textures, cloud entry points, host ring), api_lut.cpp (the transmittance and sky LUTs), clouds_launch.cpp (the cloud kernel
-// launch), api_sky.cpp (compositor, radiance cubemap), api_shadow.cpp (cloud shadow map), api_aerial.cpp (aerial-perspective volume), api_external.cpp (zero-copy frames), api_multi.cpp (the
+// launch), api_sky.cpp (compositor, radiance cubemap), api_shadow.cpp (cloud shadow map), api_aerial.cpp (aerial-perspective volume), api_rays.cpp (the direct cloud march), api_external.cpp (zero-copy frames), api_multi.cpp (the
 // multi-device handle).
 // Ownership: every device buffer, pinned buffer, event and stream of the context is a member of one of the owner types of owners.h and dies with
 // the context (csky_destroy: bind the device, wait for it, delete).  A buffer's count() is its capacity; raw pointers and raw handles in the
@@ -242,7 +242,14 @@ struct csky_ctx {
     csky::DevBuf<uint16_t> d_shafts_map;                                   // host form of the shadowed volume: the caller's shadow map, uploaded, grow-only
     csky::DevBuf<uint2> d_depth;                                           // host form of the cloud depth frame: the frame before its copy out, grow-only
     csky::DevBuf<uint2> d_cloud_aerial;                                    // host form of csky_apply_cloud_aerial: the cloud frame (corrected in place), then the depth frame, grow-only
-    bool census_lean = false;                                  // csky_census_clouds unless CSKY_CENSUS_TALLY=1: count the blocks of the kernel form that keeps no in-cloud tally (kernels.h launch_clouds)
+    // the direct march (csky_render_clouds_dirs / _view, api_rays.cpp): frame constants of its own, written by the cloud frame's set-up kernel on the
+    // context's stream (no slot of the frame ring).  One event orders both ways: recorded behind the set-up, the caller's stream waits for it; recorded
+    // again behind the march, the context's stream waits for it before the next call's set-up overwrites the block.  Both are made by the first call.
+    csky::DevBuf<csky::FrameConsts> d_rays_fc;
+    csky::Event ev_rays; bool rays_pending = false;
+    csky::DevBuf<float> d_rays_dirs;                                       // host form: the caller's directions, uploaded, grow-only
+    csky::DevBuf<uint2> d_rays_out;                                        // host forms: the image before its copy out, grow-only
+    bool census_lean = false;                                 // csky_census_clouds unless CSKY_CENSUS_TALLY=1: count the blocks of the kernel form that keeps no in-cloud tally (kernels.h launch_clouds)
     // asynchronous host form (csky_submit_clouds / csky_collect): a ring of pinned host frames + device frames on rotating internal streams
     // (a slot's capacity is h.count(), in bytes; d holds as many pixels of 8 bytes)
     struct HostSlot { csky::Stream s; csky::Event done; csky::DevBuf<uint2> d; csky::PinnedBuf h; long long ticket = -1; int w = 0, hh = 0; bool busy = false; };

@@ -70,6 +70,11 @@ hipError_t launch_static_order(int mode, int tiles_x, int slabs, int grid, uint3
 hipError_t launch_interleave_bands(const void* d_gathered, size_t member_stride_bytes, int members, size_t band_bytes, int total_bands, void* d_frame, hipStream_t s);
 // test hook: cloud_core.h::sqrt_shell over an array
 hipError_t launch_sqrt_shell(const float* d_in, float* d_out, size_t n, hipStream_t s);
+// the direct march (rays_core.h): g.w x g.h RGBA16F texels into d_out, row pitch g.pitch_px pixels, for the directions of d_dirs ([h][w][3] floats),
+// or for the view of g when d_dirs is null.  d_fc: the cloud frame's own frame constants (launch_frame_setup*).  t32: march on the exact
+// fp32-coefficient cells.  A plain launch in natural order; g travels as a kernel argument.
+struct RaysGeom;
+hipError_t launch_clouds_rays(const TexSet& t, const TexSet32* t32, const FrameConsts* d_fc, const RaysGeom& g, const float* d_dirs, uint2* d_out, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------ shadow.hip
 // the cloud shadow map (shadow_core.h): sc.w x sc.h halfs into d_out, row pitch sc.pitch_h halfs.  fc: shadow_frame_consts; both blocks travel as

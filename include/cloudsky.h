@@ -514,6 +514,43 @@ int csky_apply_cloud_aerial(csky_ctx* ctx, const csky_cloud_aerial_params* param
 int csky_apply_cloud_aerial_device(csky_ctx* ctx, const csky_cloud_aerial_params* params, const void* d_cloud_rgba16f, const void* d_depth_rgba16f,
                                    void* d_out_rgba16f, void* hip_stream);
 
+/* ---- the direct cloud march: camera views and caller-given rays --------------------- */
+/* clouds.glsl:218-236 sky(dir) is a function of a direction; only main() ties it to the hemi-octahedral grid.  These calls march the rays of a
+ * W x H image the caller describes (a direction per pixel, or a camera view) and store what the hemisphere frame would store for that ray.
+ * For pixel (i, j), N = the context's primary steps:
+ *   e       dirs form: the three floats of dirs[j * W + i], used as given (sky(dir) does not normalise either)
+ *           view form: the compositor's EYEDIR of screen pixel (i, j) for view->basis, Godot's vertical field of view and aspect = W / H, exactly
+ *                      as csky_composite_view computes it for an out_w x out_h = W x H image
+ *   accept  e.y > 0  and  0.99 <= (e.x*e.x + e.y*e.y) + e.z*e.z <= 1.01   (fp32, no contraction; NaN fails every test)
+ *           not accepted: the texel is (0, 0, 0, 0) and the ray takes no sample
+ *   ray     clouds.glsl:221-230 and :143-145 from e: t0, t1 = intersectSphere(camPos, e, Rb / Rt); start, end; shelldist = |end - start|;
+ *           raystep = e * shelldist / N; ss = |raystep|; dir = raystep / ss; p = start
+ *   texel   march() of clouds.glsl:139-215 on that ray, exactly as the hemisphere frame's: L.rgb, alpha, four halves
+ * The 1 % band on |e|^2 is not a tolerance on the result: a direction inside it is used unnormalised (the march prologue's own normalisation,
+ * :144, applies as it always has).  It keeps a garbage direction from ever computing a texture address.  Fed the directions of the hemisphere
+ * grid, the dirs form returns the bytes of csky_render_clouds.
+ * Of the push-constant block, texture_size and update_position are not read: they may hold anything, and the bytes do not depend on them.
+ * Everything else is read as for a cloud frame.  csky_set_march, csky_set_early_out, csky_set_exact_cells and csky_set_height_window act as on
+ * the cloud frame.  The call needs the noise and a sky LUT (CSKY_ERR_STATE otherwise, with csky_render_clouds' messages).  It takes no slot of
+ * the cloud frames' ring and changes nothing a cloud frame reads: frames rendered before, between and after, with any number in flight, are
+ * what they were.  Two rays calls are ordered one behind the other (they share one block of frame constants).
+ * Ranges: W, H in 1..8192; the pitch a multiple of 8 and >= 8 W; a finite basis and a field of view in (0, 180) (CSKY_ERR_INVALID otherwise,
+ * and for a NULL pointer).  The launch is a plain one in natural order: no cost-feedback schedule, no persistent form, no ray segments. */
+/* Blocking host forms: dirs_xyz is h * w * 3 floats, out h * w * 4 halfs. */
+int csky_render_clouds_dirs(csky_ctx* ctx, const csky_cloud_params* p, int w, int h, const float* dirs_xyz, uint16_t* out_rgba16f);
+int csky_render_clouds_view(csky_ctx* ctx, const csky_cloud_params* p, const csky_view* view, int w, int h, uint16_t* out_rgba16f);
+/* Device forms: asynchronous on hip_stream (the context's own stream if NULL), ordered behind the frame set-up the call enqueues on the
+ * context's stream.  d_dirs_xyz (tightly packed) is read on hip_stream.  Write the w x h texels of d_out and nothing else. */
+int csky_render_clouds_dirs_device(csky_ctx* ctx, const csky_cloud_params* p, int w, int h, const void* d_dirs_xyz, void* d_out_rgba16f,
+                                   size_t row_pitch_bytes, void* hip_stream);
+int csky_render_clouds_view_device(csky_ctx* ctx, const csky_cloud_params* p, const csky_view* view, int w, int h, void* d_out_rgba16f,
+                                   size_t row_pitch_bytes, void* hip_stream);
+/* csky_composite_view with cloud_from / cloud_to being out_w x out_h VIEW frames (csky_render_clouds_view of the same view), read at (i, j)
+ * instead of tapped bilinearly in a hemisphere frame (clouds.gdshader:106-112 become two texel reads; everything from the mix of line 112 on is
+ * csky_composite_view's).  p->cloud_w / cloud_h must equal out_w / out_h (CSKY_ERR_INVALID otherwise). */
+int csky_composite_view_frames(csky_ctx* ctx, const csky_composite_params* p, const csky_view* view, const uint16_t* cloud_from,
+                               const uint16_t* cloud_to, const uint16_t* sky_from, const uint16_t* sky_to, uint16_t* out_rgba16f);
+
 /* ---- frames in flight ---------------------------------------------------------------------------- */
 /* Policy hint for the automatic segment / schedule choice: n = 2..8: the caller keeps n frames in flight by rotating n streams
  * between consecutive csky_render_*_device calls (always safe: per-frame state lives in eight-deep rings ordered by events); the
