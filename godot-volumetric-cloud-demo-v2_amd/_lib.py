@@ -865,7 +865,9 @@ class Context:
         return order, left, scratch
 
     def read_baked_texture(self, which):
-        """Test hook: the device layouts / mip chains csky_set_noise built, as raw bytes (0 shape, 1 detail, 2 weather, 3 / 4 8-bit chains)."""
+        """Test hook: the device layouts / mip chains csky_set_noise built, as raw bytes (0 shape, 1 detail, 2 weather, 3 / 4 8-bit chains, 5 the
+        unpacked fp16 detail chain, 6 / 7 / 8 the exact fp32 cells of shape / detail / weather -- CloudSkyError with code CSKY_ERR_STATE when the
+        bound set has none --, 9 the 24 bytes the context holds from the bake: uint64 inexact; int32 rmin, rmax, bmax; float32 lod5)."""
         n = C.c_size_t()
         self._chk(self._L.csky_read_baked_texture(self._h, int(which), None, 0, C.byref(n)))
         out = np.zeros(n.value, np.uint8)

@@ -15,6 +15,7 @@
 #include <vector>
 #include "context.h"
 #include "bake_core.h"
+#include "mip_args.h"
 #include "cloud_core.h"
 #include "order_core.h"
 
@@ -207,17 +208,32 @@ int csky_read_baked_texture(csky_ctx* c, int which, void* out, size_t capacity, 
     int rc; if ((rc = bind(c))) return rc;
     const NoiseSet& ns = c->noise;
     const void* src = nullptr; size_t n = 0;
+    // 9: what the context HOLDS from the bake (NoiseHeld, not the device scratch): the values the kernels are launched with
+    struct { uint64_t inexact; int32_t rmin, rmax, bmax; float lod5; } held;
+    static_assert(sizeof held == 24, "which == 9 is 24 bytes");
+    if (which >= 6 && which <= 8 && !ns.st.cell32())          // released (or never built) by the last bind: nothing to read
+        return fail(c, CSKY_ERR_STATE, "csky_read_baked_texture: the bound textures have no exact cells (which = %d; they fit fp16 and csky_set_exact_cells is 0)", which);
     switch (which) {
         case 0: src = ns.d_shape; n = SHAPE_CELLS * sizeof(ShapeTexel); break;
         case 1: src = ns.d_detail; n = DETAIL_CELLS * sizeof(uint4); break;
         case 2: src = ns.d_weather; n = WEATHER_CELLS * sizeof(uint4); break;
         case 3: src = ns.d_raw_large; n = RAW_SHAPE_CHAIN; break;
         case 4: src = ns.d_raw_small; n = RAW_DETAIL_CHAIN; break;
-        default: return fail(c, CSKY_ERR_INVALID, "csky_read_baked_texture: which must be 0..4");
+        case 5: src = ns.d_detail_h; n = DETAIL_CELLS * sizeof(uint16_t); break;      // without the 8-half pad of the allocation
+        case 6: src = ns.d_shape32; n = SHAPE32_F4 * sizeof(float4); break;
+        case 7: src = ns.d_detail32; n = DETAIL32_F4 * sizeof(float4); break;
+        case 8: src = ns.d_weather32; n = WEATHER32_F4 * sizeof(float4); break;
+        case 9: {
+            const WeatherRange w = ns.st.range();
+            held.inexact = (uint64_t)ns.st.inexact(); held.rmin = w.rmin; held.rmax = w.rmax; held.bmax = w.bmax; held.lod5 = ns.st.detail_lod5();
+            n = sizeof held; break;
+        }
+        default: return fail(c, CSKY_ERR_INVALID, "csky_read_baked_texture: which must be 0..9");
     }
     *bytes = n;
     if (!out) return CSKY_OK;
     if (capacity < n) return fail(c, CSKY_ERR_INVALID, "csky_read_baked_texture: buffer too small (%zu < %zu)", capacity, n);
+    if (which == 9) { memcpy(out, &held, n); return CSKY_OK; }
     HIPCHK(c, hipMemcpy(out, src, n, hipMemcpyDeviceToHost));
     return CSKY_OK;
 }
@@ -291,7 +307,8 @@ int csky_census_clouds(csky_ctx* c, const csky_cloud_params* p, int tile_w, cons
 
 int csky_build_mips_device(csky_ctx* c, uint8_t* vol, int n, int ch, int levels) {
     if (!c) return fail(nullptr, CSKY_ERR_INVALID, "csky_build_mips_device: ctx is NULL");
-    if (!vol || n < 1 || n > 1024 || (n & (n - 1)) || ch < 1 || ch > 4 || levels < 1 || (n >> (levels - 1)) < 1) return fail(c, CSKY_ERR_INVALID, "csky_build_mips_device: bad arguments");
+    // mip_args.h: the host rule (levels <= 31 and a texel left at the last level, no undefined shift) and a power-of-two n <= 1024, ch <= 4
+    if (!mip_args_ok(vol, n, ch, levels, true)) return fail(c, CSKY_ERR_INVALID, "csky_build_mips_device: bad arguments");
     int rc; if ((rc = bind(c))) return rc;
     const size_t total = chain_offset(n, levels, ch), l0 = (size_t)n * n * n * ch;
     DevBuf<uint8_t> d; if ((rc = d.alloc(c, total))) return rc;

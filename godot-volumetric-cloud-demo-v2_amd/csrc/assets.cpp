@@ -13,6 +13,7 @@
 #pragma clang fp contract(off)
 #include "../../include/cloudsky.h"
 #include "noise_core.h"
+#include "mip_args.h"
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -102,7 +103,7 @@ size_t csky_mip_offset(int n, int level, int ch) {
 // 3-D mip chain, 2x2x2 box, integer round-half-up.  `vol` holds level 0 on entry and must have room for
 // csky_mip_offset(n, levels, ch) bytes.
 int csky_build_mips(uint8_t* vol, int n, int ch, int levels) {
-    if (!vol || n < 1 || ch < 1 || levels < 1 || levels > 31 || (n >> (levels - 1)) < 1) { snprintf(g_asset_err, sizeof g_asset_err, "build_mips: bad arguments"); return CSKY_ERR_INVALID; }
+    if (!csky::mip_args_ok(vol, n, ch, levels, false)) { snprintf(g_asset_err, sizeof g_asset_err, "build_mips: bad arguments"); return CSKY_ERR_INVALID; }   // mip_args.h: shared with csky_build_mips_device
     for (int l = 1; l < levels; l++) {
         const uint8_t* src = vol + csky_mip_offset(n, l - 1, ch);
         uint8_t* dst = vol + csky_mip_offset(n, l, ch);

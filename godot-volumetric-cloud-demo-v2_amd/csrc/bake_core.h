@@ -1,6 +1,7 @@
 // bake_core.h -- one texel of each device texture layout (csky_common.h) from the 8-bit mip chains, host+device:
-// the GPU bake kernels (bake_kernels.hip) and the host loops of bake.h (tests/hostsim) run the same code, so the two bakes are
-// byte-identical by construction (and tests/test_gpu_round2.py compares them).  Also the 2x2x2 box mip (Godot's
+// the GPU bake kernels (bake_kernels.hip) and the host loops of bake.h (tests/hostsim) run the same code.  That makes the two bakes twins, not
+// right: what checks this header is tests/bake_reference.py, a numpy restatement that includes nothing of it -- against the host loops in
+// tests/test_bake_reference.py, against every buffer the kernels write in tests/test_gpu_bake.py.  Also the 2x2x2 box mip (Godot's
 // mipmaps/generate=true on 3-D textures, perlworlnoise.tga.import:24 / worlnoise.bmp.import:24, as (sum + 4) >> 3).
 #pragma once
 #include "csky_common.h"

@@ -3,6 +3,8 @@
 //   shape_noise_kernel / detail_noise_kernel : the stand-in noise volumes, one voxel per lane (noise_core.h)
 //   mip_level_kernel                         : 2x2x2 box mips of an 8-bit chain
 //   bake_{shape,detail,weather}[32]_kernel   : the device texture layouts, one texel per lane (bake_core.h)
+// Checked buffer by buffer against numpy in tests/test_gpu_bake.py (tests/bake_reference.py, oracle/noise_restatement.py), not against the host
+// build of the same headers alone.
 #include <hip/hip_runtime.h>
 #include "kernels.h"
 #include "noise_core.h"
@@ -45,7 +47,7 @@ hipError_t launch_detail_noise(uint32_t seed, int n, uint8_t* d_out, hipStream_t
 // ------------------------------------------------------------------------------------------------ mip chains + texture bake on the device
 // csky_set_noise uploads the three 8-bit level-0 textures (9.2 MB) and does everything else here: 2x2x2 box mips (Godot's
 // mipmaps/generate=true), then one lane per texel of each device layout (bake_core.h: the same per-texel code as the host bake of
-// tests/hostsim, byte-identical).  Replaces ~1.5 s of host loops + 78 MB of pageable uploads per csky_set_noise by < 1 ms of kernels.
+// tests/hostsim).  Replaces ~1.5 s of host loops + 78 MB of pageable uploads per csky_set_noise by < 1 ms of kernels.
 __global__ __launch_bounds__(256) void mip_level_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int nd, int ch) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, total = (size_t)nd * nd * nd * ch;
     if (i >= total) return;

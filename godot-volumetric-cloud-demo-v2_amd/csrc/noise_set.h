@@ -91,6 +91,7 @@ public:
     bool cell32() const { return cell32_; }
     unsigned long long inexact() const { return inexact_; }
     float detail_lod5() const { return lod5_; }
+    WeatherRange range() const { return range_; }             // what rejects() decides with (csky_read_baked_texture, which == 9)
 };
 
 }  // namespace csky

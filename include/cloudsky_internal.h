@@ -67,7 +67,11 @@ int csky_set_segments(csky_ctx* ctx, int segments);
 const char* csky_variant_name(int variant);
 
 /* Test hook: read back what csky_set_noise built on the device.  which: 0 shape layout, 1 detail layout, 2 weather layout (csky_common.h),
- * 3 / 4 the 8-bit mip chains of the large / small volume.  out may be NULL to query the size. */
+ * 3 / 4 the 8-bit mip chains of the large / small volume, 5 the unpacked fp16 detail chain (one half per texel of all six levels, without the
+ * allocation's 8-half pad), 6 / 7 / 8 the exact fp32 cells of shape / detail / weather (csrc/bake_core.h: 4 / 2 / 2 float4 per texel;
+ * CSKY_ERR_STATE when the bound set has none: its textures fit fp16 and csky_set_exact_cells is 0), 9 what the context holds from the bake and
+ * launches its kernels with, 24 bytes: uint64 inexact coefficients; int32 min R, max R, max B of the weather map; float detail LOD-5 value.
+ * out may be NULL to query the size.  tests/test_gpu_bake.py compares all of them with tests/bake_reference.py. */
 int csky_read_baked_texture(csky_ctx* ctx, int which, void* out, size_t capacity, size_t* bytes);
 /* Test hook: the march's range-restricted exact square root (cloud_core.h::sqrt_shell, |p|^2 of sample positions) over an array, so that
  * a test can check it EXHAUSTIVELY against IEEE sqrtf on the range it is used on (all 30 067 floats in [3.597e13, 3.6097e13]). */

@@ -69,6 +69,18 @@ size_t hostsim_bake(const uint8_t* large_chain, const uint8_t* small_chain, cons
     return n;
 }
 
+// the device's mip chain as host loops (bake_kernels.hip::launch_mip_chain / mip_level_kernel: bake_core.h mip_texel per destination texel-channel,
+// levels at chain_offset); csky_build_mips has loops of its own.  `chain` holds level 0 and room for all levels; n a power of two.
+void hostsim_build_mips(uint8_t* chain, int n, int ch, int levels) {
+    for (int l = 1; l < levels; l++) {
+        const int nd = n >> l;
+        const uint8_t* src = chain + chain_offset(n, l - 1, ch);
+        uint8_t* dst = chain + chain_offset(n, l, ch);
+        for (int z = 0; z < nd; z++) for (int y = 0; y < nd; y++) for (int x = 0; x < nd; x++) for (int c = 0; c < ch; c++)
+            dst[((((size_t)z * nd + y) * nd + x) * ch) + c] = mip_texel(src, nd * 2, ch, x, y, z, c);
+    }
+}
+
 void hostsim_clouds(const uint8_t* large_chain, const uint8_t* small_chain, const uint8_t* weather_rgb8, const float params[28],
                     int primary_steps, int light_steps, float early_eps, const uint16_t* sky_h, int sw, int sh, int tile_w,
                     int band_rows, int first_band, int band_stride, int n_bands, uint16_t* out_h, uint64_t* incloud, int use_window, float* window_out, int use_lds_path) {
