@@ -426,7 +426,7 @@ int csky_render_clouds_device(csky_ctx* c, const csky_cloud_params* p, int tile_
     if (!c) return fail(nullptr, CSKY_ERR_INVALID, "csky_render_clouds_device: ctx is NULL");
     if (!d_out) return fail(c, CSKY_ERR_INVALID, "csky_render_clouds_device: d_out is NULL");
     int rc; if ((rc = bind(c))) return rc;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    hipStream_t s = stream_of(c, hip_stream);
     return clouds_dev(c, p, tile_w, bands, (uint2*)d_out, pitch, s, nullptr, true);
 }
 

@@ -3,7 +3,7 @@
 // shafts.hip), and the air in front of a cloud frame (csky_apply_cloud_aerial / _device; cloud_aerial_core.h, cloud_aerial.hip;
 // DESIGN.md §16), which reads the caller's two images besides.
 // The call reads the context's transmittance table and nothing else of it: no noise, no sky LUT, no cloud frame, no slot of any ring (geometry and sun
-// travel as kernel arguments), no stream of its own.
+// travel as kernel arguments), no stream of its own.  The blocking forms work in the context's stage (host_stage.h).
 #include <cmath>
 #include "context.h"
 #include "aerial_core.h"
@@ -31,8 +31,7 @@ int aerial_check(csky_ctx* c, const char* fn, const csky_aerial_params* ap, cons
     g.view_mode = 0; g.tan_half_fov_y = 1.0f; g.aspect = 1.0f;
     for (int k = 0; k < 9; k++) g.cam[k] = (k % 4 == 0) ? 1.0f : 0.0f;
     if (view) {
-        for (int k = 0; k < 9; k++) if (!std::isfinite(view->basis[k])) return fail(c, CSKY_ERR_INVALID, "%s: the view's basis is not finite", fn);
-        if (!(view->fov_y_degrees > 0.0f && view->fov_y_degrees < 180.0f)) return fail(c, CSKY_ERR_INVALID, "%s: fov_y_degrees must be in (0, 180)", fn);
+        if (const int rc = view_check(c, fn, view)) return rc;
         if (!std::isfinite(ap->aspect) || ap->aspect < 0.0f) return fail(c, CSKY_ERR_INVALID, "%s: aspect must be finite and > 0, or 0 for width / height", fn);
         g.view_mode = 1;
         for (int k = 0; k < 9; k++) g.cam[k] = view->basis[k];
@@ -47,9 +46,7 @@ int aerial_check(csky_ctx* c, const char* fn, const csky_aerial_params* ap, cons
 int aerial_launch(csky_ctx* c, const char* fn, const AerialGeom& g, uint2* d_out, hipStream_t s) {
     HIPCHK(c, hipEventRecord(c->ev_aerial, c->stream));          // the LUT may have been rendered there
     HIPCHK(c, hipStreamWaitEvent(s, c->ev_aerial, 0));
-    const hipError_t e = launch_aerial(g, c->d_trans_f, c->tw, c->th, d_out, s, c->tlut);
-    if (e != hipSuccess) return fail(c, CSKY_ERR_HIP, "%s: kernel launch failed: %s", fn, hipGetErrorString(e));
-    return CSKY_OK;
+    return launched(c, fn, launch_aerial(g, c->d_trans_f, c->tw, c->th, d_out, s, c->tlut));
 }
 
 // The shadowed forms' own arguments: the map's geometry (of sp only width, height, center and extent are read) and its pitch; m gets everything
@@ -76,9 +73,7 @@ int shafts_launch(csky_ctx* c, const char* fn, const AerialGeom& g, ShaftsMap m,
     m.lx = l[0]; m.ly = l[1]; m.lz = l[2];
     HIPCHK(c, hipEventRecord(c->ev_aerial, c->stream));
     HIPCHK(c, hipStreamWaitEvent(s, c->ev_aerial, 0));
-    const hipError_t e = launch_shafts(g, m, c->d_trans_f, c->tw, c->th, d_out, s, c->tlut);
-    if (e != hipSuccess) return fail(c, CSKY_ERR_HIP, "%s: kernel launch failed: %s", fn, hipGetErrorString(e));
-    return CSKY_OK;
+    return launched(c, fn, launch_shafts(g, m, c->d_trans_f, c->tw, c->th, d_out, s, c->tlut));
 }
 
 // csky_apply_cloud_aerial*: the argument and state checks of both forms, and the kernel's argument block with the default filled in.
@@ -99,9 +94,7 @@ int cloud_aerial_check(csky_ctx* c, const char* fn, const csky_cloud_aerial_para
 int cloud_aerial_launch(csky_ctx* c, const char* fn, const CloudAerialGeom& g, const uint2* d_cloud, const uint2* d_depth, uint2* d_out, hipStream_t s) {
     HIPCHK(c, hipEventRecord(c->ev_aerial, c->stream));
     HIPCHK(c, hipStreamWaitEvent(s, c->ev_aerial, 0));
-    const hipError_t e = launch_cloud_aerial(g, c->d_trans_f, c->tw, c->th, d_cloud, d_depth, d_out, s, c->tlut);
-    if (e != hipSuccess) return fail(c, CSKY_ERR_HIP, "%s: kernel launch failed: %s", fn, hipGetErrorString(e));
-    return CSKY_OK;
+    return launched(c, fn, launch_cloud_aerial(g, c->d_trans_f, c->tw, c->th, d_cloud, d_depth, d_out, s, c->tlut));
 }
 
 }  // namespace
@@ -115,7 +108,7 @@ int csky_apply_cloud_aerial_device(csky_ctx* c, const csky_cloud_aerial_params* 
     CloudAerialGeom g;
     int rc; if ((rc = cloud_aerial_check(c, fn, ap, g)) || (rc = bind(c))) return rc;
     return cloud_aerial_launch(c, fn, g, static_cast<const uint2*>(d_cloud), static_cast<const uint2*>(d_depth), static_cast<uint2*>(d_out),
-                               hip_stream ? (hipStream_t)hip_stream : (hipStream_t)c->stream);
+                               stream_of(c, hip_stream));
 }
 
 int csky_apply_cloud_aerial(csky_ctx* c, const csky_cloud_aerial_params* ap, const uint16_t* cloud, const uint16_t* depth, uint16_t* out) {
@@ -124,15 +117,13 @@ int csky_apply_cloud_aerial(csky_ctx* c, const csky_cloud_aerial_params* ap, con
     if (!cloud || !depth || !out) return fail(c, CSKY_ERR_INVALID, "%s: cloud, depth or out is NULL", fn);
     CloudAerialGeom g;
     int rc; if ((rc = cloud_aerial_check(c, fn, ap, g)) || (rc = bind(c))) return rc;
-    const size_t n = (size_t)g.w * g.h;
-    if ((rc = c->d_cloud_aerial.grow(c, 2 * n))) return rc;     // nothing of an earlier call is in flight: this form blocks
-    uint2* d_cloud = c->d_cloud_aerial; uint2* d_depth = d_cloud + n;
-    HIPCHK(c, hipMemcpyAsync(d_cloud, cloud, n * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_depth, depth, n * 8, hipMemcpyHostToDevice, c->stream));
-    if ((rc = cloud_aerial_launch(c, fn, g, d_cloud, d_depth, d_cloud, c->stream))) return rc;
-    HIPCHK(c, hipMemcpyAsync(out, d_cloud, n * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return CSKY_OK;
+    const size_t nb = (size_t)g.w * g.h * 8;
+    HostCall hc = host_call(c, fn, {nb, nb});                                   // the cloud frame, corrected in place, then the depth frame
+    hc.up(0, cloud, nb);
+    hc.up(1, depth, nb);
+    hc.step([&] { return cloud_aerial_launch(c, fn, g, hc.at<uint2>(0), hc.at<uint2>(1), hc.at<uint2>(0), c->stream); });
+    hc.down(out, 0, nb);
+    return hc.finish();
 }
 
 int csky_render_aerial_perspective_device(csky_ctx* c, const csky_aerial_params* ap, const csky_view* view, void* d_out, void* hip_stream) {
@@ -141,7 +132,7 @@ int csky_render_aerial_perspective_device(csky_ctx* c, const csky_aerial_params*
     if (!d_out) return fail(c, CSKY_ERR_INVALID, "%s: d_out is NULL", fn);
     AerialGeom g;
     int rc; if ((rc = aerial_check(c, fn, ap, view, g)) || (rc = bind(c))) return rc;
-    return aerial_launch(c, fn, g, static_cast<uint2*>(d_out), hip_stream ? (hipStream_t)hip_stream : (hipStream_t)c->stream);
+    return aerial_launch(c, fn, g, static_cast<uint2*>(d_out), stream_of(c, hip_stream));
 }
 
 int csky_render_aerial_perspective(csky_ctx* c, const csky_aerial_params* ap, const csky_view* view, uint16_t* out) {
@@ -150,12 +141,11 @@ int csky_render_aerial_perspective(csky_ctx* c, const csky_aerial_params* ap, co
     if (!out) return fail(c, CSKY_ERR_INVALID, "%s: out is NULL", fn);
     AerialGeom g;
     int rc; if ((rc = aerial_check(c, fn, ap, view, g)) || (rc = bind(c))) return rc;
-    const size_t n = (size_t)g.d * g.h * g.w;
-    if ((rc = c->d_aerial.grow(c, n))) return rc;               // nothing of an earlier call is in flight: this form blocks
-    if ((rc = aerial_launch(c, fn, g, c->d_aerial, c->stream))) return rc;
-    HIPCHK(c, hipMemcpyAsync(out, c->d_aerial, n * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return CSKY_OK;
+    const size_t nb = (size_t)g.d * g.h * g.w * 8;
+    HostCall hc = host_call(c, fn, {nb});
+    hc.step([&] { return aerial_launch(c, fn, g, hc.at<uint2>(0), c->stream); });
+    hc.down(out, 0, nb);
+    return hc.finish();
 }
 
 int csky_render_aerial_perspective_shadowed_device(csky_ctx* c, const csky_aerial_params* ap, const csky_view* view, const csky_shadow_params* sp,
@@ -166,7 +156,7 @@ int csky_render_aerial_perspective_shadowed_device(csky_ctx* c, const csky_aeria
     AerialGeom g; ShaftsMap m;
     int rc; if ((rc = shafts_check(c, fn, sp, d_map, pitch, m)) || (rc = aerial_check(c, fn, ap, view, g)) || (rc = bind(c))) return rc;
     m.texels = static_cast<const uint16_t*>(d_map);
-    return shafts_launch(c, fn, g, m, static_cast<uint2*>(d_out), hip_stream ? (hipStream_t)hip_stream : (hipStream_t)c->stream);
+    return shafts_launch(c, fn, g, m, static_cast<uint2*>(d_out), stream_of(c, hip_stream));
 }
 
 int csky_render_aerial_perspective_shadowed(csky_ctx* c, const csky_aerial_params* ap, const csky_view* view, const csky_shadow_params* sp,
@@ -176,14 +166,12 @@ int csky_render_aerial_perspective_shadowed(csky_ctx* c, const csky_aerial_param
     if (!out) return fail(c, CSKY_ERR_INVALID, "%s: out is NULL", fn);
     AerialGeom g; ShaftsMap m;
     int rc; if ((rc = shafts_check(c, fn, sp, map, sp ? (size_t)sp->width * 2 : 0, m)) || (rc = aerial_check(c, fn, ap, view, g)) || (rc = bind(c))) return rc;
-    const size_t n = (size_t)g.d * g.h * g.w, nm = (size_t)m.w * m.h;
-    if ((rc = c->d_aerial.grow(c, n)) || (rc = c->d_shafts_map.grow(c, nm))) return rc;   // nothing of an earlier call is in flight: this form blocks
-    HIPCHK(c, hipMemcpyAsync(c->d_shafts_map, map, nm * 2, hipMemcpyHostToDevice, c->stream));
-    m.texels = c->d_shafts_map;
-    if ((rc = shafts_launch(c, fn, g, m, c->d_aerial, c->stream))) return rc;
-    HIPCHK(c, hipMemcpyAsync(out, c->d_aerial, n * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return CSKY_OK;
+    const size_t nb = (size_t)g.d * g.h * g.w * 8, mb = (size_t)m.w * m.h * 2;
+    HostCall hc = host_call(c, fn, {mb, nb});                                   // the caller's map, then the volume
+    hc.up(0, map, mb);
+    hc.step([&] { m.texels = hc.at<uint16_t>(0); return shafts_launch(c, fn, g, m, hc.at<uint2>(1), c->stream); });
+    hc.down(out, 1, nb);
+    return hc.finish();
 }
 
 int csky_aerial_shadow_rect(const csky_aerial_params* ap, float center[2], float extent[2]) {

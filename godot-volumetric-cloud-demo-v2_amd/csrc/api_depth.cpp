@@ -1,6 +1,6 @@
 // api_depth.cpp -- the cloud depth frame's C ABI (csky_render_cloud_depth / _device; depth_core.h, depth.hip).
 // The call reads the bound noise and the push-constant block and nothing else: no LUT, no slot of the cloud frames' constants ring (both constant
-// blocks of a launch are computed here and travel as kernel arguments), no stream of its own.
+// blocks of a launch are computed here and travel as kernel arguments), no stream of its own; the blocking form works in the stage (host_stage.h).
 #include <cmath>
 #include <cstring>
 #include "context.h"
@@ -31,11 +31,8 @@ int depth_launch(csky_ctx* c, const char* fn, const csky_cloud_params* p, const 
     dc.w = dp->width; dc.h = dp->height; dc.steps = dp->steps == 0 ? c->primary_steps : dp->steps; dc.pitch_px = (uint32_t)(pitch_bytes / 8);
     FrameConsts fc;
     depth_frame_consts(cp, dc.w, dc.h, dc.steps, rej.hf_lo, rej.hf_hi, rej.ct_mode, fc);
-    TexSet32 t32; const TexSet32* t32p = nullptr;
-    if (c->noise.st.cell32()) { t32 = texset32(c); t32p = &t32; }
-    const hipError_t e = launch_cloud_depth(texset(c), t32p, fc, dc, d_out, s);
-    if (e != hipSuccess) return fail(c, CSKY_ERR_HIP, "%s: kernel launch failed: %s", fn, hipGetErrorString(e));
-    return CSKY_OK;
+    TexSet32 t32;
+    return launched(c, fn, launch_cloud_depth(texset(c), texset32_if(c, t32), fc, dc, d_out, s));
 }
 
 }  // namespace
@@ -47,7 +44,7 @@ int csky_render_cloud_depth_device(csky_ctx* c, const csky_cloud_params* p, cons
     if (!d_out) return fail(c, CSKY_ERR_INVALID, "csky_render_cloud_depth_device: d_out is NULL");
     const char* fn = "csky_render_cloud_depth_device";
     int rc; if ((rc = depth_check(c, fn, p, dp, pitch)) || (rc = bind(c))) return rc;
-    return depth_launch(c, fn, p, dp, static_cast<uint2*>(d_out), pitch, hip_stream ? (hipStream_t)hip_stream : (hipStream_t)c->stream);
+    return depth_launch(c, fn, p, dp, static_cast<uint2*>(d_out), pitch, stream_of(c, hip_stream));
 }
 
 int csky_render_cloud_depth(csky_ctx* c, const csky_cloud_params* p, const csky_depth_params* dp, uint16_t* out) {
@@ -55,12 +52,11 @@ int csky_render_cloud_depth(csky_ctx* c, const csky_cloud_params* p, const csky_
     const char* fn = "csky_render_cloud_depth";
     if (!out) return fail(c, CSKY_ERR_INVALID, "%s: out is NULL", fn);
     int rc; if ((rc = depth_check(c, fn, p, dp, dp ? (size_t)dp->width * 8 : 0)) || (rc = bind(c))) return rc;
-    const size_t n = (size_t)dp->width * dp->height;
-    if ((rc = c->d_depth.grow(c, n))) return rc;               // nothing of an earlier call is in flight: this form blocks
-    if ((rc = depth_launch(c, fn, p, dp, c->d_depth, (size_t)dp->width * 8, c->stream))) return rc;
-    HIPCHK(c, hipMemcpyAsync(out, c->d_depth, n * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return CSKY_OK;
+    const size_t nb = (size_t)dp->width * dp->height * 8;
+    HostCall hc = host_call(c, fn, {nb});
+    hc.step([&] { return depth_launch(c, fn, p, dp, hc.at<uint2>(0), (size_t)dp->width * 8, c->stream); });
+    hc.down(out, 0, nb);
+    return hc.finish();
 }
 
 }  // extern "C"

@@ -178,7 +178,7 @@ int csky_render_sky_lut_rows_device(csky_ctx* c, const csky_sky_params* p, int f
     // the rows have no consumer inside the library: they are rendered on the CALLER's stream, in order with the bands they travel with.
     // (Round 5 measured them on a side stream BESIDE the march that follows, joined behind it: a 1/8 share one frame at a time 0.409 -> 0.460 ms, eight
     // in flight 0.241 -> 0.244: two more cross-stream hops cost more than the rows they take off the critical path; profiles/r05/rows_overlap_ab.txt.)
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    hipStream_t s = stream_of(c, hip_stream);
     // The caller's buffer differs from frame to frame, so the rows of an unchanged request cannot simply stay where they are: the context keeps a
     // copy of the last rows it rendered, and the same request again is one device copy of them on the caller's stream instead of the kernel.
     // A request that differs renders into the caller's buffer as ever and leaves its copy behind (a sun that moves every frame pays that copy alone).
@@ -239,7 +239,7 @@ int csky_copy_sky_lut_device(csky_ctx* c, void* d_out, void* hip_stream) {
     if (l.st.holds == SkyLutHolds::None) return fail(c, CSKY_ERR_STATE, "csky_copy_sky_lut_device: LUT not rendered yet");
     if (!l.st.in_memory()) return fail(c, CSKY_ERR_STATE, "csky_copy_sky_lut_device: the last LUT went to the caller as rows (csky_render_sky_lut_rows_device), this context holds none");
     int rc; if ((rc = bind(c))) return rc;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    hipStream_t s = stream_of(c, hip_stream);
     // the copy runs on the context's stream right behind the LUT's render (a later render goes to the other ring slot and, like every
     // writer of a slot, is queued behind this reader on the same stream); the caller's stream then waits for it
     for (hipEvent_t ev : l.writers) HIPCHK(c, hipStreamWaitEvent(c->stream, ev, 0));   // rows written by the other devices of a csky_multi handle

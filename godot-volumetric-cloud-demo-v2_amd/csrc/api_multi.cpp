@@ -284,7 +284,7 @@ int csky_multi_render_clouds_device(csky_multi* m, const csky_cloud_params* p, i
     const int slot = (int)(m->frame_no % (unsigned long long)slots), grp = slot % G, dslot = slot / G;   // (frame_no advances only when the frame was enqueued: a failed call must not shift the slot / group rotation)
     csky_ctx* c0 = m->dev[0].ctx;
     int rc; if ((rc = bind(c0))) return mpass(m, 0, rc);
-    hipStream_t consumer = hip_stream ? (hipStream_t)hip_stream : c0->stream;
+    hipStream_t consumer = stream_of(c0, hip_stream);
     // no device may store into the frame before the consumer's earlier work on it (reads of the previous frame) is done
     if (hipEventRecord(m->ev_begin[slot], consumer) != hipSuccess) return mfail(m, CSKY_ERR_HIP, "csky_multi_render_clouds_device: hipEventRecord failed");
     for (int k = 0; k < per; k++) {

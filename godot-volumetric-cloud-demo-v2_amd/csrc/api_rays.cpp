@@ -2,7 +2,7 @@
 // clouds_rays_kernel).
 // The call reads what a cloud frame reads (noise, sky LUT, the march settings) and writes none of it.  Its frame constants come from the cloud
 // frame's own set-up kernel, enqueued on the context's stream into a block of the call's own: no slot of the frame ring, none of the ring's order,
-// feedback or head state, no stream of its own.
+// feedback or head state, no stream of its own.  The blocking forms work in the context's stage (host_stage.h).
 #include <cmath>
 #include <cstring>
 #include "context.h"
@@ -18,10 +18,7 @@ int rays_check(csky_ctx* c, const char* fn, const csky_cloud_params* p, const cs
     if (is_view && !view) return fail(c, CSKY_ERR_INVALID, "%s: view is NULL", fn);
     if (w < 1 || w > 8192 || h < 1 || h > 8192) return fail(c, CSKY_ERR_INVALID, "%s: w and h must be in [1, 8192]", fn);
     if (pitch_bytes % 8 || pitch_bytes < (size_t)w * 8) return fail(c, CSKY_ERR_INVALID, "%s: row pitch must be a multiple of 8 and >= 8 * w", fn);
-    if (is_view) {
-        for (int k = 0; k < 9; k++) if (!std::isfinite(view->basis[k])) return fail(c, CSKY_ERR_INVALID, "%s: the view's basis is not finite", fn);
-        if (!(view->fov_y_degrees > 0.0f && view->fov_y_degrees < 180.0f)) return fail(c, CSKY_ERR_INVALID, "%s: fov_y_degrees must be in (0, 180)", fn);
-    }
+    if (is_view) if (const int rc = view_check(c, fn, view)) return rc;
     if (!c->noise.st.have()) return fail(c, CSKY_ERR_STATE, "render_clouds: csky_set_noise has not been called");
     if (c->lut.st.holds == SkyLutHolds::None) return fail(c, CSKY_ERR_STATE, "render_clouds: no sky LUT yet (call csky_render_sky_lut first; cloud_sky.gd:187,242)");
     return CSKY_OK;
@@ -64,13 +61,11 @@ int rays_launch(csky_ctx* c, const char* fn, const csky_cloud_params* p, const c
         for (int k = 0; k < 9; k++) g.cam[k] = a.cam[k];
         g.tan_half_fov_y = a.tan_half_fov_y; g.aspect = a.aspect;
     }
-    TexSet32 t32; const TexSet32* t32p = nullptr;
-    if (c->noise.st.cell32()) { t32 = texset32(c); t32p = &t32; }
+    TexSet32 t32;
     const Event* kt = nullptr;                                  // timing pair of this launch (csky_set_kernel_timing), as around a cloud frame's
     if (c->kt.on && (rc = c->kt.next_pair(c, kt))) return rc;
     if (kt) HIPCHK(c, hipEventRecord(kt[0], s));
-    const hipError_t e = launch_clouds_rays(texset(c), t32p, c->d_rays_fc, g, d_dirs, d_out, s);
-    if (e != hipSuccess) return fail(c, CSKY_ERR_HIP, "%s: kernel launch failed: %s", fn, hipGetErrorString(e));
+    if ((rc = launched(c, fn, launch_clouds_rays(texset(c), texset32_if(c, t32), c->d_rays_fc, g, d_dirs, d_out, s)))) return rc;
     if (kt) HIPCHK(c, hipEventRecord(kt[1], s));
     HIPCHK(c, hipEventRecord(c->ev_rays, s));                   // the next call's set-up overwrites the block this march reads
     c->rays_pending = true;
@@ -82,18 +77,12 @@ int rays_host(csky_ctx* c, const char* fn, const csky_cloud_params* p, const csk
     if (!out) return fail(c, CSKY_ERR_INVALID, "%s: out is NULL", fn);
     if (!is_view && !dirs) return fail(c, CSKY_ERR_INVALID, "%s: dirs_xyz is NULL", fn);
     int rc; if ((rc = rays_check(c, fn, p, view, is_view, w, h, (w >= 1 && w <= 8192) ? (size_t)w * 8 : 8)) || (rc = bind(c))) return rc;
-    const size_t n = (size_t)w * h;
-    if ((rc = c->d_rays_out.grow(c, n))) return rc;            // nothing of an earlier call is in flight: this form blocks
-    const float* d_dirs = nullptr;
-    if (!is_view) {
-        if ((rc = c->d_rays_dirs.grow(c, n * 3))) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->d_rays_dirs, dirs, n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        d_dirs = c->d_rays_dirs;
-    }
-    if ((rc = rays_launch(c, fn, p, view, w, h, d_dirs, c->d_rays_out, (size_t)w * 8, c->stream))) { (void)hipStreamSynchronize(c->stream); return rc; }
-    HIPCHK(c, hipMemcpyAsync(out, c->d_rays_out, n * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return CSKY_OK;
+    const size_t n = (size_t)w * h, db = is_view ? 0 : n * 3 * sizeof(float);
+    HostCall hc = host_call(c, fn, {db, n * 8});
+    hc.up(0, dirs, db);
+    hc.step([&] { return rays_launch(c, fn, p, view, w, h, is_view ? nullptr : hc.at<float>(0), hc.at<uint2>(1), (size_t)w * 8, c->stream); });
+    hc.down(out, 1, n * 8);
+    return hc.finish();
 }
 
 }  // namespace
@@ -118,7 +107,7 @@ int csky_render_clouds_dirs_device(csky_ctx* c, const csky_cloud_params* p, int 
     if (!d_dirs || !d_out) return fail(c, CSKY_ERR_INVALID, "%s: d_dirs_xyz or d_out is NULL", fn);
     int rc; if ((rc = rays_check(c, fn, p, nullptr, false, w, h, pitch)) || (rc = bind(c))) return rc;
     return rays_launch(c, fn, p, nullptr, w, h, static_cast<const float*>(d_dirs), static_cast<uint2*>(d_out), pitch,
-                       hip_stream ? (hipStream_t)hip_stream : (hipStream_t)c->stream);
+                       stream_of(c, hip_stream));
 }
 
 int csky_render_clouds_view_device(csky_ctx* c, const csky_cloud_params* p, const csky_view* view, int w, int h, void* d_out, size_t pitch, void* hip_stream) {
@@ -126,7 +115,7 @@ int csky_render_clouds_view_device(csky_ctx* c, const csky_cloud_params* p, cons
     if (!c) return fail(nullptr, CSKY_ERR_INVALID, "%s: ctx is NULL", fn);
     if (!d_out) return fail(c, CSKY_ERR_INVALID, "%s: d_out is NULL", fn);
     int rc; if ((rc = rays_check(c, fn, p, view, true, w, h, pitch)) || (rc = bind(c))) return rc;
-    return rays_launch(c, fn, p, view, w, h, nullptr, static_cast<uint2*>(d_out), pitch, hip_stream ? (hipStream_t)hip_stream : (hipStream_t)c->stream);
+    return rays_launch(c, fn, p, view, w, h, nullptr, static_cast<uint2*>(d_out), pitch, stream_of(c, hip_stream));
 }
 
 }  // extern "C"

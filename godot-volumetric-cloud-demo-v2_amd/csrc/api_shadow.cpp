@@ -1,6 +1,6 @@
 // api_shadow.cpp -- the cloud shadow map's C ABI (csky_render_cloud_shadow / _device; shadow_core.h, shadow.hip).
 // The call reads the bound noise and the push-constant block and nothing else: no LUT, no slot of the cloud frames' constants ring (both constant
-// blocks of a launch are computed here and travel as kernel arguments), no stream of its own.
+// blocks of a launch are computed here and travel as kernel arguments), no stream of its own; the blocking form works in the stage (host_stage.h).
 #include <cmath>
 #include <cstring>
 #include "context.h"
@@ -38,11 +38,8 @@ int shadow_launch(csky_ctx* c, const char* fn, const csky_cloud_params* p, const
     FrameConsts fc;
     shadow_frame_consts(cp, sc.steps, rej.hf_lo, rej.hf_hi, rej.ct_mode, fc);
     sc.night = fc.ldir[1] > 0.0f ? 0 : 1;               // l.y <= 0; a zero LIGHT_DIRECTION (no direction: l is NaN) counts as night too
-    TexSet32 t32; const TexSet32* t32p = nullptr;
-    if (c->noise.st.cell32()) { t32 = texset32(c); t32p = &t32; }
-    const hipError_t e = launch_cloud_shadow(texset(c), t32p, fc, sc, d_out, s);
-    if (e != hipSuccess) return fail(c, CSKY_ERR_HIP, "%s: kernel launch failed: %s", fn, hipGetErrorString(e));
-    return CSKY_OK;
+    TexSet32 t32;
+    return launched(c, fn, launch_cloud_shadow(texset(c), texset32_if(c, t32), fc, sc, d_out, s));
 }
 
 }  // namespace
@@ -54,7 +51,7 @@ int csky_render_cloud_shadow_device(csky_ctx* c, const csky_cloud_params* p, con
     if (!d_out) return fail(c, CSKY_ERR_INVALID, "csky_render_cloud_shadow_device: d_out is NULL");
     const char* fn = "csky_render_cloud_shadow_device";
     int rc; if ((rc = shadow_check(c, fn, p, sp, pitch)) || (rc = bind(c))) return rc;
-    return shadow_launch(c, fn, p, sp, static_cast<uint16_t*>(d_out), pitch, hip_stream ? (hipStream_t)hip_stream : (hipStream_t)c->stream);
+    return shadow_launch(c, fn, p, sp, static_cast<uint16_t*>(d_out), pitch, stream_of(c, hip_stream));
 }
 
 int csky_render_cloud_shadow(csky_ctx* c, const csky_cloud_params* p, const csky_shadow_params* sp, uint16_t* out) {
@@ -62,12 +59,11 @@ int csky_render_cloud_shadow(csky_ctx* c, const csky_cloud_params* p, const csky
     const char* fn = "csky_render_cloud_shadow";
     if (!out) return fail(c, CSKY_ERR_INVALID, "%s: out is NULL", fn);
     int rc; if ((rc = shadow_check(c, fn, p, sp, sp ? (size_t)sp->width * 2 : 0)) || (rc = bind(c))) return rc;
-    const size_t n = (size_t)sp->width * sp->height;
-    if ((rc = c->d_shadow.grow(c, n))) return rc;              // nothing of an earlier call is in flight: this form blocks
-    if ((rc = shadow_launch(c, fn, p, sp, c->d_shadow, (size_t)sp->width * 2, c->stream))) return rc;
-    HIPCHK(c, hipMemcpyAsync(out, c->d_shadow, n * 2, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return CSKY_OK;
+    const size_t nb = (size_t)sp->width * sp->height * 2;
+    HostCall hc = host_call(c, fn, {nb});
+    hc.step([&] { return shadow_launch(c, fn, p, sp, hc.at<uint16_t>(0), (size_t)sp->width * 2, c->stream); });
+    hc.down(out, 0, nb);
+    return hc.finish();
 }
 
 int csky_set_shadow_exact_end(csky_ctx* c, int enabled) {

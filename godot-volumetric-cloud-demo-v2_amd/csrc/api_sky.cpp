@@ -1,6 +1,6 @@
 // api_sky.cpp -- the sky's C ABI: the compositor (csky_composite_sky / _view: clouds.gdshader sky() on a panorama or a camera view) and the
 // radiance cubemap (csky_render_radiance*, csky_prefilter_cube: the same sky() evaluated into a cube map (layer 0) and GGX-prefiltered into
-// roughness layers, radiance_core.h, radiance.hip).
+// roughness layers, radiance_core.h, radiance.hip).  The blocking forms work in the context's stage (host_stage.h).
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -38,22 +38,19 @@ int composite_impl(csky_ctx* c, const csky_composite_params* p, const csky_view*
     int rc; if ((rc = bind(c))) return rc;
     if ((rc = ensure_default_trans(c))) return rc;            // source_transmittance, clouds_material.tres
     const size_t cb = (size_t)p->cloud_w * p->cloud_h * 8, sb = (size_t)p->sky_w * p->sky_h * 8, ob = (size_t)p->out_w * p->out_h * 8;
-    const size_t need = 2 * cb + 2 * sb + ob;
-    if ((rc = c->d_composite.grow(c, need))) return rc;       // grow-only scratch: no allocation per call once the sizes have been seen
-    uint8_t* d = c->d_composite;
-    hipError_t e = hipSuccess;
-    auto up = [&](size_t off, const void* src, size_t n) { if (e == hipSuccess) e = hipMemcpyAsync(d + off, src, n, hipMemcpyHostToDevice, c->stream); };
-    up(0, cloud_from, cb); up(cb, cloud_to, cb); up(2 * cb, sky_from, sb); up(2 * cb + sb, sky_to, sb);
-    CompositeArgs a = composite_args(c, p, d, d + cb, d + 2 * cb, d + 2 * cb + sb);
-    if (view) {
-        composite_view_args(a, view->basis, view->fov_y_degrees, p->out_w, p->out_h);   // rays_core.h: the view march's projection is this one
-        a.cloud_mode = cloud_mode;
-    }
-    if (e == hipSuccess) e = launch_composite(a, reinterpret_cast<uint2*>(d + 2 * cb + 2 * sb), c->stream, c->tlut);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d + 2 * cb + 2 * sb, ob, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return fail(c, CSKY_ERR_HIP, "csky_composite_sky: %s", hipGetErrorString(e));
-    return CSKY_OK;
+    HostCall hc = host_call(c, "csky_composite_sky", {cb, cb, sb, sb, ob});
+    hc.up(0, cloud_from, cb); hc.up(1, cloud_to, cb); hc.up(2, sky_from, sb); hc.up(3, sky_to, sb);
+    hc.step([&] {
+        CompositeArgs a = composite_args(c, p, hc.at<void>(0), hc.at<void>(1), hc.at<void>(2), hc.at<void>(3));
+        if (view) {
+            composite_view_args(a, view->basis, view->fov_y_degrees, p->out_w, p->out_h);   // rays_core.h: the view march's projection is this one
+            a.cloud_mode = cloud_mode;
+        }
+        const hipError_t e = launch_composite(a, hc.at<uint2>(4), c->stream, c->tlut);
+        return e == hipSuccess ? CSKY_OK : fail(c, CSKY_ERR_HIP, "csky_composite_sky: %s", hipGetErrorString(e));
+    });
+    hc.down(out, 4, ob);
+    return hc.finish();
 }
 
 // ---- radiance cubemap
@@ -156,9 +153,8 @@ int csky_render_radiance_device(csky_ctx* c, const csky_composite_params* p, con
     if (!d_out) return fail(c, CSKY_ERR_INVALID, "%s: d_out is NULL", fn);
     if (first_layer == 0 && (rc = rad_sky_args(c, fn, p, S, d_cloud_from, d_cloud_to, d_sky_from, d_sky_to))) return rc;
     if ((rc = bind(c))) return rc;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
     return radiance_dev(c, fn, p, S, L, Ss, d_cloud_from, d_cloud_to, d_sky_from, d_sky_to, first_layer, n_layers,
-                        static_cast<uint2*>(d_out) + (size_t)first_layer * 6 * S * S, s);
+                        static_cast<uint2*>(d_out) + (size_t)first_layer * 6 * S * S, stream_of(c, hip_stream));
 }
 int csky_render_radiance(csky_ctx* c, const csky_composite_params* p, const csky_radiance_params* rp, const uint16_t* cloud_from, const uint16_t* cloud_to,
                          const uint16_t* sky_from, const uint16_t* sky_to, int first_layer, int n_layers, uint16_t* out) {
@@ -171,20 +167,11 @@ int csky_render_radiance(csky_ctx* c, const csky_composite_params* p, const csky
     if ((rc = bind(c))) return rc;
     const size_t cb = first_layer == 0 ? (size_t)p->cloud_w * p->cloud_h * 8 : 0, sb = first_layer == 0 ? (size_t)p->sky_w * p->sky_h * 8 : 0;
     const size_t ob = (size_t)n_layers * 6 * S * S * 8;
-    if ((rc = c->d_rad_io.grow(c, 2 * cb + 2 * sb + ob))) return rc;
-    uint8_t* d = c->d_rad_io;
-    hipError_t e = hipSuccess;
-    auto up = [&](size_t off, const void* src, size_t nb) { if (e == hipSuccess && nb) e = hipMemcpyAsync(d + off, src, nb, hipMemcpyHostToDevice, c->stream); };
-    up(0, cloud_from, cb); up(cb, cloud_to, cb); up(2 * cb, sky_from, sb); up(2 * cb + sb, sky_to, sb);
-    if (e != hipSuccess) return fail(c, CSKY_ERR_HIP, "%s: %s", fn, hipGetErrorString(e));
-    uint8_t* d_o = d + 2 * cb + 2 * sb;
-    if ((rc = radiance_dev(c, fn, p, S, L, Ss, d, d + cb, d + 2 * cb, d + 2 * cb + sb, first_layer, n_layers, reinterpret_cast<uint2*>(d_o), c->stream))) {
-        (void)hipStreamSynchronize(c->stream);
-        return rc;
-    }
-    HIPCHK(c, hipMemcpyAsync(out + (size_t)first_layer * 6 * S * S * 4, d_o, ob, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return CSKY_OK;
+    HostCall hc = host_call(c, fn, {cb, cb, sb, sb, ob});                             // the inputs are 0 bytes, and not uploaded, unless layer 0 is rendered
+    hc.up(0, cloud_from, cb); hc.up(1, cloud_to, cb); hc.up(2, sky_from, sb); hc.up(3, sky_to, sb);
+    hc.step([&] { return radiance_dev(c, fn, p, S, L, Ss, hc.at<void>(0), hc.at<void>(1), hc.at<void>(2), hc.at<void>(3), first_layer, n_layers, hc.at<uint2>(4), c->stream); });
+    hc.down(out + (size_t)first_layer * 6 * S * S * 4, 4, ob);
+    return hc.finish();
 }
 int csky_prefilter_cube(csky_ctx* c, const uint16_t* cube, int face_size, int layers, int source_size, int first_layer, int n_layers, uint16_t* out) {
     static const char* fn = "csky_prefilter_cube";
@@ -196,17 +183,16 @@ int csky_prefilter_cube(csky_ctx* c, const uint16_t* cube, int face_size, int la
     if ((rc = bind(c))) return rc;
     const size_t plane = (size_t)6 * S * S, lb = plane * 8;
     const int lo = std::max(first_layer, 1), hi = first_layer + n_layers;
-    if ((rc = c->d_rad_io.grow(c, lb * (1 + (size_t)(hi - lo))))) return rc;
-    uint8_t* d = c->d_rad_io;
-    uint2* d_o = reinterpret_cast<uint2*>(d + lb);
-    HIPCHK(c, hipMemcpyAsync(d, cube, lb, hipMemcpyHostToDevice, c->stream));
-    if (lo < hi) {
-        if ((rc = rad_prepare(c, c->rad_pf, S, Ss, c->stream))) return rc;
-        HIPCHK(c, launch_radiance_source(reinterpret_cast<const uint16_t*>(d), S, Ss, c->rad_pf.tab, c->stream));
-        if ((rc = rad_filter(c, c->rad_pf, S, L, Ss, lo, hi, d_o, c->stream))) { (void)hipStreamSynchronize(c->stream); return rc; }
-        HIPCHK(c, hipMemcpyAsync(out + (size_t)lo * plane * 4, d_o, lb * (hi - lo), hipMemcpyDeviceToHost, c->stream));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const size_t ob = lb * (size_t)(hi - lo);                         // layers [lo, hi): none when only layer 0 is asked for
+    HostCall hc = host_call(c, fn, {lb, ob});
+    hc.up(0, cube, lb);
+    if (ob) hc.step([&] {
+        if (const int r = rad_prepare(c, c->rad_pf, S, Ss, c->stream)) return r;
+        HIPCHK(c, launch_radiance_source(hc.at<uint16_t>(0), S, Ss, c->rad_pf.tab, c->stream));
+        return rad_filter(c, c->rad_pf, S, L, Ss, lo, hi, hc.at<uint2>(1), c->stream);
+    });
+    hc.down(out + (size_t)lo * plane * 4, 1, ob);
+    if ((rc = hc.finish())) return rc;
     if (first_layer == 0) memcpy(out, cube, lb);                      // layer 0 is the input
     return CSKY_OK;
 }

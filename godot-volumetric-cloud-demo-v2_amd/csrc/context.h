@@ -1,16 +1,20 @@
 // context.h -- the context of libcloudsky (csky_ctx) and the host helpers its C ABI sources share.  Internal to libcloudsky:
 // api.cpp (lifecycle, textures, cloud entry points, host ring), api_lut.cpp (the transmittance and sky LUTs), clouds_launch.cpp (the cloud kernel
-// launch), api_sky.cpp (compositor, radiance cubemap), api_shadow.cpp (cloud shadow map), api_aerial.cpp (aerial-perspective volume), api_rays.cpp (the direct cloud march), api_external.cpp (zero-copy frames), api_multi.cpp (the
-// multi-device handle).
+// launch), api_sky.cpp (compositor, radiance cubemap), api_shadow.cpp (cloud shadow map), api_depth.cpp (cloud depth frame), api_aerial.cpp
+// (aerial-perspective volume, air in front of a cloud frame), api_rays.cpp (the direct cloud march), api_external.cpp (zero-copy frames),
+// api_multi.cpp (the multi-device handle).
 // Ownership: every device buffer, pinned buffer, event and stream of the context is a member of one of the owner types of owners.h and dies with
 // the context (csky_destroy: bind the device, wait for it, delete).  A buffer's count() is its capacity; raw pointers and raw handles in the
 // struct are views of something owned elsewhere and say so.
+// The blocking host forms share one staging buffer (`stage`, host_stage.h) and go through it one way (HostCall): a new feature's host form adds no
+// member here.  The cloud frame's own host forms keep d_frame.
 // The per-frame ring is one member (FrameRing, below): each of its RING slots owns its frame constants, its two events and its order table, and the
 // ring hands out slot k's share of the four allocations the slots share.  What a slot remembers about its cached orders is frame_ring.h's.
 // Member order: `stream` is declared before everything recorded on it or ordered by it, and HostSlot::s before the rest of its slot; members die
 // in reverse order, so a stream is destroyed after the events and buffers that were used on it.  Keep new members below it.
 #pragma once
 #include <hip/hip_runtime_api.h>
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <vector>
@@ -18,6 +22,7 @@
 #include "kernels.h"
 #include "owners.h"
 #include "frame_ring.h"
+#include "host_stage.h"
 #include "noise_set.h"
 #include "sky_lut_reuse.h"
 
@@ -205,6 +210,7 @@ struct csky_ctx {
     // default stream and two frame streams, the second frame stream landed on the first one's queue and two frames in flight ran strictly one
     // after the other (profiles/r11/queue_overlap_ab.txt); with one, the four queues go round.
     csky::Stream stream;
+    csky::HostStage stage;                            // what the blocking host forms upload into and copy out of (host_stage.h), grow-only
     csky::Event ev0, ev1, ev_copy;
     csky::NoiseSet noise;
     bool use_window = true;                           // csky_set_height_window: the exact rejects of a density sample (noise_set.h)
@@ -216,7 +222,9 @@ struct csky_ctx {
     csky::RowsCache rows_cache;
     csky::FrameRing ring;
     csky::DevBuf<unsigned long long> d_stats;
-    csky::DevBuf<uint2> d_frame;                     // internal frame for the host-buffer form / timing, in pixels, grow-only
+    // internal frame of csky_render_clouds / csky_time_clouds / csky_census_clouds, in pixels, grow-only.  Not part of `stage` on purpose: the
+    // benchmark times through csky_time_clouds, and the frame path keeps the allocation it has always had
+    csky::DevBuf<uint2> d_frame;
     int primary_steps = 128, light_steps = 6;        // clouds.glsl:228, :186
     float early_eps = 0.0f;
     int variant = CSKY_DEFAULT_VARIANT;
@@ -226,29 +234,20 @@ struct csky_ctx {
     int frames_overlapping = 1;                       // how many of them the hardware queues in effect can keep apart: the launch policy's hint (clouds_dev)
     int persistent = 1; int resident_wgs = 0;         // the persistent launch form: allowed; workgroups resident at once
     csky::TimingPool kt;                              // csky_set_kernel_timing
-    csky::DevBuf<uint8_t> d_composite;                                     // grow-only scratch of csky_composite_sky
     // radiance cubemap (csky_render_radiance*, csky_prefilter_cube): source-record table and block cones, grow-only.  `rad` is the snapshot
     // of the last layer-0 call, which later calls filter from; csky_prefilter_cube works in `rad_pf` and leaves the snapshot alone
     struct RadSet { csky::DevBuf<float4> tab, src_cones, out_cones;
                     int cones_ss = 0, cones_s = 0; int S = 0, L = 0, Ss = 0; bool valid = false; };
     RadSet rad, rad_pf;
-    csky::DevBuf<uint8_t> d_rad_io;                                        // host forms: uploaded inputs + the requested output layers, grow-only
     csky::Event ev_rad;                                                    // the transmittance LUT (prologue stream) -> layer 0 (caller's stream)
     csky_cloud_stats last_stats = {0, 0, 0};
-    csky::DevBuf<uint16_t> d_shadow;                                       // host form of the cloud shadow map: the map before its copy out, grow-only
     bool shadow_exact_end = true;                                          // csky_set_shadow_exact_end (shadow_core.h shadow_march)
-    csky::DevBuf<uint2> d_aerial;                                          // host form of the aerial-perspective volume: the volume before its copy out, grow-only
     csky::Event ev_aerial;                                                 // the transmittance LUT (the context's stream) -> the volume (caller's stream)
-    csky::DevBuf<uint16_t> d_shafts_map;                                   // host form of the shadowed volume: the caller's shadow map, uploaded, grow-only
-    csky::DevBuf<uint2> d_depth;                                           // host form of the cloud depth frame: the frame before its copy out, grow-only
-    csky::DevBuf<uint2> d_cloud_aerial;                                    // host form of csky_apply_cloud_aerial: the cloud frame (corrected in place), then the depth frame, grow-only
     // the direct march (csky_render_clouds_dirs / _view, api_rays.cpp): frame constants of its own, written by the cloud frame's set-up kernel on the
     // context's stream (no slot of the frame ring).  One event orders both ways: recorded behind the set-up, the caller's stream waits for it; recorded
     // again behind the march, the context's stream waits for it before the next call's set-up overwrites the block.  Both are made by the first call.
     csky::DevBuf<csky::FrameConsts> d_rays_fc;
     csky::Event ev_rays; bool rays_pending = false;
-    csky::DevBuf<float> d_rays_dirs;                                       // host form: the caller's directions, uploaded, grow-only
-    csky::DevBuf<uint2> d_rays_out;                                        // host forms: the image before its copy out, grow-only
     bool census_lean = false;                                 // csky_census_clouds unless CSKY_CENSUS_TALLY=1: count the blocks of the kernel form that keeps no in-cloud tally (kernels.h launch_clouds)
     // asynchronous host form (csky_submit_clouds / csky_collect): a ring of pinned host frames + device frames on rotating internal streams
     // (a slot's capacity is h.count(), in bytes; d holds as many pixels of 8 bytes)
@@ -264,6 +263,18 @@ extern thread_local char g_err[512];   // error text of calls without a context 
 
 // (fail and HIPCHK: owners.h)
 inline int bind(csky_ctx* c) { HIPCHK(c, hipSetDevice(c->device)); return CSKY_OK; }
+// the stream a _device entry point launches on: the caller's, or the context's for a NULL hip_stream
+inline hipStream_t stream_of(const csky_ctx* c, void* hip_stream) { return hip_stream ? (hipStream_t)hip_stream : (hipStream_t)c->stream; }
+// the blocking host form `fn`'s way through the context's stage, on the context's stream, with room for regions of `bytes`
+inline HostCall host_call(csky_ctx* c, const char* fn, std::initializer_list<size_t> bytes) { return HostCall(c, c->stage, c->stream, fn, bytes); }
+// the result of a kernel launch made for the entry point `fn` as a CSKY code
+inline int launched(csky_ctx* c, const char* fn, hipError_t e) { return e == hipSuccess ? CSKY_OK : fail(c, CSKY_ERR_HIP, "%s: kernel launch failed: %s", fn, hipGetErrorString(e)); }
+// a camera view as the aerial volume and the direct march take it: a finite basis, a field of view in (0, 180).  fn: the entry point's name
+inline int view_check(csky_ctx* c, const char* fn, const csky_view* view) {
+    for (int k = 0; k < 9; k++) if (!std::isfinite(view->basis[k])) return fail(c, CSKY_ERR_INVALID, "%s: the view's basis is not finite", fn);
+    if (!(view->fov_y_degrees > 0.0f && view->fov_y_degrees < 180.0f)) return fail(c, CSKY_ERR_INVALID, "%s: fov_y_degrees must be in (0, 180)", fn);
+    return CSKY_OK;
+}
 
 // api.cpp
 int host_slot_prepare(csky_ctx* c, csky_ctx::HostSlot& hs, size_t px);
@@ -280,6 +291,8 @@ int lut_size(csky_ctx* c, const char* fn, const float texture_size[2], int& w, i
 // clouds_launch.cpp
 TexSet texset(const csky_ctx* c);       // the bound textures as the kernels take them: fp16-pair cells, and the exact fp32 cells of a context in that mode
 TexSet32 texset32(const csky_ctx* c);
+// the exact cells as a launch takes them: `t32` filled and its address for a context in that mode, NULL otherwise
+inline const TexSet32* texset32_if(const csky_ctx* c, TexSet32& t32) { if (!c->noise.st.cell32()) return nullptr; t32 = texset32(c); return &t32; }
 int check_bands(csky_ctx* c, const csky_bands* b, int tile_w);
 // frame set-up (when `setup`) + the cloud kernel on stream s into d_out.  d_stats: optional device counters.
 int clouds_dev(csky_ctx* c, const csky_cloud_params* p, int tile_w, const csky_bands* b, uint2* d_out, size_t pitch_bytes, hipStream_t s,

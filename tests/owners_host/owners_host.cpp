@@ -2,7 +2,7 @@
 // The HIP entry points the owners use are defined HERE as counting stubs: they hand out distinct fake handles (never dereferenced), refuse a release
 // of a handle that is not live, and log every release in order.  No GPU call is made and the HIP runtime is not linked.
 // Two pieces of the frame ring's and the timing pool's own code (context.h) run over the same stubs: the growth of the order tables and a pool growth
-// that fails part-way.
+// that fails part-way.  So does the blocking host forms' staging (host_stage.h): its layout function, and a HostCall's way through the stage.
 // Prints one "name value" line per figure and "FAIL: ..." per broken expectation; exit status 1 if any.  tests/test_owners_host.py checks both.
 #include <cstdarg>
 #include <cstdint>
@@ -15,7 +15,10 @@
 namespace {
 
 enum Kind { DEV, PINNED, EVENT, STREAM, KINDS };                     // in g_calls a release is its kind + KINDS
-const Kind DEVICE_SYNC = static_cast<Kind>(2 * KINDS);                // hipDeviceSynchronize: an entry of g_calls ONLY, no kind -- never an index of the arrays below
+// entries of g_calls ONLY, no kinds -- never an index of the arrays below: hipDeviceSynchronize; hipMemcpyAsync to and from the device,
+// hipStreamSynchronize, and the mark a HostCall's enqueue step leaves when the test's own step runs
+const Kind DEVICE_SYNC = static_cast<Kind>(2 * KINDS), COPY_UP = static_cast<Kind>(2 * KINDS + 1), COPY_DOWN = static_cast<Kind>(2 * KINDS + 2),
+           STREAM_SYNC = static_cast<Kind>(2 * KINDS + 3), STEP = static_cast<Kind>(2 * KINDS + 4);
 const char* const kind_name[KINDS] = {"dev", "pinned", "event", "stream"};
 struct Release { Kind kind; void* handle; };
 
@@ -26,6 +29,10 @@ std::vector<Kind> g_calls;             // every acquire (its kind) and release (
 long g_made[KINDS] = {}, g_bad_release = 0, g_last_error_calls = 0;
 int g_fail_next_malloc = 0;
 int g_fail_event_in = 0;                 // n > 0: the n-th event creation from here on fails
+int g_fail_copy_in = 0;                  // n > 0: the n-th hipMemcpyAsync from here on fails
+struct Copy { void* dst; const void* src; size_t bytes; hipStream_t s; };
+std::vector<Copy> g_copies;            // every hipMemcpyAsync that succeeded, in order
+hipStream_t g_synced = nullptr;        // the stream of the last hipStreamSynchronize
 std::vector<size_t> g_malloc_bytes;    // of every hipMalloc that succeeded, in order
 long g_device_syncs = 0;
 int g_failures = 0;
@@ -74,6 +81,13 @@ hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { return acquire(EVE
 hipError_t hipEventDestroy(hipEvent_t e) { return release(EVENT, e); }
 hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned int) { return acquire(STREAM, reinterpret_cast<void**>(s)); }
 hipError_t hipStreamDestroy(hipStream_t s) { return release(STREAM, s); }
+hipError_t hipMemcpyAsync(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s) {
+    g_calls.push_back(kind == hipMemcpyHostToDevice ? COPY_UP : COPY_DOWN);
+    if (g_fail_copy_in && --g_fail_copy_in == 0) return hipErrorInvalidValue;
+    g_copies.push_back({dst, src, bytes, s});
+    return hipSuccess;
+}
+hipError_t hipStreamSynchronize(hipStream_t s) { g_calls.push_back(STREAM_SYNC); g_synced = s; return hipSuccess; }
 hipError_t hipGetLastError(void) { g_last_error_calls++; return hipSuccess; }
 const char* hipGetErrorString(hipError_t e) { return e == hipErrorOutOfMemory ? "out of memory (stub)" : "error (stub)"; }
 }
@@ -168,7 +182,10 @@ void test_context() {
     rc |= c->kt.grow(c, 70);   // a grown pool: the vector moved its events
     expect(c->kt.ev.size() == 70, "the timing pool did not grow to 70 events");
     for (csky_ctx::RadSet* r : {&c->rad_pf, &c->rad}) { rc |= r->out_cones.alloc(c, 6); rc |= r->src_cones.alloc(c, 6); rc |= r->tab.alloc(c, 12); }
-    rc |= c->d_rad_io.alloc(c, 64); rc |= c->ev_rad.create(c, hipEventDisableTiming); rc |= c->d_composite.alloc(c, 64);
+    rc |= c->ev_rad.create(c, hipEventDisableTiming); rc |= c->stage.d.alloc(c, 64);
+    rc |= c->ev_rays.create(c, hipEventDisableTiming); rc |= c->d_rays_fc.alloc(c, 1); rc |= c->ev_aerial.create(c, hipEventDisableTiming);
+    for (Event& e : c->rows_cache.ev_read) rc |= e.create(c, hipEventDisableTiming);
+    rc |= c->rows_cache.ev_fill.create(c, hipEventDisableTiming); rc |= c->rows_cache.d.alloc(c, 16);
     rc |= c->ring.d_heads.alloc(c, RING * 16); rc |= c->ring.d_sort_scratch.alloc(c, 8); rc |= c->ring.d_feedback_order.alloc(c, 8); rc |= c->ring.d_cost.alloc(c, 8);
     for (FrameSlot& k : c->ring.slot) { rc |= k.order.alloc(c, 8); rc |= k.ev_clouds.create(c, hipEventDisableTiming); rc |= k.ev_setup.create(c, hipEventDisableTiming); rc |= k.fc.alloc(c, 1); }
     rc |= c->d_frame.alloc(c, 64); rc |= c->d_stats.alloc(c, 130);
@@ -185,8 +202,11 @@ void test_context() {
     expect(rc == 0, "populating the context failed");
     void* const main_stream = static_cast<hipStream_t>(c->stream);
     const long made[KINDS] = {g_made[DEV] - made0[DEV], g_made[PINNED] - made0[PINNED], g_made[EVENT] - made0[EVENT] - 1, g_made[STREAM] - made0[STREAM]};
-    // the owning members of context.h, counted by hand
-    const long want[KINDS] = {12 + 2 + 4 + RING + 2 + RING + 4 + 1 + 6 + 1 + HOST_RING, HOST_RING, 4 + 2 * RING + 70 + HOST_RING, 1 + HOST_RING};
+    // the owning members of context.h, counted by hand, in its order.
+    // device buffers: the stage 1, the noise set 12, the transmittance LUT 2, the sky LUT's ring 4, the rows cache 1, the frame ring RING frame
+    //   constants + RING order tables + 4 shared, d_stats and d_frame 2, the two radiance sets 3 each, d_rays_fc 1, one per host slot
+    // events: ev0 ev1 ev_copy 3, the rows cache 1 + RING, two per frame slot, the timing pool 70, ev_rad ev_aerial ev_rays 3, one per host slot
+    const long want[KINDS] = {1 + 12 + 2 + 4 + 1 + RING + RING + 4 + 2 + 6 + 1 + HOST_RING, HOST_RING, 3 + 1 + RING + 2 * RING + 70 + 3 + HOST_RING, 1 + HOST_RING};
     for (int k = 0; k < KINDS; k++) expect(made[k] == want[k], "context: %ld %s handles made, %ld expected", made[k], kind_name[k], want[k]);
 
     delete c;
@@ -286,6 +306,146 @@ void test_timing_pool() {
     expect(live_total() == 0, "timing pool: %ld handles left alive", live_total());
 }
 
+// 10. the layout of a blocking call's regions (host_stage.h stage_layout): pure arithmetic, no HIP call
+void test_stage_layout() {
+    const size_t calls0 = g_calls.size();
+    const size_t A = STAGE_ALIGN;
+    auto check = [&](const char* what, std::vector<size_t> bytes) {
+        size_t off[STAGE_MAX_REGIONS], total = 0;
+        const int n = (int)bytes.size();
+        bool ok = stage_layout(bytes.data(), n, off, total) == CSKY_OK && off[0] == 0 && total == off[n - 1] + bytes[n - 1];
+        for (int i = 0; ok && i < n; i++) ok = off[i] % A == 0;
+        // in order and apart: a region begins at or after the end of the one before it, less than one alignment step after it
+        for (int i = 1; ok && i < n; i++) ok = off[i] >= off[i - 1] + bytes[i - 1] && off[i] - (off[i - 1] + bytes[i - 1]) < A;
+        // a region of no bytes costs nothing: the next region begins where it does
+        for (int i = 0; ok && i + 1 < n; i++) if (bytes[i] == 0) ok = off[i + 1] == off[i];
+        expect(ok, "stage layout: %s", what);
+        return ok ? total : (size_t)0;
+    };
+    const size_t image = (size_t)8192 * 8192 * 8, volume = (size_t)512 * 512 * 256 * 8, map = (size_t)8192 * 8192 * 2;
+    const size_t t_image = check("an 8192 x 8192 RGBA16F image", {image});
+    const size_t t_shafts = check("an 8192 x 8192 R16F map and a 512 x 512 x 256 volume", {map, volume});
+    const size_t t_ragged = check("ragged sizes", {1, 255, 256, 257, 2});
+    const size_t t_zero = check("regions of no bytes between others", {0, 33 * 9 * 8, 0, 0, 7});
+    const size_t t_view = check("no directions, then the image (the direct march of a view)", {0, 33 * 9 * 8});
+    check("all regions empty", {0, 0, 0});
+    expect(t_image == image && t_shafts == map + volume, "stage layout: aligned sizes at the forms' limits leave no gaps (%zu, %zu)", t_image, t_shafts);
+    expect(t_ragged == 5 * A + 2 && t_zero == 2560 + 7 && t_view == 33 * 9 * 8, "stage layout: totals %zu %zu %zu", t_ragged, t_zero, t_view);
+    printf("stage_layout_image_total %zu\nstage_layout_shafts_total %zu\nstage_layout_ragged_total %zu\nstage_layout_zero_regions_total %zu\n", t_image, t_shafts, t_ragged, t_zero);
+
+    // sums that do not fit in size_t, in the addition and in the rounding up; region counts out of range
+    size_t off[STAGE_MAX_REGIONS + 1], total = 1;
+    const size_t over_add[] = {SIZE_MAX - 100, 200}, over_pad[] = {SIZE_MAX - 3, 0}, fits[] = {SIZE_MAX - A, 0}, six[STAGE_MAX_REGIONS + 1] = {};
+    const bool refused = stage_layout(over_add, 2, off, total) == CSKY_ERR_INVALID && total == 0 && stage_layout(over_pad, 2, off, total) == CSKY_ERR_INVALID &&
+                         stage_layout(six, STAGE_MAX_REGIONS + 1, off, total) == CSKY_ERR_INVALID && stage_layout(six, 0, off, total) == CSKY_ERR_INVALID;
+    expect(refused, "stage layout: an overflowing sum or a bad region count was not refused");
+    expect(stage_layout(fits, 2, off, total) == CSKY_OK && total == SIZE_MAX - A + 1, "stage layout: a sum that just fits was refused");
+    // ... and reserve nothing: the stage keeps what it has, makes no call and names the caller
+    csky_ctx* c = new csky_ctx();
+    c->err[0] = 0;
+    HostCall over = host_call(c, "some_entry_point", {SIZE_MAX - 100, 200});
+    over.up(0, &total, sizeof total);
+    over.step([] { g_calls.push_back(STEP); return (int)CSKY_OK; });
+    const int rc = over.finish();
+    expect(rc == CSKY_ERR_INVALID && !c->stage.d && c->stage.d.count() == 0, "stage: an overflowing reservation returned %d or reserved something", rc);
+    printf("stage_overflow_refused %d\nstage_overflow_is_invalid %d\nstage_overflow_error_text %s\n", refused, rc == CSKY_ERR_INVALID, c->err);
+    delete c;
+    expect(g_calls.size() == calls0, "stage layout: %zu HIP calls made", g_calls.size() - calls0);
+    printf("stage_layout_hip_calls %zu\n", g_calls.size() - calls0);
+}
+
+// 11. a blocking call's way through the stage (host_stage.h HostCall): reserve, uploads, the step, the download, ONE wait -- and the wait whenever
+// something was enqueued, whatever failed
+void test_host_call() {
+    csky_ctx* c = new csky_ctx();
+    expect(c->stream.create(c, hipStreamNonBlocking) == CSKY_OK, "host call: the context's stream");
+    const hipStream_t s = c->stream;
+    char in0[300] = {}, in1[40] = {}, out[64] = {};
+    auto since = [](size_t from) { return std::vector<Kind>(g_calls.begin() + (long)from, g_calls.end()); };
+    auto step_ok = [&] { g_calls.push_back(STEP); return (int)CSKY_OK; };
+
+    // a call that succeeds, on an empty stage: one allocation of exactly the total, then uploads, step, download, wait
+    size_t calls0 = g_calls.size(), copies0 = g_copies.size(), mallocs0 = g_malloc_bytes.size();
+    HostCall a = host_call(c, "first", {sizeof in0, 0, sizeof in1, sizeof out});
+    a.up(0, in0, sizeof in0); a.up(1, in0, 0); a.up(2, in1, sizeof in1);
+    a.step(step_ok);
+    a.down(out, 3, sizeof out);
+    int rc = a.finish();
+    const bool first_ok = rc == CSKY_OK && since(calls0) == std::vector<Kind>{DEV, COPY_UP, COPY_UP, STEP, COPY_DOWN, STREAM_SYNC};
+    expect(first_ok, "host call: a successful call made %zu calls, not malloc, 2 uploads, the step, the download and one wait", g_calls.size() - calls0);
+    uint8_t* const base = c->stage.d;
+    expect(g_malloc_bytes.size() == mallocs0 + 1 && g_malloc_bytes.back() == 512 + 256 + sizeof out && c->stage.d.count() == 512 + 256 + sizeof out, "host call: the stage is not the call's total");
+    bool copies_ok = g_copies.size() == copies0 + 3 && g_synced == s;
+    if (copies_ok) {
+        const Copy& u0 = g_copies[copies0]; const Copy& u1 = g_copies[copies0 + 1]; const Copy& d0 = g_copies[copies0 + 2];
+        copies_ok = u0.dst == base && u0.src == in0 && u0.bytes == sizeof in0 && u0.s == s && u1.dst == base + 512 && u1.src == in1 && u1.bytes == sizeof in1 && u1.s == s &&
+                    d0.dst == out && d0.src == base + 768 && d0.bytes == sizeof out && d0.s == s && a.at<char>(1) == (char*)base + 512 && a.at<uint2>(3) == (uint2*)(base + 768);
+    }
+    expect(copies_ok, "host call: a copy has the wrong region, size or stream, or the wait is not for the context's stream");
+    printf("host_call_success_in_order %d\nhost_call_copies_in_their_regions %d\n", first_ok, copies_ok);
+
+    // a second call that needs less: no allocation call, the same memory
+    calls0 = g_calls.size();
+    HostCall b = host_call(c, "second", {16});
+    b.step(step_ok);
+    b.down(out, 0, 16);
+    rc = b.finish();
+    const bool smaller_ok = rc == CSKY_OK && since(calls0) == std::vector<Kind>{STEP, COPY_DOWN, STREAM_SYNC} && c->stage.d == base;
+    expect(smaller_ok, "host call: a call within the stage's size allocated, or made %zu calls", g_calls.size() - calls0);
+    // a third that needs more: the old buffer goes before the new one is asked for
+    calls0 = g_calls.size();
+    HostCall g = host_call(c, "third", {4096, 4096});
+    g.step(step_ok);
+    rc = g.finish();
+    const bool larger_ok = rc == CSKY_OK && since(calls0) == std::vector<Kind>{static_cast<Kind>(DEV + KINDS), DEV, STEP, STREAM_SYNC} && c->stage.d.count() == 8192;
+    expect(larger_ok, "host call: a call beyond the stage's size did not free, then allocate");
+    printf("host_call_smaller_allocates_nothing %d\nhost_call_larger_frees_then_allocates %d\n", smaller_ok, larger_ok);
+
+    // the step fails: no download, one wait, the step's code and text
+    calls0 = g_calls.size(); c->err[0] = 0;
+    HostCall f = host_call(c, "fourth", {sizeof in0, sizeof out});
+    f.up(0, in0, sizeof in0);
+    f.step([&] { g_calls.push_back(STEP); return fail(c, CSKY_ERR_STATE, "the step's own text"); });
+    f.down(out, 1, sizeof out);
+    rc = f.finish();
+    const bool step_fail_ok = rc == CSKY_ERR_STATE && since(calls0) == std::vector<Kind>{COPY_UP, STEP, STREAM_SYNC};
+    expect(step_fail_ok, "host call: a failed step returned %d after %zu calls", rc, g_calls.size() - calls0);
+    printf("host_call_step_failure_waits_once %d\nhost_call_step_failure_error_text %s\n", step_fail_ok, c->err);
+
+    // the first upload fails: nothing was enqueued, so no step, no download and no wait
+    calls0 = g_calls.size(); c->err[0] = 0; g_fail_copy_in = 1;
+    HostCall h = host_call(c, "fifth", {sizeof in0, sizeof in1, sizeof out});
+    h.up(0, in0, sizeof in0); h.up(1, in1, sizeof in1);
+    h.step(step_ok);
+    h.down(out, 2, sizeof out);
+    rc = h.finish();
+    const bool up0_fail_ok = rc == CSKY_ERR_HIP && since(calls0) == std::vector<Kind>{COPY_UP};
+    expect(up0_fail_ok, "host call: a failed first upload returned %d after %zu calls", rc, g_calls.size() - calls0);
+    printf("host_call_first_upload_failure_waits_never %d\nhost_call_upload_failure_error_text %s\n", up0_fail_ok, c->err);
+    // the second upload fails: the first is in flight from the caller's memory, so one wait; still no step and no download
+    calls0 = g_calls.size(); g_fail_copy_in = 2;
+    HostCall k = host_call(c, "sixth", {sizeof in0, sizeof in1, sizeof out});
+    k.up(0, in0, sizeof in0); k.up(1, in1, sizeof in1);
+    k.step(step_ok);
+    k.down(out, 2, sizeof out);
+    rc = k.finish();
+    const bool up1_fail_ok = rc == CSKY_ERR_HIP && since(calls0) == std::vector<Kind>{COPY_UP, COPY_UP, STREAM_SYNC};
+    expect(up1_fail_ok, "host call: a failed second upload returned %d after %zu calls", rc, g_calls.size() - calls0);
+    printf("host_call_second_upload_failure_waits_once %d\n", up1_fail_ok);
+    // a reservation that fails: nothing else happens
+    calls0 = g_calls.size(); g_fail_next_malloc = 1;
+    HostCall m = host_call(c, "seventh", {1 << 20});
+    m.up(0, in0, sizeof in0);
+    m.step(step_ok);
+    m.down(out, 0, sizeof out);
+    rc = m.finish();
+    const bool reserve_fail_ok = rc == CSKY_ERR_HIP && since(calls0) == std::vector<Kind>{static_cast<Kind>(DEV + KINDS), DEV} && !c->stage.d;
+    expect(reserve_fail_ok, "host call: a failed reservation returned %d after %zu calls", rc, g_calls.size() - calls0);
+    printf("host_call_reserve_failure_enqueues_nothing %d\n", reserve_fail_ok);
+    delete c;
+    expect(live_total() == 0, "host call: %ld handles left alive", live_total());
+}
+
 }  // namespace
 
 int main() {
@@ -298,6 +458,8 @@ int main() {
     test_empty_context();
     test_order_table_growth();
     test_timing_pool();
+    test_stage_layout();
+    test_host_call();
     printf("double_releases %ld\nlive_handles_at_exit %ld\nfailures %d\n", g_bad_release, live_total(), g_failures);
     return g_failures ? 1 : 0;
 }

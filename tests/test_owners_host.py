@@ -1,6 +1,7 @@
 """The owner types of csrc/owners.h (DevBuf, PinnedBuf, Event, Stream) and the destruction of a csky_ctx, on the CPU: tests/owners_host defines the
 HIP entry points the owners use as counting stubs, populates every owning member of a real csky_ctx through them and deletes it.  This is the leak and
-double-release check of the host layer; nothing here touches a GPU."""
+double-release check of the host layer.  The same tool walks the blocking host forms' staging (csrc/host_stage.h) over the stubs: the layout of a
+call's regions, and the one way through them.  Nothing here touches a GPU."""
 import os
 import subprocess
 
@@ -58,8 +59,12 @@ def test_failed_malloc_leaves_an_empty_owner_and_an_error_text(report):
 
 def test_a_full_context_returns_every_handle_once(report):
     _, _, figures = report
-    # 8 ring slots, 8 pinned host slots, two radiance sets, a timing pool grown from 2 to 70 events (context.h)
-    want = {"dev": 56, "pinned": 8, "event": 4 + 16 + 70 + 8, "stream": 9}
+    # counts of the owning members of context.h, with 8 ring slots, 8 pinned host slots and a timing pool grown from 2 to 70 events.
+    # device buffers: the stage 1, the noise set 12, the transmittance LUT 2, the sky LUT's ring 4, the rows cache 1, the frame ring 8 + 8 + 4,
+    #   d_stats and d_frame 2, two radiance sets of 3, d_rays_fc 1, the host slots 8
+    # events: ev0 ev1 ev_copy 3, the rows cache 1 + 8, the frame slots 16, the timing pool 70, ev_rad ev_aerial ev_rays 3, the host slots 8
+    want = {"dev": 1 + 12 + 2 + 4 + 1 + 20 + 2 + 6 + 1 + 8, "pinned": 8, "event": 3 + 9 + 16 + 70 + 3 + 8, "stream": 9}
+    assert want["dev"] == 57 and want["event"] == 109
     for kind, n in want.items():
         assert int(one(figures, "context_%s_made" % kind)) == n
         assert int(one(figures, "context_%s_released" % kind)) == n
@@ -102,3 +107,34 @@ def test_the_timing_pool_starts_at_512_events_and_doubles(report):
     _, _, figures = report
     assert int(one(figures, "pool_events_after_256_pairs")) == 512
     assert int(one(figures, "pool_events_after_257_pairs")) == 1024
+
+
+def test_the_stage_layout_is_aligned_gapless_and_refuses_overflow(report):
+    _, _, figures = report
+    # an 8192 x 8192 RGBA16F image; an 8192 x 8192 R16F map in front of a 512 x 512 x 256 volume: sizes that are multiples of 256 leave no gap
+    assert int(one(figures, "stage_layout_image_total")) == 8192 * 8192 * 8
+    assert int(one(figures, "stage_layout_shafts_total")) == 8192 * 8192 * 2 + 512 * 512 * 256 * 8
+    assert int(one(figures, "stage_layout_ragged_total")) == 5 * 256 + 2             # regions of 1, 255, 256, 257 and 2 bytes
+    assert int(one(figures, "stage_layout_zero_regions_total")) == 2560 + 7         # 0, 2376, 0, 0 and 7 bytes: the empty ones cost nothing
+    assert int(one(figures, "stage_overflow_refused")) == 1
+    assert int(one(figures, "stage_overflow_is_invalid")) == 1                      # CSKY_ERR_INVALID, nothing reserved (the tool's own expectation)
+    assert "some_entry_point" in one(figures, "stage_overflow_error_text")
+    assert int(one(figures, "stage_layout_hip_calls")) == 0
+
+
+def test_a_blocking_call_goes_one_way_through_the_stage(report):
+    _, _, figures = report
+    assert int(one(figures, "host_call_success_in_order")) == 1                     # allocation, uploads, the step, the download, one wait
+    assert int(one(figures, "host_call_copies_in_their_regions")) == 1
+    assert int(one(figures, "host_call_smaller_allocates_nothing")) == 1
+    assert int(one(figures, "host_call_larger_frees_then_allocates")) == 1
+
+
+def test_a_blocking_call_waits_for_what_it_enqueued_whatever_failed(report):
+    _, _, figures = report
+    assert int(one(figures, "host_call_step_failure_waits_once")) == 1              # no download, one wait, the step's code
+    assert one(figures, "host_call_step_failure_error_text") == "the step's own text"
+    assert int(one(figures, "host_call_first_upload_failure_waits_never")) == 1     # nothing was enqueued: no step, no wait
+    assert "hipMemcpyAsync" in one(figures, "host_call_upload_failure_error_text")
+    assert int(one(figures, "host_call_second_upload_failure_waits_once")) == 1     # the first upload is in flight: no step, one wait
+    assert int(one(figures, "host_call_reserve_failure_enqueues_nothing")) == 1
