@@ -514,7 +514,9 @@ CSKY_HD float sample_density(const TS& T, const FrameConsts& fc, float px, float
 
 // (Round-2 experiment, measured and removed: the cells of detail LODs 2..4 / 3..4 staged in LDS per workgroup and served to the light march
 // with one ds_read_b128 per tap: frames bit-identical, C3 2.16 / 2.08 ms against 2.05 ms (LODs 2..4 need 9.3 KB and cost a wavefront per SIMD;
-// LODs 3..4 remove 2 of 28 gathers per in-cloud sample and add a workgroup barrier + staging): profiles/r02/layout_lds_ab.txt.)
+// LODs 3..4 remove 2 of 28 gathers per in-cloud sample and add a workgroup barrier + staging): profiles/r02/layout_lds_ab.txt.
+// Round 19: LODs 3..4 again, in PERSISTENT launches only, where a workgroup stages the 72 cells once per launch in front of the barrier it has anyway:
+// TexSetSmallDetail, sample_density_eager<true, true> below; profiles/r19/small_detail_lds_ab.txt.)
 // (Round 6, measured and removed, profiles/r06/fp16_filter_ab.txt -- the one experiment on PRECISION, VERDICT r5 item 4: the y / z stages of every
 // polynomial cell in packed fp16 -- Q = P0 + fy P1 on both halves of a cell's (c_even, c_odd) fp16 pairs with v_pk_fma_f16, weights from one
 // v_cvt_pk_f16_f32, only the last stage lo + fx hi widened by v_fma_mix_f32: 69.5 M v_fma_mix + 69.5 M v_fmac per C3 frame became 69.5 M v_pk_fma_f16 +
@@ -531,7 +533,10 @@ CSKY_HD float sample_density(const TS& T, const FrameConsts& fc, float px, float
 #if CSKY_SHAPE_POLY == 3
 // EAGER_DETAIL = false fetches the weather and shape cells together and the detail cell only after reject (2): the form for the
 // primary march, where 77 % of the samples inside the height window reach the shape tap but only 31 % the detail tap.
-template <bool EAGER_DETAIL = true, class TS>
+// SMALL_TABLE (persistent launches, TS::small_detail): the caller passes lod_detail >= 3 only.  At 3 and 4 the tap reads the LDS table of those two levels;
+// at 5 (light sample j = 5 of the second loop of light_march_terms) there is no tap at all, as in every form: `tap` below is false and the sample takes
+// T.detail_lod5.  The table index below relies on that: it tells level 3 from "not 3", so a tap at level 5 would read the first cell of LOD 4.
+template <bool EAGER_DETAIL = true, bool SMALL_TABLE = false, class TS>
 CSKY_HD float sample_density_eager(const TS& T, const FrameConsts& fc, float px, float py, float pz, float hf, float wx, float wy,
                                    int lod_shape, int lod_detail) {
     if constexpr (TS::cell32) return sample_density(T, fc, px, py, pz, hf, wx, wy, lod_shape, lod_detail);   // exact cells: the lazy form (not the tuned path)
@@ -567,8 +572,21 @@ CSKY_HD float sample_density_eager(const TS& T, const FrameConsts& fc, float px,
             int dix, diy, diz;
             split_coord(dsx * dfn - 0.5f, dix, dax); split_coord(dsy * dfn - 0.5f, diy, day); split_coord(dsz * dfn - 0.5f, diz, daz);
             const uint32_t dsh = (uint32_t)(5 - lod_detail);
-            const uint32_t didx = detail_level_offset(lod_detail) + ((((((uint32_t)(diz & dm)) << dsh) | (uint32_t)(diy & dm)) << dsh) | (uint32_t)(dix & dm));
-            dq = *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(T.detail) + (didx << 4));
+            const uint32_t dlo = detail_level_offset(lod_detail), dcell = (((((uint32_t)(diz & dm)) << dsh) | (uint32_t)(diy & dm)) << dsh) | (uint32_t)(dix & dm);
+            const uint32_t didx = dlo + dcell;
+            if constexpr (SMALL_TABLE) {
+                // persistent launches: LODs 3 and 4 (light samples j = 3, 4) are 72 cells staged in LDS once per launch; the same cell through
+                // one ds_read_b128 instead of a 64-lane gather through the TA.  The index is didx - detail_level_offset(3) with the level's
+                // start inside the table (0 or the 64 cells of LOD 3) chosen on the scalar side: the address is one v_lshl_add, no more VALU
+                // than the global one.  Which samples come here is the light march's business (light_march_terms): a branch on the level
+                // per sample in here cost what the table saved.
+                static_assert(TS::small_detail && EAGER_DETAIL, "the table belongs to the persistent form's light march");
+                const uint32_t dfirst = lod_detail == TS::SMALL_DETAIL_FIRST ? 0u : detail_level_offset(TS::SMALL_DETAIL_FIRST + 1) - detail_level_offset(TS::SMALL_DETAIL_FIRST);
+                const SmallDetailCell c = T.det_small[dfirst + dcell];
+                dq.x = c.x; dq.y = c.y; dq.z = c.z; dq.w = c.w;
+            } else {
+                dq = *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(T.detail) + (didx << 4));
+            }
         }
         // ---- the arithmetic of density() (clouds.glsl:109-137) on the fetched cells
         CSKY_PRIO(CSKY_PRIO_MATH);
@@ -601,7 +619,7 @@ CSKY_HD float sample_density_eager(const TS& T, const FrameConsts& fc, float px,
     return d;
 }
 #else
-template <bool EAGER_DETAIL = true, class TS>
+template <bool EAGER_DETAIL = true, bool SMALL_TABLE = false, class TS>
 CSKY_HD float sample_density_eager(const TS& T, const FrameConsts& fc, float px, float py, float pz, float hf, float wx, float wy,
                                    int lod_shape, int lod_detail) {
     return sample_density(T, fc, px, py, pz, hf, wx, wy, lod_shape, lod_detail);

@@ -205,13 +205,33 @@ template <class TS, class Late>
 __device__ __forceinline__ void light_march_terms(const TS& T, const FrameConsts& fc, const int ls, const float nd, float ex, float ey, float ez, Late&& late,
                                                   float& Dr, float& Dg, float& Db, float& rq, float& dt) {
     float lx = ex, ly = ey, lz = ez, cd = 0.0f;
+#if CSKY_EAGER_LIGHT
+    constexpr int JS = TS::small_detail ? 3 : 6;                // persistent launches: samples j = 3, 4 (and a j = 5 that taps nothing) run in a loop of their own
+#else
+    constexpr int JS = 6;
+#endif
 #pragma unroll 1                                                 // scalar j: one loop body (unrolling measured no faster in rounds 2 and 5, 6x the code: profiles/r05/kernel_experiments.txt)
-    for (int j = 0; j < 6; j++) {                                                                      // :186 (light_steps <= 6)
+    for (int j = 0; j < JS; j++) {                                                                     // :186 (light_steps <= 6)
         if (j >= ls) break;
         advance(lx, ly, lz, fc.linc[j][0], fc.linc[j][1], fc.linc[j][2]);                              // :187
         const float lhf = height_fraction(length3_shell(lx, ly, lz));                                  // :188
         cd += CSKY_LIGHT_SAMPLE(T, fc, lx, ly, lz, lhf, fc.wpos_x, fc.wpos_y, j > 2 ? j - 2 : 0, j);   // :189-191
     }
+#if CSKY_EAGER_LIGHT
+    if constexpr (TS::small_detail) {
+        // the same samples with their detail tap (LODs 3, 4) served from the LDS table: a second copy of the loop body, so that which path a tap takes is
+        // decided by where the code is, not by a branch per sample.  The one-loop form (a scalar branch on the level inside the tap: two more branches and
+        // ~4 SALU per light sample) took the same loads off the TA and gained 0.4 % of the headline; this form 3.5 %, of which 2.3 are the split's own (with j >= 3
+        // known the shape level and the levels' extents fold: SALU -13 %) and 1.2 the table's (profiles/r19/small_detail_lds_ab.txt)
+#pragma unroll 1
+        for (int j = JS; j < 6; j++) {
+            if (j >= ls) break;
+            advance(lx, ly, lz, fc.linc[j][0], fc.linc[j][1], fc.linc[j][2]);                          // :187
+            const float lhf = height_fraction(length3_shell(lx, ly, lz));                              // :188
+            cd += sample_density_eager<true, true>(T, fc, lx, ly, lz, lhf, fc.wpos_x, fc.wpos_y, j - 2, j);   // :189-191
+        }
+    }
+#endif
     {   // distant sample, :195-199
         lx = ex; ly = ey; lz = ez;
         advance(lx, ly, lz, fc.ldist[0], fc.ldist[1], fc.ldist[2]);
@@ -685,6 +705,12 @@ __global__ __launch_bounds__(256, VARIANT == 3 ? CSKY_COMPACT_WAVES : 7) void cl
     xcc &= 7u;                                                 // eight sequences: MI355X has 8 XCDs; a part with fewer just leaves sequences to be stolen, one with more folds two XCDs onto one sequence (both still correct: every entry is popped exactly once)
     __shared__ uint32_t ticket, slot_ready[2], slot_reads[2], slot_entry[2], slot_rec[2];
     if (threadIdx.x == 0) { ticket = 0; slot_ready[0] = slot_ready[1] = 0; slot_reads[0] = slot_reads[1] = 0; }
+    // Detail LODs 3 and 4 (72 cells, 1 152 bytes) in LDS for the light march's taps j = 3, 4: a workgroup lives for the whole launch, so one 16-byte
+    // load by 72 threads in front of the barrier it has anyway is all the staging costs (round 2 staged per 4-tile workgroup of a plain launch, behind
+    // a barrier of its own, and lost: docs/EXPERIMENTS.md §5).  Staged from the set THIS launch was given: a rebind needs no care.
+    static_assert(VARIANT == 3, "the persistent form exists for the compact march only: its light march is the one that reads the table");
+    __shared__ __attribute__((aligned(16))) uint4 det_small[TexSetSmallDetail::SMALL_DETAIL_CELLS];
+    if (threadIdx.x < (unsigned)TexSetSmallDetail::SMALL_DETAIL_CELLS) det_small[threadIdx.x] = T.detail[detail_level_offset(TexSetSmallDetail::SMALL_DETAIL_FIRST) + threadIdx.x];
     __syncthreads();
     const bool lane0 = (threadIdx.x & 63) == 0;
     for (;;) {
@@ -728,7 +754,12 @@ __global__ __launch_bounds__(256, VARIANT == 3 ? CSKY_COMPACT_WAVES : 7) void cl
             }
             return;
         }
-        if (logical != 0xffffffffu) render_block<VARIANT, 1, TexSet, TALLY>(T, fcp, G, logical, rec, out, stats, wg_cost, tile);
+        if (logical != 0xffffffffu) {
+            TexSetSmallDetail Ts;
+            static_cast<TexSet&>(Ts) = T;
+            Ts.det_small = (SmallDetailTable)det_small;                        // generic -> LDS: a C-style cast is the only one that may change the address space
+            render_block<VARIANT, 1, TexSetSmallDetail, TALLY>(Ts, fcp, G, logical, rec, out, stats, wg_cost, tile);
+        }
     }
 }
 

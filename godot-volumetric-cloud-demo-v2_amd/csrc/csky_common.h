@@ -70,6 +70,7 @@ struct ShapeTexel { uint4 r, f; };
 #endif
 struct TexSet {
     static constexpr bool cell32 = false;   // fp16-pair cells (the layouts above)
+    static constexpr bool small_detail = false;   // no LDS table of detail LODs 3 and 4 (TexSetSmallDetail below has one)
     const ShapeTexel* shape;   // all mip levels back to back; level l starts at shape_level_offset(l) texels (cloud_core.h)
     const uint4* detail;    // all mip levels back to back; level l starts at detail_level_offset(l)
     const uint4* weather;   // 512*512
@@ -81,6 +82,25 @@ struct TexSet {
 #ifdef CSKY_BRICK_BOUND
     const float* brick;     // experiment build only (round 3): per 8^3-texel brick of shape level 0 (+1 apron) an upper bound of base_cloud
 #endif
+};
+
+// The same set inside a persistent launch (cloud_kernels.hip::clouds_kernel_persistent): the cells of detail LODs 3 and 4 (4^3 + 2^3 = 72 cells of
+// 16 bytes, adjacent in the baked chain) also sit in LDS, staged once per launch, and the light march's eager tap reads them from there
+// (cloud_core.h::sample_density_eager).  A type of its own, never a kernel argument: whether the table is present is a compile-time property of the
+// march (no run-time pointer test), and the kernels' argument layout stays what it was.
+// The table's pointer carries the LDS address space in its type: as two generic pointers the compiler folded the LDS read and the global gather
+// of the other levels into ONE flat load of a selected address, which goes through the TA like the gather it was to replace.
+#if defined(__HIPCC__)
+typedef unsigned int SmallDetailCell __attribute__((ext_vector_type(4)));
+typedef const __attribute__((address_space(3))) SmallDetailCell* SmallDetailTable;
+#else
+typedef uint4 SmallDetailCell;
+typedef const uint4* SmallDetailTable;
+#endif
+struct TexSetSmallDetail : TexSet {
+    static constexpr bool small_detail = true;
+    static constexpr int SMALL_DETAIL_FIRST = 3, SMALL_DETAIL_CELLS = 64 + 8;   // first level in the table; cells of levels 3 and 4
+    SmallDetailTable det_small;    // LDS: T.detail[detail_level_offset(3) + i], i < SMALL_DETAIL_CELLS
 };
 
 // The same set with EXACT cells (fp32 coefficients, bake_core.h): bound instead of TexSet when some coefficient of the textures does not fit fp16
