@@ -374,7 +374,9 @@ class CloudSky:
         (csky_render_aerial_perspective_shadowed): a shadow_size x shadow_size (or (w, h)) cloud shadow map is rendered over the rectangle
         aerial_shadow_rect gives for far_km and the sun, and the volume taps it; with device_buffers=True both run back to back on the march
         stream, without a host hop.  A sun at or below the horizon casts no shafts: the plain volume is rendered.  A sun so low that the rectangle
-        leaves the shadow map's range (within a quarter of a degree of the horizon at 32 km) raises CloudSkyError, as aerial_shadow_rect does."""
+        leaves the shadow map's range (within a quarter of a degree of the horizon at 32 km) raises CloudSkyError, as aerial_shadow_rect does;
+        above that limit every texel of the map, and so every half of the volume, is defined (sun lines that pass over the cloud base far out:
+        include/cloudsky.h)."""
         sun = self.frame_data.LIGHT_DIRECTION
         if cloud_shadows and float(np.float32(sun[1])) > 0.0:
             return self._aerial_perspective_shadowed(sun, width, height, depth, far_km, steps_per_slice, view, shadow_size)

@@ -2,8 +2,8 @@
 //
 // T(i, j) is the transmittance of the cloud layer from a ground point g of the observer's tangent plane towards the sun: the primary march's own
 // extinction (clouds.glsl:172-178, :207, :210) along the parallel ray g + l t between the two cloud shells, N samples at the mid-points of N equal
-// steps, without the view march's jitter.  What is new here is only the general intersect_sphere (cloud_core.h's assumes the camera position) and
-// the texel -> ray set-up; a sample is cloud_core.h's sample_density_eager<false> behind its exact rejects, as in the primary march.
+// steps, without the view march's jitter.  What is new here is only the general sphere intersection (cloud_core.h's assumes the camera position), the
+// texel -> ray set-up and its three kinds of texel; a sample is cloud_core.h's sample_density_eager<false> behind its exact rejects, as in the primary march.
 //
 // Host+device (CSKY_HD) like cloud_core.h: tests/shadow_host runs this per-lane code on a CPU against a numpy restatement of the definition that calls
 // the oracle per sample.  The product instantiates it inside shadow.hip only.
@@ -28,14 +28,29 @@ struct ShadowConsts {
 // =================================================================================================
 #pragma clang fp contract(off)
 
-// clouds.glsl:97-105 for any position (dot products summed left to right)
-CSKY_HD float intersect_sphere(float px, float py, float pz, float dx, float dy, float dz, float r) {
-    const float a = dx * dx + dy * dy + dz * dz;
-    const float b = 2.0f * (dx * px + dy * py + dz * pz);
+// clouds.glsl:97-105 for any position (dot products summed left to right), taken apart: the line g + l t is tested against both shells before a
+// root is taken.  disc < 0: the line does not meet the sphere.
+struct SphereLine { float a, b; };
+CSKY_HD SphereLine sphere_line(float px, float py, float pz, float dx, float dy, float dz) {
+    SphereLine q;
+    q.a = dx * dx + dy * dy + dz * dz;
+    q.b = 2.0f * (dx * px + dy * py + dz * pz);
+    return q;
+}
+CSKY_HD float sphere_disc(const SphereLine& q, float px, float py, float pz, float r) {
     const float c = (px * px + py * py + pz * pz) - (r * r);
-    const float d = sqrtf((b * b) - 4.0f * a * c);
-    const float p = -b - d, p2 = -b + d;
-    return fmaxf(p, p2) / (2.0f * a);
+    return (q.b * q.b) - 4.0f * q.a * c;
+}
+// the larger (the shader's) and the smaller root for a discriminant >= 0
+CSKY_HD float sphere_far(const SphereLine& q, float disc) {
+    const float d = sqrtf(disc);
+    const float p = -q.b - d, p2 = -q.b + d;
+    return fmaxf(p, p2) / (2.0f * q.a);
+}
+CSKY_HD float sphere_near(const SphereLine& q, float disc) {
+    const float d = sqrtf(disc);
+    const float p = -q.b - d, p2 = -q.b + d;
+    return fminf(p, p2) / (2.0f * q.a);
 }
 
 // The fields of FrameConsts a density sample reads (sample_density, density, the coordinate helpers), from the push-constant block alone: the
@@ -53,10 +68,15 @@ CSKY_HD void shadow_frame_consts(const CloudParams& P, int steps, float hf_lo, f
     fc.hf_lo = hf_lo; fc.hf_hi = hf_hi; fc.ct_mode = ct_mode;
 }
 
+// The three kinds of texel (cloudsky.h).  A ground point of the tangent plane lies above the inner shell from 134 km out, and under a low sun its
+// line can pass over that shell (CHORD: it crosses the layer from the outer shell to the outer shell) or over both (MISS: no cloud on it).
+enum ShadowKind { SHADOW_ORDINARY = 0, SHADOW_CHORD = 1, SHADOW_MISS = 2 };
+
 struct ShadowRay {
     float px, py, pz;     // first sample position: start + step / 2
     float sx, sy, sz;     // step
     float ss;             // step length
+    int kind;             // ShadowKind; a SHADOW_MISS ray has no samples and all-zero fields
 };
 
 // texel (i, j) -> its ray.  fc.ldir = normalize(LIGHT_DIRECTION), fc.steps_f = N.
@@ -65,8 +85,12 @@ CSKY_HD ShadowRay shadow_ray_setup(const ShadowConsts& sc, const FrameConsts& fc
     const float u = ((float)i + 0.5f) / (float)sc.w, v = ((float)j + 0.5f) / (float)sc.h;
     const float gx = sc.cx + (u - 0.5f) * sc.ex, gy = G_RADIUS, gz = sc.cz + (v - 0.5f) * sc.ez;
     const float lx = fc.ldir[0], ly = fc.ldir[1], lz = fc.ldir[2];
-    const float t0 = intersect_sphere(gx, gy, gz, lx, ly, lz, SKY_B_RADIUS);
-    const float t1 = intersect_sphere(gx, gy, gz, lx, ly, lz, SKY_T_RADIUS);
+    const SphereLine q = sphere_line(gx, gy, gz, lx, ly, lz);
+    const float disc_b = sphere_disc(q, gx, gy, gz, SKY_B_RADIUS), disc_t = sphere_disc(q, gx, gy, gz, SKY_T_RADIUS);
+    r.kind = disc_b >= 0.0f ? SHADOW_ORDINARY : disc_t >= 0.0f ? SHADOW_CHORD : SHADOW_MISS;
+    if (r.kind == SHADOW_MISS) { r.px = r.py = r.pz = r.sx = r.sy = r.sz = r.ss = 0.0f; return r; }
+    const float t0 = r.kind == SHADOW_ORDINARY ? sphere_far(q, disc_b) : sphere_near(q, disc_t);
+    const float t1 = sphere_far(q, disc_t);
     const float s0x = gx + lx * t0, s0y = gy + ly * t0, s0z = gz + lz * t0;                   // start
     const float e0x = gx + lx * t1, e0y = gy + ly * t1, e0z = gz + lz * t1;                   // end
     const float sd = length3_exact(e0x - s0x, e0y - s0y, e0z - s0z);
@@ -94,6 +118,7 @@ template <class TS>
 CSKY_HD uint16_t shadow_march(const TS& T, const FrameConsts& fc, const ShadowConsts& sc, const ShadowRay& r, bool live, unsigned long long* taken) {
     float px = r.px, py = r.py, pz = r.pz, tau = 0.0f;
     const float k = fc.density * r.ss;
+    const bool chord = r.kind == SHADOW_CHORD;
     unsigned n = 0;
     for (int i = 0; i < sc.steps; i++) {
         bool more = false;                                                                   // this lane may still meet a non-zero sample that matters
@@ -103,7 +128,7 @@ CSKY_HD uint16_t shadow_march(const TS& T, const FrameConsts& fc, const ShadowCo
             advance(px, py, pz, r.sx, r.sy, r.sz);
             n++;
             if (sc.exact_end && k * tau >= SHADOW_TAU_END) live = false;
-            more = live && !(hf >= fc.hf_hi);
+            more = live && (chord || !(hf >= fc.hf_hi));
         }
         if ((i & 3) == 3 && CSKY_WAVE_ALL(!more)) break;
     }
@@ -116,7 +141,8 @@ template <class TS>
 CSKY_HD uint16_t shadow_texel(const TS& T, const FrameConsts& fc, const ShadowConsts& sc, int i, int j, bool valid, unsigned long long* taken) {
     if (sc.night) return 0;                                                                  // uniform over the launch
     const ShadowRay r = shadow_ray_setup(sc, fc, valid ? i : 0, valid ? j : 0);
-    return shadow_march(T, fc, sc, r, valid, taken);
+    const uint16_t h = shadow_march(T, fc, sc, r, valid && r.kind != SHADOW_MISS, taken);     // a line that meets no cloud is not live: it only votes
+    return r.kind == SHADOW_MISS ? (uint16_t)0x3C00 : h;                                      // and stores the half 1.0
 }
 
 }  // namespace csky

@@ -328,8 +328,17 @@ int csky_prefilter_cube(csky_ctx* ctx, const uint16_t* cube_rgba16f, int face_si
  * packed for the frame (cloud_sky.gd:251-289).  Needs the noise (CSKY_ERR_STATE without it) and NO LUT: the map does not depend on the atmosphere.
  * Lookup in a host shader, for a world position (x, z) in this frame (observer at (0, 0)):
  *     uv = ((x, z) - center) / extent + 0.5          texel centres at ((i + 0.5) / W, (j + 0.5) / H); sample with linear filtering, clamp to edge
- * The ground is the tangent plane, not the sphere (33 m above it 20 km from the observer); far enough out (134 km) the plane leaves the cloud
- * layer's base and the formula above, which is still what is stored, stops describing a shadow. */
+ * The ground is the tangent plane, not the sphere (33 m above it 20 km from the observer); 134 km out the plane leaves the cloud layer's base, and
+ * under a low sun (below about 2.3 degrees) the line g + l t can then pass over the inner shell.  The discriminants of clouds.glsl:97-105, in the fp32
+ * order above, decide (a = dot(l, l), b = 2 dot(l, g), c(R) = dot(g, g) - R * R):
+ *     disc_b = b*b - 4*a*c(Rb),   disc_t = b*b - 4*a*c(Rt)
+ *     disc_b >= 0:                    start and end as written above (the larger roots); the ordinary texel
+ *     !(disc_b >= 0), disc_t >= 0:    the line misses the cloud base and crosses the layer on a chord:
+ *                                     start = g + l * min(p, p2) / (2a),  end = g + l * max(p, p2) / (2a),  both roots of Rt; sd, ss, step, the N
+ *                                     mid-point samples and the exp as written.  The whole line counts, the part behind g included, like the
+ *                                     whole-layer map that over-shadows inside the layer (light shafts, below).
+ *     !(disc_t >= 0):                 the line meets no cloud: T = 1.0, no sample is taken.
+ * So a map never holds a NaN for finite arguments.  (A line that meets the inner shell behind g keeps the formula's value: negative roots, finite.) */
 typedef struct {
     int   width, height;   /* texels, 1..8192 each                                                        */
     float center[2];       /* x, z of the map's centre, metres, the shader's frame (observer at 0, 0)     */

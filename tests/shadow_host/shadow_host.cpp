@@ -41,4 +41,23 @@ int shadow_host_map(const uint8_t* large_chain, const uint8_t* small_chain, cons
     return 0;
 }
 
+// The ray of every texel as shadow_ray_setup makes it: out_rays holds height x width x 7 floats (first sample position, step, step length) and
+// out_kind height x width ints (ShadowKind).  Needs no texture: the set-up reads the light direction, the step count and the map's geometry.
+int shadow_host_rays(const float params[28], int width, int height, const float center[2], const float extent[2], int steps, float* out_rays, int* out_kind) {
+    if (steps < 1 || steps > 1024 || width < 1 || height < 1) return -1;
+    CloudParams P; memcpy(&P, params, sizeof P);
+    ShadowConsts sc;
+    sc.w = width; sc.h = height; sc.cx = center[0]; sc.cz = center[1]; sc.ex = extent[0]; sc.ez = extent[1];
+    sc.steps = steps; sc.exact_end = 0; sc.night = 0; sc.pitch_h = (uint32_t)width;
+    FrameConsts fc;
+    shadow_frame_consts(P, steps, 0.0f, 1.0f, 0, fc);
+    for (int j = 0; j < height; j++) for (int i = 0; i < width; i++) {
+        const ShadowRay r = shadow_ray_setup(sc, fc, i, j);
+        float* o = out_rays + ((size_t)j * width + i) * 7;
+        o[0] = r.px; o[1] = r.py; o[2] = r.pz; o[3] = r.sx; o[4] = r.sy; o[5] = r.sz; o[6] = r.ss;
+        out_kind[(size_t)j * width + i] = r.kind;
+    }
+    return 0;
+}
+
 }

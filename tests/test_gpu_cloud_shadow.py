@@ -1,7 +1,9 @@
 """The cloud shadow map on the GPU (csky_render_cloud_shadow / _device; csrc/shadow.hip) against the numpy restatement of its definition
 (tests/shadow_reference.py, which calls the oracle per sample), at the project's gate for values rendered from the shipped assets: every texel
 within 2 fp16 ulp, 99.9 % within 1, largest difference 2e-3.  Then what a launch may touch: its W x H halfs and nothing else, no state of the
-cloud frames, the same bytes whatever the exact end does."""
+cloud frames, the same bytes whatever the exact end does.  Tests 9 and 10: the scene sweep of shadow_reference.SCENES (12 scenes, suns from the
+zenith down to a third of a degree over the rectangles csky_aerial_shadow_rect hands out, ordinary, chord and miss texels) on every context of the
+scene's weather map, and two of its low-sun scenes device form against host form; 21 tests in all."""
 import ctypes as C
 
 import numpy as np
@@ -61,23 +63,21 @@ def test_scenes_match_reference(gpu_ctx, fresh_ctx, exact_ctx, oracle, otex, nam
     SR.assert_gate(e, ref, "GPU, exact cells, scene " + name)
 
 
-@pytest.mark.parametrize("size", [(64, 64, 32, (0.0, 0.0), (16384.0, 16384.0)), (37, 21, 17, (1000.0, -3000.0), (9000.0, 9000.0))], ids=["64x64", "37x21"])
-def test_write_coverage(gpu_ctx, oracle, size):
-    """Test 6: the device form into a tensor of 0xFFFF halfs (a NaN no map contains) with guard rows and row padding."""
+def poisoned_render(ctx, p, W, H, center, extent, N, runs=3):
+    """The device form into a tensor of 0xFFFF halfs (a NaN no map contains) with GUARD rows before and after and PAD bytes behind each row: nothing
+    of the poison is left inside the map, none is lost outside it, and the bytes are the host form's.  Returns the host form's map."""
     import torch
-    W, H, N, center, extent = size
-    p = SR.scene(oracle, "A")
-    host = gpu_ctx.render_cloud_shadow(p, W, H, center, extent, N)
-    assert not (bits(host) == 0xFFFF).any() and len(np.unique(bits(host))) > 8
+    host = ctx.render_cloud_shadow(p, W, H, center, extent, N)
+    assert not (bits(host) == 0xFFFF).any()
     pitch = 2 * W + PAD
     s = torch.cuda.Stream()
-    for run in range(3):
+    for run in range(runs):
         with torch.cuda.stream(s):
             t = torch.empty((H + 2 * GUARD, pitch // 2), dtype=torch.int16, device="cuda")
             t.fill_(-1)
             share = t[GUARD:GUARD + H, :W]
             assert share.stride(0) * 2 == pitch
-            out = gpu_ctx.render_cloud_shadow(p, W, H, center, extent, N, out=share, stream=s.cuda_stream)
+            out = ctx.render_cloud_shadow(p, W, H, center, extent, N, out=share, stream=s.cuda_stream)
             assert out is share
             got = t.cpu().numpy().view(np.uint16)
         inside = np.zeros(got.shape, bool)
@@ -85,6 +85,15 @@ def test_write_coverage(gpu_ctx, oracle, size):
         assert not (got[inside] == 0xFFFF).any(), (run, np.argwhere(inside & (got == 0xFFFF))[:4])
         assert (got[~inside] == 0xFFFF).all(), (run, np.argwhere(~inside & (got != 0xFFFF))[:4])
         assert (got[GUARD:GUARD + H, :W] == bits(host)).all(), run
+    return host
+
+
+@pytest.mark.parametrize("size", [(64, 64, 32, (0.0, 0.0), (16384.0, 16384.0)), (37, 21, 17, (1000.0, -3000.0), (9000.0, 9000.0))], ids=["64x64", "37x21"])
+def test_write_coverage(gpu_ctx, oracle, size):
+    """Test 6: the device form into a tensor of 0xFFFF halfs (a NaN no map contains) with guard rows and row padding."""
+    W, H, N, center, extent = size
+    host = poisoned_render(gpu_ctx, SR.scene(oracle, "A"), W, H, center, extent, N)
+    assert len(np.unique(bits(host))) > 8
 
 
 def test_isolation(gpu_ctx, oracle):
@@ -147,6 +156,11 @@ def test_error_paths(pkg, gpu_ctx, oracle):
         assert host(s=bad) == INV and dev(s=bad, pitch=2 * 8193) == INV, (bad.width, bad.height, bad.steps, list(bad.center), list(bad.extent))
     assert host(s=sp(steps=0)) == lib.OK and host(s=sp(steps=1)) == lib.OK and host(s=sp(steps=1024)) == lib.OK
     assert host(s=sp(center=(997952.0, 0.0), extent=(4096.0, 4096.0))) == lib.OK          # |center| + extent / 2 == 1e6
+    up = float(np.nextafter(np.float32(997952.0), np.float32(np.inf)))                     # the next float up: 1e6 + 2^-4 is a float, and refused
+    assert np.float32(up) + np.float32(2048.0) == np.nextafter(np.float32(1.0e6), np.float32(np.inf))
+    for bad in (sp(center=(up, 0.0), extent=(4096.0, 4096.0)), sp(center=(0.0, -up), extent=(4096.0, 4096.0))):
+        assert host(s=bad) == INV and dev(s=bad) == INV
+    assert host(s=sp(center=(0.0, -997952.0), extent=(4096.0, 4096.0))) == lib.OK
     # non-finite floats: the map's own and every field of the block that is read
     for bad in (sp(center=(float("nan"), 0.0)), sp(center=(0.0, float("inf"))), sp(extent=(float("inf"), 4096.0)), sp(extent=(4096.0, float("nan")))):
         assert host(s=bad) == INV and dev(s=bad) == INV
@@ -200,3 +214,70 @@ def test_python_mirror(pkg, noise):
             assert (bits(r) == bits(sky.ctx.render_cloud_shadow(sky._fill_push_constant(), 40, 24, (100.0, -200.0), (8192.0, 4096.0), 16))).all()
         finally:
             sky.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------- the scene sweep (shadow_reference.SCENES)
+@pytest.fixture(scope="module")
+def sweep_ctxs(pkg, noise, gpu_ctx, fresh_ctx, exact_ctx):
+    """weather name -> the contexts a scene of that weather runs on (the white-noise weather map: exact-cells mode, the mixed cloud-type branch)"""
+    large, small, weather = noise
+    stratus, white = pkg.Context(0), pkg.Context(0)
+    stratus.set_noise(large, small, SR.weather_map(weather, "stratus"))
+    white.set_exact_cells(1)
+    white.set_noise(large, small, SR.weather_map(weather, "white"))
+    yield {"shipped": {"": gpu_ctx, ", no LUT": fresh_ctx, ", exact cells": exact_ctx}, "stratus": {", stratus": stratus}, "white": {", exact cells, white-noise weather": white}}
+    stratus.close()
+    white.close()
+
+
+@pytest.fixture(scope="module")
+def sweep_otex(oracle, noise, otex):
+    large, small, weather = noise
+    cache = {"shipped": otex}
+
+    def get(which):
+        if which not in cache:
+            cache[which] = oracle.OracleTextures(large, small, SR.weather_map(weather, which))
+        return cache[which]
+    return get
+
+
+@pytest.mark.parametrize("name", list(SR.SCENES))
+def test_sweep_matches_reference(sweep_ctxs, sweep_otex, oracle, name):
+    """Test 9: every scene of the sweep through the C ABI at the gate over all its texels, no NaN anywhere; suns down to a third of a degree, the
+    helper's rectangles, ordinary, chord and miss texels (cloudsky.h) in one wavefront's tile, step counts that end between the wave votes."""
+    from test_shadow_host import sweep_preconditions
+    sc = SR.SCENES[name]
+    p, size = SR.sweep_scene(oracle, name)
+    n = size["steps"] or 64
+    kind = SR.texel_kinds(p, size["width"], size["height"], size["center"], size["extent"])
+    ref, _ = SR.shadow_map(oracle, sweep_otex(sc["weather"]), p, **dict(size, steps=n))
+    sweep_preconditions(name, ref, kind)
+    args = (p, size["width"], size["height"], size["center"], size["extent"], size["steps"])     # steps as the table has it: 0 = 64
+    first = None
+    for what, ctx in sweep_ctxs[sc["weather"]].items():
+        m = ctx.render_cloud_shadow(*args)
+        SR.assert_gate(m, ref, "GPU%s, sweep %s" % (what, name))
+        assert (bits(m)[kind == SR.MISS] == 0x3C00).all()
+        if what == ", no LUT":
+            assert (bits(m) == bits(first)).all() and ctx.sky_lut_launches() == 0
+        first = m if first is None else first
+    if sc["mixed"] and sc["weather"] == "shipped":                # chord lanes and ordinary lanes share a wave vote: the bytes do not depend on the exits
+        ctx = sweep_ctxs["shipped"][""]
+        try:
+            ctx.set_shadow_exact_end(False)
+            ctx.set_height_window(0)
+            plain = ctx.render_cloud_shadow(*args)
+        finally:
+            ctx.set_shadow_exact_end(True)
+            ctx.set_height_window(1)
+        assert (bits(plain) == bits(first)).all()
+
+
+@pytest.mark.parametrize("name", ["deg1.1", "deg0.66-z"])
+def test_sweep_write_coverage(gpu_ctx, oracle, name):
+    """Test 10: two low-sun scenes, device form against host form, in test 6's poisoned, pitched and guarded tensor."""
+    p, size = SR.sweep_scene(oracle, name)
+    assert SR.SCENES[name]["kinds"][1] > 0
+    host = poisoned_render(gpu_ctx, p, size["width"], size["height"], size["center"], size["extent"], size["steps"], runs=2)
+    assert np.isfinite(host.astype(np.float32)).all() and len(np.unique(bits(host))) > 8

@@ -1,7 +1,8 @@
 """The shadowed aerial-perspective volume on the GPU (csky_render_aerial_perspective_shadowed / _device; csrc/shafts.hip) through the C ABI: against
 the host-compiled core (tests/shafts_host: the definition the kernel must equal) and the numpy restatement of the contract
 (tests/shafts_reference.py) at the volume's gate, every half within 1 fp16 ulp; then what ties it to the plain volume, the chunk boundaries of the
-kernel, what a launch may touch, what state it needs and leaves, every error path, and CloudSky's pair of launches.  The host core and the
+kernel, what a launch may touch, what state it needs and leaves, every error path, CloudSky's pair of launches, and the chain rectangle -> map ->
+volume at suns about one degree up, where the map has chord texels (include/cloudsky.h).  The host core and the
 restatement are given the GPU's own transmittance table: the volume kernel alone is compared."""
 import ctypes as C
 
@@ -9,9 +10,11 @@ import numpy as np
 import pytest
 
 import aerial_reference as AR
+import shadow_reference as SHR
 import shafts_reference as SR
 from test_aerial_host import CASES, SUNS, case_view
-from test_shafts_host import C4, M, M_CENTER, M_EXTENT, shafts_host, shafts_volume  # noqa: F401  (shafts_host: the module-scoped fixture)
+from test_shafts_host import (C4, LOW_MAP, LOW_SUNS, LOW_VIEWS, LOW_VOLUME, M, M_CENTER, M_EXTENT, low_sun_map_args, low_sun_reference, shafts_host,  # noqa: F401
+                              shafts_volume)                                             # (shafts_host: the module-scoped fixture)
 
 pytestmark = pytest.mark.gpu
 GUARD = 64                          # halfs of guard before and after the volume (a multiple of 4: texels are stored whole)
@@ -89,6 +92,34 @@ def test_height_rule(ctxs, tables, shafts_host, mapping):  # noqa: F811
     d_core, _ = AR.gate(got, core, what="height rule mapping %d, GPU vs host core" % mapping)
     d_ref, cancel = AR.gate(got, ref["out"], st[..., :4], ref["L"], what="height rule mapping %d, GPU vs restatement" % mapping)
     print("height rule mapping %d: %d of %d halves differ from the host core, %d from the restatement (%d let through as cancellation)" % (mapping, d_core, got.size, d_ref, cancel))
+
+
+# ---------------------------------------------------------------------------------------------------------------- G1b. rectangle -> map -> volume at sunrise
+@pytest.mark.parametrize("sun", list(LOW_SUNS))
+def test_low_sun_chain(pkg, gpu_ctx, ctxs, tables, shafts_host, oracle, sun):  # noqa: F811
+    """The chain the product runs, at suns 1.1 and 0.66 degrees up: a 64 x 16 map rendered on the GPU over the helper's rectangle (it has chord
+    texels: cloudsky.h) inside a 13 x 7 x 8 volume, through the panorama and a camera view.  Every half is finite; the volume meets the gates of G1
+    against the host core and the restatement fed the same map; alpha is the plain volume's."""
+    p, l, center, extent, kind = low_sun_map_args(oracle, sun)
+    want = pkg.aerial_shadow_rect(l, LOW_VOLUME["far"])
+    assert np.allclose(want[0], center, rtol=1e-6, atol=0) and np.allclose(want[1], extent, rtol=1e-6, atol=0)
+    shadow = gpu_ctx.render_cloud_shadow(p, LOW_MAP["width"], LOW_MAP["height"], center, extent, LOW_MAP["steps"])
+    assert np.isfinite(shadow.astype(np.float32)).all() and len(np.unique(bits(shadow)[kind == SHR.CHORD])) > 2
+    v = LOW_VOLUME
+    for view in LOW_VIEWS:
+        ref, n_chord, n_tapped = low_sun_reference(tables[0], 0, l, shadow, center, extent, kind, view)
+        vw, aspect = case_view(view)
+        aspect = 0.0 if vw is None else aspect
+        got = gpu_shafts(ctxs[0], v["W"], v["H"], v["D"], v["S"], v["far"], l, shadow, center, extent, view=vw, aspect=aspect)
+        assert got.shape == (v["D"], v["H"], v["W"], 4) and np.isfinite(got.astype(np.float32)).all()
+        core, st = shafts_volume(shafts_host, 0, tables[0], v["W"], v["H"], v["D"], v["S"], v["far"], l, shadow, center, extent, vw, aspect, state=True)
+        what = "low sun %s %s" % (sun, view)
+        d_core, _ = AR.gate(got, core, what=what + ", GPU vs host core")
+        d_ref, cancel = AR.gate(got, ref["out"], st[..., :4], ref["L"], what=what + ", GPU vs restatement")
+        print("%s: %d of %d tapped steps project into a chord texel; %d of %d halves differ from the host core, %d from the restatement (%d let through as cancellation)"
+              % (what, n_chord, n_tapped, d_core, got.size, d_ref, cancel))
+        plain = ctxs[0].render_aerial_perspective(l, v["W"], v["H"], v["D"], v["far"], v["S"], vw, aspect)
+        assert (bits(got[..., 3]) == bits(plain[..., 3])).all() and (bits(got[..., :3]) != bits(plain[..., :3])).any()
 
 
 # ---------------------------------------------------------------------------------------------------------------- G2. the ties to the plain volume
@@ -308,6 +339,18 @@ def test_cloud_sky_light_shafts(pkg, noise):
         c2, e2 = pkg.aerial_shadow_rect(sun, 40.0)
         s2 = sky.cloud_shadow_map((48, 32), e2, c2).cpu().numpy()
         assert (bits(r) == bits(sky.ctx.render_aerial_perspective_shadowed(sun, s2, c2, e2, 13, 7, 5, 40.0, 3, (AR.camera_basis(30.0, -30.0), 70.0)))).all()
+        # a sun about 1 degree up: the helper's rectangle reaches 260 km out, where the map has chord texels (cloudsky.h); nothing is NaN
+        sky.sun = pkg.cloud_sky.DirectionalLight(direction=(-0.6, 0.012, 0.3))
+        sky.update_sky()
+        low = np.asarray(sky.frame_data.LIGHT_DIRECTION, np.float32)
+        assert 0.5 < np.degrees(np.arcsin(low[1] / np.linalg.norm(low))) < 1.5
+        lv = sky.aerial_perspective(cloud_shadows=True, shadow_size=64).cpu().numpy()
+        assert np.isfinite(lv.astype(np.float32)).all()
+        c3, e3 = pkg.aerial_shadow_rect(low, 32.0)
+        s3 = sky.cloud_shadow_map(64, e3, c3).cpu().numpy()
+        assert np.isfinite(s3.astype(np.float32)).all()
+        assert (bits(lv) == bits(sky.ctx.render_aerial_perspective_shadowed(low, s3, c3, e3))).all()
+        assert (bits(lv[..., 3]) == bits(sky.aerial_perspective().cpu().numpy()[..., 3])).all()
         # a sun under the horizon: the plain volume
         sky.sun = pkg.cloud_sky.DirectionalLight(direction=(-0.6, -0.05, 0.3))
         sky.update_sky()

@@ -2,7 +2,8 @@
 must equal), compiled for the host by tests/shafts_host, against the unshadowed core (tests/aerial_host) and the numpy restatement of the contract
 (tests/shafts_reference.py).  A unit test of device code, not a render path: libcloudsky itself has no CPU implementation.
 
-The gate is the volume's own (aerial_reference.gate): every half within 1 fp16 ulp."""
+The gate is the volume's own (aerial_reference.gate): every half within 1 fp16 ulp.  C6 is the chain the product runs at sunrise: the helper's
+rectangle, a cloud shadow map with chord texels from the host build of the shadow core (tests/shadow_host), the volume."""
 import ctypes as C
 import os
 import subprocess
@@ -11,14 +12,47 @@ import numpy as np
 import pytest
 
 import aerial_reference as AR
+import shadow_reference as SHR
 import shafts_reference as SR
 from conftest import ROOT
 from test_aerial_host import CASES, SUNS, P, aerial_host, case_view, host_luts, host_volume  # noqa: F401  (aerial_host, host_luts: module-scoped fixtures)
+from test_shadow_host import chains, host_map, shadow_host  # noqa: F401  (shadow_host, chains: module-scoped fixtures)
 from test_tlut_mapping import tlut_host  # noqa: F401  (host_luts needs it)
 
 M, M_CENTER, M_EXTENT = SR.synthetic_map()
 # the height rule's case (C4): panorama 8 x 4, D = 40, S = 1, 8 km, a zenith sun, one black texel over 100 km
 C4 = dict(W=8, H=4, D=40, S=1, far=8.0, sun=np.array([0.0, 1.0, 0.0], np.float32), shadow=np.zeros((1, 1), np.float16), center=(0.0, 0.0), extent=(100000.0, 100000.0))
+
+
+# the chain the product runs at sunrise: the helper's rectangle -> a 64 x 16 cloud shadow map -> a 13 x 7 x 8 volume, S = 2, 32 km.  The map's push
+# constants are the sweep scene's of that sun (tests/shadow_reference.py); the views: the panorama and the camera of case "up".
+LOW_SUNS = {"deg1.1": "deg1.1", "deg0.66": "deg0.66-z"}
+LOW_MAP = dict(width=64, height=16, steps=32)
+LOW_VOLUME = dict(W=13, H=7, D=8, S=2, far=32.0)
+LOW_VIEWS = ("panorama", "up")
+
+
+def low_sun_map_args(oracle, sun):
+    """(push-constant block, its unit sun, the helper's (center, extent) by the contract's text, the kind of every texel of the 64 x 16 map)"""
+    p, _ = SHR.sweep_scene(oracle, LOW_SUNS[sun])
+    l = np.asarray(p[16:19], np.float32)
+    center, extent = SHR.helper_rect(l, LOW_VOLUME["far"])
+    return p, l, center, extent, SHR.texel_kinds(p, LOW_MAP["width"], LOW_MAP["height"], center, extent)
+
+
+def low_sun_reference(trans, mapping, l, shadow, center, extent, kind, view):
+    """The restatement's volume over `shadow`, behind its precondition: at least one tapped step projects into a chord texel of the map."""
+    v = LOW_VOLUME
+    vw, aspect = case_view(view)
+    ref = SR.volume(v["W"], v["H"], v["D"], v["S"], v["far"], l, trans, shadow, center, extent, mapping, vw, 0.0 if vw is None else aspect)
+    assert not ref["near"].any() and np.isfinite(ref["out"].astype(np.float32)).all()
+    tapped = ref["take"] & ref["tapped"]
+    i = np.floor(((ref["gx"][tapped] - np.float32(center[0])) / np.float32(extent[0]) + 0.5) * LOW_MAP["width"]).astype(int)
+    j = np.floor(((ref["gz"][tapped] - np.float32(center[1])) / np.float32(extent[1]) + 0.5) * LOW_MAP["height"]).astype(int)
+    ok = (i >= 0) & (i < LOW_MAP["width"]) & (j >= 0) & (j < LOW_MAP["height"])
+    in_chord = kind[j[ok], i[ok]] == SHR.CHORD
+    assert in_chord.any(), "no tapped step projects into a chord texel"
+    return ref, int(in_chord.sum()), int(tapped.sum())
 
 
 def bits(a):
@@ -244,6 +278,29 @@ def test_shadow_rect_errors_and_default(pkg):
     two = (C.c_float * 2)()
     assert L.csky_aerial_shadow_rect(None, two, two) == lib.ERR_INVALID and L.csky_aerial_shadow_rect(C.byref(p), None, two) == lib.ERR_INVALID
     assert L.csky_aerial_shadow_rect(C.byref(p), two, None) == lib.ERR_INVALID
+
+
+# ---------------------------------------------------------------------------------------------------------------- C6. rectangle -> map -> volume at sunrise
+@pytest.mark.parametrize("view", LOW_VIEWS)
+@pytest.mark.parametrize("sun", list(LOW_SUNS))
+def test_low_sun_chain(shafts_host, aerial_host, host_luts, shadow_host, chains, oracle, sun, view):  # noqa: F811
+    """A map with chord texels (cloudsky.h: the sun's line passes over the cloud base) from the host build of the shadow core, inside the volume:
+    finite, at the volume's gate against the restatement fed the same map, and alpha is the plain volume's."""
+    p, l, center, extent, kind = low_sun_map_args(oracle, sun)
+    assert (kind == SHR.CHORD).any()
+    shadow, _ = host_map(shadow_host, chains, p, center=center, extent=extent, **LOW_MAP)
+    assert np.isfinite(shadow.astype(np.float32)).all() and len(np.unique(bits(shadow)[kind == SHR.CHORD])) > 2
+    ref, n_chord, n_tapped = low_sun_reference(host_luts[0], 0, l, shadow, center, extent, kind, view)
+    print("%s %s: %d of %d tapped steps project into a chord texel" % (sun, view, n_chord, n_tapped))
+    v = LOW_VOLUME
+    vw, aspect = case_view(view)
+    aspect = 0.0 if vw is None else aspect
+    got, st = shafts_volume(shafts_host, 0, host_luts[0], v["W"], v["H"], v["D"], v["S"], v["far"], l, shadow, center, extent, vw, aspect, state=True)
+    assert np.isfinite(got.astype(np.float32)).all() and np.isfinite(st).all()
+    differ, cancel = AR.gate(got, ref["out"], st[..., :4], ref["L"], what="low sun %s %s" % (sun, view))
+    print("low sun %s %s: %d of %d halves differ from the restatement, %d let through as cancellation" % (sun, view, differ, got.size, cancel))
+    plain = host_volume(aerial_host, 0, host_luts[0], v["W"], v["H"], v["D"], v["S"], v["far"], l, vw, aspect)
+    assert (bits(got[..., 3]) == bits(plain[..., 3])).all() and (bits(got[..., :3]) != bits(plain[..., :3])).any()
 
 
 # ---------------------------------------------------------------------------------------------------------------- the C ABI, without a GPU
