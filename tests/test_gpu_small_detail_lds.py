@@ -53,19 +53,23 @@ def persistent(pkg, noise):
     ctx.close()
 
 
-def _host_frame(ctx, p):
+def _host_frame(ctx, p, tile_w=None, tile_h=None):
     """csky_render_clouds: a launch with a stats buffer (TALLY = true)"""
-    img = ctx.render_clouds(p).view(np.uint16).copy()
+    img = ctx.render_clouds(p, tile_w, tile_h).view(np.uint16).copy()
     return img, ctx.cloud_stats()
 
 
-def _device_frames(ctx, p, W, H, fif):
-    """csky_render_clouds_device, no stats buffer (TALLY = false): every one of `fif` streams and output tensors twice, the second time over 0xFFFF halfs"""
+def _device_frames(ctx, p, W, H, fif, sun=None, bands=None):
+    """csky_render_clouds_device, no stats buffer (TALLY = false): every one of `fif` streams and output tensors twice, the second time over 0xFFFF halfs.
+    `bands`: the rows to render (default: H rows as bands of 8); `sun`: the unit vector the context's sky LUT was rendered for (default: norm(SUN))."""
     import torch
-    bands = (8, 0, 1, (H + 7) // 8)
+    if bands is None:
+        bands = (8, 0, 1, (H + 7) // 8)
+    if sun is None:
+        sun = norm(SUN)
     ctx.set_frames_in_flight(fif)
     streams = [torch.cuda.Stream() for _ in range(fif)]
-    outs = [torch.zeros((bands[3] * 8, W, 4), dtype=torch.int16, device="cuda") for _ in range(fif)]
+    outs = [torch.zeros((bands[3] * bands[0], W, 4), dtype=torch.int16, device="cuda") for _ in range(fif)]
     torch.cuda.synchronize()
     frames = []
     try:
@@ -75,7 +79,7 @@ def _device_frames(ctx, p, W, H, fif):
                 if k >= fif:
                     frames.append(outs[i].cpu().numpy().copy())
                     outs[i].fill_(-1)
-                ctx.render_sky_lut_device(norm(SUN), 200, 100, streams[i].cuda_stream)
+                ctx.render_sky_lut_device(sun, 200, 100, streams[i].cuda_stream)
                 ctx.render_clouds_device(p, W, bands, outs[i].data_ptr(), W * 8, streams[i].cuda_stream)
         torch.cuda.synchronize()
     finally:

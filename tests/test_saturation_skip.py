@@ -3,13 +3,12 @@ cores, the full march against the march that freezes (L, alpha) the first time t
 the earliest any flush of march_compact can latch the ray.  Required everywhere: no ray stores a different half, and the in-cloud tally is the
 full march's.  Fired shares are printed for every case (pytest -s); only the headline view must fire."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import ROOT, norm
+from saturation_scenes import TABLE, check_fired, load_satwalk, mip_chains, params
 
 
 def P(a):
@@ -18,15 +17,12 @@ def P(a):
 
 @pytest.fixture(scope="module")
 def satwalk():
-    d = os.path.join(ROOT, "tests", "satwalk")
-    subprocess.check_call(["make", "-C", d, "-s"])
-    return C.CDLL(os.path.join(d, "libsatwalk.so"))
+    return load_satwalk(ROOT)
 
 
 @pytest.fixture(scope="module")
 def chains(pkg, noise):
-    large, small, weather = noise
-    return pkg.assets.build_mips(large, 8), pkg.assets.build_mips(small, 6), weather
+    return mip_chains(pkg, noise)
 
 
 def walk(satwalk, chains, oracle, o_trans, w, h, sun, coverage=0.2, density=0.05, primary=128, light=6, alpha_min=-1.0, b_scale=1.0, params=None):
@@ -89,6 +85,16 @@ def test_sun_below_the_horizon(satwalk, chains, oracle, o_trans):
 def test_other_march_lengths(satwalk, chains, oracle, o_trans, primary, light):
     """64 x 4 steps, and 1024 primary steps (the accumulation slop is sized from the step count)."""
     exact(walk(satwalk, chains, oracle, o_trans, 192, 96, (1, 1, 0), coverage=0.35, primary=primary, light=light))
+
+
+@pytest.mark.parametrize("sc", TABLE, ids=lambda s: s.name)
+def test_scene_table(satwalk, chains, oracle, o_trans, sc):
+    """tests/saturation_scenes.py: where the bound is tight and where the guards L >= 2^-14 and hi < 65504 bind.  The firing counts of the table are this
+    walk's; a scene that fires must keep firing (a third of its count), a control must not fire."""
+    r = walk(satwalk, chains, oracle, o_trans, sc.size[0], sc.size[1], sc.sun, coverage=sc.coverage, density=sc.density, primary=sc.primary, light=sc.light,
+             params=params(oracle, sc))
+    exact(r)
+    check_fired(sc, r["fired"])
 
 
 def test_negative_colour_switches_the_skip_off(satwalk, chains, oracle, o_trans):

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, norm
+from saturation_scenes import TABLE, check_fired, mip_chains, params
 
 BLOCK = ("light_marched", "incloud", "wave_steps", "lanes_weather", "lanes_shape", "lanes_detail", "differ", "latched")
 
@@ -29,19 +30,18 @@ def tilewalk():
 
 @pytest.fixture(scope="module")
 def chains(pkg, noise):
-    large, small, weather = noise
-    return pkg.assets.build_mips(large, 8), pkg.assets.build_mips(small, 6), weather
+    return mip_chains(pkg, noise)
 
 
 def cut(a, b):
     return 100.0 * (a - b) / max(1, a)
 
 
-def walk(tilewalk, chains, oracle, o_trans, w, h, sun, coverage=0.2, primary=128, light=6, alpha_min=-1.0, b_scale=1.0):
+def walk(tilewalk, chains, oracle, o_trans, w, h, sun, coverage=0.2, primary=128, light=6, alpha_min=-1.0, b_scale=1.0, params=None):
     from bench import usable_cores
     lc, sc, weather = chains
     sky = np.ascontiguousarray(oracle.sky_lut(norm(sun), o_trans, 200, 100)).view(np.uint16)
-    p = np.ascontiguousarray(oracle.default_params(w, h, sun, coverage=coverage), np.float32)
+    p = np.ascontiguousarray(oracle.default_params(w, h, sun, coverage=coverage) if params is None else params, np.float32)
     out, misc = np.zeros(24, np.float64), np.zeros(2, np.float64)
     tilewalk.tile_walk(P(lc), P(sc), P(weather), P(p), primary, light, P(sky), 200, 100, w, h, C.c_float(alpha_min), C.c_float(b_scale),
                        max(1, min(16, usable_cores())), P(out), P(misc))
@@ -97,6 +97,24 @@ def test_grazing_suns_of_the_sweep(tilewalk, chains, oracle, o_trans, deg):
 @pytest.mark.parametrize("primary,light", [(64, 4), (1024, 6)])
 def test_other_march_lengths(tilewalk, chains, oracle, o_trans, primary, light):
     exact(walk(tilewalk, chains, oracle, o_trans, 192, 96, (1, 1, 0), coverage=0.35, primary=primary, light=light))
+
+
+@pytest.mark.parametrize("sc", TABLE, ids=lambda s: s.name)
+def test_scene_table(tilewalk, chains, oracle, o_trans, sc):
+    """tests/saturation_scenes.py in both TALLY forms.  A scene that fires must latch at least the floor of the table (the test after the last flush
+    latches a few rays more than the per-sample walk of tests/satwalk sees fire).  A control must leave no sample behind a latch: both forms light-march
+    every in-cloud sample and the dead-lane form removes no lane-step; and no ray latches at all, except in the two shortest marches, whose steps are so
+    long that alpha reaches 1 at the LAST flush, where nothing is left to skip (4 512 rays of the 2 x 0 scene latch there)."""
+    r = walk(tilewalk, chains, oracle, o_trans, sc.size[0], sc.size[1], sc.sun, coverage=sc.coverage, primary=sc.primary, light=sc.light, params=params(oracle, sc))
+    exact(r)
+    if sc.fired:
+        check_fired(sc, r["tally"]["latched"])
+        assert r["tally"]["light_marched"] < r["plain"]["light_marched"], r
+    else:
+        if sc.name not in ("2x0", "1x6"):       # hi < 65504 / L >= 2^-14 / alpha >= 1 - 2^-12 can never hold in the other controls: no latch at all
+            assert r["tally"]["latched"] == 0 and r["dead"]["latched"] == 0, r
+        assert r["tally"]["light_marched"] == r["plain"]["light_marched"] == r["plain"]["incloud"], r
+        assert all(r["dead"][k] == r["tally"][k] for k in ("wave_steps", "lanes_weather", "lanes_shape", "lanes_detail")), r
 
 
 def test_mutation_control(tilewalk, chains, oracle, o_trans):
