@@ -15,30 +15,25 @@ namespace {
 
 template <int TLUT> __global__ __launch_bounds__(256) void cloud_aerial_kernel(const CloudAerialGeom g, const float4* __restrict__ trans, int tw, int th,
                                                                                  const uint2* cloud, const uint2* depth, uint2* out) {
-    const int tiles_x = (g.w + 31) >> 5;
-    const int slab = (int)blockIdx.x / tiles_x, bx = (int)blockIdx.x - slab * tiles_x;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int i = bx * 32 + wave * 8 + (lane & 7);
-    const int j = slab * 8 + (lane >> 3);
-    const bool valid = i < g.w && j < g.h;                     // a ragged frame masks the lanes of its partial tiles
-    const size_t at = (size_t)(valid ? j : 0) * (size_t)g.w + (size_t)(valid ? i : 0);
+    const TilePixel p = tile_pixel(g.w, g.h);
+    const size_t at = (size_t)(p.valid ? p.j : 0) * (size_t)g.w + (size_t)(p.valid ? p.i : 0);
     uint2 c, z;
     c.x = c.y = z.x = z.y = 0u;
-    if (valid) { c = cloud[at]; z = depth[at]; }
-    const bool work = valid && !cloud_aerial_passes(c, z);
+    if (p.valid) { c = cloud[at]; z = depth[at]; }
+    const bool work = p.valid && !cloud_aerial_passes(c, z);
     if (__builtin_amdgcn_ballot_w64(work) == 0ull) {           // clear sky, or the frame's edge under the horizon
-        if (valid) out[at] = c;
+        if (p.valid) out[at] = c;
         return;
     }
-    if (work) c = cloud_aerial_pixel<TLUT>(g, i, j, c, z, trans, tw, th);
-    if (valid) out[at] = c;
+    if (work) c = cloud_aerial_pixel<TLUT>(g, p.i, p.j, c, z, trans, tw, th);
+    if (p.valid) out[at] = c;
 }
 
 }  // namespace
 
 hipError_t launch_cloud_aerial(const CloudAerialGeom& g, const float4* d_trans, int tw, int th, const uint2* d_cloud, const uint2* d_depth, uint2* d_out,
                                hipStream_t s, int tlut) {
-    const int grid = ((g.w + 31) >> 5) * ((g.h + 7) >> 3);     // <= 256 x 1024 for the largest frame
+    const int grid = tile_grid(g.w, g.h);
     if (tlut == TLUT_BRUNETON) cloud_aerial_kernel<TLUT_BRUNETON><<<grid, 256, 0, s>>>(g, d_trans, tw, th, d_cloud, d_depth, d_out);
     else cloud_aerial_kernel<TLUT_REFERENCE><<<grid, 256, 0, s>>>(g, d_trans, tw, th, d_cloud, d_depth, d_out);
     return hipGetLastError();

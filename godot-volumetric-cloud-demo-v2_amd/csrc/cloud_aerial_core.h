@@ -2,12 +2,12 @@
 // and the cloud of every pixel of a hemisphere frame, the cloud placed at the mean distance its depth frame holds (depth_core.h).  Per pixel it
 // is one column of the aerial-perspective volume (aerial_core.h; §14) with D = 1, S = n and far_km the pixel's own distance, composited the way
 // the header tells a host to composite a surface: aerial_ray, the skip rule, sky_step, sky_accumulate and sky_output are used unchanged.  What
-// is new here is only the pixel -> direction step (depth_core.h pixel_dir, the cloud march's own) and the composite.
+// is new here is only the pixel -> direction step (cloud_core.h pixel_dir, the cloud march's own) and the composite.
 // Host+device like the other cores: cloud_aerial_pixel is the definition, what tests/cloud_aerial_host runs and what cloud_aerial.hip must equal
 // bit for bit.  FP contraction off.  Units: km.
 #pragma once
 #include "csky_common.h"
-#include "depth_core.h"
+#include "cloud_core.h"
 #include "aerial_core.h"
 
 namespace csky {

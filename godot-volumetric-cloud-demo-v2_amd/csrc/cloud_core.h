@@ -102,12 +102,12 @@ CSKY_HD float intersect_sphere_cam(float dx, float dy, float dz, float r) {
     return fmaxf(p, p2) / (2.0f * a);
 }
 
-// clouds.glsl:258-262 (main), :248-256 (oct_to_vec3), :218-231 (sky) and :143-145 (march prologue).
-// gx, gy = gl_GlobalInvocationID.xy.
-CSKY_HD Ray ray_setup(const FrameConsts& fc, int gx, int gy) {
-    Ray r;
-    const int px = gx + fc.upd_x, py = gy + fc.upd_y;
-    const float ex = (float)px / fc.tex_w, ey = (float)py / fc.tex_h;
+// The ray of a grid pixel is pixel_dir then ray_from_dir: clouds.glsl:258-262 (main), :248-256 (oct_to_vec3), then :218-231 (sky) and :143-145
+// (march prologue).  The depth frame and the aerial pass take the direction alone, the direct march (rays_core.h) a ray from a direction of its own.
+
+// The direction of pixel (i, j) of a tex_w x tex_h frame: main() up to the .xzy swizzle (clouds.glsl:258-262, :248-256).
+CSKY_HD void pixel_dir(float tex_w, float tex_h, int i, int j, float& dx, float& dy, float& dz) {
+    const float ex = (float)i / tex_w, ey = (float)j / tex_h;
     float nx = ex - ey;
     float ny = (ex + ey) - 1.0f;
     const float nz = 1.0f - fabsf(nx) - fabsf(ny);
@@ -117,7 +117,12 @@ CSKY_HD Ray ray_setup(const FrameConsts& fc, int gx, int gy) {
         nx = wx; ny = wy;
     }
     const float nl = length3_exact(nx, ny, nz);
-    const float dx = nx / nl, dy = nz / nl, dz = ny / nl;  // .xzy swizzle, clouds.glsl:262
+    dx = nx / nl; dy = nz / nl; dz = ny / nl;  // .xzy swizzle, clouds.glsl:262
+}
+
+// The march's ray of a unit direction: sky() and the march prologue (clouds.glsl:221-230, :143-145).  Under the horizon: `above = false`, zero fields.
+CSKY_HD Ray ray_from_dir(const FrameConsts& fc, float dx, float dy, float dz) {
+    Ray r;
     r.above = dy > 0.0f;
     if (!r.above) { r.px = r.py = r.pz = r.sx = r.sy = r.sz = r.dx = r.dy = r.dz = r.ss = 0.0f; return r; }
     const float t0 = intersect_sphere_cam(dx, dy, dz, SKY_B_RADIUS);
@@ -134,6 +139,13 @@ CSKY_HD Ray ray_setup(const FrameConsts& fc, int gx, int gy) {
     // tests/test_oracle_structure.py checks the oracle's literal evaluation).  Hence p = pos exactly.
     r.px = s0x; r.py = s0y; r.pz = s0z;
     return r;
+}
+
+// gx, gy = gl_GlobalInvocationID.xy.
+CSKY_HD Ray ray_setup(const FrameConsts& fc, int gx, int gy) {
+    float dx, dy, dz;
+    pixel_dir(fc.tex_w, fc.tex_h, gx + fc.upd_x, gy + fc.upd_y, dx, dy, dz);
+    return ray_from_dir(fc, dx, dy, dz);
 }
 
 // weather texture coordinate, clouds.glsl:174 / :189 / :197 : p.xz * 0.00006 + 0.5 + weather_pos
@@ -184,6 +196,22 @@ CSKY_HD void frame_setup_tap_uv(const float light[3], int tap, float& sx, float&
     else { sx = sky_lut_uv_x(0.0f, inv); sy = sky_lut_uv_y(tap == 1 ? inv : -inv); }
 }
 
+// The fields of FrameConsts a density sample and ray_from_dir read (sample_density, density, the coordinate helpers), from the push-constant block
+// alone: every path that samples the clouds fills them here (frame_setup_f; shadow_core.h and depth_core.h, which need no sky LUT).
+CSKY_HD void density_frame_consts(const CloudParams& P, int steps, float hf_lo, float hf_hi, FrameConsts& fc) {
+    fc.cloud_off_x = 20.0f * P.cloud_pos[0] * 0.6f; fc.cloud_off_z = 20.0f * P.cloud_pos[1] * 0.6f;
+    fc.det_off_x = P.detailed_pos[0] * 40.0f; fc.det_off_z = P.detailed_pos[1] * 40.0f; fc.det_off_y = P.time * 40.0f;
+    fc.wpos_x = P.weather_pos[0]; fc.wpos_y = P.weather_pos[1];
+    fc.density = P.density; fc.coverage = P.cloud_coverage; fc.cov255 = P.cloud_coverage * (1.0f / 255.0f);
+    fc.primary_steps = steps; fc.steps_f = (float)steps;
+    fc.hf_lo = hf_lo; fc.hf_hi = hf_hi;
+}
+CSKY_HD void light_dir_consts(const CloudParams& P, FrameConsts& fc) {
+    const float lx = P.LIGHT_DIRECTION[0], ly = P.LIGHT_DIRECTION[1], lz = P.LIGHT_DIRECTION[2];
+    const float ll = length3_exact(lx, ly, lz);
+    fc.ldir[0] = lx / ll; fc.ldir[1] = ly / ll; fc.ldir[2] = lz / ll;                       // clouds.glsl:150
+}
+
 // fetch(tap, corner, x, y): texel (x, y) of the sky LUT, asked for by tap 0..2 (frame_setup_tap_uv) as corner 0..3 of its cell
 template <class Fetch> CSKY_HD void frame_setup_f(const CloudParams& P, Fetch fetch, int sky_w, int sky_h, int primary_steps, int light_steps,
                                                   float early_eps, float hf_lo, float hf_hi, FrameConsts& fc) {
@@ -192,12 +220,8 @@ template <class Fetch> CSKY_HD void frame_setup_f(const CloudParams& P, Fetch fe
                             {0.28128598f, 0.42443639f, -0.86065785f}, {-0.16852403f, 0.14748697f, 0.97460106f}};  // clouds.glsl:140
     fc.tex_w = P.texture_size[0]; fc.tex_h = P.texture_size[1];
     fc.upd_x = (int)P.update_position[0]; fc.upd_y = (int)P.update_position[1];
-    fc.cloud_off_x = 20.0f * P.cloud_pos[0] * 0.6f; fc.cloud_off_z = 20.0f * P.cloud_pos[1] * 0.6f;
-    fc.det_off_x = P.detailed_pos[0] * 40.0f; fc.det_off_z = P.detailed_pos[1] * 40.0f; fc.det_off_y = P.time * 40.0f;
-    fc.wpos_x = P.weather_pos[0]; fc.wpos_y = P.weather_pos[1];
-    const float lx = P.LIGHT_DIRECTION[0], ly = P.LIGHT_DIRECTION[1], lz = P.LIGHT_DIRECTION[2];
-    const float ll = length3_exact(lx, ly, lz);
-    fc.ldir[0] = lx / ll; fc.ldir[1] = ly / ll; fc.ldir[2] = lz / ll;
+    density_frame_consts(P, primary_steps, hf_lo, hf_hi, fc);
+    light_dir_consts(P, fc);
     const float lss = (SKY_T_RADIUS - SKY_B_RADIUS) / 64.0f;                              // clouds.glsl:148-149
     for (int j = 0; j < 6; j++) for (int k = 0; k < 3; k++) fc.linc[j][k] = (fc.ldir[k] + RV[j][k] * (float)j) * lss;
     for (int k = 0; k < 3; k++) fc.ldist[k] = fc.ldir[k] * 18.0f * lss;
@@ -216,10 +240,8 @@ template <class Fetch> CSKY_HD void frame_setup_f(const CloudParams& P, Fetch fe
     for (int k = 0; k < 3; k++) s[k] = s[k] * 5.0f * 0.05f;
     len = length3_exact(s[0], s[1], s[2]);
     for (int k = 0; k < 3; k++) fc.gnd_c[k] = s[k] * (1.0f - 0.5f) + (P.ground_color[k] * len) * 0.5f;  // clouds.glsl:167
-    fc.density = P.density; fc.coverage = P.cloud_coverage; fc.cov255 = P.cloud_coverage * (1.0f / 255.0f);
-    fc.primary_steps = primary_steps; fc.light_steps = light_steps; fc.steps_f = (float)primary_steps;
+    fc.light_steps = light_steps;
     fc.early_eps = early_eps;
-    fc.hf_lo = hf_lo; fc.hf_hi = hf_hi;
     fc.ct_mode = 0;                   // set by the caller that knows the weather map's range (clouds_launch.cpp::clouds_dev fills SetupArgs; lut_kernels.hip store_frame_consts)
     // The saturation skip (ray_saturated, section B) is proved for frames whose light, ambient and ground colours are finite and >= 0, whose density is
     // >= 0 (every step transmittance dt = exp(-density t ss) <= 1) and whose march is at most 65536 steps long (the slop terms below are first order

@@ -922,7 +922,7 @@ template <int SRC, class TS>
 __global__ __launch_bounds__(256, CSKY_COMPACT_WAVES) void clouds_rays_kernel(TS T, const FrameConsts* __restrict__ fcp, RaysGeom G, const float* __restrict__ dirs,
                                                                               uint2* __restrict__ out) {
     __shared__ float lds[4][CQ_FLOATS];
-    const int tiles_x = (G.w + 31) >> 5;
+    const int tiles_x = (G.w + 31) >> 5;                       // csky_common.h tile_pixel's arithmetic, kept as its own copy (through that function this kernel's code is not the parent's)
     const int slab = (int)blockIdx.x / tiles_x, bx = (int)blockIdx.x - slab * tiles_x;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int gx = bx * 32 + wave * 8 + (lane & 7);

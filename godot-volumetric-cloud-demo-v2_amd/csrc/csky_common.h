@@ -180,6 +180,23 @@ CSKY_HD uint2 pack_half4(uint16_t hx, uint16_t hy, uint16_t hz, uint16_t hw) {  
     uint2 r; r.x = (uint32_t)hx | ((uint32_t)hy << 16); r.y = (uint32_t)hz | ((uint32_t)hw << 16); return r;
 }
 
+// A w x h image in natural order (shadow.hip, depth.hip, cloud_aerial.hip): workgroup b of 256 threads is footprint b, row-major, 32 x 8 pixels: four
+// wavefronts' 8x8 tiles side by side (lane = ly*8 + lx), the cloud kernel's footprint.  A ragged image masks the lanes of its partial tiles (`valid`).
+CSKY_HD int tile_grid(int w, int h) { return ((w + 31) >> 5) * ((h + 7) >> 3); }   // <= 256 x 1024 for the largest image
+#if defined(__HIPCC__)
+struct TilePixel { int i, j; bool valid; };
+CSKY_D TilePixel tile_pixel(int w, int h) {
+    const int tiles_x = (w + 31) >> 5;
+    const int slab = (int)blockIdx.x / tiles_x, bx = (int)blockIdx.x - slab * tiles_x;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    TilePixel p;
+    p.i = bx * 32 + wave * 8 + (lane & 7);
+    p.j = slab * 8 + (lane >> 3);
+    p.valid = p.i < w && p.j < h;
+    return p;
+}
+#endif
+
 CSKY_HD float clampf(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
 CSKY_HD float sat(float x) { return fminf(fmaxf(x, 0.0f), 1.0f); }
 CSKY_HD float lerpf(float a, float b, float f) { return a + (b - a) * f; }

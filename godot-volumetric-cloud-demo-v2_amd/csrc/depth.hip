@@ -12,21 +12,16 @@ namespace {
 // Both constant blocks are kernel arguments (scalar loads from the kernarg segment): nothing of a depth call lives in device memory besides the frame.
 template <class TS>
 __global__ __launch_bounds__(256) void depth_kernel(TS T, const FrameConsts fc, const DepthConsts dc, uint2* __restrict__ out) {
-    const int tiles_x = (dc.w + 31) >> 5;
-    const int slab = (int)blockIdx.x / tiles_x, bx = (int)blockIdx.x - slab * tiles_x;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int i = bx * 32 + wave * 8 + (lane & 7);
-    const int j = slab * 8 + (lane >> 3);
-    const bool valid = i < dc.w && j < dc.h;                   // a ragged frame masks the lanes of its partial tiles: they take part in the votes only
+    const TilePixel p = tile_pixel(dc.w, dc.h);                // the lanes outside a ragged frame take part in the votes only
     T.detail_lds = nullptr;                                    // compile-time constant here: the LDS tap path folds away
-    const DepthTexel t = depth_pixel(T, fc, dc, i, j, valid, nullptr, nullptr);
-    if (valid) out[(size_t)j * dc.pitch_px + (size_t)i] = pack_half4(t.h[0], t.h[1], t.h[2], t.h[3]);
+    const DepthTexel t = depth_pixel(T, fc, dc, p.i, p.j, p.valid, nullptr, nullptr);
+    if (p.valid) out[(size_t)p.j * dc.pitch_px + (size_t)p.i] = pack_half4(t.h[0], t.h[1], t.h[2], t.h[3]);
 }
 
 }  // namespace
 
 hipError_t launch_cloud_depth(const TexSet& t, const TexSet32* t32, const FrameConsts& fc, const DepthConsts& dc, uint2* d_out, hipStream_t s) {
-    const int grid = ((dc.w + 31) >> 5) * ((dc.h + 7) >> 3);   // <= 256 x 1024 for the largest frame
+    const int grid = tile_grid(dc.w, dc.h);
     if (t32) depth_kernel<TexSet32><<<grid, 256, 0, s>>>(*t32, fc, dc, d_out);
     else depth_kernel<TexSet><<<grid, 256, 0, s>>>(t, fc, dc, d_out);
     return hipGetLastError();

@@ -1,10 +1,10 @@
 // depth_core.h -- the cloud depth frame (cloudsky.h csky_render_cloud_depth), written for one pixel per lane.
 //
 // Where along each ray of a hemisphere frame the cloud sits: the primary march of clouds.glsl:172-178, :207, :210 over the frame's own rays
-// (cloud_core.h ray_setup, unchanged) without the light march, keeping per ray the distance of the first and the last in-cloud sample and the
-// mean of the sample distances weighted by what each sample adds to alpha, T (1 - dt).  What is new here is only that bookkeeping and the
-// distance t0 of the shell entry, which ray_setup computes and does not return; a sample is cloud_core.h's sample_density_eager<false> behind
-// its exact rejects, as in the primary march.
+// (cloud_core.h pixel_dir and ray_from_dir, ray_setup's two halves) without the light march, keeping per ray the distance of the first and the
+// last in-cloud sample and the mean of the sample distances weighted by what each sample adds to alpha, T (1 - dt).  What is new here is only
+// that bookkeeping and the distance t0 of the shell entry, which depth_pixel takes from the direction with the ray's own intersect_sphere_cam; a
+// sample is cloud_core.h's sample_density_eager<false> behind its exact rejects, as in the primary march.
 //
 // Host+device (CSKY_HD) like cloud_core.h: tests/cloud_aerial_host runs this per-lane code on a CPU against a numpy restatement of the
 // definition that calls the oracle per sample.  The product instantiates it inside depth.hip only.
@@ -26,34 +26,12 @@ struct DepthConsts {
 // =================================================================================================
 #pragma clang fp contract(off)
 
-// The fields of FrameConsts ray_setup and a density sample read, from the push-constant block alone (shadow_core.h shadow_frame_consts without
-// the sun, which this path never reads): the frame is the whole W x H image, update position 0.  Everything else is zero.
+// The frame is the whole W x H image, update position 0, and reads no sun: the density constants (cloud_core.h).  Everything else is zero.
 CSKY_HD void depth_frame_consts(const CloudParams& P, int w, int h, int steps, float hf_lo, float hf_hi, int ct_mode, FrameConsts& fc) {
     memset(&fc, 0, sizeof fc);
     fc.tex_w = (float)w; fc.tex_h = (float)h;
-    fc.cloud_off_x = 20.0f * P.cloud_pos[0] * 0.6f; fc.cloud_off_z = 20.0f * P.cloud_pos[1] * 0.6f;
-    fc.det_off_x = P.detailed_pos[0] * 40.0f; fc.det_off_z = P.detailed_pos[1] * 40.0f; fc.det_off_y = P.time * 40.0f;
-    fc.wpos_x = P.weather_pos[0]; fc.wpos_y = P.weather_pos[1];
-    fc.density = P.density; fc.coverage = P.cloud_coverage; fc.cov255 = P.cloud_coverage * (1.0f / 255.0f);
-    fc.primary_steps = steps; fc.steps_f = (float)steps;
-    fc.hf_lo = hf_lo; fc.hf_hi = hf_hi; fc.ct_mode = ct_mode;
-}
-
-// ray_setup's dx, dy, dz for pixel (i, j) of a tex_w x tex_h frame at update position 0: its lines up to the .xzy swizzle (clouds.glsl:258-262,
-// :248-256), restated because ray_setup returns the direction only after the march prologue has re-normalised it and returns nothing at all
-// under the horizon.  tests/test_cloud_aerial_host.py holds the two together.
-CSKY_HD void pixel_dir(float tex_w, float tex_h, int i, int j, float& dx, float& dy, float& dz) {
-    const float ex = (float)i / tex_w, ey = (float)j / tex_h;
-    float nx = ex - ey;
-    float ny = (ex + ey) - 1.0f;
-    const float nz = 1.0f - fabsf(nx) - fabsf(ny);
-    if (!(nz >= 0.0f)) {
-        const float sx = nx >= 0.0f ? 1.0f : -1.0f, sy = ny >= 0.0f ? 1.0f : -1.0f;
-        const float wx = (1.0f - fabsf(ny)) * sx, wy = (1.0f - fabsf(nx)) * sy;
-        nx = wx; ny = wy;
-    }
-    const float nl = length3_exact(nx, ny, nz);
-    dx = nx / nl; dy = nz / nl; dz = ny / nl;
+    density_frame_consts(P, steps, hf_lo, hf_hi, fc);
+    fc.ct_mode = ct_mode;
 }
 
 // What a ray has met so far.  front < 0: no in-cloud sample yet (a distance is > 0).
@@ -125,9 +103,9 @@ template <class TS>
 CSKY_HD DepthTexel depth_pixel(const TS& T, const FrameConsts& fc, const DepthConsts& dc, int i, int j, bool valid, unsigned long long* taken,
                                unsigned long long* incloud, float* t0_out = nullptr, float* ss_out = nullptr) {
     const int pi = valid ? i : 0, pj = valid ? j : 0;
-    const Ray ray = ray_setup(fc, pi, pj);
     float dx, dy, dz;
     pixel_dir(fc.tex_w, fc.tex_h, pi, pj, dx, dy, dz);
+    const Ray ray = ray_from_dir(fc, dx, dy, dz);
     const float t0 = ray.above ? intersect_sphere_cam(dx, dy, dz, SKY_B_RADIUS) : 0.0f;
     if (t0_out) *t0_out = t0;
     if (ss_out) *ss_out = ray.ss;

@@ -2,8 +2,7 @@
 //
 // A cloud texel is a function of a direction: clouds.glsl:218-236 sky(dir).  Only main() ties it to the hemi-octahedral grid.  This file makes the
 // march's Ray from a direction the caller gives (a buffer of directions, or a camera view through composite_core.h's composite_eyedir) instead of from
-// a grid pixel: ray_from_dir restates the tail of cloud_core.h ray_setup (lines 121-135), the way depth_core.h pixel_dir restates its head, and
-// ray_setup itself stays as it is.  tests/test_clouds_rays_host.py holds ray_from_dir(pixel_dir(i, j)) and ray_setup(i, j) together bit for bit.
+// a grid pixel, with cloud_core.h ray_from_dir: the half of ray_setup behind the pixel's direction, so a grid pixel's own direction gives its own ray.
 //
 // Host+device (CSKY_HD) like cloud_core.h: tests/rays_host runs this per-lane code on a CPU.  The product instantiates it inside cloud_kernels.hip only.
 #pragma once
@@ -52,25 +51,7 @@ CSKY_HD bool rays_accept(float dx, float dy, float dz) {
     return dy > 0.0f && l2 >= 0.99f && l2 <= 1.01f;
 }
 
-// cloud_core.h ray_setup from `r.above = dy > 0.0f` on (clouds.glsl:221-230, :143-145), for a direction that has passed rays_accept.
-CSKY_HD Ray ray_from_dir(const FrameConsts& fc, float dx, float dy, float dz) {
-    Ray r;
-    r.above = dy > 0.0f;
-    if (!r.above) { r.px = r.py = r.pz = r.sx = r.sy = r.sz = r.dx = r.dy = r.dz = r.ss = 0.0f; return r; }
-    const float t0 = intersect_sphere_cam(dx, dy, dz, SKY_B_RADIUS);
-    const float t1 = intersect_sphere_cam(dx, dy, dz, SKY_T_RADIUS);
-    const float s0x = 0.0f + dx * t0, s0y = G_RADIUS + dy * t0, s0z = 0.0f + dz * t0;  // start, clouds.glsl:224
-    const float e0x = 0.0f + dx * t1, e0y = G_RADIUS + dy * t1, e0z = 0.0f + dz * t1;  // end,   clouds.glsl:225
-    const float shelldist = length3_exact(e0x - s0x, e0y - s0y, e0z - s0z);
-    const float rx = dx * shelldist / fc.steps_f, ry = dy * shelldist / fc.steps_f, rz = dz * shelldist / fc.steps_f;  // :230
-    r.ss = length3_exact(rx, ry, rz);                                                  // :143
-    r.dx = rx / r.ss; r.dy = ry / r.ss; r.dz = rz / r.ss;                              // :144
-    r.sx = r.dx * r.ss; r.sy = r.dy * r.ss; r.sz = r.dz * r.ss;
-    r.px = s0x; r.py = s0y; r.pz = s0z;                                                // :145 (hash() == 0: ray_setup)
-    return r;
-}
-
-// The ray of a direction as a lane uses it: marched when accepted, `above = false` (no sample, a zero texel) otherwise.
+// The ray of a direction as a lane uses it: cloud_core.h ray_from_dir when accepted, `above = false` (no sample, a zero texel) otherwise.
 CSKY_HD Ray rays_ray(const FrameConsts& fc, float dx, float dy, float dz) {
     const bool ok = rays_accept(dx, dy, dz);
     Ray r = ray_from_dir(fc, ok ? dx : 0.0f, ok ? dy : 0.0f, ok ? dz : 0.0f);

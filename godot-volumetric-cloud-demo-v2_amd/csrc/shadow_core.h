@@ -53,19 +53,13 @@ CSKY_HD float sphere_near(const SphereLine& q, float disc) {
     return fminf(p, p2) / (2.0f * q.a);
 }
 
-// The fields of FrameConsts a density sample reads (sample_density, density, the coordinate helpers), from the push-constant block alone: the
-// expressions of frame_setup_f, which needs a sky LUT for the colours this path never reads.  Everything else is zero.
+// What a shadow ray reads of FrameConsts: the density constants and the sun's direction (cloud_core.h), which frame_setup_f fills the same way
+// but only with a sky LUT, for the colours this path never reads.  Everything else is zero.
 CSKY_HD void shadow_frame_consts(const CloudParams& P, int steps, float hf_lo, float hf_hi, int ct_mode, FrameConsts& fc) {
     memset(&fc, 0, sizeof fc);
-    fc.cloud_off_x = 20.0f * P.cloud_pos[0] * 0.6f; fc.cloud_off_z = 20.0f * P.cloud_pos[1] * 0.6f;
-    fc.det_off_x = P.detailed_pos[0] * 40.0f; fc.det_off_z = P.detailed_pos[1] * 40.0f; fc.det_off_y = P.time * 40.0f;
-    fc.wpos_x = P.weather_pos[0]; fc.wpos_y = P.weather_pos[1];
-    const float lx = P.LIGHT_DIRECTION[0], ly = P.LIGHT_DIRECTION[1], lz = P.LIGHT_DIRECTION[2];
-    const float ll = length3_exact(lx, ly, lz);
-    fc.ldir[0] = lx / ll; fc.ldir[1] = ly / ll; fc.ldir[2] = lz / ll;                       // clouds.glsl:150
-    fc.density = P.density; fc.coverage = P.cloud_coverage; fc.cov255 = P.cloud_coverage * (1.0f / 255.0f);
-    fc.primary_steps = steps; fc.steps_f = (float)steps;
-    fc.hf_lo = hf_lo; fc.hf_hi = hf_hi; fc.ct_mode = ct_mode;
+    density_frame_consts(P, steps, hf_lo, hf_hi, fc);
+    light_dir_consts(P, fc);
+    fc.ct_mode = ct_mode;
 }
 
 // The three kinds of texel (cloudsky.h).  A ground point of the tangent plane lies above the inner shell from 134 km out, and under a low sun its

@@ -1,8 +1,8 @@
 """The cloud depth frame and the aerial perspective on a cloud frame (include/cloudsky.h) restated in numpy for the tests (test
 infrastructure, not product).
 
-Written from the definitions, not from csrc/depth_core.h or csrc/cloud_aerial_core.h: the rays, positions and distances in float32, one operation
-per line in the order the definition gives (dot products summed left to right, IEEE sqrt and divide: numpy's float32 ufuncs are exactly that), and
+Written from the definitions, not from csrc/depth_core.h or csrc/cloud_aerial_core.h: the rays (tests/ray_reference.py), positions and distances
+in float32, one operation per line in the order the definition gives (dot products summed left to right, IEEE sqrt and divide: numpy's float32 ufuncs are exactly that), and
 per sample the oracle's own weather tap (csko_tap_weather, clouds.glsl:174) and density() (csko_density_probe, clouds.glsl:109-137, mip 0).  The
 exp of a sample is numpy's, in float64, rounded once.  The apply step's air is tests/aerial_reference.columns with D = 1, S = n and one reach per
 pixel; the transmittance behind its steps, which columns() keeps to itself, is restated beside it from the same lines."""
@@ -11,66 +11,23 @@ import ctypes as C
 import numpy as np
 
 import aerial_reference as AR
-import shadow_reference as SR
 import tlut_reference as TR
 from oracle import numpy_restatement as NR
+from ray_reference import pixel_dirs, ray  # noqa: F401  (CR.pixel_dirs: what the tests of the core's direction compare with)
 
 F = np.float32
-RG, RB, RT = SR.RG, SR.RB, SR.RT
 
 SIZE = dict(width=64, height=32)
 STEPS = {"A": 128, "B": 30}          # B: not a multiple of four (the early exit is tried every fourth step)
 THIN = F(2.0 ** -6)                  # below this alpha the mean distance is only held between front and back
 
 
-def pixel_dirs(width, height):
-    """clouds.glsl:258-262, :248-256 at update_position 0: the normalised direction of every pixel, float32 [height, width, 3]."""
-    i = np.arange(width, dtype=F)[None, :] + np.zeros((height, 1), F)
-    j = np.arange(height, dtype=F)[:, None] + np.zeros((1, width), F)
-    ex = i / F(width)
-    ey = j / F(height)
-    nx = ex - ey
-    ny = ex + ey
-    ny = ny - F(1.0)
-    nz = F(1.0) - np.abs(nx)
-    nz = nz - np.abs(ny)
-    assert (nz >= 0).all()                                           # oct_wrap (:239-244) is dead for uv in [0, 1)^2
-    nl = nx * nx
-    nl = nl + ny * ny
-    nl = nl + nz * nz
-    nl = np.sqrt(nl)
-    e = np.stack([nx / nl, nz / nl, ny / nl], -1)                    # .xzy
-    assert e.dtype == F
-    return e
-
-
 def rays(width, height, steps):
-    """(e [H, W, 3], above [H, W], t0 [H, W], ss [H, W], start [3, H, W], step [3, H, W]): clouds.glsl:218-231, :143-145 with `steps` for 128.
-    Pixels that are not above hold whatever the arithmetic gives: nothing reads them."""
+    """(e [H, W, 3], above [H, W], t0 [H, W], ss [H, W], start [3, H, W], step [3, H, W]) of every pixel: tests/ray_reference.py's ray of its
+    direction.  Pixels that are not above hold whatever the arithmetic gives: nothing reads them."""
     e = pixel_dirs(width, height)
-    dx, dy, dz = e[..., 0], e[..., 1], e[..., 2]
-    above = dy > 0
-    zero, gy = np.zeros_like(dx), np.full_like(dx, RG)
-    with np.errstate(invalid="ignore", divide="ignore"):
-        t0 = SR._intersect_sphere(zero, gy, zero, dx, dy, dz, RB)
-        t1 = SR._intersect_sphere(zero, gy, zero, dx, dy, dz, RT)
-        sx0, sy0, sz0 = zero + dx * t0, gy + dy * t0, zero + dz * t0
-        ex0, ey0, ez0 = zero + dx * t1, gy + dy * t1, zero + dz * t1
-        qx, qy, qz = ex0 - sx0, ey0 - sy0, ez0 - sz0
-        sd = qx * qx
-        sd = sd + qy * qy
-        sd = sd + qz * qz
-        sd = np.sqrt(sd)
-        N = F(steps)
-        rx, ry, rz = dx * sd / N, dy * sd / N, dz * sd / N           # :230
-        ss = rx * rx
-        ss = ss + ry * ry
-        ss = ss + rz * rz
-        ss = np.sqrt(ss)                                             # :143
-        nx, ny, nz = rx / ss, ry / ss, rz / ss                       # :144
-        stx, sty, stz = nx * ss, ny * ss, nz * ss                    # dir * ss, :173
-    assert ss.dtype == F and stx.dtype == F and t0.dtype == F
-    return e, above, t0, ss, np.stack([sx0, sy0, sz0]), np.stack([stx, sty, stz])
+    r = ray(e, steps)
+    return e, e[..., 1] > 0, r["t0"], r["ss"], np.moveaxis(r["p"], -1, 0), np.moveaxis(r["inc"], -1, 0)
 
 
 _cache = {}

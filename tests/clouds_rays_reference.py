@@ -8,7 +8,7 @@ For pixel (i, j) of a W x H image, N = the context's primary steps:
     accept   e.y > 0  and  0.99 <= (e.x*e.x + e.y*e.y) + e.z*e.z <= 1.01      float32, one operation per line; NaN fails every test
              not accepted: the texel is (0, 0, 0, 0) and the ray takes no sample
     ray      clouds.glsl:221-230, :143-145 from e: t0, t1 = intersectSphere(camPos, e, Rb / Rt); start, end; shelldist = |end - start|;
-             raystep = e * shelldist / N; ss = |raystep|; dir = raystep / ss; inc = dir * ss; p = start
+             raystep = e * shelldist / N; ss = |raystep|; dir = raystep / ss; inc = dir * ss; p = start      (tests/ray_reference.py)
     texel    march() of clouds.glsl:139-215 on that ray, exactly as the hemisphere frame's
 
 Written from the definition, not from csrc/rays_core.h: float32 throughout, one operation per line in the order written (numpy's float32 add,
@@ -20,12 +20,13 @@ import ctypes.util
 
 import numpy as np
 
+from ray_reference import ray  # noqa: F401  (RR.ray: the one restatement of the ray, shared with the depth frame's)
+
 _libm = ctypes.CDLL(ctypes.util.find_library("m") or "libm.so.6")
 _libm.tanf.restype = ctypes.c_float
 _libm.tanf.argtypes = [ctypes.c_float]
 
 F = np.float32
-RG, RB, RT = F(6000000.0), F(6001500.0), F(6004000.0)   # clouds.glsl:43-45
 
 VIEW = dict(width=64, height=36, fov=70.0, pitch=25.0, yaw=40.0)   # the camera of the view tests
 
@@ -90,47 +91,3 @@ def accept(e):
         l2 = l2 + y * y
         l2 = l2 + z * z
         return (y > F(0.0)) & (l2 >= F(0.99)) & (l2 <= F(1.01))
-
-
-def _intersect_sphere_cam(dx, dy, dz, r):   # clouds.glsl:97-105 with pos = camPos = (0, g_radius, 0)
-    a = dx * dx
-    a = a + dy * dy
-    a = a + dz * dz
-    b = dx * F(0.0)
-    b = b + dy * RG
-    b = b + dz * F(0.0)
-    b = F(2.0) * b
-    c = F(0.0) * F(0.0) + RG * RG
-    c = c + F(0.0) * F(0.0)
-    c = c - r * r
-    e = F(4.0) * a
-    e = e * c
-    d = b * b
-    d = d - e
-    d = np.sqrt(d)
-    p = -b - d
-    p2 = -b + d
-    return np.maximum(p, p2) / (F(2.0) * a)
-
-
-def ray(e, steps):
-    """The ray of accepted directions float32 [n, 3]: dict(p, inc, dir float32 [n, 3], ss float32 [n])."""
-    e = np.asarray(e, F)
-    dx, dy, dz = e[:, 0], e[:, 1], e[:, 2]
-    n = F(steps)
-    t0 = _intersect_sphere_cam(dx, dy, dz, RB)
-    t1 = _intersect_sphere_cam(dx, dy, dz, RT)
-    sx, sy, sz = F(0.0) + dx * t0, RG + dy * t0, F(0.0) + dz * t0
-    ex, ey, ez = F(0.0) + dx * t1, RG + dy * t1, F(0.0) + dz * t1
-    qx, qy, qz = ex - sx, ey - sy, ez - sz
-    sd = qx * qx
-    sd = sd + qy * qy
-    sd = sd + qz * qz
-    sd = np.sqrt(sd)
-    rx, ry, rz = dx * sd / n, dy * sd / n, dz * sd / n
-    ss = rx * rx
-    ss = ss + ry * ry
-    ss = ss + rz * rz
-    ss = np.sqrt(ss)
-    ux, uy, uz = rx / ss, ry / ss, rz / ss
-    return dict(p=np.stack([sx, sy, sz], -1), dir=np.stack([ux, uy, uz], -1), inc=np.stack([ux * ss, uy * ss, uz * ss], -1), ss=ss)

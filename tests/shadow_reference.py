@@ -54,10 +54,6 @@ def _sphere_roots(px, py, pz, dx, dy, dz, r):   # clouds.glsl:97-105, both roots
         return disc, np.minimum(p, p2) / (F(2.0) * a), np.maximum(p, p2) / (F(2.0) * a)
 
 
-def _intersect_sphere(px, py, pz, dx, dy, dz, r):   # clouds.glsl:97-105 as the shader has it: the larger root, NaN where the line misses
-    return _sphere_roots(px, py, pz, dx, dy, dz, r)[2]
-
-
 ORDINARY, CHORD, MISS = 0, 1, 2                # the three kinds of texel: the line meets the inner shell; only the outer one, on a chord; neither
 
 

@@ -1,6 +1,6 @@
 """The front end of the direct cloud march (csrc/rays_core.h: what the lanes of clouds_rays_kernel run in front of the march), compiled for the host
-by tests/rays_host, held to cloud_core.h's ray_setup, to the host frame of tests/hostsim and to the numpy restatement of its definition
-(tests/clouds_rays_reference.py).  A unit test of device code, not a render path: libcloudsky itself has no CPU implementation."""
+by tests/rays_host, and cloud_core.h's ray_setup behind it, held to the host frame of tests/hostsim and to the numpy restatement of their definition
+(tests/clouds_rays_reference.py, tests/ray_reference.py).  A unit test of device code, not a render path: libcloudsky itself has no CPU implementation."""
 import ctypes as C
 import os
 import subprocess
@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import clouds_rays_reference as RR
+import ray_reference as XR
 from conftest import ROOT, SUNS, norm
 from test_hostsim_core import hs_clouds
 
@@ -26,7 +27,7 @@ def rays_host():
     L = C.CDLL(os.path.join(d, "librays_host.so"))
     for f in ("rays_host_grid", "rays_host_view_dirs", "rays_host_accept", "rays_host_march", "rays_host_walk", "rays_host_composite"):
         getattr(L, f).restype = None
-    L.rays_host_grid.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rays_host_grid.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.rays_host_view_dirs.argtypes = [C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_void_p]
     L.rays_host_accept.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
     L.rays_host_march.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
@@ -44,10 +45,10 @@ def chains(pkg, noise):
 
 
 def grid(L, w, h, steps):
-    """(dirs [h, w, 3], ray_setup's fields [h, w, 11], ray_from_dir(pixel_dir)'s [h, w, 11]) of a w x h hemisphere frame"""
-    d, a, b = np.zeros((h, w, 3), F), np.zeros((h, w, 11), F), np.zeros((h, w, 11), F)
-    L.rays_host_grid(w, h, steps, P(d), P(a), P(b))
-    return d, a, b
+    """(dirs [h, w, 3], ray_setup's fields [h, w, 11]) of a w x h hemisphere frame"""
+    d, a = np.zeros((h, w, 3), F), np.zeros((h, w, 11), F)
+    L.rays_host_grid(w, h, steps, P(d), P(a))
+    return d, a
 
 
 def host_view_dirs(L, basis, fov, w, h):
@@ -80,21 +81,19 @@ def host_composite(L, mode, basis, fov, out_w, out_h, cf, ct, sf, st, trans, ble
 # ---- H1
 @pytest.mark.parametrize("w,h", [(64, 32), (37, 21)])
 @pytest.mark.parametrize("steps", [128, 30])
-def test_ray_from_dir_of_the_grid_direction_is_ray_setup_bit_for_bit(rays_host, w, h, steps):
-    _, a, b = grid(rays_host, w, h, steps)
-    assert a[..., 10].sum() > 0.9 * w * h                    # the grid's rays are above the horizon but for its rim
-    assert (a.view(np.uint32) == b.view(np.uint32)).all()
-
-
-def test_numpy_restatement_of_the_ray_equals_the_core(rays_host):
-    d, a, _ = grid(rays_host, 37, 21, 30)
-    up = a[..., 10] > 0
-    r = RR.ray(d[up], 30)
-    got = a[up]
-    assert (r["p"].view(np.uint32) == got[:, 0:3].view(np.uint32)).all()
-    assert (r["inc"].view(np.uint32) == got[:, 3:6].view(np.uint32)).all()
-    assert (r["dir"].view(np.uint32) == got[:, 6:9].view(np.uint32)).all()
-    assert (r["ss"].view(np.uint32) == got[:, 9].view(np.uint32)).all()
+def test_ray_setup_is_the_numpy_restatement_of_the_ray_bit_for_bit(rays_host, w, h, steps):
+    """All eleven fields of ray_setup(i, j), which is ray_from_dir(pixel_dir(i, j)), against the restatement of the definition: `above` and the zero
+    fields under the horizon included."""
+    e = XR.pixel_dirs(w, h)
+    up = e[..., 1] > 0
+    assert up.sum() > 0.9 * w * h                            # the RESTATEMENT's rays are above the horizon but for the grid's rim
+    r = XR.ray(e, steps)
+    want = np.concatenate([r["p"], r["inc"], r["dir"], r["ss"][..., None], np.ones((h, w, 1), F)], -1)
+    want = np.where(up[..., None], want, F(0.0))
+    assert want.dtype == F and want.shape == (h, w, 11)
+    d, got = grid(rays_host, w, h, steps)
+    assert (d.view(np.uint32) == e.view(np.uint32)).all()
+    assert (got.view(np.uint32) == want.view(np.uint32)).all()
 
 
 # ---- H2
@@ -102,7 +101,7 @@ def test_numpy_restatement_of_the_ray_equals_the_core(rays_host):
 def test_host_march_over_the_grid_directions_gives_the_bytes_of_the_host_frame(rays_host, hostsim, pkg, oracle, noise, chains, o_skies, sun):
     p = oracle.default_params(64, 32, SUNS[sun])
     ref, ic_ref = hs_clouds(hostsim, pkg, noise, p, o_skies[sun], 64, (8, 0, 1, 4))
-    d, _, _ = grid(rays_host, 64, 32, 128)
+    d, _ = grid(rays_host, 64, 32, 128)
     q = p.copy()
     q[0:4] = np.nan                                          # texture_size and update_position are not read
     img, marched, inc = host_march(rays_host, chains, q, o_skies[sun], d)

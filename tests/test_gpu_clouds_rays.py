@@ -73,7 +73,7 @@ def test_grid_directions_give_the_bytes_of_the_cloud_frame(whole_ctx, exact_ctx,
     try:
         with_lut(ctx, p)
         frame = ctx.render_clouds(p, 64, 32)
-        d, _, _ = grid(rays_host, 64, 32, N)
+        d, _ = grid(rays_host, 64, 32, N)
         s = torch.cuda.Stream()
         with torch.cuda.stream(s):
             dd = torch.from_numpy(d).cuda()

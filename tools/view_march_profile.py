@@ -46,7 +46,7 @@ def walk():
     L = C.CDLL(os.path.join(d, "librays_host.so"))
     for f in ("rays_host_grid", "rays_host_view_dirs", "rays_host_march"):
         getattr(L, f).restype = None
-    L.rays_host_grid.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rays_host_grid.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.rays_host_view_dirs.argtypes = [C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_void_p]
     L.rays_host_march.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p]
@@ -54,7 +54,7 @@ def walk():
     chains = (gvcd_amd.assets.build_mips(large, 8), gvcd_amd.assets.build_mips(small, 6), np.ascontiguousarray(weather, np.uint8))
     p = c3_params(W, H)
     sky = O.sky_lut(p[16:19], O.transmittance_lut(256, 64), 200, 100)
-    hemi, _, _ = T.grid(L, W, H, STEPS)
+    hemi, _ = T.grid(L, W, H, STEPS)
     view = T.host_view_dirs(L, basis(PITCH), FOV, VW, VH)
     for name, dirs in (("hemisphere %d x %d" % (W, H), hemi), ("view %d x %d, fov %g, pitched up %g" % (VW, VH, FOV, PITCH), view)):
         sub = np.ascontiguousarray(dirs[8::16, 8::16])
