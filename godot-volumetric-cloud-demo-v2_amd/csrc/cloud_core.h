@@ -446,13 +446,19 @@ CSKY_HD float height_fraction(float r) { return sat((r - SKY_B_RADIUS) * (1.0f /
 //    both reciprocals come from ONE v_rcp_f32: r = 1 / (d1 d2), 1/d1 = r d2, 1/d2 = r d1, with the widths d1 = gy-gx, d2 = gw-gz linear in ct
 //    like the corners.  55 -> 42 issue cycles per evaluation (7.5 M wave-level evaluations per C3 frame, profiles/r04/line_profile_*.txt);
 //    the value moves by ~1e-7 (section B tolerance; the height window keeps 0.03 of slack in g, bake.h).
+//  * CT: the cloud-type mode as a compile-time value.  0 is the generic form, which reads fc.ct_mode per call; 1 and 2 are the frame-wide branches
+//    alone, for a caller whose launch was picked by the mode the frame set-up wrote (cloud_kernels.hip launch_clouds): no load of the field, no
+//    scalar branch per evaluation and no corner constants of the other modes held in registers.  Each branch is the same expression in every form
+//    (tests/test_density_gradient_modes.py compares the bits on the host build).
+template <int CT = 0>
 CSKY_HD float density_height_gradient(const FrameConsts& fc, float hf, float ct) {
+    static_assert(CT >= 0 && CT <= 2, "cloud-type mode: 0 generic, 1 every texel >= 0.5, 2 every texel < 0.5");
     const float c = ct;
     constexpr float K = 1.0f / 255.0f;
     float gx, d1, gz, d2;
-    if (fc.ct_mode == 1) {
+    if (CT == 1 || (CT == 0 && fc.ct_mode == 1)) {
         gx = 0.03f + c * (-0.02f * K); d1 = (0.3375f - 0.03f) + c * ((-0.275f + 0.02f) * K); gz = 0.18f + c * (0.6f * K); d2 = (0.25f - 0.18f) + c * ((0.75f - 0.6f) * K);
-    } else if (fc.ct_mode == 2) {
+    } else if (CT == 2 || (CT == 0 && fc.ct_mode == 2)) {
         gx = 0.02f + c * 0.0f; d1 = (0.05f - 0.02f) + c * (0.3f * K); gz = 0.09f + c * (0.78f * K); d2 = (0.11f - 0.09f) + c * ((1.03f - 0.78f) * K);
     } else {
         const bool hi = ct >= 127.5f;
@@ -473,11 +479,11 @@ CSKY_HD float density_height_gradient(const FrameConsts& fc, float hf, float ct)
 //      gives 0 and pow(0, e >= 0.5) = 0.  The shape tap is never needed.  wc == 0 (divide by zero -> NaN ->
 //      clamp -> 0 in the oracle) also lands here.
 //  (2) after :125, base_cloud <= 0 makes :135-136 return 0 for the same reason: the detail tap is dead.
-template <class TS>
+template <int CT = 0, class TS>
 CSKY_HD float density(const TS& T, const FrameConsts& fc, float px, float py, float pz, float hf, float wr, float wb,
                       int lod_shape, int lod_detail) {
     const float wc = fc.cov255 * wb;                                         // :123 (wb on the texel scale)
-    const float g = density_height_gradient(fc, hf, wr);                    // :121
+    const float g = density_height_gradient<CT>(fc, hf, wr);                // :121
     const float omw = 1.0f - wc;
     if (!(g > omw)) return 0.0f;                                             // exact reject (1)
     float qx, qy, qz, sx, sy, sz;
@@ -522,7 +528,7 @@ CSKY_HD float density(const TS& T, const FrameConsts& fc, float px, float py, fl
 // for ANY texel of the bound weather map (bake.h height_window: g <= smoothstep(gx,gy,hf) below the cloud body and
 // g <= 1 - smoothstep(gz,gw,hf) above it, maximised over the map's cloud-type range), so reject (1) would fire anyway:
 // the weather tap and the gradient are skipped.  Samples above/below the cloud body cost ~20 VALU instead of ~100.
-template <class TS>
+template <int CT = 0, class TS>
 CSKY_HD float sample_density(const TS& T, const FrameConsts& fc, float px, float py, float pz, float hf, float wx, float wy,
                              int lod_shape, int lod_detail) {
     CSKY_STAGE(0);
@@ -531,7 +537,7 @@ CSKY_HD float sample_density(const TS& T, const FrameConsts& fc, float px, float
     weather_coord(px, pz, wx, wy, wsx, wsy);
     weather_tap_ts(T, wsx, wsy, wr, wb);
     CSKY_STAGE(1);
-    return density(T, fc, px, py, pz, hf, wr, wb, lod_shape, lod_detail);
+    return density<CT>(T, fc, px, py, pz, hf, wr, wb, lod_shape, lod_detail);
 }
 
 // (Round-2 experiment, measured and removed: the cells of detail LODs 2..4 / 3..4 staged in LDS per workgroup and served to the light march
@@ -558,10 +564,19 @@ CSKY_HD float sample_density(const TS& T, const FrameConsts& fc, float px, float
 // SMALL_TABLE (persistent launches, TS::small_detail): the caller passes lod_detail >= 3 only.  At 3 and 4 the tap reads the LDS table of those two levels;
 // at 5 (light sample j = 5 of the second loop of light_march_terms) there is no tap at all, as in every form: `tap` below is false and the sample takes
 // T.detail_lod5.  The table index below relies on that: it tells level 3 from "not 3", so a tap at level 5 would read the first cell of LOD 4.
-template <bool EAGER_DETAIL = true, bool SMALL_TABLE = false, class TS>
+// A level's first cell as a value the compiler must hold in a scalar register.  Where the level is a constant of the place (the straight-line light
+// march of the persistent forms) the compiler otherwise folds the offset into the 64-bit address: a v_lshl_add_u64 and a carry pair per tap where
+// one v_add_lshl_u32 on the 32-bit offset did (VALU +0.7 % per C3 frame, profiles/r22/march_specialised_ab.txt).  The value is unchanged.
+CSKY_HD uint32_t level_offset_scalar(uint32_t off) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+s"(off));
+#endif
+    return off;
+}
+template <bool EAGER_DETAIL = true, bool SMALL_TABLE = false, int CT = 0, class TS>
 CSKY_HD float sample_density_eager(const TS& T, const FrameConsts& fc, float px, float py, float pz, float hf, float wx, float wy,
                                    int lod_shape, int lod_detail) {
-    if constexpr (TS::cell32) return sample_density(T, fc, px, py, pz, hf, wx, wy, lod_shape, lod_detail);   // exact cells: the lazy form (not the tuned path)
+    if constexpr (TS::cell32) return sample_density<CT>(T, fc, px, py, pz, hf, wx, wy, lod_shape, lod_detail);   // exact cells: the lazy form (not the tuned path)
     // (round 4: ONE result register written where the sample survives every reject -- three early `return 0` cost a v_mov each per sample -- and
     // the single-texel LOD 5 of the detail volume as its own wave-uniform case instead of zero-filled tap registers)
     float d = 0.0f;
@@ -580,7 +595,8 @@ CSKY_HD float sample_density_eager(const TS& T, const FrameConsts& fc, float px,
         int six, siy, siz; float sax, say, saz;
         split_coord(sx * sfn - 0.5f, six, sax); split_coord(sy * sfn - 0.5f, siy, say); split_coord(sz * sfn - 0.5f, siz, saz);
         const uint32_t ssh = (uint32_t)(7 - lod_shape);
-        const uint32_t sidx = shape_level_offset(lod_shape) + shape_cell_offset((uint32_t)(six & sm), (uint32_t)(siy & sm), (uint32_t)(siz & sm), ssh);
+        const uint32_t slo = CT != 0 ? level_offset_scalar(shape_level_offset(lod_shape)) : shape_level_offset(lod_shape);   // (CT != 0: the forms whose levels may be constants)
+        const uint32_t sidx = slo + shape_cell_offset((uint32_t)(six & sm), (uint32_t)(siy & sm), (uint32_t)(siz & sm), ssh);
         const uint4* __restrict__ sp = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(T.shape) + (sidx << 5));
         const uint4 tr = sp[0], tf = sp[1];
         float dsx, dsy, dsz;
@@ -594,7 +610,7 @@ CSKY_HD float sample_density_eager(const TS& T, const FrameConsts& fc, float px,
             int dix, diy, diz;
             split_coord(dsx * dfn - 0.5f, dix, dax); split_coord(dsy * dfn - 0.5f, diy, day); split_coord(dsz * dfn - 0.5f, diz, daz);
             const uint32_t dsh = (uint32_t)(5 - lod_detail);
-            const uint32_t dlo = detail_level_offset(lod_detail), dcell = (((((uint32_t)(diz & dm)) << dsh) | (uint32_t)(diy & dm)) << dsh) | (uint32_t)(dix & dm);
+            const uint32_t dlo = (CT != 0 && !SMALL_TABLE) ? level_offset_scalar(detail_level_offset(lod_detail)) : detail_level_offset(lod_detail), dcell = (((((uint32_t)(diz & dm)) << dsh) | (uint32_t)(diy & dm)) << dsh) | (uint32_t)(dix & dm);
             const uint32_t didx = dlo + dcell;
             if constexpr (SMALL_TABLE) {
                 // persistent launches: LODs 3 and 4 (light samples j = 3, 4) are 72 cells staged in LDS once per launch; the same cell through
@@ -615,7 +631,7 @@ CSKY_HD float sample_density_eager(const TS& T, const FrameConsts& fc, float px,
         const float wr = fmaf(way, lerp_h(wq.y, wax), lerp_h(wq.x, wax));       // texel scale 0..255 (weather_filter)
         const float wb = fmaf(way, lerp_h(wq.w, wax), lerp_h(wq.z, wax));
         const float wc = fc.cov255 * wb;                                         // :123 (wb on the texel scale)
-        const float g = density_height_gradient(fc, hf, wr);                    // :121
+        const float g = density_height_gradient<CT>(fc, hf, wr);                // :121
         const float omw = 1.0f - wc;
         if (g > omw) {                                                           // else: exact reject (1)
             const float nr = fmaf(saz, fmaf(say, lerp_h(tr.w, sax), lerp_h(tr.z, sax)), fmaf(say, lerp_h(tr.y, sax), lerp_h(tr.x, sax))) * (1.0f / 255.0f);
@@ -641,10 +657,10 @@ CSKY_HD float sample_density_eager(const TS& T, const FrameConsts& fc, float px,
     return d;
 }
 #else
-template <bool EAGER_DETAIL = true, bool SMALL_TABLE = false, class TS>
+template <bool EAGER_DETAIL = true, bool SMALL_TABLE = false, int CT = 0, class TS>
 CSKY_HD float sample_density_eager(const TS& T, const FrameConsts& fc, float px, float py, float pz, float hf, float wx, float wy,
                                    int lod_shape, int lod_detail) {
-    return sample_density(T, fc, px, py, pz, hf, wx, wy, lod_shape, lod_detail);
+    return sample_density<CT>(T, fc, px, py, pz, hf, wx, wy, lod_shape, lod_detail);
 }
 #endif
 

@@ -14,6 +14,7 @@
 #include "kernels.h"
 #include "cloud_core.h"
 #include "order_core.h"
+#include <type_traits>
 // FP contraction OFF for the code of this file, like section A of cloud_core.h: what a march adds and multiplies itself (the phase value's dot product,
 // the segments' compositing sums) rounds as written.  Stated here because otherwise the last header decides it, and cloud_core.h ends with contraction on.
 #pragma clang fp contract(off)
@@ -180,20 +181,20 @@ constexpr int CQ_FLOATS = 5 * CQ_CAP + CQ_CAP / 4 + 3 * CQ_STEPS + 2 + 128 + 320
 #define CSKY_EAGER_LIGHT 1
 #endif
 #if CSKY_EAGER_LIGHT
-#define CSKY_LIGHT_SAMPLE sample_density_eager<true>
+#define CSKY_LIGHT_SAMPLE(CT) sample_density_eager<true, false, CT>
 #else
-#define CSKY_LIGHT_SAMPLE sample_density
+#define CSKY_LIGHT_SAMPLE(CT) sample_density<CT>
 #endif
 #ifndef CSKY_EAGER_PRIMARY
 #define CSKY_EAGER_PRIMARY 0   // eager fetches in the PRIMARY march measured slower (1: weather + shape together +1 %, 2: all three +4.5 %): only
                                // 56 % / 22 % of its samples need the shape / detail cell, the extra gathers cost more than the latency they hide
 #endif
 #if CSKY_EAGER_PRIMARY == 1
-#define CSKY_PRIMARY_SAMPLE sample_density_eager<false>
+#define CSKY_PRIMARY_SAMPLE(CT) sample_density_eager<false, false, CT>
 #elif CSKY_EAGER_PRIMARY == 2
-#define CSKY_PRIMARY_SAMPLE sample_density_eager<true>
+#define CSKY_PRIMARY_SAMPLE(CT) sample_density_eager<true, false, CT>
 #else
-#define CSKY_PRIMARY_SAMPLE sample_density
+#define CSKY_PRIMARY_SAMPLE(CT) sample_density<CT>
 #endif
 // Step B of the compact march for ONE queued in-cloud sample: the reference's light march (clouds.glsl:186-199) from its position and the
 // state-independent half of its shading (:178, :202-209).  In: position, density t, height fraction, the owner ray's step length and phase
@@ -201,24 +202,52 @@ constexpr int CQ_FLOATS = 5 * CQ_CAP + CQ_CAP / 4 + 3 * CQ_STEPS + 2 + 128 + 320
 // CUs' wavefronts and got byte-identical frames: docs/EXPERIMENTS.md §5).
 // `late(et, ehf, ess, eph)` delivers the four inputs the light march itself does not need AFTER it (the owner reads them from its LDS queue
 // then: four registers fewer across the march).
-template <class TS, class Late>
+#ifndef CSKY_LIGHT_STRAIGHT
+#define CSKY_LIGHT_STRAIGHT 1   // 0: the specialised persistent forms keep round 19's two loops (the A/B of the mode alone, profiles/r22/march_specialised_ab.txt)
+#endif
+#if CSKY_EAGER_LIGHT
+// Cone samples J, J + 1, ... 5 of the persistent form's light march as straight-line code: every sample index has its own copy of the body, so its
+// levels, their extents and offsets, the offset of linc[J] and whether the detail tap reads the LDS table (J = 3, 4), the global cell (J < 3) or nothing
+// (J = 5) are constants of the place, not scalar arithmetic and scalar branches per sample (round 19's rule carried to every index).  The wave-uniform
+// exit `J >= ls` stays in front of every sample: 0..6 light steps.
+template <int CT, int J, class TS>
+__device__ __forceinline__ void light_samples_from(const TS& T, const FrameConsts& fc, const int ls, float& lx, float& ly, float& lz, float& cd) {
+    if constexpr (J < 6) {
+        if (J >= ls) return;
+        advance(lx, ly, lz, fc.linc[J][0], fc.linc[J][1], fc.linc[J][2]);                              // :187
+        const float lhf = height_fraction(length3_shell(lx, ly, lz));                                  // :188
+        cd += sample_density_eager<true, (J > 2), CT>(T, fc, lx, ly, lz, lhf, fc.wpos_x, fc.wpos_y, J > 2 ? J - 2 : 0, J);   // :189-191
+        light_samples_from<CT, J + 1>(T, fc, ls, lx, ly, lz, cd);
+    }
+}
+#endif
+// CT: the cloud-type mode of cloud_core.h density_height_gradient (0: read from fc per evaluation).
+template <int CT = 0, class TS, class Late>
 __device__ __forceinline__ void light_march_terms(const TS& T, const FrameConsts& fc, const int ls, const float nd, float ex, float ey, float ez, Late&& late,
                                                   float& Dr, float& Dg, float& Db, float& rq, float& dt) {
     float lx = ex, ly = ey, lz = ez, cd = 0.0f;
 #if CSKY_EAGER_LIGHT
-    constexpr int JS = TS::small_detail ? 3 : 6;                // persistent launches: samples j = 3, 4 (and a j = 5 that taps nothing) run in a loop of their own
+    constexpr int JS = TS::small_detail ? 3 : 6;                // persistent launches: samples j = 3, 4 (and a j = 5 that taps nothing) run in code of their own
+    // persistent launches whose cloud-type mode is compiled in: one copy of the body per sample index (light_samples_from).  The generic form keeps the
+    // two loops: straight-line it has 273 / 288 basic blocks (the census build counts 256) and spills inside the flush loop (profiles/r22/march_specialised_ab.txt)
+    constexpr bool STRAIGHT = CSKY_LIGHT_STRAIGHT && TS::small_detail && CT != 0;
 #else
     constexpr int JS = 6;
+    constexpr bool STRAIGHT = false;
 #endif
-#pragma unroll 1                                                 // scalar j: one loop body (unrolling measured no faster in rounds 2 and 5, 6x the code: profiles/r05/kernel_experiments.txt)
-    for (int j = 0; j < JS; j++) {                                                                     // :186 (light_steps <= 6)
-        if (j >= ls) break;
-        advance(lx, ly, lz, fc.linc[j][0], fc.linc[j][1], fc.linc[j][2]);                              // :187
-        const float lhf = height_fraction(length3_shell(lx, ly, lz));                                  // :188
-        cd += CSKY_LIGHT_SAMPLE(T, fc, lx, ly, lz, lhf, fc.wpos_x, fc.wpos_y, j > 2 ? j - 2 : 0, j);   // :189-191
+    if constexpr (!STRAIGHT) {
+#pragma unroll 1                                                 // scalar j: one loop body (the plain kernel: 6x the code bought nothing in rounds 2 and 5, profiles/r05/kernel_experiments.txt)
+        for (int j = 0; j < JS; j++) {                                                                 // :186 (light_steps <= 6)
+            if (j >= ls) break;
+            advance(lx, ly, lz, fc.linc[j][0], fc.linc[j][1], fc.linc[j][2]);                          // :187
+            const float lhf = height_fraction(length3_shell(lx, ly, lz));                              // :188
+            cd += CSKY_LIGHT_SAMPLE(CT)(T, fc, lx, ly, lz, lhf, fc.wpos_x, fc.wpos_y, j > 2 ? j - 2 : 0, j);   // :189-191
+        }
     }
 #if CSKY_EAGER_LIGHT
-    if constexpr (TS::small_detail) {
+    if constexpr (STRAIGHT) {
+        light_samples_from<CT, 0>(T, fc, ls, lx, ly, lz, cd);
+    } else if constexpr (TS::small_detail) {
         // the same samples with their detail tap (LODs 3, 4) served from the LDS table: a second copy of the loop body, so that which path a tap takes is
         // decided by where the code is, not by a branch per sample.  The one-loop form (a scalar branch on the level inside the tap: two more branches and
         // ~4 SALU per light sample) took the same loads off the TA and gained 0.4 % of the headline; this form 3.5 %, of which 2.3 are the split's own (with j >= 3
@@ -228,7 +257,7 @@ __device__ __forceinline__ void light_march_terms(const TS& T, const FrameConsts
             if (j >= ls) break;
             advance(lx, ly, lz, fc.linc[j][0], fc.linc[j][1], fc.linc[j][2]);                          // :187
             const float lhf = height_fraction(length3_shell(lx, ly, lz));                              // :188
-            cd += sample_density_eager<true, true>(T, fc, lx, ly, lz, lhf, fc.wpos_x, fc.wpos_y, j - 2, j);   // :189-191
+            cd += sample_density_eager<true, true, CT>(T, fc, lx, ly, lz, lhf, fc.wpos_x, fc.wpos_y, j - 2, j);   // :189-191
         }
     }
 #endif
@@ -236,7 +265,7 @@ __device__ __forceinline__ void light_march_terms(const TS& T, const FrameConsts
         lx = ex; ly = ey; lz = ez;
         advance(lx, ly, lz, fc.ldist[0], fc.ldist[1], fc.ldist[2]);
         const float lhf = height_fraction(length3_shell(lx, ly, lz));
-        const float ld = CSKY_LIGHT_SAMPLE(T, fc, lx, ly, lz, lhf, 0.0f, 0.0f, 3, 5);                  // :197 has no weather_pos
+        const float ld = CSKY_LIGHT_SAMPLE(CT)(T, fc, lx, ly, lz, lhf, 0.0f, 0.0f, 3, 5);              // :197 has no weather_pos
         cd += fast_pow(ld, (1.0f - lhf) * 0.8f + 0.5f);                                                // :198 (second pow)
     }
     float et, ehf, ess, eph;
@@ -256,7 +285,8 @@ __device__ __forceinline__ void light_march_terms(const TS& T, const FrameConsts
 // false to `below_top`, so the every-4th-step ballot ends the wavefront once every lane is latched or above the window.  The queue receives the same
 // samples in the same order either way (a latched ray's were never queued), so flushes, latch tests and the stored halfs are those of TALLY = true
 // (tests/tilewalk emulates both per tile; tests/test_gpu_latched_rays.py compares the frames).  MarchOut::incloud is 0 and must not be read.
-template <bool WHOLE, bool TALLY, class TS>
+// CT: the cloud-type mode of the frame as a compile-time value (cloud_core.h density_height_gradient); 0 reads fc.ct_mode per evaluation.
+template <bool WHOLE, bool TALLY, int CT = 0, class TS>
 __device__ __forceinline__ MarchOut march_compact(const TS& T, const FrameConsts& fc, Ray ray, float* __restrict__ q, int step_begin, int step_end) {
     constexpr bool SAT = WHOLE && !TS::cell32;
     constexpr bool DEAD = SAT && !TALLY;                      // a latched ray stops marching
@@ -303,7 +333,7 @@ __device__ __forceinline__ MarchOut march_compact(const TS& T, const FrameConsts
             if (live) {
                 advance(px, py, pz, ray.sx, ray.sy, ray.sz);                                                   // :173
                 hf = height_fraction(length3_shell(px, py, pz));                                               // :175
-                t = CSKY_PRIMARY_SAMPLE(T, fc, px, py, pz, hf, fc.wpos_x, fc.wpos_y, 0, 0);                    // :174, :177
+                t = CSKY_PRIMARY_SAMPLE(CT)(T, fc, px, py, pz, hf, fc.wpos_x, fc.wpos_y, 0, 0);                // :174, :177
                 have = t > 0.0f;                                                                               // :184
                 below_top = !(hf >= fc.hf_hi);
             }
@@ -339,7 +369,7 @@ __device__ __forceinline__ MarchOut march_compact(const TS& T, const FrameConsts
         if constexpr (TALLY) { if (lane == 0) tally[0] += (unsigned)n; }
         if (lane < n) {
             float Dr, Dg, Db, rq, dt;
-            light_march_terms(T, fc, ls, nd, ev_px[lane], ev_py[lane], ev_pz[lane],
+            light_march_terms<CT>(T, fc, ls, nd, ev_px[lane], ev_py[lane], ev_pz[lane],
                               [&](float& et, float& ehf, float& ess, float& eph) { et = ev_t[lane]; ehf = ev_hf[lane]; const int ow = ev_owner[lane]; ess = ray_ss[ow]; eph = ray_ph[ow]; }, Dr, Dg, Db, rq, dt);
             ev_px[lane] = Dr; ev_py[lane] = Dg; ev_pz[lane] = Db; ev_t[lane] = rq; ev_hf[lane] = dt;           // the sample's slot now holds its terms
         }
@@ -608,7 +638,7 @@ __global__ __launch_bounds__(1024) void clouds_kernel_lds(TexSet T, const FrameC
                                // together) 7 waves x 72 VGPRs beat 8 waves x 64 VGPRs + spills: whole frame 1.83 -> 1.80 ms, 1/4 frame 0.49 -> 0.48
 #endif
 // One workgroup's footprint (4 tiles / SEG): `logical` = slab * tiles_x + bx, `rec` = its position in the launch order (the persistent form: its cost-feedback slot).
-template <int VARIANT, int SEG, class TS = TexSet, bool TALLY = true>
+template <int VARIANT, int SEG, class TS = TexSet, bool TALLY = true, int CT = 0>
 __device__ __forceinline__ void render_block(TS T, const FrameConsts* __restrict__ fcp, const RenderGeom& G, const uint32_t logical, const uint32_t rec,
                                              uint2* __restrict__ out, unsigned long long* __restrict__ stats, uint32_t* __restrict__ wg_cost, const int tile_of_wave = -1) {
     constexpr int BW = 32 / SEG;                               // workgroup footprint width in pixels
@@ -637,7 +667,7 @@ __device__ __forceinline__ void render_block(TS T, const FrameConsts* __restrict
     } else {
         __shared__ float lds[4][VARIANT == 3 ? CQ_FLOATS : Q_FLOATS];
         const int s0 = (fc.primary_steps * seg) / SEG, s1 = (fc.primary_steps * (seg + 1)) / SEG;
-        if constexpr (VARIANT == 3) o = march_compact<SEG == 1, TALLY>(T, fc, ray, &lds[wave][0], s0, s1);
+        if constexpr (VARIANT == 3) o = march_compact<SEG == 1, TALLY, CT>(T, fc, ray, &lds[wave][0], s0, s1);
         else o = march_queue(T, fc, ray, &lds[wave][0], s0, s1);
         if constexpr (SEG > 1) {
             __shared__ float comb[4][5][64];
@@ -696,7 +726,9 @@ __global__ __launch_bounds__(256, VARIANT == 3 ? CSKY_COMPACT_WAVES : 7) void cl
 //     wavefront out zeroes them again (a memset node in front of every launch cost 46 us on a busy chip).
 // Used for launches of 12 Ki - 64 Ki wavefronts while two frames are in flight (launch_policy.h has the policy and the
 // numbers; profiles/r02/persistent_launch_ab.txt).
-template <int VARIANT, bool TALLY = true>
+//   * CT: the cloud-type mode the frame set-up wrote into *fcp (launch_clouds picks the instantiation from the same value), 0 for a mixed map or
+//     csky_set_height_window(0): the march reads the mode from the frame constants as every other kernel does.
+template <int VARIANT, bool TALLY = true, int CT = 0>
 __global__ __launch_bounds__(256, VARIANT == 3 ? CSKY_COMPACT_WAVES : 7) void clouds_kernel_persistent(TexSet T, const FrameConsts* __restrict__ fcp, RenderGeom G,
         const uint32_t* __restrict__ order, const uint32_t n_items, uint32_t* __restrict__ heads, uint2* __restrict__ out, unsigned long long* __restrict__ stats,
         uint32_t* __restrict__ wg_cost) {
@@ -758,7 +790,7 @@ __global__ __launch_bounds__(256, VARIANT == 3 ? CSKY_COMPACT_WAVES : 7) void cl
             TexSetSmallDetail Ts;
             static_cast<TexSet&>(Ts) = T;
             Ts.det_small = (SmallDetailTable)det_small;                        // generic -> LDS: a C-style cast is the only one that may change the address space
-            render_block<VARIANT, 1, TexSetSmallDetail, TALLY>(Ts, fcp, G, logical, rec, out, stats, wg_cost, tile);
+            render_block<VARIANT, 1, TexSetSmallDetail, TALLY, CT>(Ts, fcp, G, logical, rec, out, stats, wg_cost, tile);
         }
     }
 }
@@ -864,8 +896,10 @@ int cloud_variant_count() { return (int)(sizeof(kVariantNames) / sizeof(kVariant
 const char* cloud_variant_name(int v) { return (v >= 0 && v < cloud_variant_count()) ? kVariantNames[v] : nullptr; }
 
 hipError_t launch_clouds(int variant, int seg, const TexSet& t, const FrameConsts* d_fc, const RenderGeom& g, const uint32_t* d_order, int grid,
-                         uint2* d_out, unsigned long long* d_stats, uint32_t* d_wg_cost, hipStream_t s, uint32_t* d_heads, int resident, const TexSet32* t32, bool census_lean) {
+                         uint2* d_out, unsigned long long* d_stats, uint32_t* d_wg_cost, hipStream_t s, uint32_t* d_heads, int resident, const TexSet32* t32, bool census_lean,
+                         int ct_mode) {
     if (grid <= 0) return hipSuccess;
+    if (ct_mode < 0 || ct_mode > 2) return hipErrorInvalidValue;
     // the in-cloud count has a reader only when the launch was given somewhere to put it: without one the whole-ray compact kernel runs in the form whose
     // latched rays stop marching (march_compact, TALLY = false).  census_lean: that form WITH a stats buffer, which only the census build's counters write.
     const bool tally = (d_stats != nullptr || d_wg_cost != nullptr) && !census_lean;
@@ -875,8 +909,18 @@ hipError_t launch_clouds(int variant, int seg, const TexSet& t, const FrameConst
         return hipGetLastError();
     }
     if (d_heads && variant == 3 && seg == 1) {                 // persistent form, see clouds_kernel_persistent
-        if (tally) clouds_kernel_persistent<3, true><<<grid < resident ? grid : resident, 256, 0, s>>>(t, d_fc, g, d_order, (uint32_t)grid, d_heads, d_out, d_stats, d_wg_cost);
-        else clouds_kernel_persistent<3, false><<<grid < resident ? grid : resident, 256, 0, s>>>(t, d_fc, g, d_order, (uint32_t)grid, d_heads, d_out, d_stats, d_wg_cost);
+        // the instantiation of the frame's cloud-type mode: ct_mode is what the set-up of d_fc was given (clouds_launch.cpp setup_args), so the compiled-in
+        // branch is the one the generic form would take on fc.ct_mode
+        const unsigned n = (unsigned)(grid < resident ? grid : resident);
+        const auto go = [&](auto tl, auto ct) {
+            clouds_kernel_persistent<3, decltype(tl)::value, decltype(ct)::value><<<n, 256, 0, s>>>(t, d_fc, g, d_order, (uint32_t)grid, d_heads, d_out, d_stats, d_wg_cost);
+        };
+        const auto with_mode = [&](auto tl) {
+            if (ct_mode == 1) go(tl, std::integral_constant<int, 1>());
+            else if (ct_mode == 2) go(tl, std::integral_constant<int, 2>());
+            else go(tl, std::integral_constant<int, 0>());
+        };
+        if (tally) with_mode(std::true_type()); else with_mode(std::false_type());
         return hipGetLastError();
     }
     if (variant == 0 && seg == 1) clouds_kernel<0, 1><<<grid, 256, 0, s>>>(t, d_fc, g, d_order, d_out, d_stats, d_wg_cost);

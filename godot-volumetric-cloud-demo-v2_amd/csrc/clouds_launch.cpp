@@ -45,11 +45,18 @@ int ensure_order(csky_ctx* c, int slot, int mode, int tiles_x, int slabs, hipStr
     return CSKY_OK;
 }
 
+// What the set-up of a frame with these push constants is given.  The launch asks again for the same frame (clouds_dev), so that the march it
+// picks by SetupArgs::ct_mode is the one compiled for the mode in the slot's FrameConsts; a launch without a set-up of its own (csky_time_clouds)
+// follows one of the same call, with the same noise set and switches.
+SetupArgs setup_args(csky_ctx* c, const CloudParams& cp) {
+    const ExactRejects rej = c->noise.st.rejects(cp.cloud_coverage, c->use_window);
+    return {c->primary_steps, c->light_steps, c->early_eps, rej.hf_lo, rej.hf_hi, rej.ct_mode, c->use_window ? 1 : 0};
+}
+
 // Frame set-up on the context's stream (beside the caller's: context.h) into the next slot of the ring; the launch stream s waits for it.
 int frame_setup(csky_ctx* c, const CloudParams& cp, hipStream_t s) {
-    const ExactRejects rej = c->noise.st.rejects(cp.cloud_coverage, c->use_window);
+    const SetupArgs sa = setup_args(c, cp);
     int f, rc; if ((rc = c->ring.next_slot(c, c->stream, f))) return rc;
-    const SetupArgs sa = {c->primary_steps, c->light_steps, c->early_eps, rej.hf_lo, rej.hf_hi, rej.ct_mode, c->use_window ? 1 : 0};
     const SkyLut& l = c->lut;
     if (l.st.own_taps())                             // the set-up renders the texels of its three taps (clouds.glsl:163-167) itself
         HIPCHK(c, launch_frame_setup_taps(cp, l.st.sun, c->d_trans_f, c->tw, c->th, l.st.w, l.st.h, sa, c->ring.slot[f].fc, c->stream, c->tlut));
@@ -112,7 +119,8 @@ int clouds_dev(csky_ctx* c, const csky_cloud_params* p, int tile_w, const csky_b
     // second stream at equal or lowest priority to back-fill the tail: one frame at a time 2.00 -> 2.00-2.05 ms, frames identical.  The tail is the last wavefronts'
     // serial chains, not idle slots; the next frame fills it.)
     {   // a failed persistent launch may leave the slot's pop counters armed: re-zero them so that the next launch on this slot starts clean
-        const hipError_t le = launch_clouds(pl.variant, pl.seg, texset(c), ring.fc(), g, order, grid, d_out, d_stats, cost, s, heads, c->resident_wgs, t32p, c->census_lean);
+        const hipError_t le = launch_clouds(pl.variant, pl.seg, texset(c), ring.fc(), g, order, grid, d_out, d_stats, cost, s, heads, c->resident_wgs, t32p, c->census_lean,
+                                                setup_args(c, cp).ct_mode);
         if (le != hipSuccess) { if (heads) (void)hipMemsetAsync(heads, 0, 16 * sizeof(uint32_t), s); return fail(c, CSKY_ERR_HIP, "cloud kernel launch failed: %s", hipGetErrorString(le)); }
     }
     if (kt) HIPCHK(c, hipEventRecord(kt[1], s));

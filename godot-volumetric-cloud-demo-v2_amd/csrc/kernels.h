@@ -56,7 +56,8 @@ hipError_t launch_bake32(const uint8_t* d_large_chain, const uint8_t* d_small_ch
 // d_order[grid]: physical workgroup -> workgroup-footprint id (0xffffffff = idle), see clouds_launch.cpp::clouds_dev.
 hipError_t launch_clouds(int variant, int seg, const TexSet& t, const FrameConsts* d_fc, const RenderGeom& g, const uint32_t* d_order, int grid,
                          uint2* d_out, unsigned long long* d_stats, uint32_t* d_wg_cost, hipStream_t s, uint32_t* d_heads = nullptr, int resident = 0,
-                         const TexSet32* t32 = nullptr, bool census_lean = false);   // t32: march on the exact fp32-coefficient cells (variant 3, seg 1 only)
+                         const TexSet32* t32 = nullptr, bool census_lean = false,    // t32: march on the exact fp32-coefficient cells (variant 3, seg 1 only)
+                         int ct_mode = 0);   // the SetupArgs::ct_mode *d_fc was set up with: a persistent launch runs the march compiled for that mode (0: the generic one)
 // resident 256-thread workgroups per CU of the "compact" kernel (its launch bound): the size of a persistent launch
 int cloud_resident_workgroups_per_cu();
 int cloud_variant_count();

@@ -61,7 +61,8 @@ def kernels_of(asm_files):
 def base_name(mangled):
     """_ZN4csky23frame_setup_taps_kernelILi0EEEv... -> frame_setup_taps_kernel<0>: enough to pair a kernel across a change of its parameters.
     Template arguments may be integers, class names of the namespace and bools; a trailing `true` is dropped, so that a kernel that gained a
-    bool parameter pairs its <..., true> instantiation with the parent's kernel (<..., false> has no counterpart there)."""
+    bool parameter pairs its <..., true> instantiation with the parent's kernel (<..., false> has no counterpart there); trailing `0`s likewise, for a
+    kernel that gained an integer parameter whose 0 is the form the parent had."""
     m = re.match(r"_ZN4csky(\d+)", mangled)
     n = int(m.group(1))
     name, rest = mangled[m.end():m.end() + n], mangled[m.end() + n:]
@@ -80,7 +81,7 @@ def base_name(mangled):
             k = int(t.group(1))
             args.append(rest[t.end():t.end() + k])
             rest = rest[t.end() + k + 1:]                      # the name and the E that closes the nested name
-    if args and args[-1] == "true":
+    while args and args[-1] in ("true", "0"):
         args.pop()
     return name + ("<%s>" % ",".join(args) if args else "")
 

@@ -37,8 +37,10 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 # "plain" / "persistent": the instantiations the headline path and every timed launch run, without the in-cloud tally and with latched rays stopped
 # (cloud_kernels.hip march_compact, TALLY = false): what csky_census_clouds launches, and what bench.py compares with the hardware counters;
 # "*_tally": the ones a launch with a stats buffer runs, which csky_census_clouds launches with CSKY_CENSUS_TALLY=1 in the environment
-KERNELS = {"plain": "_ZN4csky13clouds_kernelILi3ELi1ENS_6TexSetELb0E", "persistent": "_ZN4csky24clouds_kernel_persistentILi3ELb0E",
-           "plain_tally": "_ZN4csky13clouds_kernelILi3ELi1ENS_6TexSetELb1E", "persistent_tally": "_ZN4csky24clouds_kernel_persistentILi3ELb1E"}
+# The persistent form is compiled per cloud-type mode (cloud_kernels.hip clouds_kernel_persistent<3, TALLY, CT>; launch_clouds picks CT from the bound
+# weather map): the shipped map's red channel is >= 128 everywhere, so every timed launch and csky_census_clouds run CT = 1, and that is what is counted.
+KERNELS = {"plain": "_ZN4csky13clouds_kernelILi3ELi1ENS_6TexSetELb0E", "persistent": "_ZN4csky24clouds_kernel_persistentILi3ELb0ELi1E",
+           "plain_tally": "_ZN4csky13clouds_kernelILi3ELi1ENS_6TexSetELb1E", "persistent_tally": "_ZN4csky24clouds_kernel_persistentILi3ELb1ELi1E"}
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-fno-slp-vectorize", "--offload-arch=gfx950", "-Wno-unused-function", "-Wno-unknown-pragmas", "-Wno-pass-failed"]
 N_CTR_VGPR = 4                      # 256 block counters per kernel
 CENSUS_BYTE_OFFSET = 16             # the kernel's own two 64-bit tallies come first in the stats buffer
