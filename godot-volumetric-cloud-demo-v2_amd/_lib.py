@@ -245,6 +245,7 @@ SYMBOLS = [
     ("csky_build_mips_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     ("csky_read_baked_texture", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("csky_test_sqrt_shell", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    ("csky_test_primitive", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     ("csky_test_static_order", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]),
     ("csky_test_lpt_order", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("csky_census_clouds", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.c_int, C.POINTER(Bands), C.c_void_p, C.c_int]),
@@ -302,6 +303,33 @@ def lib():
 
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+# csky_test_primitive (include/cloudsky_internal.h, csrc/primitives_core.h): name -> (op, inputs, outputs), an array = (dtype, words per element)
+_F, _U, _I = np.float32, np.uint32, np.int32
+PRIMITIVES = {
+    "sqrt_exact": (0, [(_F, 1)], [(_F, 1)]), "sqrtf": (1, [(_F, 1)], [(_F, 1)]), "div": (2, [(_F, 1), (_F, 1)], [(_F, 1)]),
+    "split_coord": (3, [(_F, 1)], [(_I, 1), (_F, 1)]), "lerp_h": (4, [(_U, 1), (_F, 1)], [(_F, 1)]), "lerp_h2": (5, [(_U, 1), (_F, 1)], [(_F, 1)]),
+    "f2h_normal": (6, [(_F, 1)], [(_U, 1)]), "fast_rcp": (7, [(_F, 1)], [(_F, 1)]), "fast_exp2": (8, [(_F, 1)], [(_F, 1)]),
+    "fast_log2": (9, [(_F, 1)], [(_F, 1)]), "fast_exp": (10, [(_F, 1)], [(_F, 1)]), "fast_pow": (11, [(_F, 1), (_F, 1)], [(_F, 1)]),
+    "rad_rcp": (12, [(_F, 1)], [(_F, 1)]), "ray": (13, [(_F, 3), (_F, 1)], [(_F, 10)]), "pixel_dir": (14, [(_I, 2), (_F, 2)], [(_F, 3)]),
+}
+
+
+def run_primitive(call, op, arrays):
+    """One primitive over arrays: `call(op code, in0, in1, in2, out0, out1, n)` is csky_test_primitive bound to a context, or the host build's
+    export of the same table (tests/hostsim).  Inputs are [n] or [n, words] arrays of the op's types; -> the output array, or a tuple of two."""
+    code, ins, outs = PRIMITIVES[op]
+    if len(arrays) != len(ins):
+        raise ValueError("%s takes %d arrays" % (op, len(ins)))
+    a = [np.ascontiguousarray(x, dt).reshape(-1, w) for x, (dt, w) in zip(arrays, ins)]
+    n = a[0].shape[0]
+    if any(x.shape[0] != n for x in a):
+        raise ValueError("%s: arrays of different lengths" % op)
+    o = [np.zeros((n, w) if w > 1 else (n,), dt) for dt, w in outs]
+    ptr = [_ptr(x) for x in a] + [None] * (3 - len(a)) + [_ptr(x) for x in o] + [None] * (2 - len(o))
+    call(code, *ptr, n)
+    return o[0] if len(o) == 1 else tuple(o)
 
 
 def cloud_params(values):
@@ -848,6 +876,10 @@ class Context:
         out = np.zeros_like(x)
         self._chk(self._L.csky_test_sqrt_shell(self._h, _ptr(x), _ptr(out), x.size))
         return out
+
+    def test_primitive(self, op, *arrays):
+        """Test hook: one of the march's arithmetic primitives (PRIMITIVES) on the device over arrays, one element per lane."""
+        return run_primitive(lambda *a: self._chk(self._L.csky_test_primitive(self._h, *a)), op, arrays)
 
     def test_static_order(self, mode, tiles_x, slabs):
         """Test hook: the static workgroup order (mode 1, 2 or 5) of a tiles_x x slabs launch as the device writes it; its length is the launch's grid."""

@@ -18,6 +18,7 @@
 #include "mip_args.h"
 #include "cloud_core.h"
 #include "order_core.h"
+#include "primitives_core.h"
 
 using namespace csky;
 
@@ -245,6 +246,33 @@ int csky_test_sqrt_shell(csky_ctx* c, const float* in, float* out, size_t n) {
     HIPCHK(c, hipMemcpyAsync(d, in, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, launch_sqrt_shell(d, d + n, n, c->stream));
     HIPCHK(c, hipMemcpyAsync(out, d + n, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return CSKY_OK;
+}
+
+int csky_test_primitive(csky_ctx* c, int op, const void* in0, const void* in1, const void* in2, void* out0, void* out1, size_t n) {
+    if (!c) return fail(c, CSKY_ERR_INVALID, "csky_test_primitive: NULL context");
+    if (op < 0 || op >= PRIM_COUNT || n > ((size_t)1 << 24)) return fail(c, CSKY_ERR_INVALID, "csky_test_primitive: op in [0, %d), n <= 2^24", (int)PRIM_COUNT);
+    const PrimShape sh = prim_shape(op);
+    const void* const in[3] = {in0, in1, in2};
+    void* const out[2] = {out0, out1};
+    size_t words = 4;
+    for (int k = 0; k < 3; k++) { if (sh.in[k] && !in[k]) return fail(c, CSKY_ERR_INVALID, "csky_test_primitive: op %d needs input %d", op, k); words += (size_t)sh.in[k] * n; }
+    for (int k = 0; k < 2; k++) { if (sh.out[k] && !out[k]) return fail(c, CSKY_ERR_INVALID, "csky_test_primitive: op %d needs output %d", op, k); words += (size_t)sh.out[k] * n; }
+    if (n == 0) return CSKY_OK;
+    int rc; if ((rc = bind(c))) return rc;
+    DevBuf<uint32_t> d; if ((rc = d.alloc(c, words))) return rc;
+    const uint32_t* d_in[3] = {nullptr, nullptr, nullptr};
+    uint32_t* d_out[2] = {nullptr, nullptr};
+    uint32_t* at = d;
+    for (int k = 0; k < 3; k++) if (sh.in[k]) {
+        d_in[k] = at;
+        HIPCHK(c, hipMemcpyAsync(at, in[k], (size_t)sh.in[k] * n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        at += (size_t)sh.in[k] * n;
+    }
+    for (int k = 0; k < 2; k++) if (sh.out[k]) { d_out[k] = at; at += (size_t)sh.out[k] * n; }
+    HIPCHK(c, launch_primitive(op, d_in, d_out, n, c->stream));
+    for (int k = 0; k < 2; k++) if (sh.out[k]) HIPCHK(c, hipMemcpyAsync(out[k], d_out[k], (size_t)sh.out[k] * n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return CSKY_OK;
 }

@@ -7,8 +7,14 @@
 // Section A is compiled with FP contraction OFF and IEEE-exact sqrt/div: it holds every expression whose
 // fp32 rounding decides WHERE a sample lands (ray set-up, |p|, texture coordinates).  Those reproduce the
 // reference's evaluation order bit for bit (positions are ~6e6 m, ulp 0.5 m; intersectSphere
-// cancels catastrophically).  Section B (filtering, remaps, shading) may contract and uses the hardware
-// exp2/log2/rcp approximations; its error is continuous and ~1e-6 relative (tests state the tolerance).
+// cancels catastrophically): the plain `/` and sqrtf are IEEE through the compiler's default (csrc/Makefile sets no flag that relaxes them), which
+// tests/test_gpu_primitives.py pins on the MI355X (test_divide_is_correctly_rounded, test_sqrt_is_correctly_rounded[sqrtf-*]) together with
+// pixel_dir and ray_from_dir themselves, field by field against tests/ray_reference.py.  Section B (filtering, remaps, shading) may contract and
+// uses the hardware exp2/log2/rcp approximations.  Their error, measured there against float64 in ulp of the correctly rounded float32 result
+// (measured, not documented: the toolchain ships no statement): v_rcp_f32 0.882, v_exp_f32 0.769, v_log_f32 0.99986, all under 1 ulp; fast_exp on
+// [-88, 0] at most 3.9e-6 relative (bound 2^-23 + ln 2 |x log2 e| 2^-23), fast_pow on [2^-24, 1] x [0.5, 1.3] at most 2.4e-6 (bound
+// 2^-23 + ln 2 |y log2 x| 2^-22).  Denormal arguments and results are flushed (fast_log2 -> -inf, fast_exp2 below -126 -> 0): absolute error
+// under 2^-63 for that fast_pow, under 2^-126 for fast_exp2 (test_denormal_inputs_and_results_are_harmless).
 #pragma once
 #include "csky_common.h"
 
@@ -54,9 +60,16 @@ struct Ray {
     bool above;           // dir.y > 0 (clouds.glsl:221)
 };
 
-// Correctly rounded sqrt for NORMAL positive inputs (|p|^2 ~ 3.6e13, ray set-up values): v_sqrt_f32 (1 ulp) plus the
-// residual test of its two neighbours -- the same fix-up LLVM emits for an IEEE sqrtf, minus the denormal pre-scaling
-// that can never trigger here (17 -> 9 VALU).  Bit-identical to the oracle's sqrtf.
+// Correctly rounded sqrt for x in [SQRT_EXACT_MIN, FLT_MAX] = [2^-102, FLT_MAX] (|p|^2 ~ 3.6e13, ray set-up values): v_sqrt_f32 (1 ulp) plus the
+// residual test of its two neighbours -- the same fix-up LLVM emits for an IEEE sqrtf, minus the denormal pre-scaling (17 -> 9 VALU).  On that
+// range it is bit-identical to the oracle's sqrtf: tests/test_gpu_primitives.py::test_sqrt_is_correctly_rounded runs it on the MI355X over every
+// float of [1, 4) (the mantissa behaviour repeats with the exponent pair), over the mantissa edges and 4096 random mantissas of every exponent, and
+// over the ray set-up's own operands.  Why 2^-102: the residuals x - s' s are multiples of 2^(2 e - 46) for a root in [2^e, 2^(e+1)), and keep
+// their sign and their being zero or not through the FMA's rounding only while that is >= 2^-149.  Below, a residual can round to zero and the test picks the lower
+// neighbour: measured, 1 ulp low on ~2 % of the floats under 2^-110 (denormals come back as 2^-149; 0, inf and NaN as themselves).  Nothing per
+// ray is that small (|n|^2 >= 1/3, shell distances >= 2500 m, step lengths >= 2500 m / steps); the once-per-frame set-up, whose operands are the caller's
+// or filtered LUT texels, takes length3_ieee below.
+constexpr float SQRT_EXACT_MIN = 1.97215226e-31f;   // 2^-102
 CSKY_HD float sqrt_exact(float x) {
 #if defined(__HIP_DEVICE_COMPILE__)
     const float s = __builtin_amdgcn_sqrtf(x);
@@ -70,6 +83,9 @@ CSKY_HD float sqrt_exact(float x) {
 #endif
 }
 CSKY_HD float length3_exact(float x, float y, float z) { return sqrt_exact(x * x + y * y + z * z); }
+// The same over the whole range, for the frame set-up (one lane, once per frame): the compiler's IEEE sqrtf with its denormal scaling, which
+// test_sqrt_is_correctly_rounded[sqrtf-*] pins on every exponent and test_sqrt_outside_the_specified_range on 0, denormals, inf and NaN.
+CSKY_HD float length3_ieee(float x, float y, float z) { return sqrtf(x * x + y * y + z * z); }
 
 // Correctly rounded sqrt for |p|^2 of SAMPLE positions, which only ever lie between the two cloud shells plus the light march's reach:
 // |p| in [5 997 500, 6 008 000] m, i.e. x in [3.597e13, 3.6097e13] -- 30 067 consecutive floats.  On that range the two-FMA Newton step
@@ -208,7 +224,7 @@ CSKY_HD void density_frame_consts(const CloudParams& P, int steps, float hf_lo, 
 }
 CSKY_HD void light_dir_consts(const CloudParams& P, FrameConsts& fc) {
     const float lx = P.LIGHT_DIRECTION[0], ly = P.LIGHT_DIRECTION[1], lz = P.LIGHT_DIRECTION[2];
-    const float ll = length3_exact(lx, ly, lz);
+    const float ll = length3_ieee(lx, ly, lz);                                              // the caller's vector: any length
     fc.ldir[0] = lx / ll; fc.ldir[1] = ly / ll; fc.ldir[2] = lz / ll;                       // clouds.glsl:150
 }
 
@@ -233,12 +249,12 @@ template <class Fetch> CSKY_HD void frame_setup_f(const CloudParams& P, Fetch fe
     frame_setup_tap_uv(P.LIGHT_DIRECTION, 1, sx, sy);
     sky_lut_tap_f([&fetch](int c, int x, int y) { return fetch(1, c, x, y); }, sky_w, sky_h, sx, sy, s);   // clouds.glsl:164
     for (int k = 0; k < 3; k++) s[k] = s[k] * 0.05f;
-    float len = length3_exact(s[0], s[1], s[2]);
+    float len = length3_ieee(s[0], s[1], s[2]);                                              // filtered texels: any size, zero included
     for (int k = 0; k < 3; k++) fc.amb_c[k] = s[k] * (1.0f - 0.5f) + len * 0.5f;           // clouds.glsl:165
     frame_setup_tap_uv(P.LIGHT_DIRECTION, 2, sx, sy);
     sky_lut_tap_f([&fetch](int c, int x, int y) { return fetch(2, c, x, y); }, sky_w, sky_h, sx, sy, s);   // clouds.glsl:166
     for (int k = 0; k < 3; k++) s[k] = s[k] * 5.0f * 0.05f;
-    len = length3_exact(s[0], s[1], s[2]);
+    len = length3_ieee(s[0], s[1], s[2]);
     for (int k = 0; k < 3; k++) fc.gnd_c[k] = s[k] * (1.0f - 0.5f) + (P.ground_color[k] * len) * 0.5f;  // clouds.glsl:167
     fc.light_steps = light_steps;
     fc.early_eps = early_eps;
@@ -275,7 +291,9 @@ extern thread_local int csky_stage;
 // a + f*d for an fp16 pair packed in one dword: lo = texel(x) = a, hi = texel(x+1) - texel(x) = d (the x-neighbour DIFFERENCE is
 // stored, not the neighbour: an integer in [-2040, 2040], exact in fp16).  On gfx950 this is ONE v_fma_mix_f32: the f16 -> f32
 // widening is free inside the FMA (4.4 cycles; byte texels needed cvt + cvt + sub + fma = 17, profiles/r01/valu_issue_rates_gfx950.txt; today's measurement: tools/ubench/valu_rates2.hip), and
-// it is literally the reference sampler's a + (b - a)*f with an exact (b - a).
+// it is literally the reference sampler's a + (b - a)*f with an exact (b - a).  Both forms against the exactly computed, once (lerp_h) or twice
+// (lerp_h2) rounded value, every low half and every high half, fp16 denormals and both signs of the difference:
+// tests/test_gpu_primitives.py::test_lerp_is_one_rounding_of_the_exact_value.
 CSKY_HD float lerp_h(uint32_t p, float f) {
 #if defined(__HIP_DEVICE_COMPILE__)
     float r;
@@ -301,7 +319,8 @@ CSKY_HD float lerp_h2(uint32_t a_lo_b_hi, float f) {
 
 // Texel coordinate -> (floor as int, fraction).  gfx950 has v_cvt_flr_i32_f32 (float -> int with floor rounding) and
 // v_fract_f32, so the pair costs 2 instructions instead of floor + cvt + sub; u - floor(u) is exact in fp32 and v_fract returns
-// the same value (it only clamps the one-in-2^25 case u = -tiny to 1 - 2^-24 instead of 1.0).
+// the same value (it only clamps the one-in-2^25 case u = -tiny to 1 - 2^-24 instead of 1.0): tests/test_gpu_primitives.py::
+// test_split_coord_is_floor_and_fraction, at every integer and half-integer of [-4096, 4096], +-2^22..24 and 2^20 tap coordinates.
 // (Round 2 tried the full-rate alternative t = fma(s, n, 1.5*2^23 - 1), i = bits(t), f = u - (t - 1.5*2^23): four full-rate instead of one
 // full + two half-rate instructions per axis.  It is NOT bit-identical -- when u is an exact integer, round-to-nearest-even lands on the cell
 // below with f = 1 for half of them, which is the same sample point but three roundings instead of one in the y / z lerps -- and it measured
@@ -733,7 +752,8 @@ CSKY_HD void shade_sample(const FrameConsts& fc, float phase, float t, float hf,
 constexpr float SAT_ALPHA_MIN = 1.0f - 0.000244140625f;       // 1 - 2^-12
 constexpr float SAT_BEERS_MAX = 0.7699f;                      // > 4 / (3 sqrt 3)
 // the half a value is stored as, for 2^-14 <= x < 65520 (normal halfs, where v_cvt_f16_f32 in the default round-to-nearest-even mode is f2h whatever the
-// denormal mode); the predicate does not fire outside that range
+// denormal mode); the predicate does not fire outside that range.  Checked on the MI355X at every normal half, every midpoint between two, their
+// +-2 ulp32 neighbours and 2^20 random values: tests/test_gpu_primitives.py::test_f2h_normal_is_the_software_f2h_on_its_range.
 CSKY_HD uint16_t f2h_normal(float x) {
 #if defined(__HIP_DEVICE_COMPILE__)
     const _Float16 h = (_Float16)x;

@@ -119,4 +119,9 @@ hipError_t launch_radiance_cones(int n, float4* d_cones, hipStream_t s);
 hipError_t launch_radiance_filter(const float4* d_tab, const float4* d_src_cones, const float4* d_out_cones, int n, int ns, const RadLayer* ly, int nl, bool cull,
                                   uint2* d_out, hipStream_t s);
 
+// ------------------------------------------------------------------------------------------------ primitives.hip
+// test hook: primitive `op` (primitives_core.h PrimOp) over n elements, one per lane.  d_in / d_out: prim_shape(op) words per element each; an
+// array the op does not use may be null.
+hipError_t launch_primitive(int op, const uint32_t* const d_in[3], uint32_t* const d_out[2], size_t n, hipStream_t s);
+
 }  // namespace csky

@@ -112,6 +112,7 @@ CSKY_HD RadLayer rad_layer(int k, int L) {
     return RadLayer{(float)a2, (float)((1.0 - a2) * 0.25)};
 }
 
+// v_rcp_f32: at most 0.882 ulp on [0.5, 2), 1 / 2^k exact (measured; tests/test_gpu_primitives.py::test_rcp_error[rad_rcp], test_known_answers)
 CSKY_HD float rad_rcp(float x) {
 #if defined(__HIP_DEVICE_COMPILE__)
     return __builtin_amdgcn_rcpf(x);

@@ -76,6 +76,25 @@ int csky_read_baked_texture(csky_ctx* ctx, int which, void* out, size_t capacity
 /* Test hook: the march's range-restricted exact square root (cloud_core.h::sqrt_shell, |p|^2 of sample positions) over an array, so that
  * a test can check it EXHAUSTIVELY against IEEE sqrtf on the range it is used on (all 30 067 floats in [3.597e13, 3.6097e13]). */
 int csky_test_sqrt_shell(csky_ctx* ctx, const float* in, float* out, size_t n);
+/* Test hook: one of the march's arithmetic primitives over arrays on the device, one element per lane, through the SAME inline functions the kernels
+ * call (csrc/primitives_core.h, which also lists what every op reads and writes; csrc/primitives.hip, a translation unit of its own built with the
+ * product's flags).  Arrays are 32-bit words, float or uint32 by op; an array the op does not use may be NULL; n <= 2^24; copies and the launch run
+ * on the context's stream.  tests/test_gpu_primitives.py holds every op against numpy: bit equality for the exact ones, an ulp gate for the
+ * hardware approximations.
+ *    op  name          in0              in1            out0                                       out1
+ *     0  sqrt_exact    x                               cloud_core.h::sqrt_exact
+ *     1  sqrtf         x                               sqrtf(x) as Section A of cloud_core.h gets it
+ *     2  div           a                b              a / b as Section A gets it (contraction off)
+ *     3  split_coord   u                               i (int32)                                  f
+ *     4  lerp_h        fp16 pair (u32)  f              a + f d
+ *     5  lerp_h2       fp16 pair (u32)  f              lo + f (hi - lo), the two-step form
+ *     6  f2h_normal    x                               the half's bits (uint32)
+ *     7  fast_rcp   8  fast_exp2   9  fast_log2   10  fast_exp      x -> f(x)
+ *    11  fast_pow      x                y              fast_pow(x, y)
+ *    12  rad_rcp       x                               radiance_core.h::rad_rcp
+ *    13  ray           [n][3] unit dir  steps (float)  [n][10] Ray px py pz ss dx dy dz sx sy sz of ray_from_dir
+ *    14  pixel_dir     [n][2] i j (i32) [n][2] w h     [n][3] direction */
+int csky_test_primitive(csky_ctx* ctx, int op, const void* in0, const void* in1, const void* in2, void* out0, void* out1, size_t n);
 /* Test hooks of the launch orders (csrc/order_core.h; tests/test_gpu_launch_order.py compares both with the host's tables and with numpy).
  * csky_test_static_order: the table of workgroup order `mode` (1, 2 or 5) for a launch of tiles_x x slabs footprints, written by the kernel the
  * frame path runs, and in *grid its number of entries = the launch's workgroups.  table may be NULL to query the grid; capacity is in entries. */

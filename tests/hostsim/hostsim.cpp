@@ -14,6 +14,7 @@
 #include "../../godot-volumetric-cloud-demo-v2_amd/csrc/bc7_tables.h"
 #include "../../godot-volumetric-cloud-demo-v2_amd/csrc/launch_policy.h"
 #include "../../godot-volumetric-cloud-demo-v2_amd/csrc/order_core.h"
+#include "../../godot-volumetric-cloud-demo-v2_amd/csrc/primitives_core.h"
 
 using namespace csky;
 
@@ -264,5 +265,13 @@ int hostsim_lpt_shift(int primary_steps) { return lpt_shift(primary_steps); }
 // pop number j of sequence y for every (j, y), j < n_j: out[j * 8 + y] = the order index, or 0xffffffff when the sequence is empty there
 void hostsim_persistent_pops(uint32_t n_items, uint32_t j0, uint32_t n_j, uint32_t* out) {
     for (uint32_t j = 0; j < n_j; j++) for (uint32_t y = 0; y < 8; y++) { uint32_t i; out[j * 8 + y] = persistent_pop_index(j0 + j, y, n_items, i) ? i : 0xffffffffu; }
+}
+}
+
+extern "C" {
+// primitives_core.h on the host: the same table csky_test_primitive runs on the device, here through the `#else` branches (libm's sqrtf, floorf and
+// fmaf, 1.0f / x, the software f2h) -- the definitions the device forms are held against (tests/test_primitives_host.py).  Returns 0, or -1 for an unknown op.
+int hostsim_primitive(int op, const uint32_t* in0, const uint32_t* in1, const uint32_t* in2, uint32_t* out0, uint32_t* out1, size_t n) {
+    return prim_apply_range(op, in0, in1, in2, out0, out1, 0, n) ? 0 : -1;
 }
 }
