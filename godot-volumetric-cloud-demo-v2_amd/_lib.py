@@ -196,6 +196,14 @@ SYMBOLS = [
     ("csky_render_clouds_dirs_device", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("csky_render_clouds_view", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.POINTER(View), C.c_int, C.c_int, C.c_void_p]),
     ("csky_render_clouds_view_device", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.POINTER(View), C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("csky_render_cloud_depth_dirs", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    ("csky_render_cloud_depth_dirs_device", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("csky_render_cloud_depth_view", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.POINTER(View), C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    ("csky_render_cloud_depth_view_device", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.POINTER(View), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("csky_apply_cloud_aerial_dirs", C.c_int, [C.c_void_p, C.POINTER(CloudAerialParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("csky_apply_cloud_aerial_dirs_device", C.c_int, [C.c_void_p, C.POINTER(CloudAerialParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("csky_apply_cloud_aerial_view", C.c_int, [C.c_void_p, C.POINTER(CloudAerialParams), C.POINTER(View), C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("csky_apply_cloud_aerial_view_device", C.c_int, [C.c_void_p, C.POINTER(CloudAerialParams), C.POINTER(View), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("csky_composite_view_frames", C.c_int, [C.c_void_p, C.POINTER(CompositeParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("csky_time_clouds", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.c_int, C.POINTER(Bands), C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(CloudStats)]),
     ("csky_get_cloud_stats", C.c_int, [C.c_void_p, C.POINTER(CloudStats)]),
@@ -703,6 +711,110 @@ class Context:
         else:
             self._chk(self._L.csky_render_clouds_view(self._h, C.byref(p), C.byref(v), shape[1], shape[0], _ptr(out)))
         return out
+
+    @staticmethod
+    def _view(basis, fov_y_degrees):
+        return View((C.c_float * 9)(*[float(x) for x in np.asarray(basis, np.float32).T.reshape(-1)]), float(fov_y_degrees))   # column-major basis
+
+    def render_cloud_depth_dirs(self, params, dirs, steps=0, out=None, stream=None):
+        """The depth frame of a ray frame (csky_render_cloud_depth_dirs*, definition: include/cloudsky.h): for each direction of `dirs`
+        ([h, w, 3] float32, used as given, accepted as render_clouds_dirs accepts them) the cloud's mean, first and last distance in km and the
+        ray's alpha, float16 [h, w, 4]; zero where the direction is not accepted.  steps 0 = the context's primary step count, render_clouds_dirs'
+        own.  Host path (dirs a numpy array): blocks, returns numpy.  Device path (dirs a contiguous float32 torch tensor on this context's GPU;
+        out a [h, w, 4] tensor of 2-byte elements whose texels are contiguous, its row stride the pitch, or None for a new one): asynchronous
+        on `stream`, returns the tensor.  Needs the noise and no LUT."""
+        p = cloud_params(params)
+        if len(dirs.shape) != 3 or int(dirs.shape[2]) != 3:
+            raise ValueError("render_cloud_depth_dirs: dirs must be a [h, w, 3] float32 array (or torch tensor on the GPU)")
+        shape = (int(dirs.shape[0]), int(dirs.shape[1]), 4)
+        if hasattr(dirs, "data_ptr"):
+            import torch
+            if dirs.dtype != torch.float32 or not dirs.is_contiguous():
+                raise ValueError("render_cloud_depth_dirs: a device dirs must be a contiguous float32 tensor")
+            if out is None:
+                out = torch.empty(shape, dtype=torch.float16, device=dirs.device)
+            dev, out, pitch = self._rays_out("render_cloud_depth_dirs", shape, out)
+            if not dev:
+                raise ValueError("render_cloud_depth_dirs: with device dirs, out must be a torch tensor")
+            self._chk(self._L.csky_render_cloud_depth_dirs_device(self._h, C.byref(p), shape[1], shape[0], int(steps), C.c_void_p(int(dirs.data_ptr())),
+                                                                  C.c_void_p(int(out.data_ptr())), C.c_size_t(int(pitch)), C.c_void_p(stream or 0)))
+            return out
+        d = np.ascontiguousarray(dirs, np.float32)
+        dev, out, _ = self._rays_out("render_cloud_depth_dirs", shape, out)
+        if dev:
+            raise ValueError("render_cloud_depth_dirs: with host dirs, out must be a numpy array")
+        self._chk(self._L.csky_render_cloud_depth_dirs(self._h, C.byref(p), shape[1], shape[0], int(steps), _ptr(d), _ptr(out)))
+        return out
+
+    def render_cloud_depth_view(self, params, basis, fov_y_degrees, width, height, steps=0, out=None, stream=None):
+        """The depth frame of a camera view (csky_render_cloud_depth_view*, definition: include/cloudsky.h): render_cloud_depth for the rays of
+        render_clouds_view's image, float16 [height, width, 4].  steps 0 = the context's primary step count, the view frame's own.  Host path
+        (out None or a numpy float16 array): blocks, returns numpy.  Device path (out a [height, width, 4] torch tensor of 2-byte elements on
+        this context's GPU whose texels are contiguous; its row stride is the pitch): asynchronous on `stream`, written in place, returns the
+        tensor.  Needs the noise and no LUT."""
+        p = cloud_params(params)
+        shape = (int(height), int(width), 4)
+        v = self._view(basis, fov_y_degrees)
+        dev, out, pitch = self._rays_out("render_cloud_depth_view", shape, out)
+        if dev:
+            self._chk(self._L.csky_render_cloud_depth_view_device(self._h, C.byref(p), C.byref(v), shape[1], shape[0], int(steps), C.c_void_p(int(out.data_ptr())),
+                                                                  C.c_size_t(int(pitch)), C.c_void_p(stream or 0)))
+        else:
+            self._chk(self._L.csky_render_cloud_depth_view(self._h, C.byref(p), C.byref(v), shape[1], shape[0], int(steps), _ptr(out)))
+        return out
+
+    def _apply_rays(self, name, sun, cloud, depth, steps, out, stream, host_call, device_call, dirs=None):
+        """apply_cloud_aerial's argument handling for the ray forms: host_call / device_call take (params, cloud, depth, out[, stream]) pointers."""
+        shape = tuple(int(x) for x in cloud.shape)
+        if len(shape) != 3 or shape[2] != 4 or tuple(int(x) for x in depth.shape) != shape:
+            raise ValueError("%s: cloud and depth must be [h, w, 4] images of one size" % name)
+        if dirs is not None and tuple(int(x) for x in dirs.shape) != (shape[0], shape[1], 3):
+            raise ValueError("%s: dirs must be a [h, w, 3] float32 image of the frames' size" % name)
+        p = CloudAerialParams(shape[1], shape[0], int(steps), (C.c_float * 3)(*[float(x) for x in sun]))
+        if hasattr(cloud, "data_ptr"):
+            import torch
+            if out is None:
+                out = torch.empty(shape, dtype=torch.float16, device=cloud.device)
+            for t in (cloud, depth, out):
+                if not hasattr(t, "data_ptr") or tuple(t.shape) != shape or t.element_size() != 2 or not t.is_contiguous():
+                    raise ValueError("%s: with a device frame, cloud, depth and out must be contiguous %s tensors of 2-byte elements" % (name, shape))
+            if dirs is not None and (not hasattr(dirs, "data_ptr") or dirs.dtype != torch.float32 or not dirs.is_contiguous()):
+                raise ValueError("%s: with a device frame, dirs must be a contiguous float32 tensor" % name)
+            self._chk(device_call(C.byref(p), dirs, C.c_void_p(int(cloud.data_ptr())), C.c_void_p(int(depth.data_ptr())), C.c_void_p(int(out.data_ptr())),
+                                  C.c_void_p(stream or 0)))
+            return out
+        cloud, depth = np.ascontiguousarray(cloud), np.ascontiguousarray(depth)
+        if cloud.dtype != np.float16 or depth.dtype != np.float16:
+            raise ValueError("%s: cloud and depth must be float16 arrays (or torch tensors on the GPU)" % name)
+        if dirs is not None:
+            if hasattr(dirs, "data_ptr"):
+                raise ValueError("%s: with host frames, dirs must be a numpy array" % name)
+            dirs = np.ascontiguousarray(dirs, np.float32)
+        if out is None:
+            out = np.zeros(shape, np.float16)
+        if out.shape != shape or out.dtype != np.float16 or not out.flags.c_contiguous:
+            raise ValueError("%s: out must be a contiguous float16 %s array" % (name, shape))
+        self._chk(host_call(C.byref(p), dirs, _ptr(cloud), _ptr(depth), _ptr(out)))
+        return out
+
+    def apply_cloud_aerial_dirs(self, sun, dirs, cloud, depth, steps=16, out=None, stream=None):
+        """apply_cloud_aerial for a ray frame (csky_apply_cloud_aerial_dirs*, definition: include/cloudsky.h): `cloud` the image of
+        render_clouds_dirs for `dirs` ([h, w, 3] float32) and `depth` that of render_cloud_depth_dirs.  A pixel whose direction the march does
+        not accept leaves as it came.  Host path (numpy arrays) and device path (contiguous torch tensors on this context's GPU) as
+        apply_cloud_aerial's; out may be `cloud`.  Needs the transmittance LUT and nothing else."""
+        return self._apply_rays("apply_cloud_aerial_dirs", sun, cloud, depth, steps, out, stream,
+                                lambda p, d, c, z, o: self._L.csky_apply_cloud_aerial_dirs(self._h, p, _ptr(d), c, z, o),
+                                lambda p, d, c, z, o, s: self._L.csky_apply_cloud_aerial_dirs_device(self._h, p, C.c_void_p(int(d.data_ptr())), c, z, o, s), dirs=dirs)
+
+    def apply_cloud_aerial_view(self, sun, basis, fov_y_degrees, cloud, depth, steps=16, out=None, stream=None):
+        """apply_cloud_aerial for a view frame (csky_apply_cloud_aerial_view*, definition: include/cloudsky.h): `cloud` the image of
+        render_clouds_view for this camera and `depth` that of render_cloud_depth_view, both float16 [h, w, 4].  Host path (numpy arrays) and
+        device path (contiguous torch tensors on this context's GPU) as apply_cloud_aerial's; out may be `cloud`.  Needs the transmittance LUT
+        and nothing else."""
+        v = self._view(basis, fov_y_degrees)
+        return self._apply_rays("apply_cloud_aerial_view", sun, cloud, depth, steps, out, stream,
+                                lambda p, d, c, z, o: self._L.csky_apply_cloud_aerial_view(self._h, p, C.byref(v), c, z, o),
+                                lambda p, d, c, z, o, s: self._L.csky_apply_cloud_aerial_view_device(self._h, p, C.byref(v), c, z, o, s))
 
     def set_shadow_exact_end(self, enabled=True):
         """A/B switch (cloudsky_internal.h): False makes every texel of the shadow map take all its samples; the maps are byte-identical."""

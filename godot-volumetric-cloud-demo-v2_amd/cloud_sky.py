@@ -265,31 +265,62 @@ class CloudSky:
         sf, st = (host(t) for t in self.sky_lut.back_texture)   # sky_blend_from/to_texture = the two OLDER ring copies (cloud_sky.gd:147-148)
         return self.ctx.composite_sky(bf, bt, sf, st, self.frame_data.LIGHT_DIRECTION, self.blend_amount, self.sun_disk_scale, out_w, out_h)
 
-    def cloud_view(self, basis, fov_y_degrees=75.0, out_w=1152, out_h=648):
+    def cloud_view(self, basis, fov_y_degrees=75.0, out_w=1152, out_h=648, aerial=False, aerial_steps=16):
         """The clouds of the current frame data marched along the rays of a perspective camera's SCREEN pixels instead of the hemisphere frame's
         (csky_render_clouds_view; the definition: include/cloudsky.h): float16 [out_h, out_w, 4], what the hemisphere frame would store for each
         ray, at the camera's own angular resolution; zero under the horizon.  The block _fill_push_constant() packs, the context's step counts.
-        basis as sky_view takes it.  A torch CUDA tensor with device_buffers=True.  Not called by update_sky()."""
+        basis as sky_view takes it.  A torch CUDA tensor with device_buffers=True.  Not called by update_sky().
+        aerial=True: the air in front of the view's clouds under the current sun, aerial_steps steps per pixel (the view's own depth frame, then
+        csky_apply_cloud_aerial_view; with device_buffers=True the three kernels run back to back on the march stream).  Alpha is unchanged."""
         pc = self._fill_push_constant()
+        sun = self.frame_data.LIGHT_DIRECTION
         if not self.device_buffers:
-            return self.ctx.render_clouds_view(pc, basis, fov_y_degrees, out_w, out_h)
+            cv = self.ctx.render_clouds_view(pc, basis, fov_y_degrees, out_w, out_h)
+            if not aerial:
+                return cv
+            return self.ctx.apply_cloud_aerial_view(sun, basis, fov_y_degrees, cv, self.ctx.render_cloud_depth_view(pc, basis, fov_y_degrees, out_w, out_h),
+                                                    aerial_steps)
         import torch
-        out = torch.empty((int(out_h), int(out_w), 4), dtype=torch.float16, device=torch.device("cuda", self.ctx.device_id))
+        dev = torch.device("cuda", self.ctx.device_id)
+        out = torch.empty((int(out_h), int(out_w), 4), dtype=torch.float16, device=dev)
         stream, done = self._march_stream()
         self.ctx.render_clouds_view(pc, basis, fov_y_degrees, out_w, out_h, out=out, stream=stream)
+        if aerial:
+            depth = torch.empty((int(out_h), int(out_w), 4), dtype=torch.float16, device=dev)
+            self.ctx.render_cloud_depth_view(pc, basis, fov_y_degrees, out_w, out_h, out=depth, stream=stream)   # the apply step reads both on the same stream
+            self.ctx.apply_cloud_aerial_view(sun, basis, fov_y_degrees, out, depth, aerial_steps, out=out, stream=stream)   # in place
         done()
         return out
 
-    def sky_view(self, basis, fov_y_degrees=75.0, out_w=1152, out_h=648, direct=False):
+    def cloud_view_depth(self, basis, fov_y_degrees=75.0, out_w=1152, out_h=648):
+        """Where along each ray of cloud_view's image the clouds of the current frame data sit: the mean, first and last distance from the
+        observer in km and the view frame's alpha, float16 [out_h, out_w, 4] at the context's step count, so that the samples are the view
+        frame's (csky_render_cloud_depth_view; the definition: include/cloudsky.h).  A torch CUDA tensor with device_buffers=True.  Independent
+        of the sky LUTs and of the blend textures; not called by update_sky()."""
+        pc = self._fill_push_constant()
+        if not self.device_buffers:
+            return self.ctx.render_cloud_depth_view(pc, basis, fov_y_degrees, out_w, out_h)
+        import torch
+        out = torch.empty((int(out_h), int(out_w), 4), dtype=torch.float16, device=torch.device("cuda", self.ctx.device_id))
+        stream, done = self._march_stream()
+        self.ctx.render_cloud_depth_view(pc, basis, fov_y_degrees, out_w, out_h, out=out, stream=stream)
+        done()
+        return out
+
+    def sky_view(self, basis, fov_y_degrees=75.0, out_w=1152, out_h=648, direct=False, aerial=False):
         """The same through a perspective camera: one EYEDIR per SCREEN pixel, the way the engine evaluates clouds.gdshader
         (csky_composite_view).  basis: 3x3, columns = the camera's right / up / back axes (Camera3D.global_transform.basis).
         direct=True: the clouds are marched for this very view (cloud_view) instead of tapped from the hemisphere frames, and composited with
-        csky_composite_view_frames; both cloud images are that one frame, so blend_amount has no effect on the clouds."""
+        csky_composite_view_frames; both cloud images are that one frame, so blend_amount has no effect on the clouds.
+        aerial=True (with direct=True only: ValueError otherwise): the view frame gets the air in front of its clouds before it is composited
+        (cloud_view(aerial=True)); for the hemisphere frames that step is aerial_clouds()."""
         def host(t):
             return t.cpu().numpy() if hasattr(t, "cpu") else t
+        if aerial and not direct:
+            raise ValueError("sky_view: aerial=True needs direct=True (the hemisphere frames take their air from aerial_clouds())")
         self.flush()
         if direct:
-            cv = host(self.cloud_view(basis, fov_y_degrees, out_w, out_h))
+            cv = host(self.cloud_view(basis, fov_y_degrees, out_w, out_h, aerial=aerial))
             sf, st = (host(t) for t in self.sky_lut.back_texture)
             return self.ctx.composite_view_frames(cv, cv, sf, st, self.frame_data.LIGHT_DIRECTION, basis, fov_y_degrees, self.blend_amount, self.sun_disk_scale)
         bf, bt = host(self.textures[self.texture_to_blend_from]), host(self.textures[self.texture_to_blend_to])

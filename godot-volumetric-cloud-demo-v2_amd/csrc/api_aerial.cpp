@@ -1,7 +1,8 @@
 // api_aerial.cpp -- the aerial-perspective volume's C ABI (csky_render_aerial_perspective / _device; aerial_core.h, aerial.hip), and
 // the same volume with a cloud shadow map inside it (csky_render_aerial_perspective_shadowed / _device, csky_aerial_shadow_rect; shafts_core.h,
 // shafts.hip), and the air in front of a cloud frame (csky_apply_cloud_aerial / _device; cloud_aerial_core.h, cloud_aerial.hip;
-// DESIGN.md §16), which reads the caller's two images besides.
+// DESIGN.md §16), which reads the caller's two images besides, and that step on a view frame or a ray frame (csky_apply_cloud_aerial_dirs / _view and
+// their _device forms; view_depth_core.h).
 // The call reads the context's transmittance table and nothing else of it: no noise, no sky LUT, no cloud frame, no slot of any ring (geometry and sun
 // travel as kernel arguments), no stream of its own.  The blocking forms work in the context's stage (host_stage.h).
 #include <cmath>
@@ -9,6 +10,7 @@
 #include "aerial_core.h"
 #include "shafts_core.h"
 #include "cloud_aerial_core.h"
+#include "view_depth_core.h"
 
 using namespace csky;
 
@@ -97,9 +99,77 @@ int cloud_aerial_launch(csky_ctx* c, const char* fn, const CloudAerialGeom& g, c
     return launched(c, fn, launch_cloud_aerial(g, c->d_trans_f, c->tw, c->th, d_cloud, d_depth, d_out, s, c->tlut));
 }
 
+// The ray forms' launch: the directions of d_dirs, or of `view` when d_dirs is NULL (read on s like the images).
+int cloud_aerial_rays_launch(csky_ctx* c, const char* fn, const CloudAerialGeom& g, const csky_view* view, const float* d_dirs, const uint2* d_cloud,
+                             const uint2* d_depth, uint2* d_out, hipStream_t s) {
+    const RaysGeom rg = rays_geom(view ? view->basis : nullptr, view ? view->fov_y_degrees : 0.0f, g.w, g.h, (uint32_t)g.w);   // as csky_render_clouds_view's
+    HIPCHK(c, hipEventRecord(c->ev_aerial, c->stream));
+    HIPCHK(c, hipStreamWaitEvent(s, c->ev_aerial, 0));
+    return launched(c, fn, launch_cloud_aerial_rays(g, rg, d_dirs, c->d_trans_f, c->tw, c->th, d_cloud, d_depth, d_out, s, c->tlut));
+}
+
+// The ray forms' checks: cloud_aerial_check, and the view's own.
+int cloud_aerial_rays_check(csky_ctx* c, const char* fn, const csky_cloud_aerial_params* ap, const csky_view* view, bool is_view, CloudAerialGeom& g) {
+    if (is_view && !view) return fail(c, CSKY_ERR_INVALID, "%s: view is NULL", fn);
+    if (!ap) return fail(c, CSKY_ERR_INVALID, "%s: params is NULL", fn);
+    if (is_view) if (const int rc = view_check(c, fn, view)) return rc;
+    return cloud_aerial_check(c, fn, ap, g);
+}
+
+// The blocking ray forms: the two images and dirs (NULL for a view) up, the cloud frame, corrected in place, down.
+int cloud_aerial_rays_host(csky_ctx* c, const char* fn, const csky_cloud_aerial_params* ap, const csky_view* view, bool is_view, const float* dirs,
+                           const uint16_t* cloud, const uint16_t* depth, uint16_t* out) {
+    if (!cloud || !depth || !out) return fail(c, CSKY_ERR_INVALID, "%s: cloud, depth or out is NULL", fn);
+    if (!is_view && !dirs) return fail(c, CSKY_ERR_INVALID, "%s: dirs_xyz is NULL", fn);
+    CloudAerialGeom g;
+    int rc; if ((rc = cloud_aerial_rays_check(c, fn, ap, view, is_view, g)) || (rc = bind(c))) return rc;
+    const size_t n = (size_t)g.w * g.h, nb = n * 8, db = is_view ? 0 : n * 3 * sizeof(float);
+    HostCall hc = host_call(c, fn, {nb, nb, db});
+    hc.up(0, cloud, nb);
+    hc.up(1, depth, nb);
+    hc.up(2, dirs, db);
+    hc.step([&] { return cloud_aerial_rays_launch(c, fn, g, view, is_view ? nullptr : hc.at<float>(2), hc.at<uint2>(0), hc.at<uint2>(1), hc.at<uint2>(0), c->stream); });
+    hc.down(out, 0, nb);
+    return hc.finish();
+}
+
 }  // namespace
 
 extern "C" {
+
+int csky_apply_cloud_aerial_dirs(csky_ctx* c, const csky_cloud_aerial_params* ap, const float* dirs, const uint16_t* cloud, const uint16_t* depth, uint16_t* out) {
+    const char* fn = "csky_apply_cloud_aerial_dirs";
+    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "%s: ctx is NULL", fn);
+    return cloud_aerial_rays_host(c, fn, ap, nullptr, false, dirs, cloud, depth, out);
+}
+
+int csky_apply_cloud_aerial_view(csky_ctx* c, const csky_cloud_aerial_params* ap, const csky_view* view, const uint16_t* cloud, const uint16_t* depth, uint16_t* out) {
+    const char* fn = "csky_apply_cloud_aerial_view";
+    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "%s: ctx is NULL", fn);
+    return cloud_aerial_rays_host(c, fn, ap, view, true, nullptr, cloud, depth, out);
+}
+
+int csky_apply_cloud_aerial_dirs_device(csky_ctx* c, const csky_cloud_aerial_params* ap, const void* d_dirs, const void* d_cloud, const void* d_depth, void* d_out,
+                                        void* hip_stream) {
+    const char* fn = "csky_apply_cloud_aerial_dirs_device";
+    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "%s: ctx is NULL", fn);
+    if (!d_dirs || !d_cloud || !d_depth || !d_out) return fail(c, CSKY_ERR_INVALID, "%s: d_dirs_xyz, d_cloud, d_depth or d_out is NULL", fn);
+    CloudAerialGeom g;
+    int rc; if ((rc = cloud_aerial_rays_check(c, fn, ap, nullptr, false, g)) || (rc = bind(c))) return rc;
+    return cloud_aerial_rays_launch(c, fn, g, nullptr, static_cast<const float*>(d_dirs), static_cast<const uint2*>(d_cloud), static_cast<const uint2*>(d_depth),
+                                    static_cast<uint2*>(d_out), stream_of(c, hip_stream));
+}
+
+int csky_apply_cloud_aerial_view_device(csky_ctx* c, const csky_cloud_aerial_params* ap, const csky_view* view, const void* d_cloud, const void* d_depth, void* d_out,
+                                        void* hip_stream) {
+    const char* fn = "csky_apply_cloud_aerial_view_device";
+    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "%s: ctx is NULL", fn);
+    if (!d_cloud || !d_depth || !d_out) return fail(c, CSKY_ERR_INVALID, "%s: d_cloud, d_depth or d_out is NULL", fn);
+    CloudAerialGeom g;
+    int rc; if ((rc = cloud_aerial_rays_check(c, fn, ap, view, true, g)) || (rc = bind(c))) return rc;
+    return cloud_aerial_rays_launch(c, fn, g, view, nullptr, static_cast<const uint2*>(d_cloud), static_cast<const uint2*>(d_depth), static_cast<uint2*>(d_out),
+                                    stream_of(c, hip_stream));
+}
 
 int csky_apply_cloud_aerial_device(csky_ctx* c, const csky_cloud_aerial_params* ap, const void* d_cloud, const void* d_depth, void* d_out, void* hip_stream) {
     const char* fn = "csky_apply_cloud_aerial_device";

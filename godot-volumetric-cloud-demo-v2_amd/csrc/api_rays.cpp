@@ -51,16 +51,7 @@ int rays_launch(csky_ctx* c, const char* fn, const csky_cloud_params* p, const c
     // Fixed values keep whatever the caller left there (NaNs included) out of every conversion.
     cp.texture_size[0] = cp.texture_size[1] = 1.0f; cp.update_position[0] = cp.update_position[1] = 0.0f;
     int rc; if ((rc = rays_setup(c, cp, s))) return rc;
-    RaysGeom g;
-    g.w = w; g.h = h; g.pitch_px = (uint32_t)(pitch_bytes / 8);
-    for (int k = 0; k < 9; k++) g.cam[k] = (k % 4 == 0) ? 1.0f : 0.0f;
-    g.tan_half_fov_y = 1.0f; g.aspect = 1.0f;
-    if (view) {
-        CompositeArgs a{};
-        composite_view_args(a, view->basis, view->fov_y_degrees, w, h);   // the projection of csky_composite_view
-        for (int k = 0; k < 9; k++) g.cam[k] = a.cam[k];
-        g.tan_half_fov_y = a.tan_half_fov_y; g.aspect = a.aspect;
-    }
+    const RaysGeom g = rays_geom(view ? view->basis : nullptr, view ? view->fov_y_degrees : 0.0f, w, h, (uint32_t)(pitch_bytes / 8));
     TexSet32 t32;
     const Event* kt = nullptr;                                  // timing pair of this launch (csky_set_kernel_timing), as around a cloud frame's
     if (c->kt.on && (rc = c->kt.next_pair(c, kt))) return rc;

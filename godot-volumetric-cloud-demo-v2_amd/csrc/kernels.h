@@ -98,6 +98,10 @@ hipError_t launch_shafts(const AerialGeom& g, const ShaftsMap& m, const float4* 
 // travel as kernel arguments.  t32: march on the exact fp32-coefficient cells.
 struct DepthConsts;
 hipError_t launch_cloud_depth(const TexSet& t, const TexSet32* t32, const FrameConsts& fc, const DepthConsts& dc, uint2* d_out, hipStream_t s);
+// the depth frame of a ray frame (view_depth_core.h): the same texels for the directions of d_dirs ([h][w][3] floats, tightly packed), or for the
+// view of g (g.w x g.h = dc.w x dc.h) when d_dirs is null.  All three blocks travel as kernel arguments.
+hipError_t launch_cloud_depth_rays(const TexSet& t, const TexSet32* t32, const FrameConsts& fc, const DepthConsts& dc, const RaysGeom& g, const float* d_dirs,
+                                   uint2* d_out, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------ cloud_aerial.hip
 // the air in front of a cloud frame (cloud_aerial_core.h): g.w x g.h RGBA16F texels of d_cloud, placed by d_depth, into d_out, all tightly packed;
@@ -105,6 +109,10 @@ hipError_t launch_cloud_depth(const TexSet& t, const TexSet32* t32, const FrameC
 struct CloudAerialGeom;
 hipError_t launch_cloud_aerial(const CloudAerialGeom& g, const float4* d_trans, int tw, int th, const uint2* d_cloud, const uint2* d_depth, uint2* d_out,
                                hipStream_t s, int tlut = 0);
+// the same step on a ray frame (view_depth_core.h): every pixel's direction from d_dirs ([h][w][3] floats, tightly packed), or from the view of rg
+// (rg.w x rg.h = g.w x g.h) when d_dirs is null
+hipError_t launch_cloud_aerial_rays(const CloudAerialGeom& g, const RaysGeom& rg, const float* d_dirs, const float4* d_trans, int tw, int th, const uint2* d_cloud,
+                                    const uint2* d_depth, uint2* d_out, hipStream_t s, int tlut = 0);
 
 // ------------------------------------------------------------------------------------------------ bc7enc.hip
 // BC7 (BPTC) blocks of n_img images of w x h RGBA8 texels (what compress/mode=2 of the *.import files asks the importer for)

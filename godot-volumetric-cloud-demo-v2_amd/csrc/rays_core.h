@@ -35,6 +35,22 @@ CSKY_HD void composite_view_args(CompositeArgs& A, const float basis[9], float f
     A.out_w = w; A.out_h = h;
 }
 
+// The geometry block of a w x h rays launch: the projection above for the view forms (basis: csky_view.basis), an identity camera nobody reads for
+// the dirs forms (basis NULL).  The one place that fills it: the direct march, the depth frame and the aerial step of a ray frame all call this.
+CSKY_HD RaysGeom rays_geom(const float* basis, float fov_y_degrees, int w, int h, uint32_t pitch_px) {
+    RaysGeom g;
+    g.w = w; g.h = h; g.pitch_px = pitch_px;
+    for (int k = 0; k < 9; k++) g.cam[k] = (k % 4 == 0) ? 1.0f : 0.0f;
+    g.tan_half_fov_y = 1.0f; g.aspect = 1.0f;
+    if (basis) {
+        CompositeArgs a{};
+        composite_view_args(a, basis, fov_y_degrees, w, h);   // the projection of csky_composite_view
+        for (int k = 0; k < 9; k++) g.cam[k] = a.cam[k];
+        g.tan_half_fov_y = a.tan_half_fov_y; g.aspect = a.aspect;
+    }
+    return g;
+}
+
 // EYEDIR of pixel (i, j) of the view g: composite_eyedir, which reads these fields of its argument block and no other.  (view_mode is 1 in a way the
 // compiler sees: the panorama and cube-face branches fold away.)
 CSKY_HD void rays_view_dir(const RaysGeom& g, int i, int j, float& ex, float& ey, float& ez) {

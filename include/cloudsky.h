@@ -560,6 +560,58 @@ int csky_render_clouds_view_device(csky_ctx* ctx, const csky_cloud_params* p, co
 int csky_composite_view_frames(csky_ctx* ctx, const csky_composite_params* p, const csky_view* view, const uint16_t* cloud_from,
                                const uint16_t* cloud_to, const uint16_t* sky_from, const uint16_t* sky_to, uint16_t* out_rgba16f);
 
+/* ---- depth and aerial perspective for view frames and ray frames ------------------- */
+/* csky_render_cloud_depth and csky_apply_cloud_aerial above serve the hemisphere frame: both take every pixel's direction from the hemi-octahedral
+ * grid.  These calls are the same two steps for the image of a direct march (csky_render_clouds_dirs / _view): the direction of pixel (i, j) of a
+ * W x H image is the caller's.
+ *   e       exactly the direct march's.  dirs forms: the three floats of dirs[j * W + i], used as given.  view forms: the compositor's EYEDIR of
+ *           screen pixel (i, j) for view->basis, Godot's vertical field of view and aspect = W / H, as csky_render_clouds_view computes it.
+ *   accept  e.y > 0  and  0.99 <= (e.x*e.x + e.y*e.y) + e.z*e.z <= 1.01   (fp32, no contraction; NaN fails every test), the direct march's rule.
+ * Depth (csky_render_cloud_depth_dirs / _view), N = steps:
+ *   not accepted: the texel is (0, 0, 0, 0) and the ray takes no sample.
+ *   ray     the direct march's ray of e with N for the primary step count: t0, t1 = intersectSphere(camPos, e, Rb / Rt), start, end,
+ *           raystep = e * |end - start| / N, ss = |raystep|, p = start.
+ *   t0    = intersectSphere(camPos, e, Rb), the float the ray set-up computes.
+ *   texel   the definition of csky_render_cloud_depth from "T = 1, alpha = 0, sw = 0, ..." on, unchanged: the same samples, s = t0 + (float)(k + 1) * ss,
+ *           mean / front / back in km and the frame's alpha.
+ *   t0 is the parameter of the shell entry along e AS GIVEN and ss the length of a step in metres.  For a unit direction t0 is metres and so is
+ *   s = t0 + (k + 1) * ss, exactly as for the hemisphere frame.  For a direction inside the band that is not a unit vector t0 is metres divided by
+ *   |e|, so s is not metres exactly (it is off by up to 0.5 % in its t0 part); the samples themselves are where the direct march takes them.
+ *   Pass unit directions when the distances matter.
+ *   steps is 0..1024, 0 = the context's primary step count (the direct march's own N: pass 0 and the samples are the view frame's).  Of the
+ *   push-constant block the fields csky_render_cloud_depth reads are read (cloud_pos, detailed_pos, weather_pos, time, density, cloud_coverage)
+ *   and no other.  Needs the noise (CSKY_ERR_STATE without it) and NO LUT.  csky_set_height_window and csky_set_exact_cells act as on the
+ *   hemisphere depth frame.  Takes no slot of any ring, shares nothing with the direct march's calls and leaves nothing behind on the device.
+ * Aerial (csky_apply_cloud_aerial_dirs / _view), c the cloud texel and z the depth texel of pixel (i, j), both images W x H = params->width x height,
+ * RGBA16F, tightly packed:
+ *   if c.a (the half) == 0, or !(z.r > 0), or e is not accepted:   out = c, byte for byte
+ *   otherwise the column and the composite of csky_apply_cloud_aerial with e in place of the grid's direction.  e is used as given (NOT normalised
+ *   here, like the sun): a direction inside the band that is not a unit vector walks far_km * |e| kilometres of air.
+ *   out may be the cloud image (not the depth image, not dirs).  Needs the transmittance table (CSKY_ERR_STATE without it, and after a change of
+ *   its mapping until it is rendered again) and nothing else; respects the mapping; changes no state.
+ * Fed the directions of the hemisphere grid, the dirs forms return the bytes of csky_render_cloud_depth and of csky_apply_cloud_aerial.
+ * Ranges and errors: those of csky_render_cloud_depth (W, H in 1..8192, steps in 0..1024, finite fields read, the pitch a multiple of 8 and
+ * >= 8 W) and of csky_apply_cloud_aerial (W, H in 1..8192, n in 1..64 or 0 = 16, a finite sun); for the view forms a finite basis and a field of
+ * view in (0, 180); CSKY_ERR_INVALID otherwise, and for a NULL pointer (dirs and view included). */
+/* Blocking host forms: dirs_xyz is h * w * 3 floats, images h * w * 4 halfs. */
+int csky_render_cloud_depth_dirs(csky_ctx* ctx, const csky_cloud_params* p, int w, int h, int steps, const float* dirs_xyz, uint16_t* out_rgba16f);
+int csky_render_cloud_depth_view(csky_ctx* ctx, const csky_cloud_params* p, const csky_view* view, int w, int h, int steps, uint16_t* out_rgba16f);
+int csky_apply_cloud_aerial_dirs(csky_ctx* ctx, const csky_cloud_aerial_params* params, const float* dirs_xyz, const uint16_t* cloud_rgba16f,
+                                 const uint16_t* depth_rgba16f, uint16_t* out_rgba16f);
+int csky_apply_cloud_aerial_view(csky_ctx* ctx, const csky_cloud_aerial_params* params, const csky_view* view, const uint16_t* cloud_rgba16f,
+                                 const uint16_t* depth_rgba16f, uint16_t* out_rgba16f);
+/* Device forms: asynchronous on hip_stream (the context's own stream if NULL).  d_dirs_xyz (tightly packed) and the images are read on hip_stream.
+ * The depth forms write rows of row_pitch_bytes, the w x h texels and nothing else; the aerial forms are ordered behind what the context's stream
+ * has done to the transmittance table and write the width x height texels of d_out (tightly packed) and nothing else. */
+int csky_render_cloud_depth_dirs_device(csky_ctx* ctx, const csky_cloud_params* p, int w, int h, int steps, const void* d_dirs_xyz, void* d_out_rgba16f,
+                                        size_t row_pitch_bytes, void* hip_stream);
+int csky_render_cloud_depth_view_device(csky_ctx* ctx, const csky_cloud_params* p, const csky_view* view, int w, int h, int steps, void* d_out_rgba16f,
+                                        size_t row_pitch_bytes, void* hip_stream);
+int csky_apply_cloud_aerial_dirs_device(csky_ctx* ctx, const csky_cloud_aerial_params* params, const void* d_dirs_xyz, const void* d_cloud_rgba16f,
+                                        const void* d_depth_rgba16f, void* d_out_rgba16f, void* hip_stream);
+int csky_apply_cloud_aerial_view_device(csky_ctx* ctx, const csky_cloud_aerial_params* params, const csky_view* view, const void* d_cloud_rgba16f,
+                                        const void* d_depth_rgba16f, void* d_out_rgba16f, void* hip_stream);
+
 /* ---- frames in flight ---------------------------------------------------------------------------- */
 /* Policy hint for the automatic segment / schedule choice: n = 2..8: the caller keeps n frames in flight by rotating n streams
  * between consecutive csky_render_*_device calls (always safe: per-frame state lives in eight-deep rings ordered by events); the
