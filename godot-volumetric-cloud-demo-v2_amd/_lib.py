@@ -36,7 +36,7 @@ def aerial_shadow_rect(sun, far_km=32.0):
     """csky_aerial_shadow_rect (host only, no GPU): the rectangle (center, extent), two (x, z) pairs in metres, that a cloud shadow map must cover
     for an aerial-perspective volume of reach far_km under the sun `sun`.  Raises CloudSkyError (CSKY_ERR_INVALID) when the sun is not above the
     horizon, or so low that the rectangle leaves the range of csky_shadow_params."""
-    p = AerialParams(0, 0, 0, 0, float(far_km), 0.0, (C.c_float * 3)(*[float(x) for x in sun]))
+    p = _aerial_params(sun, 0, 0, 0, far_km, 0, 0.0)
     center, extent = (C.c_float * 2)(), (C.c_float * 2)()
     rc = lib().csky_aerial_shadow_rect(C.byref(p), center, extent)
     if rc != OK:
@@ -350,6 +350,96 @@ def cloud_params(values):
     return p
 
 
+# ---- the structs of include/cloudsky.h from the methods' arguments: each is built here and nowhere else
+def _sun3(v):
+    return (C.c_float * 3)(*[float(x) for x in v])   # used as given
+
+
+def _frame_size(p, tile_w, tile_h):
+    """(w, h) of a cloud frame: the push constants' texture_size where the caller names none."""
+    return int(p.f[0]) if tile_w is None else int(tile_w), int(p.f[1]) if tile_h is None else int(tile_h)
+
+
+def _sky_params(sun_dir, w, h):
+    p = SkyParams()
+    p.f[0], p.f[1] = float(w), float(h)
+    p.f[4], p.f[5], p.f[6] = [float(x) for x in sun_dir]
+    return p
+
+
+def _view(basis, fov_y_degrees):
+    return View((C.c_float * 9)(*[float(x) for x in np.asarray(basis, np.float32).T.reshape(-1)]), float(fov_y_degrees))   # column-major basis
+
+
+def _composite_params(out_w, out_h, cloud_wh, sky_wh, light_dir, blend_amount, sun_disk_scale):
+    return CompositeParams(int(out_w), int(out_h), int(cloud_wh[0]), int(cloud_wh[1]), int(sky_wh[0]), int(sky_wh[1]), float(blend_amount), float(sun_disk_scale),
+                           _sun3(light_dir[k] for k in range(3)))   # the first three of a longer vector, as these methods always took them
+
+
+def _shadow_params(w, h, center, extent, steps):
+    return ShadowParams(int(w), int(h), (C.c_float * 2)(float(center[0]), float(center[1])), (C.c_float * 2)(float(extent[0]), float(extent[1])), int(steps))
+
+
+def _aerial_params(sun, width, height, depth, far_km, steps_per_slice, aspect):
+    return AerialParams(int(width), int(height), int(depth), int(steps_per_slice), float(far_km), float(aspect), _sun3(sun))
+
+
+def _aerial_args(sun, width, height, depth, far_km, steps_per_slice, view, aspect):
+    """(the volume's shape, its csky_aerial_params, its csky_view by reference or None for the panorama) of the two aerial-perspective methods."""
+    p = _aerial_params(sun, width, height, depth, far_km, steps_per_slice, aspect)
+    return (p.depth, p.height, p.width, 4), p, None if view is None else C.byref(_view(view[0], view[1]))
+
+
+# ---- image arguments.  Every refusal is a ValueError that names the method, raised before any library call.
+def _host_frames(cloud_from, cloud_to, sky_from, sky_to):
+    """The compositor's four float16 [h, w, 4] host inputs as the library reads them, and (w, h) of the cloud frames and of the sky LUTs."""
+    a = [np.ascontiguousarray(x).view(np.uint16) for x in (cloud_from, cloud_to, sky_from, sky_to)]
+    return a, (a[0].shape[1], a[0].shape[0]), (a[2].shape[1], a[2].shape[0])
+
+
+def _host_image(name, shape, out):
+    """The host image a call writes: `out` if it can be written in place, a new one for None."""
+    if out is None:
+        return np.zeros(shape, np.float16)
+    if out.shape != shape or out.dtype != np.float16 or not out.flags.c_contiguous:
+        raise ValueError("%s: out must be a contiguous float16 %s array" % (name, shape))
+    return out
+
+
+def _device_image(name, what, shape, t, pitched=False):
+    """The row pitch in bytes of the device image `t`: a torch tensor of `shape` and 2-byte elements whose rows t[j], of whatever rank, are each
+    contiguous (a dimension of one element has no stride to test).  The pitch is stride(0)'s, and a row's own size for a single row, whatever its
+    stride(0) says; unless `pitched`, the call has no pitch argument and the rows must follow each other: a contiguous tensor."""
+    ok = hasattr(t, "data_ptr") and tuple(t.shape) == tuple(shape) and t.element_size() == 2
+    if ok:
+        row = 1
+        for n, s in zip(reversed(shape[1:]), reversed(t.stride()[1:])):
+            ok, row = ok and (n == 1 or s == row), row * n
+        pitch = t.stride(0) * 2 if shape[0] > 1 else row * 2
+        ok = ok and (pitched or pitch == row * 2)
+    if not ok:
+        raise ValueError("%s: %s must be a %s tensor of 2-byte elements, %s" % (name, what, tuple(shape), "its rows contiguous" if pitched else "contiguous"))
+    return pitch
+
+
+def _dirs_size(name, dirs):
+    if len(dirs.shape) != 3 or int(dirs.shape[2]) != 3:
+        raise ValueError("%s: dirs must be a [h, w, 3] float32 array (or torch tensor on the GPU)" % name)
+    return int(dirs.shape[1]), int(dirs.shape[0])
+
+
+def _dirs_arg(name, dirs, device):
+    """The pointer argument for a direction image: a device call takes a contiguous float32 tensor as it is, a host call an array, converted if need be."""
+    if device:
+        import torch
+        if not hasattr(dirs, "data_ptr") or dirs.dtype != torch.float32 or not dirs.is_contiguous():
+            raise ValueError("%s: with a device frame, dirs must be a contiguous float32 tensor" % name)
+        return C.c_void_p(int(dirs.data_ptr()))
+    if hasattr(dirs, "data_ptr"):
+        raise ValueError("%s: with host frames, dirs must be a numpy array" % name)
+    return _ptr(np.ascontiguousarray(dirs, np.float32))   # (the pointer object keeps the array alive)
+
+
 class Context:
     """One csky_ctx = one GPU.  Thin, explicit wrapper; raises CloudSkyError on any non-zero return."""
 
@@ -471,34 +561,27 @@ class Context:
         return out.view(np.float16)
 
     def render_sky_lut(self, sun_dir, w=200, h=100, readback=True):
-        p = SkyParams()
-        p.f[0], p.f[1] = float(w), float(h)
-        p.f[4], p.f[5], p.f[6] = [float(x) for x in sun_dir]
+        p = _sky_params(sun_dir, w, h)
         out = np.zeros((h, w, 4), np.uint16) if readback else None
         self._chk(self._L.csky_render_sky_lut(self._h, C.byref(p), _ptr(out) if readback else None))
         return out.view(np.float16) if readback else None
 
     def render_clouds(self, params, tile_w=None, tile_h=None):
         p = cloud_params(params)
-        w = int(p.f[0]) if tile_w is None else int(tile_w)
-        h = int(p.f[1]) if tile_h is None else int(tile_h)
+        w, h = _frame_size(p, tile_w, tile_h)
         out = np.zeros((h, w, 4), np.uint16)
         self._chk(self._L.csky_render_clouds(self._h, C.byref(p), w, h, _ptr(out), w * 8))
         return out.view(np.float16)
 
     # ---- device-buffer forms
     def render_sky_lut_device(self, sun_dir, w=200, h=100, stream=None):
-        p = SkyParams()
-        p.f[0], p.f[1] = float(w), float(h)
-        p.f[4], p.f[5], p.f[6] = [float(x) for x in sun_dir]
+        p = _sky_params(sun_dir, w, h)
         self._chk(self._L.csky_render_sky_lut_device(self._h, C.byref(p), C.c_void_p(stream or 0)))
 
     def render_sky_lut_rows_device(self, sun_dir, first_row, row_stride, d_rows_out, capacity_bytes, w=200, h=100, stream=None):
         """One rank's rows first_row::row_stride of the sky LUT (N processes splitting a frame), compact RGBA16F into the caller's device buffer
         on `stream`; the context keeps no LUT, render_clouds_device renders the texels its frame set-up needs itself."""
-        p = SkyParams()
-        p.f[0], p.f[1] = float(w), float(h)
-        p.f[4], p.f[5], p.f[6] = [float(x) for x in sun_dir]
+        p = _sky_params(sun_dir, w, h)
         self._chk(self._L.csky_render_sky_lut_rows_device(self._h, C.byref(p), int(first_row), int(row_stride), C.c_void_p(int(d_rows_out)),
                                                           C.c_size_t(int(capacity_bytes)), C.c_void_p(stream or 0)))
 
@@ -523,20 +606,8 @@ class Context:
         [height, width], row j = z, column i = x.  Host path (out None or a numpy float16 array): blocks, returns numpy.  Device path (out a
         2-D torch tensor of 2-byte elements on this context's GPU, unit column stride; its row stride is the pitch): asynchronous on `stream`,
         returns the tensor.  Needs the noise and no LUT."""
-        p = cloud_params(params)
-        sp = ShadowParams(int(width), int(height), (C.c_float * 2)(float(center[0]), float(center[1])), (C.c_float * 2)(float(extent[0]), float(extent[1])), int(steps))
-        if out is not None and hasattr(out, "data_ptr"):
-            if out.dim() != 2 or out.element_size() != 2 or tuple(out.shape) != (int(height), int(width)) or (int(width) > 1 and out.stride(1) != 1):
-                raise ValueError("render_cloud_shadow: out must be a [%d, %d] tensor of 2-byte elements with unit column stride" % (int(height), int(width)))
-            pitch = out.stride(0) * 2 if int(height) > 1 else int(width) * 2
-            self._chk(self._L.csky_render_cloud_shadow_device(self._h, C.byref(p), C.byref(sp), C.c_void_p(int(out.data_ptr())), C.c_size_t(int(pitch)), C.c_void_p(stream or 0)))
-            return out
-        if out is None:
-            out = np.zeros((int(height), int(width)), np.float16)
-        if out.shape != (int(height), int(width)) or out.dtype != np.float16 or not out.flags.c_contiguous:
-            raise ValueError("render_cloud_shadow: out must be a contiguous float16 [%d, %d] array" % (int(height), int(width)))
-        self._chk(self._L.csky_render_cloud_shadow(self._h, C.byref(p), C.byref(sp), _ptr(out)))
-        return out
+        sp = _shadow_params(width, height, center, extent, steps)
+        return self._render_image("render_cloud_shadow", params, (C.byref(sp),), (sp.height, sp.width), out, stream)
 
     def render_aerial_perspective(self, sun, width=32, height=32, depth=32, far_km=32.0, steps_per_slice=2, view=None, aspect=0.0, out=None, stream=None):
         """The aerial-perspective volume (csky_render_aerial_perspective*, definition: include/cloudsky.h): in-scattered light (rgb, the sky LUT's
@@ -545,20 +616,12 @@ class Context:
         camera's right / up / back axes as columns, fov_y_degrees) with `aspect` the screen's width / height (0 = width / height).  Host path (out
         None or a numpy float16 array): blocks, returns numpy.  Device path (out a contiguous torch tensor of 2-byte elements on this context's
         GPU): asynchronous on `stream`, written in place, returns the tensor.  Needs the transmittance LUT and nothing else."""
-        shape = (int(depth), int(height), int(width), 4)
-        p = AerialParams(shape[2], shape[1], shape[0], int(steps_per_slice), float(far_km), float(aspect), (C.c_float * 3)(*[float(x) for x in sun]))
-        v = None
-        if view is not None:
-            v = C.byref(View((C.c_float * 9)(*[float(x) for x in np.asarray(view[0], np.float32).T.reshape(-1)]), float(view[1])))   # column-major basis
+        shape, p, v = _aerial_args(sun, width, height, depth, far_km, steps_per_slice, view, aspect)
         if out is not None and hasattr(out, "data_ptr"):
-            if tuple(out.shape) != shape or out.element_size() != 2 or not out.is_contiguous():
-                raise ValueError("render_aerial_perspective: out must be a contiguous %s tensor of 2-byte elements" % (shape,))
+            _device_image("render_aerial_perspective", "out", shape, out)
             self._chk(self._L.csky_render_aerial_perspective_device(self._h, C.byref(p), v, C.c_void_p(int(out.data_ptr())), C.c_void_p(stream or 0)))
             return out
-        if out is None:
-            out = np.zeros(shape, np.float16)
-        if out.shape != shape or out.dtype != np.float16 or not out.flags.c_contiguous:
-            raise ValueError("render_aerial_perspective: out must be a contiguous float16 %s array" % (shape,))
+        out = _host_image("render_aerial_perspective", shape, out)
         self._chk(self._L.csky_render_aerial_perspective(self._h, C.byref(p), v, _ptr(out)))
         return out
 
@@ -570,34 +633,28 @@ class Context:
         numpy float16 array): blocks, returns numpy.  Device path (shadow a 2-D torch tensor of 2-byte elements on this context's GPU with unit
         column stride, whose row stride gives the pitch; out a contiguous torch tensor of 2-byte elements or None): asynchronous on `stream`, on
         which the map is read; returns the tensor.  Needs the transmittance LUT and nothing else."""
-        shape = (int(depth), int(height), int(width), 4)
-        p = AerialParams(shape[2], shape[1], shape[0], int(steps_per_slice), float(far_km), float(aspect), (C.c_float * 3)(*[float(x) for x in sun]))
-        v = None
-        if view is not None:
-            v = C.byref(View((C.c_float * 9)(*[float(x) for x in np.asarray(view[0], np.float32).T.reshape(-1)]), float(view[1])))   # column-major basis
+        name = "render_aerial_perspective_shadowed"
+        shape, p, v = _aerial_args(sun, width, height, depth, far_km, steps_per_slice, view, aspect)
         if hasattr(shadow, "data_ptr"):
-            if shadow.dim() != 2 or shadow.element_size() != 2 or (shadow.shape[1] > 1 and shadow.stride(1) != 1):
-                raise ValueError("render_aerial_perspective_shadowed: shadow must be a 2-D tensor of 2-byte elements with unit column stride")
-            mh, mw = int(shadow.shape[0]), int(shadow.shape[1])
-            pitch = shadow.stride(0) * 2 if mh > 1 else mw * 2
-            sp = ShadowParams(mw, mh, (C.c_float * 2)(float(center[0]), float(center[1])), (C.c_float * 2)(float(extent[0]), float(extent[1])), 0)
+            if shadow.dim() != 2:
+                raise ValueError("%s: shadow must be a 2-D tensor of 2-byte elements with unit column stride" % name)
+            pitch = _device_image(name, "shadow", tuple(shadow.shape), shadow, pitched=True)
+            sp = _shadow_params(shadow.shape[1], shadow.shape[0], center, extent, 0)
             if out is None:
                 import torch
                 out = torch.empty(shape, dtype=torch.float16, device=shadow.device)
-            if not hasattr(out, "data_ptr") or tuple(out.shape) != shape or out.element_size() != 2 or not out.is_contiguous():
-                raise ValueError("render_aerial_perspective_shadowed: with a device map, out must be a contiguous %s tensor of 2-byte elements" % (shape,))
-            self._chk(self._L.csky_render_aerial_perspective_shadowed_device(self._h, C.byref(p), v, C.byref(sp), C.c_void_p(int(shadow.data_ptr())), C.c_size_t(int(pitch)),
+            _device_image(name, "out", shape, out)
+            self._chk(self._L.csky_render_aerial_perspective_shadowed_device(self._h, C.byref(p), v, C.byref(sp), C.c_void_p(int(shadow.data_ptr())), C.c_size_t(pitch),
                                                                              C.c_void_p(int(out.data_ptr())), C.c_void_p(stream or 0)))
             return out
         shadow = np.asarray(shadow)
         if shadow.ndim != 2 or shadow.dtype != np.float16:
-            raise ValueError("render_aerial_perspective_shadowed: shadow must be a float16 [h, w] array (or a 2-D torch tensor on the GPU)")
+            raise ValueError("%s: shadow must be a float16 [h, w] array (or a 2-D torch tensor on the GPU)" % name)
         shadow = np.ascontiguousarray(shadow)
-        sp = ShadowParams(int(shadow.shape[1]), int(shadow.shape[0]), (C.c_float * 2)(float(center[0]), float(center[1])), (C.c_float * 2)(float(extent[0]), float(extent[1])), 0)
-        if out is None:
-            out = np.zeros(shape, np.float16)
-        if not isinstance(out, np.ndarray) or out.shape != shape or out.dtype != np.float16 or not out.flags.c_contiguous:
-            raise ValueError("render_aerial_perspective_shadowed: with a host map, out must be a contiguous float16 %s array" % (shape,))
+        sp = _shadow_params(shadow.shape[1], shadow.shape[0], center, extent, 0)
+        if out is not None and not isinstance(out, np.ndarray):   # this method alone refuses what is no array at all (the others fail on its missing attributes)
+            raise ValueError("%s: with a host map, out must be a numpy array" % name)
+        out = _host_image(name, shape, out)
         self._chk(self._L.csky_render_aerial_perspective_shadowed(self._h, C.byref(p), v, C.byref(sp), _ptr(shadow), _ptr(out)))
         return out
 
@@ -607,21 +664,8 @@ class Context:
         [height, width, 4].  steps 0 = the context's primary step count.  Host path (out None or a numpy float16 array): blocks, returns numpy.
         Device path (out a [height, width, 4] torch tensor of 2-byte elements on this context's GPU whose texels are contiguous; its row stride
         is the pitch): asynchronous on `stream`, written in place, returns the tensor.  Needs the noise and no LUT."""
-        p = cloud_params(params)
-        shape = (int(height), int(width), 4)
-        dp = DepthParams(shape[1], shape[0], int(steps))
-        if out is not None and hasattr(out, "data_ptr"):
-            if out.dim() != 3 or out.element_size() != 2 or tuple(out.shape) != shape or out.stride(2) != 1 or (shape[1] > 1 and out.stride(1) != 4):
-                raise ValueError("render_cloud_depth: out must be a %s tensor of 2-byte elements with contiguous texels" % (shape,))
-            pitch = out.stride(0) * 2 if shape[0] > 1 else shape[1] * 8
-            self._chk(self._L.csky_render_cloud_depth_device(self._h, C.byref(p), C.byref(dp), C.c_void_p(int(out.data_ptr())), C.c_size_t(int(pitch)), C.c_void_p(stream or 0)))
-            return out
-        if out is None:
-            out = np.zeros(shape, np.float16)
-        if out.shape != shape or out.dtype != np.float16 or not out.flags.c_contiguous:
-            raise ValueError("render_cloud_depth: out must be a contiguous float16 %s array" % (shape,))
-        self._chk(self._L.csky_render_cloud_depth(self._h, C.byref(p), C.byref(dp), _ptr(out)))
-        return out
+        dp = DepthParams(int(width), int(height), int(steps))
+        return self._render_image("render_cloud_depth", params, (C.byref(dp),), (dp.height, dp.width, 4), out, stream)
 
     def apply_cloud_aerial(self, sun, cloud, depth, steps=16, out=None, stream=None):
         """The air in front of a cloud frame (csky_apply_cloud_aerial*, definition: include/cloudsky.h): `cloud` a hemisphere frame and `depth`
@@ -629,41 +673,26 @@ class Context:
         over each pixel's mean cloud distance under the sun `sun` (used as given), its alpha unchanged.  Host path (numpy arrays): blocks,
         returns numpy.  Device path (contiguous torch tensors of 2-byte elements on this context's GPU): asynchronous on `stream`, returns
         `out`, a new tensor unless given; out may be `cloud`.  Needs the transmittance LUT and nothing else."""
-        shape = tuple(int(x) for x in cloud.shape)
-        if len(shape) != 3 or shape[2] != 4 or tuple(int(x) for x in depth.shape) != shape:
-            raise ValueError("apply_cloud_aerial: cloud and depth must be [h, w, 4] images of one size")
-        p = CloudAerialParams(shape[1], shape[0], int(steps), (C.c_float * 3)(*[float(x) for x in sun]))
-        if hasattr(cloud, "data_ptr"):
+        return self._apply_rays("apply_cloud_aerial", (), sun, cloud, depth, steps, out, stream)
+
+    def _render_image(self, name, params, mid, shape, out, stream, dirs=None):
+        """The one path of every method that renders an image of `shape` from a push-constant block: csky_<name>(ctx, params, *mid[, dirs], out) for a host
+        image (None: a new one), csky_<name>_device(ctx, params, *mid[, dirs], out, pitch, stream) for a tensor, whose row stride is the pitch.  With `dirs`
+        ([h, w, 3]) the directions decide which of the two it is: `out` must be of their kind, and a missing device `out` is made next to them."""
+        p = cloud_params(params)
+        device = hasattr(out if dirs is None else dirs, "data_ptr")
+        if dirs is not None:
+            mid += (_dirs_arg(name, dirs, device),)
+        if device:
             if out is None:
                 import torch
-                out = torch.empty(shape, dtype=torch.float16, device=cloud.device)
-            for t in (cloud, depth, out):
-                if not hasattr(t, "data_ptr") or tuple(t.shape) != shape or t.element_size() != 2 or not t.is_contiguous():
-                    raise ValueError("apply_cloud_aerial: with a device frame, cloud, depth and out must be contiguous %s tensors of 2-byte elements" % (shape,))
-            self._chk(self._L.csky_apply_cloud_aerial_device(self._h, C.byref(p), C.c_void_p(int(cloud.data_ptr())), C.c_void_p(int(depth.data_ptr())),
-                                                             C.c_void_p(int(out.data_ptr())), C.c_void_p(stream or 0)))
-            return out
-        cloud, depth = np.ascontiguousarray(cloud), np.ascontiguousarray(depth)
-        if cloud.dtype != np.float16 or depth.dtype != np.float16:
-            raise ValueError("apply_cloud_aerial: cloud and depth must be float16 arrays (or torch tensors on the GPU)")
-        if out is None:
-            out = np.zeros(shape, np.float16)
-        if out.shape != shape or out.dtype != np.float16 or not out.flags.c_contiguous:
-            raise ValueError("apply_cloud_aerial: out must be a contiguous float16 %s array" % (shape,))
-        self._chk(self._L.csky_apply_cloud_aerial(self._h, C.byref(p), _ptr(cloud), _ptr(depth), _ptr(out)))
+                out = torch.empty(shape, dtype=torch.float16, device=dirs.device)
+            pitch = _device_image(name, "out", shape, out, pitched=True)     # (refuses a numpy out beside device dirs)
+            self._chk(getattr(self._L, "csky_%s_device" % name)(self._h, C.byref(p), *mid, C.c_void_p(int(out.data_ptr())), C.c_size_t(pitch), C.c_void_p(stream or 0)))
+        else:
+            out = _host_image(name, shape, out)                              # (refuses a tensor beside host dirs: it is no float16 array)
+            self._chk(getattr(self._L, "csky_" + name)(self._h, C.byref(p), *mid, _ptr(out)))
         return out
-
-    def _rays_out(self, name, shape, out):
-        """(device?, out, pitch) for the image of a rays call: a [h, w, 4] torch tensor of 2-byte elements with contiguous texels, or a numpy array."""
-        if out is not None and hasattr(out, "data_ptr"):
-            if out.dim() != 3 or out.element_size() != 2 or tuple(out.shape) != shape or out.stride(2) != 1 or (shape[1] > 1 and out.stride(1) != 4):
-                raise ValueError("%s: out must be a %s tensor of 2-byte elements with contiguous texels" % (name, shape))
-            return True, out, (out.stride(0) * 2 if shape[0] > 1 else shape[1] * 8)
-        if out is None:
-            out = np.zeros(shape, np.float16)
-        if out.shape != shape or out.dtype != np.float16 or not out.flags.c_contiguous:
-            raise ValueError("%s: out must be a contiguous float16 %s array" % (name, shape))
-        return False, out, shape[1] * 8
 
     def render_clouds_dirs(self, params, dirs, out=None, stream=None):
         """The direct cloud march over caller-given rays (csky_render_clouds_dirs*, definition: include/cloudsky.h): `dirs` is [h, w, 3] float32, a
@@ -672,28 +701,8 @@ class Context:
         are not read.  Host path (dirs a numpy array; out None or a numpy float16 array): blocks, returns numpy.  Device path (dirs a contiguous
         float32 torch tensor on this context's GPU; out a [h, w, 4] tensor of 2-byte elements whose texels are contiguous, its row stride the
         pitch, or None for a new one): asynchronous on `stream`, returns the tensor.  Needs the noise and a sky LUT."""
-        p = cloud_params(params)
-        if len(dirs.shape) != 3 or int(dirs.shape[2]) != 3:
-            raise ValueError("render_clouds_dirs: dirs must be a [h, w, 3] float32 array (or torch tensor on the GPU)")
-        shape = (int(dirs.shape[0]), int(dirs.shape[1]), 4)
-        if hasattr(dirs, "data_ptr"):
-            import torch
-            if dirs.dtype != torch.float32 or not dirs.is_contiguous():
-                raise ValueError("render_clouds_dirs: a device dirs must be a contiguous float32 tensor")
-            if out is None:
-                out = torch.empty(shape, dtype=torch.float16, device=dirs.device)
-            dev, out, pitch = self._rays_out("render_clouds_dirs", shape, out)
-            if not dev:
-                raise ValueError("render_clouds_dirs: with device dirs, out must be a torch tensor")
-            self._chk(self._L.csky_render_clouds_dirs_device(self._h, C.byref(p), shape[1], shape[0], C.c_void_p(int(dirs.data_ptr())), C.c_void_p(int(out.data_ptr())),
-                                                             C.c_size_t(int(pitch)), C.c_void_p(stream or 0)))
-            return out
-        d = np.ascontiguousarray(dirs, np.float32)
-        dev, out, _ = self._rays_out("render_clouds_dirs", shape, out)
-        if dev:
-            raise ValueError("render_clouds_dirs: with host dirs, out must be a numpy array")
-        self._chk(self._L.csky_render_clouds_dirs(self._h, C.byref(p), shape[1], shape[0], _ptr(d), _ptr(out)))
-        return out
+        w, h = _dirs_size("render_clouds_dirs", dirs)
+        return self._render_image("render_clouds_dirs", params, (w, h), (h, w, 4), out, stream, dirs=dirs)
 
     def render_clouds_view(self, params, basis, fov_y_degrees, width, height, out=None, stream=None):
         """The direct cloud march of a camera view (csky_render_clouds_view*, definition: include/cloudsky.h): the ray of every SCREEN pixel of a
@@ -701,20 +710,8 @@ class Context:
         the hemisphere frame's rays are; float16 [height, width, 4], zero under the horizon.  Host path (out None or a numpy float16 array):
         blocks, returns numpy.  Device path (out a [height, width, 4] torch tensor of 2-byte elements on this context's GPU whose texels are
         contiguous; its row stride is the pitch): asynchronous on `stream`, written in place, returns the tensor.  Needs the noise and a sky LUT."""
-        p = cloud_params(params)
-        shape = (int(height), int(width), 4)
-        v = View((C.c_float * 9)(*[float(x) for x in np.asarray(basis, np.float32).T.reshape(-1)]), float(fov_y_degrees))   # column-major basis
-        dev, out, pitch = self._rays_out("render_clouds_view", shape, out)
-        if dev:
-            self._chk(self._L.csky_render_clouds_view_device(self._h, C.byref(p), C.byref(v), shape[1], shape[0], C.c_void_p(int(out.data_ptr())), C.c_size_t(int(pitch)),
-                                                             C.c_void_p(stream or 0)))
-        else:
-            self._chk(self._L.csky_render_clouds_view(self._h, C.byref(p), C.byref(v), shape[1], shape[0], _ptr(out)))
-        return out
-
-    @staticmethod
-    def _view(basis, fov_y_degrees):
-        return View((C.c_float * 9)(*[float(x) for x in np.asarray(basis, np.float32).T.reshape(-1)]), float(fov_y_degrees))   # column-major basis
+        v = _view(basis, fov_y_degrees)
+        return self._render_image("render_clouds_view", params, (C.byref(v), int(width), int(height)), (int(height), int(width), 4), out, stream)
 
     def render_cloud_depth_dirs(self, params, dirs, steps=0, out=None, stream=None):
         """The depth frame of a ray frame (csky_render_cloud_depth_dirs*, definition: include/cloudsky.h): for each direction of `dirs`
@@ -723,28 +720,8 @@ class Context:
         own.  Host path (dirs a numpy array): blocks, returns numpy.  Device path (dirs a contiguous float32 torch tensor on this context's GPU;
         out a [h, w, 4] tensor of 2-byte elements whose texels are contiguous, its row stride the pitch, or None for a new one): asynchronous
         on `stream`, returns the tensor.  Needs the noise and no LUT."""
-        p = cloud_params(params)
-        if len(dirs.shape) != 3 or int(dirs.shape[2]) != 3:
-            raise ValueError("render_cloud_depth_dirs: dirs must be a [h, w, 3] float32 array (or torch tensor on the GPU)")
-        shape = (int(dirs.shape[0]), int(dirs.shape[1]), 4)
-        if hasattr(dirs, "data_ptr"):
-            import torch
-            if dirs.dtype != torch.float32 or not dirs.is_contiguous():
-                raise ValueError("render_cloud_depth_dirs: a device dirs must be a contiguous float32 tensor")
-            if out is None:
-                out = torch.empty(shape, dtype=torch.float16, device=dirs.device)
-            dev, out, pitch = self._rays_out("render_cloud_depth_dirs", shape, out)
-            if not dev:
-                raise ValueError("render_cloud_depth_dirs: with device dirs, out must be a torch tensor")
-            self._chk(self._L.csky_render_cloud_depth_dirs_device(self._h, C.byref(p), shape[1], shape[0], int(steps), C.c_void_p(int(dirs.data_ptr())),
-                                                                  C.c_void_p(int(out.data_ptr())), C.c_size_t(int(pitch)), C.c_void_p(stream or 0)))
-            return out
-        d = np.ascontiguousarray(dirs, np.float32)
-        dev, out, _ = self._rays_out("render_cloud_depth_dirs", shape, out)
-        if dev:
-            raise ValueError("render_cloud_depth_dirs: with host dirs, out must be a numpy array")
-        self._chk(self._L.csky_render_cloud_depth_dirs(self._h, C.byref(p), shape[1], shape[0], int(steps), _ptr(d), _ptr(out)))
-        return out
+        w, h = _dirs_size("render_cloud_depth_dirs", dirs)
+        return self._render_image("render_cloud_depth_dirs", params, (w, h, int(steps)), (h, w, 4), out, stream, dirs=dirs)
 
     def render_cloud_depth_view(self, params, basis, fov_y_degrees, width, height, steps=0, out=None, stream=None):
         """The depth frame of a camera view (csky_render_cloud_depth_view*, definition: include/cloudsky.h): render_cloud_depth for the rays of
@@ -752,49 +729,35 @@ class Context:
         (out None or a numpy float16 array): blocks, returns numpy.  Device path (out a [height, width, 4] torch tensor of 2-byte elements on
         this context's GPU whose texels are contiguous; its row stride is the pitch): asynchronous on `stream`, written in place, returns the
         tensor.  Needs the noise and no LUT."""
-        p = cloud_params(params)
-        shape = (int(height), int(width), 4)
-        v = self._view(basis, fov_y_degrees)
-        dev, out, pitch = self._rays_out("render_cloud_depth_view", shape, out)
-        if dev:
-            self._chk(self._L.csky_render_cloud_depth_view_device(self._h, C.byref(p), C.byref(v), shape[1], shape[0], int(steps), C.c_void_p(int(out.data_ptr())),
-                                                                  C.c_size_t(int(pitch)), C.c_void_p(stream or 0)))
-        else:
-            self._chk(self._L.csky_render_cloud_depth_view(self._h, C.byref(p), C.byref(v), shape[1], shape[0], int(steps), _ptr(out)))
-        return out
+        v = _view(basis, fov_y_degrees)
+        return self._render_image("render_cloud_depth_view", params, (C.byref(v), int(width), int(height), int(steps)), (int(height), int(width), 4), out, stream)
 
-    def _apply_rays(self, name, sun, cloud, depth, steps, out, stream, host_call, device_call, dirs=None):
-        """apply_cloud_aerial's argument handling for the ray forms: host_call / device_call take (params, cloud, depth, out[, stream]) pointers."""
+    def _apply_rays(self, name, mid, sun, cloud, depth, steps, out, stream, dirs=None):
+        """The one path of apply_cloud_aerial and its ray forms: csky_<name>(ctx, params, *mid[, dirs], cloud, depth, out) for host frames,
+        csky_<name>_device(..., stream) for tensors; `cloud` decides which, and every other image must be of its kind.  These calls take no pitch."""
         shape = tuple(int(x) for x in cloud.shape)
         if len(shape) != 3 or shape[2] != 4 or tuple(int(x) for x in depth.shape) != shape:
             raise ValueError("%s: cloud and depth must be [h, w, 4] images of one size" % name)
         if dirs is not None and tuple(int(x) for x in dirs.shape) != (shape[0], shape[1], 3):
             raise ValueError("%s: dirs must be a [h, w, 3] float32 image of the frames' size" % name)
-        p = CloudAerialParams(shape[1], shape[0], int(steps), (C.c_float * 3)(*[float(x) for x in sun]))
-        if hasattr(cloud, "data_ptr"):
-            import torch
+        p = CloudAerialParams(shape[1], shape[0], int(steps), _sun3(sun))
+        device = hasattr(cloud, "data_ptr")
+        if dirs is not None:
+            mid += (_dirs_arg(name, dirs, device),)
+        if device:
             if out is None:
+                import torch
                 out = torch.empty(shape, dtype=torch.float16, device=cloud.device)
-            for t in (cloud, depth, out):
-                if not hasattr(t, "data_ptr") or tuple(t.shape) != shape or t.element_size() != 2 or not t.is_contiguous():
-                    raise ValueError("%s: with a device frame, cloud, depth and out must be contiguous %s tensors of 2-byte elements" % (name, shape))
-            if dirs is not None and (not hasattr(dirs, "data_ptr") or dirs.dtype != torch.float32 or not dirs.is_contiguous()):
-                raise ValueError("%s: with a device frame, dirs must be a contiguous float32 tensor" % name)
-            self._chk(device_call(C.byref(p), dirs, C.c_void_p(int(cloud.data_ptr())), C.c_void_p(int(depth.data_ptr())), C.c_void_p(int(out.data_ptr())),
-                                  C.c_void_p(stream or 0)))
+            for what, t in (("cloud", cloud), ("depth", depth), ("out", out)):
+                _device_image(name, what, shape, t)
+            self._chk(getattr(self._L, "csky_%s_device" % name)(self._h, C.byref(p), *mid, *[C.c_void_p(int(t.data_ptr())) for t in (cloud, depth, out)],
+                                                                 C.c_void_p(stream or 0)))
             return out
         cloud, depth = np.ascontiguousarray(cloud), np.ascontiguousarray(depth)
         if cloud.dtype != np.float16 or depth.dtype != np.float16:
             raise ValueError("%s: cloud and depth must be float16 arrays (or torch tensors on the GPU)" % name)
-        if dirs is not None:
-            if hasattr(dirs, "data_ptr"):
-                raise ValueError("%s: with host frames, dirs must be a numpy array" % name)
-            dirs = np.ascontiguousarray(dirs, np.float32)
-        if out is None:
-            out = np.zeros(shape, np.float16)
-        if out.shape != shape or out.dtype != np.float16 or not out.flags.c_contiguous:
-            raise ValueError("%s: out must be a contiguous float16 %s array" % (name, shape))
-        self._chk(host_call(C.byref(p), dirs, _ptr(cloud), _ptr(depth), _ptr(out)))
+        out = _host_image(name, shape, out)
+        self._chk(getattr(self._L, "csky_" + name)(self._h, C.byref(p), *mid, _ptr(cloud), _ptr(depth), _ptr(out)))
         return out
 
     def apply_cloud_aerial_dirs(self, sun, dirs, cloud, depth, steps=16, out=None, stream=None):
@@ -802,19 +765,15 @@ class Context:
         render_clouds_dirs for `dirs` ([h, w, 3] float32) and `depth` that of render_cloud_depth_dirs.  A pixel whose direction the march does
         not accept leaves as it came.  Host path (numpy arrays) and device path (contiguous torch tensors on this context's GPU) as
         apply_cloud_aerial's; out may be `cloud`.  Needs the transmittance LUT and nothing else."""
-        return self._apply_rays("apply_cloud_aerial_dirs", sun, cloud, depth, steps, out, stream,
-                                lambda p, d, c, z, o: self._L.csky_apply_cloud_aerial_dirs(self._h, p, _ptr(d), c, z, o),
-                                lambda p, d, c, z, o, s: self._L.csky_apply_cloud_aerial_dirs_device(self._h, p, C.c_void_p(int(d.data_ptr())), c, z, o, s), dirs=dirs)
+        return self._apply_rays("apply_cloud_aerial_dirs", (), sun, cloud, depth, steps, out, stream, dirs=dirs)
 
     def apply_cloud_aerial_view(self, sun, basis, fov_y_degrees, cloud, depth, steps=16, out=None, stream=None):
         """apply_cloud_aerial for a view frame (csky_apply_cloud_aerial_view*, definition: include/cloudsky.h): `cloud` the image of
         render_clouds_view for this camera and `depth` that of render_cloud_depth_view, both float16 [h, w, 4].  Host path (numpy arrays) and
         device path (contiguous torch tensors on this context's GPU) as apply_cloud_aerial's; out may be `cloud`.  Needs the transmittance LUT
         and nothing else."""
-        v = self._view(basis, fov_y_degrees)
-        return self._apply_rays("apply_cloud_aerial_view", sun, cloud, depth, steps, out, stream,
-                                lambda p, d, c, z, o: self._L.csky_apply_cloud_aerial_view(self._h, p, C.byref(v), c, z, o),
-                                lambda p, d, c, z, o, s: self._L.csky_apply_cloud_aerial_view_device(self._h, p, C.byref(v), c, z, o, s))
+        v = _view(basis, fov_y_degrees)
+        return self._apply_rays("apply_cloud_aerial_view", (C.byref(v),), sun, cloud, depth, steps, out, stream)
 
     def set_shadow_exact_end(self, enabled=True):
         """A/B switch (cloudsky_internal.h): False makes every texel of the shadow map take all its samples; the maps are byte-identical."""
@@ -846,8 +805,7 @@ class Context:
     def submit_clouds(self, params, tile_w=None, tile_h=None):
         """Enqueue march + copy into a pinned ring slot; returns the ticket at once."""
         p = cloud_params(params)
-        w = int(p.f[0]) if tile_w is None else int(tile_w)
-        h = int(p.f[1]) if tile_h is None else int(tile_h)
+        w, h = _frame_size(p, tile_w, tile_h)
         t = C.c_int64(-1)
         self._chk(self._L.csky_submit_clouds(self._h, C.byref(p), w, h, C.byref(t)))
         self._shapes = getattr(self, "_shapes", {})
@@ -884,36 +842,26 @@ class Context:
 
     def composite_sky(self, cloud_from, cloud_to, sky_from, sky_to, light_dir, blend_amount=0.0, sun_disk_scale=2.0, out_w=2048, out_h=1024):
         """clouds.gdshader sky() on an equirectangular panorama; inputs float16 [h, w, 4] host arrays."""
-        a = [np.ascontiguousarray(x).view(np.uint16) for x in (cloud_from, cloud_to, sky_from, sky_to)]
-        p = CompositeParams(out_w, out_h, a[0].shape[1], a[0].shape[0], a[2].shape[1], a[2].shape[0], float(blend_amount), float(sun_disk_scale))
-        for k in range(3):
-            p.light_direction[k] = float(light_dir[k])
-        out = np.zeros((out_h, out_w, 4), np.uint16)
-        self._chk(self._L.csky_composite_sky(self._h, C.byref(p), _ptr(a[0]), _ptr(a[1]), _ptr(a[2]), _ptr(a[3]), _ptr(out)))
-        return out.view(np.float16)
+        return self._composite(self._L.csky_composite_sky, (), (cloud_from, cloud_to, sky_from, sky_to), light_dir, blend_amount, sun_disk_scale, out_w, out_h)
 
     def composite_view(self, cloud_from, cloud_to, sky_from, sky_to, light_dir, basis, fov_y_degrees, blend_amount=0.0, sun_disk_scale=2.0, out_w=1152, out_h=648):
         """clouds.gdshader sky() per SCREEN pixel of a perspective camera (basis: 3x3, columns = the camera's right / up / back axes)."""
-        a = [np.ascontiguousarray(x).view(np.uint16) for x in (cloud_from, cloud_to, sky_from, sky_to)]
-        p = CompositeParams(out_w, out_h, a[0].shape[1], a[0].shape[0], a[2].shape[1], a[2].shape[0], float(blend_amount), float(sun_disk_scale))
-        for k in range(3):
-            p.light_direction[k] = float(light_dir[k])
-        v = (C.c_float * 10)(*([float(x) for x in np.asarray(basis, np.float32).T.reshape(-1)] + [float(fov_y_degrees)]))   # column-major basis, then the fov
-        out = np.zeros((out_h, out_w, 4), np.uint16)
-        self._chk(self._L.csky_composite_view(self._h, C.byref(p), C.cast(v, C.c_void_p), _ptr(a[0]), _ptr(a[1]), _ptr(a[2]), _ptr(a[3]), _ptr(out)))
-        return out.view(np.float16)
+        v = _view(basis, fov_y_degrees)
+        return self._composite(self._L.csky_composite_view, (C.byref(v),), (cloud_from, cloud_to, sky_from, sky_to), light_dir, blend_amount, sun_disk_scale, out_w, out_h)
 
     def composite_view_frames(self, cloud_from, cloud_to, sky_from, sky_to, light_dir, basis, fov_y_degrees, blend_amount=0.0, sun_disk_scale=2.0):
         """composite_view with cloud_from / cloud_to being VIEW frames of the same camera (render_clouds_view), float16 [out_h, out_w, 4]: each
         screen pixel reads its own cloud texel instead of tapping a hemisphere frame (csky_composite_view_frames)."""
-        a = [np.ascontiguousarray(x).view(np.uint16) for x in (cloud_from, cloud_to, sky_from, sky_to)]
-        out_h, out_w = a[0].shape[0], a[0].shape[1]
-        p = CompositeParams(out_w, out_h, a[0].shape[1], a[0].shape[0], a[2].shape[1], a[2].shape[0], float(blend_amount), float(sun_disk_scale))
-        for k in range(3):
-            p.light_direction[k] = float(light_dir[k])
-        v = (C.c_float * 10)(*([float(x) for x in np.asarray(basis, np.float32).T.reshape(-1)] + [float(fov_y_degrees)]))   # column-major basis, then the fov
+        v = _view(basis, fov_y_degrees)
+        out_h, out_w = np.shape(cloud_from)[:2]
+        return self._composite(self._L.csky_composite_view_frames, (C.byref(v),), (cloud_from, cloud_to, sky_from, sky_to), light_dir, blend_amount, sun_disk_scale, out_w, out_h)
+
+    def _composite(self, call, view, frames, light_dir, blend_amount, sun_disk_scale, out_w, out_h):
+        """The compositor's host forms: call(ctx, params, *view, the four frames, out) -> the out_h x out_w image, float16 [out_h, out_w, 4]."""
+        a, cloud_wh, sky_wh = _host_frames(*frames)
+        p = _composite_params(out_w, out_h, cloud_wh, sky_wh, light_dir, blend_amount, sun_disk_scale)
         out = np.zeros((out_h, out_w, 4), np.uint16)
-        self._chk(self._L.csky_composite_view_frames(self._h, C.byref(p), C.cast(v, C.c_void_p), _ptr(a[0]), _ptr(a[1]), _ptr(a[2]), _ptr(a[3]), _ptr(out)))
+        self._chk(call(self._h, C.byref(p), *view, *[_ptr(x) for x in a], _ptr(out)))
         return out.view(np.float16)
 
     def render_radiance(self, cloud_from, cloud_to, sky_from, sky_to, light_dir, blend_amount=0.0, sun_disk_scale=2.0, face_size=64, layers=8, source_size=0,
@@ -923,26 +871,18 @@ class Context:
         (into `out` when given)."""
         S, L = int(face_size), int(layers)
         n_layers = L - int(first_layer) if n_layers is None else int(n_layers)
-        a = [np.ascontiguousarray(x).view(np.uint16) for x in (cloud_from, cloud_to, sky_from, sky_to)]
-        p = CompositeParams(S, S, a[0].shape[1], a[0].shape[0], a[2].shape[1], a[2].shape[0], float(blend_amount), float(sun_disk_scale))
-        for k in range(3):
-            p.light_direction[k] = float(light_dir[k])
+        a, cloud_wh, sky_wh = _host_frames(cloud_from, cloud_to, sky_from, sky_to)
+        p = _composite_params(S, S, cloud_wh, sky_wh, light_dir, blend_amount, sun_disk_scale)
         rp = RadianceParams(S, L, int(source_size))
-        if out is None:
-            out = np.zeros((L, 6, S, S, 4), np.float16)
-        if out.shape != (L, 6, S, S, 4) or out.dtype != np.float16 or not out.flags.c_contiguous:
-            raise ValueError("render_radiance: out must be a contiguous float16 [%d, 6, %d, %d, 4] array" % (L, S, S))
-        self._chk(self._L.csky_render_radiance(self._h, C.byref(p), C.byref(rp), _ptr(a[0]), _ptr(a[1]), _ptr(a[2]), _ptr(a[3]), int(first_layer), n_layers,
-                                               _ptr(out)))
+        out = _host_image("render_radiance", (L, 6, S, S, 4), out)
+        self._chk(self._L.csky_render_radiance(self._h, C.byref(p), C.byref(rp), *[_ptr(x) for x in a], int(first_layer), n_layers, _ptr(out)))
         return out
 
     def render_radiance_device(self, d_cloud_from, d_cloud_to, d_sky_from, d_sky_to, cloud_wh, sky_wh, light_dir, blend_amount, sun_disk_scale, face_size,
                                layers, source_size, first_layer, n_layers, d_out, stream=None):
         """csky_render_radiance_device: device pointers in and out (d_out: the whole [L, 6, S, S, 4] half array), asynchronous on `stream`."""
         S = int(face_size)
-        p = CompositeParams(S, S, int(cloud_wh[0]), int(cloud_wh[1]), int(sky_wh[0]), int(sky_wh[1]), float(blend_amount), float(sun_disk_scale))
-        for k in range(3):
-            p.light_direction[k] = float(light_dir[k])
+        p = _composite_params(S, S, cloud_wh, sky_wh, light_dir, blend_amount, sun_disk_scale)
         rp = RadianceParams(S, int(layers), int(source_size))
         ptrs = [C.c_void_p(int(x) if x else 0) for x in (d_cloud_from, d_cloud_to, d_sky_from, d_sky_to)]
         self._chk(self._L.csky_render_radiance_device(self._h, C.byref(p), C.byref(rp), *ptrs, int(first_layer), int(n_layers), C.c_void_p(int(d_out)),
@@ -1151,15 +1091,12 @@ class MultiContext:
         self._chk(self._L.csky_multi_set_staged(self._h, 1 if staged else 0))
 
     def render_sky_lut(self, sun_dir, w=200, h=100):
-        p = SkyParams()
-        p.f[0], p.f[1] = float(w), float(h)
-        p.f[4], p.f[5], p.f[6] = [float(x) for x in sun_dir]
+        p = _sky_params(sun_dir, w, h)
         self._chk(self._L.csky_multi_render_sky_lut(self._h, C.byref(p)))
 
     def render_clouds(self, params, tile_w=None, tile_h=None):
         p = cloud_params(params)
-        w = int(p.f[0]) if tile_w is None else int(tile_w)
-        h = int(p.f[1]) if tile_h is None else int(tile_h)
+        w, h = _frame_size(p, tile_w, tile_h)
         out = np.zeros((h, w, 4), np.uint16)
         self._chk(self._L.csky_multi_render_clouds(self._h, C.byref(p), w, h, _ptr(out), w * 8))
         return out.view(np.float16)
@@ -1177,8 +1114,7 @@ class MultiContext:
 
     def submit_clouds(self, params, tile_w=None, tile_h=None):
         p = cloud_params(params)
-        w = int(p.f[0]) if tile_w is None else int(tile_w)
-        h = int(p.f[1]) if tile_h is None else int(tile_h)
+        w, h = _frame_size(p, tile_w, tile_h)
         t = C.c_int64(-1)
         self._chk(self._L.csky_multi_submit_clouds(self._h, C.byref(p), w, h, C.byref(t)))
         self._shapes = getattr(self, "_shapes", {})
