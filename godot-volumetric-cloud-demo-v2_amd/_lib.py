@@ -196,6 +196,9 @@ SYMBOLS = [
     ("csky_render_clouds_dirs_device", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("csky_render_clouds_view", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.POINTER(View), C.c_int, C.c_int, C.c_void_p]),
     ("csky_render_clouds_view_device", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.POINTER(View), C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("csky_render_clouds_view_update", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.POINTER(View), C.POINTER(View), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    ("csky_render_clouds_view_update_device", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.POINTER(View), C.POINTER(View), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                        C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("csky_render_cloud_depth_dirs", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     ("csky_render_cloud_depth_dirs_device", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("csky_render_cloud_depth_view", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.POINTER(View), C.c_int, C.c_int, C.c_int, C.c_void_p]),
@@ -712,6 +715,39 @@ class Context:
         contiguous; its row stride is the pitch): asynchronous on `stream`, written in place, returns the tensor.  Needs the noise and a sky LUT."""
         v = _view(basis, fov_y_degrees)
         return self._render_image("render_clouds_view", params, (C.byref(v), int(width), int(height)), (int(height), int(width), 4), out, stream)
+
+    def render_clouds_view_update(self, params, basis, fov_y_degrees, width, height, block, phase, prev=None, prev_basis=None, prev_fov=None, out=None, stream=None):
+        """The temporal split of a view frame (csky_render_clouds_view_update*, definition: include/cloudsky.h): one pixel of every block x block
+        pixels (the one at (phase % block, phase // block)) is marched as render_clouds_view marches it, every other pixel is taken from `prev`,
+        the view frame of the camera (prev_basis, prev_fov), through that camera; a pixel `prev` does not cover is marched.  prev None: no
+        history, the result is render_clouds_view's.  float16 [height, width, 4].  Host path (prev None or a numpy float16 array; out None or a
+        numpy float16 array): blocks, returns numpy.  Device path (prev and out [height, width, 4] torch tensors of 2-byte elements on this
+        context's GPU whose texels are contiguous, each with its own row stride as its pitch; out None for a new one beside prev): asynchronous
+        on `stream`, returns the tensor.  prev and out must not overlap.  Needs the noise and a sky LUT."""
+        name = "render_clouds_view_update"
+        p = cloud_params(params)
+        v = _view(basis, fov_y_degrees)
+        shape = (int(height), int(width), 4)
+        if prev is not None and (prev_basis is None or prev_fov is None):
+            raise ValueError("%s: prev needs prev_basis and prev_fov" % name)
+        pv = None if prev is None else C.byref(_view(prev_basis, prev_fov))
+        mid = (C.byref(v), pv, shape[1], shape[0], int(block), int(phase))
+        if hasattr(out if prev is None else prev, "data_ptr"):
+            if out is None:
+                import torch
+                out = torch.empty(shape, dtype=torch.float16, device=prev.device)
+            prev_pitch = 0 if prev is None else _device_image(name, "prev", shape, prev, pitched=True)
+            pitch = _device_image(name, "out", shape, out, pitched=True)     # (refuses a numpy out beside a device prev)
+            self._chk(self._L.csky_render_clouds_view_update_device(self._h, C.byref(p), *mid, None if prev is None else C.c_void_p(int(prev.data_ptr())), C.c_size_t(prev_pitch),
+                                                                    C.c_void_p(int(out.data_ptr())), C.c_size_t(pitch), C.c_void_p(stream or 0)))
+            return out
+        if prev is not None:
+            prev = np.ascontiguousarray(prev)
+            if prev.shape != shape or prev.dtype != np.float16:
+                raise ValueError("%s: prev must be a float16 %s array (or a torch tensor on the GPU)" % (name, shape))
+        out = _host_image(name, shape, out)                                  # (refuses a tensor beside a host prev: it is no float16 array)
+        self._chk(self._L.csky_render_clouds_view_update(self._h, C.byref(p), *mid, None if prev is None else _ptr(prev), _ptr(out)))
+        return out
 
     def render_cloud_depth_dirs(self, params, dirs, steps=0, out=None, stream=None):
         """The depth frame of a ray frame (csky_render_cloud_depth_dirs*, definition: include/cloudsky.h): for each direction of `dirs`

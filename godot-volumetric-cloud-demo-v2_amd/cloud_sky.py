@@ -111,6 +111,7 @@ class CloudSky:
         self.rank, self.world_size, self.dist = int(rank), int(world_size), dist
         self.last_frame = None
         self._side_stream = None
+        self._temporal = None            # cloud_view_temporal's history
         # the sky's radiance cubemap (radiance_cubemap / update_radiance): [L, 6, S, S, 4] float16, its (S, L, Ss) and the layer the next
         # update_radiance() call refreshes
         self.radiance = None
@@ -250,6 +251,7 @@ class CloudSky:
         self.texture_to_update, self.texture_to_blend_from, self.texture_to_blend_to = 0, 1, 2
         self.update_position = [0, 0]
         self.textures = [None, None, None]
+        self._temporal = None                                               # cloud_view_temporal's two frames, previous camera and call counter
 
     def close(self):  # NOTIFICATION_PREDELETE, cloud_sky.gd:193-195
         self.cleanup()
@@ -290,6 +292,54 @@ class CloudSky:
             self.ctx.render_cloud_depth_view(pc, basis, fov_y_degrees, out_w, out_h, out=depth, stream=stream)   # the apply step reads both on the same stream
             self.ctx.apply_cloud_aerial_view(sun, basis, fov_y_degrees, out, depth, aerial_steps, out=out, stream=stream)   # in place
         done()
+        return out
+
+    TEMPORAL_BLOCK_CHOICES = (1, 2, 4, 8)
+
+    @staticmethod
+    def temporal_phases(block):
+        """The order in which the block x block pixels of a block are refreshed: phase k of the list is the pixel (phase % block, phase // block)
+        whose ordered-dither (Bayer) index is k, so that any run of consecutive calls spreads its fresh pixels evenly over the block."""
+        m = [[0]]
+        while len(m) < block:                                    # M(2n) = [[4M, 4M + 2], [4M + 3, 4M + 1]]
+            m = [[4 * v for v in r] + [4 * v + 2 for v in r] for r in m] + [[4 * v + 3 for v in r] + [4 * v + 1 for v in r] for r in m]
+        order = [0] * (block * block)
+        for y, row in enumerate(m):
+            for x, v in enumerate(row):
+                order[v] = y * block + x
+        return order
+
+    def cloud_view_temporal(self, basis, fov_y_degrees=75.0, out_w=1152, out_h=648, block=4):
+        """cloud_view spread over block * block calls (csky_render_clouds_view_update; the definition: include/cloudsky.h): each call marches one
+        pixel of every block x block pixels, in the order of temporal_phases(block), and takes the others from the frame of the call before
+        through that call's camera; what that frame does not cover is marched.  The first call, and the first after a change of the size or of
+        `block` or after cleanup(), has no history and marches every pixel.  With a still camera and unchanged frame data, block * block calls
+        give cloud_view's frame; with changing frame data a pixel is up to block * block - 1 calls old.  The object keeps two frames and
+        alternates between them: the returned frame is valid until the call after the next.  float16 [out_h, out_w, 4]; a torch CUDA tensor with
+        device_buffers=True.  Not called by update_sky()."""
+        if block not in self.TEMPORAL_BLOCK_CHOICES:
+            raise ValueError("block must be one of %s" % (self.TEMPORAL_BLOCK_CHOICES,))
+        key = (int(out_w), int(out_h), int(block))
+        t = self._temporal
+        if t is None or t["key"] != key:
+            t = self._temporal = {"key": key, "frames": [None, None], "prev": None, "calls": 0}
+        shape = (key[1], key[0], 4)
+        at = t["calls"] % 2
+        if t["frames"][at] is None:
+            if self.device_buffers:
+                import torch
+                t["frames"][at] = torch.empty(shape, dtype=torch.float16, device=torch.device("cuda", self.ctx.device_id))
+            else:
+                t["frames"][at] = np.zeros(shape, np.float16)
+        out = t["frames"][at]
+        prev, prev_view = (t["frames"][1 - at], t["prev"]) if t["prev"] is not None else (None, (None, None))
+        phase = self.temporal_phases(block)[t["calls"] % (block * block)]
+        stream, done = self._march_stream()
+        self.ctx.render_clouds_view_update(self._fill_push_constant(), basis, fov_y_degrees, key[0], key[1], block, phase, prev=prev, prev_basis=prev_view[0],
+                                           prev_fov=prev_view[1], out=out, stream=stream)
+        done()
+        t["prev"] = (np.array(basis, np.float32), float(fov_y_degrees))
+        t["calls"] += 1
         return out
 
     def cloud_view_depth(self, basis, fov_y_degrees=75.0, out_w=1152, out_h=648):

@@ -1,5 +1,5 @@
 // api_rays.cpp -- the direct cloud march's C ABI (csky_render_clouds_dirs / _view and their _device forms; rays_core.h, cloud_kernels.hip
-// clouds_rays_kernel).
+// clouds_rays_kernel) and the temporal split of a view frame (csky_render_clouds_view_update*; view_update_core.h).
 // The call reads what a cloud frame reads (noise, sky LUT, the march settings) and writes none of it.  Its frame constants come from the cloud
 // frame's own set-up kernel, enqueued on the context's stream into a block of the call's own: no slot of the frame ring, none of the ring's order,
 // feedback or head state, no stream of its own.  The blocking forms work in the context's stage (host_stage.h).
@@ -7,6 +7,7 @@
 #include <cstring>
 #include "context.h"
 #include "rays_core.h"
+#include "view_update_core.h"
 
 using namespace csky;
 
@@ -43,24 +44,30 @@ int rays_setup(csky_ctx* c, const CloudParams& cp, hipStream_t s) {
     return CSKY_OK;
 }
 
-// Set-up and launch on stream s, for arguments rays_check has passed.  d_dirs: NULL for the view forms.
-int rays_launch(csky_ctx* c, const char* fn, const csky_cloud_params* p, const csky_view* view, int w, int h, const float* d_dirs, uint2* d_out, size_t pitch_bytes,
-                hipStream_t s) {
+// Set-up and the call's march on stream s, for arguments the checks have passed.  `launch(t, t32)` enqueues the march (one launch, or the update's
+// two) on s with the frame constants in c->d_rays_fc and returns its hipError_t.
+template <class F> int rays_run(csky_ctx* c, const char* fn, const csky_cloud_params* p, hipStream_t s, F launch) {
     CloudParams cp; memcpy(&cp, p, sizeof cp);
-    // texture_size and update_position are not read by this path; the set-up kernel copies them into fields no lane of the rays kernel looks at.
+    // texture_size and update_position are not read by this path; the set-up kernel copies them into fields no lane of the rays kernels looks at.
     // Fixed values keep whatever the caller left there (NaNs included) out of every conversion.
     cp.texture_size[0] = cp.texture_size[1] = 1.0f; cp.update_position[0] = cp.update_position[1] = 0.0f;
     int rc; if ((rc = rays_setup(c, cp, s))) return rc;
-    const RaysGeom g = rays_geom(view ? view->basis : nullptr, view ? view->fov_y_degrees : 0.0f, w, h, (uint32_t)(pitch_bytes / 8));
     TexSet32 t32;
-    const Event* kt = nullptr;                                  // timing pair of this launch (csky_set_kernel_timing), as around a cloud frame's
+    const Event* kt = nullptr;                                  // timing pair of this call (csky_set_kernel_timing), as around a cloud frame's
     if (c->kt.on && (rc = c->kt.next_pair(c, kt))) return rc;
     if (kt) HIPCHK(c, hipEventRecord(kt[0], s));
-    if ((rc = launched(c, fn, launch_clouds_rays(texset(c), texset32_if(c, t32), c->d_rays_fc, g, d_dirs, d_out, s)))) return rc;
+    if ((rc = launched(c, fn, launch(texset(c), texset32_if(c, t32))))) return rc;
     if (kt) HIPCHK(c, hipEventRecord(kt[1], s));
     HIPCHK(c, hipEventRecord(c->ev_rays, s));                   // the next call's set-up overwrites the block this march reads
     c->rays_pending = true;
     return CSKY_OK;
+}
+
+// The dirs and view forms' march.  d_dirs: NULL for the view forms.
+int rays_launch(csky_ctx* c, const char* fn, const csky_cloud_params* p, const csky_view* view, int w, int h, const float* d_dirs, uint2* d_out, size_t pitch_bytes,
+                hipStream_t s) {
+    const RaysGeom g = rays_geom(view ? view->basis : nullptr, view ? view->fov_y_degrees : 0.0f, w, h, (uint32_t)(pitch_bytes / 8));
+    return rays_run(c, fn, p, s, [&](const TexSet& t, const TexSet32* t32) { return launch_clouds_rays(t, t32, c->d_rays_fc, g, d_dirs, d_out, s); });
 }
 
 // The blocking host forms: dirs (NULL for a view) up, the image down, on the context's stream.
@@ -76,9 +83,60 @@ int rays_host(csky_ctx* c, const char* fn, const csky_cloud_params* p, const csk
     return hc.finish();
 }
 
+// ---- the temporal split of a view frame (view_update_core.h)
+// What the update forms check beyond rays_check, before it (a bad argument is CSKY_ERR_INVALID whatever the context holds).  prev / out: device
+// pointers of the device form, host pointers of the host form; both are byte ranges of (h - 1) * pitch + 8 * w bytes.
+int update_check(csky_ctx* c, const char* fn, const csky_view* prev_view, int w, int h, int block, int phase, const void* prev, size_t prev_pitch, const void* out, size_t pitch) {
+    if (block < 1 || block > 8) return fail(c, CSKY_ERR_INVALID, "%s: block must be in [1, 8]", fn);
+    if (phase < 0 || phase >= block * block) return fail(c, CSKY_ERR_INVALID, "%s: phase must be in [0, block * block)", fn);
+    if (!prev) return CSKY_OK;                                  // no history: prev_view and prev_pitch are not read
+    if (!prev_view) return fail(c, CSKY_ERR_INVALID, "%s: prev_view is NULL beside a previous frame", fn);
+    if (const int rc = view_check(c, fn, prev_view)) return rc;
+    if (w < 1 || w > 8192 || h < 1 || h > 8192) return CSKY_OK;   // rays_check refuses it
+    if (prev_pitch % 8 || prev_pitch < (size_t)w * 8) return fail(c, CSKY_ERR_INVALID, "%s: the previous frame's row pitch must be a multiple of 8 and >= 8 * w", fn);
+    if (pitch < (size_t)w * 8) return CSKY_OK;                  // likewise
+    const uintptr_t a = (uintptr_t)prev, b = (uintptr_t)out;
+    const size_t na = (size_t)(h - 1) * prev_pitch + (size_t)w * 8, nb = (size_t)(h - 1) * pitch + (size_t)w * 8;
+    if (a < b + nb && b < a + na) return fail(c, CSKY_ERR_INVALID, "%s: the previous frame and out overlap", fn);
+    return CSKY_OK;
+}
+
+// The update's two launches, one timing pair around both.  d_prev: NULL without history (prev_view is then not read).
+int update_launch(csky_ctx* c, const char* fn, const csky_cloud_params* p, const csky_view* view, const csky_view* prev_view, int w, int h, int block, int phase,
+                  const uint2* d_prev, size_t prev_pitch, uint2* d_out, size_t pitch_bytes, hipStream_t s) {
+    static_assert(sizeof(csky_view) == 10 * sizeof(float), "csky_view is ten floats");
+    const ViewUpdateGeom g = view_update_geom(reinterpret_cast<const float*>(view), d_prev ? reinterpret_cast<const float*>(prev_view) : nullptr, w, h,
+                                              (uint32_t)(pitch_bytes / 8), d_prev ? (uint32_t)(prev_pitch / 8) : 0u, block, phase);
+    return rays_run(c, fn, p, s, [&](const TexSet& t, const TexSet32* t32) { return launch_clouds_view_update(t, t32, c->d_rays_fc, g, d_prev, d_out, s); });
+}
+
 }  // namespace
 
 extern "C" {
+
+int csky_render_clouds_view_update(csky_ctx* c, const csky_cloud_params* p, const csky_view* view, const csky_view* prev_view, int w, int h, int block, int phase,
+                                   const uint16_t* prev, uint16_t* out) {
+    const char* fn = "csky_render_clouds_view_update";
+    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "%s: ctx is NULL", fn);
+    if (!out) return fail(c, CSKY_ERR_INVALID, "%s: out is NULL", fn);
+    const size_t tight = (w >= 1 && w <= 8192) ? (size_t)w * 8 : 8;
+    int rc; if ((rc = update_check(c, fn, prev_view, w, h, block, phase, prev, tight, out, tight)) || (rc = rays_check(c, fn, p, view, true, w, h, tight)) || (rc = bind(c))) return rc;
+    const size_t n = (size_t)w * h, pb = prev ? n * 8 : 0;
+    HostCall hc = host_call(c, fn, {pb, n * 8});
+    hc.up(0, prev, pb);
+    hc.step([&] { return update_launch(c, fn, p, view, prev_view, w, h, block, phase, prev ? hc.at<uint2>(0) : nullptr, tight, hc.at<uint2>(1), tight, c->stream); });
+    hc.down(out, 1, n * 8);
+    return hc.finish();
+}
+
+int csky_render_clouds_view_update_device(csky_ctx* c, const csky_cloud_params* p, const csky_view* view, const csky_view* prev_view, int w, int h, int block, int phase,
+                                          const void* d_prev, size_t prev_pitch, void* d_out, size_t pitch, void* hip_stream) {
+    const char* fn = "csky_render_clouds_view_update_device";
+    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "%s: ctx is NULL", fn);
+    if (!d_out) return fail(c, CSKY_ERR_INVALID, "%s: d_out is NULL", fn);
+    int rc; if ((rc = update_check(c, fn, prev_view, w, h, block, phase, d_prev, prev_pitch, d_out, pitch)) || (rc = rays_check(c, fn, p, view, true, w, h, pitch)) || (rc = bind(c))) return rc;
+    return update_launch(c, fn, p, view, prev_view, w, h, block, phase, static_cast<const uint2*>(d_prev), prev_pitch, static_cast<uint2*>(d_out), pitch, stream_of(c, hip_stream));
+}
 
 int csky_render_clouds_dirs(csky_ctx* c, const csky_cloud_params* p, int w, int h, const float* dirs, uint16_t* out) {
     const char* fn = "csky_render_clouds_dirs";

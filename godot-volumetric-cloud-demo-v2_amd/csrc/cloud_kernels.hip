@@ -1000,3 +1000,89 @@ hipError_t launch_clouds_rays(const TexSet& t, const TexSet32* t32, const FrameC
 }
 
 }  // namespace csky
+
+// ---- the temporal split of a view frame ----------------------------------------------------------------------------
+// One pixel of every B x B block of a view is marched per call (the fresh pixels), the others are taken from the previous view frame through the
+// previous camera, and a pixel that frame does not cover (a hole) is marched.  Two launches that write disjoint pixels: the order between them does
+// not matter.  Both are clouds_rays_kernel's shape: one pixel per lane, an 8x8 tile per wavefront, four tiles per workgroup, the same LDS queue and
+// launch bound, march_compact<true, false> on the frame constants the cloud frame's set-up kernel wrote.
+#include "view_update_core.h"
+#pragma clang fp contract(off)   // (view_update_core.h ends with contraction on, like rays_core.h)
+
+namespace csky {
+
+// The fresh pixels, run over the SUB-GRID: lane (gx, gy) of G.sub_w x G.sub_h marches pixel (gx * B + px, gy * B + py) and stores there.  The
+// fresh rays fill whole 8x8 tiles: a wavefront of 64 fresh rays, not 4 lanes of every wavefront of the image.
+template <class TS>
+__global__ __launch_bounds__(256, CSKY_COMPACT_WAVES) void clouds_view_fresh_kernel(TS T, const FrameConsts* __restrict__ fcp, ViewUpdateGeom G, uint2* __restrict__ out) {
+    __shared__ float lds[4][CQ_FLOATS];
+    const int tiles_x = (G.sub_w + 31) >> 5;
+    const int slab = (int)blockIdx.x / tiles_x, bx = (int)blockIdx.x - slab * tiles_x;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int gx = bx * 32 + wave * 8 + (lane & 7);
+    const int gy = slab * 8 + (lane >> 3);
+    const bool valid = gx < G.sub_w && gy < G.sub_h;
+    const int i = valid ? gx * G.block + G.px : 0, j = valid ? gy * G.block + G.py : 0;   // < G.w, G.h by the sub-grid's size
+    const FrameConsts& fc = *fcp;
+    T.detail_lds = nullptr;                                    // compile-time constant here: the LDS tap path folds away
+    float ex, ey, ez;
+    view_update_dir(G, i, j, ex, ey, ez);
+    Ray ray = rays_ray(fc, ex, ey, ez);
+    if (!valid) ray.above = false;
+    const MarchOut o = march_compact<true, false>(T, fc, ray, &lds[wave][0], 0, fc.primary_steps);
+    if (valid) out[(size_t)j * G.pitch_px + i] = pack_half4(f2h(o.r), f2h(o.g), f2h(o.b), f2h(o.a));
+}
+
+// Every other pixel, one per lane over the full image.  A lane that is not fresh stores zeros (not accepted), its history texel, or is a hole.  A
+// wavefront without a hole returns before it touches its LDS queue; otherwise its hole lanes march and store.  Fresh lanes store nothing.
+// prev: the previous frame (NULL without history: every accepted lane that is not fresh is then a hole); it does not overlap out.
+template <class TS>
+__global__ __launch_bounds__(256, CSKY_COMPACT_WAVES) void clouds_view_reproject_kernel(TS T, const FrameConsts* __restrict__ fcp, ViewUpdateGeom G,
+                                                                                        const uint2* __restrict__ prev, uint2* __restrict__ out) {
+    __shared__ float lds[4][CQ_FLOATS];
+    const int tiles_x = (G.w + 31) >> 5;
+    const int slab = (int)blockIdx.x / tiles_x, bx = (int)blockIdx.x - slab * tiles_x;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int gx = bx * 32 + wave * 8 + (lane & 7);
+    const int gy = slab * 8 + (lane >> 3);
+    const bool valid = gx < G.w && gy < G.h;
+    const FrameConsts& fc = *fcp;
+    T.detail_lds = nullptr;
+    float ex, ey, ez;
+    view_update_dir(G, valid ? gx : 0, valid ? gy : 0, ex, ey, ez);
+    const ViewUpdateClass c = view_update_classify(G, gx, gy, ex, ey, ez);
+    const int kind = valid ? c.kind : VU_FRESH;                // a lane outside the image stores nothing, like a fresh one
+    uint2* __restrict__ dst = out + ((size_t)gy * G.pitch_px + gx);
+    if (kind == VU_ZERO) { uint2 z; z.x = 0u; z.y = 0u; *dst = z; }
+    else if (kind == VU_COPY) *dst = prev[(size_t)gy * G.prev_pitch_px + gx];
+    else if (kind == VU_TAP) *dst = view_update_tap(prev, G.prev_pitch_px, G.w, G.h, c.ux, c.uy);
+    const bool hole = kind == VU_HOLE;
+    if (__builtin_amdgcn_ballot_w64(hole) == 0ull) return;
+    Ray ray = rays_ray(fc, hole ? ex : 0.0f, hole ? ey : 0.0f, hole ? ez : 0.0f);   // (0, 0, 0) fails rays_accept: no sample, no address
+    if (!hole) ray.above = false;
+    const MarchOut o = march_compact<true, false>(T, fc, ray, &lds[wave][0], 0, fc.primary_steps);
+    if (hole) *dst = pack_half4(f2h(o.r), f2h(o.g), f2h(o.b), f2h(o.a));
+}
+
+template <class TS>
+static hipError_t launch_view_update_ts(const TS& t, const FrameConsts* d_fc, const ViewUpdateGeom& g, const uint2* d_prev, uint2* d_out, hipStream_t s) {
+    if (g.sub_w > 0 && g.sub_h > 0) {
+        const unsigned fresh = (unsigned)(((g.sub_w + 31) >> 5) * ((g.sub_h + 7) >> 3));
+        clouds_view_fresh_kernel<TS><<<fresh, 256, 0, s>>>(t, d_fc, g, d_out);
+    }
+    if (g.block > 1) {                                          // B = 1: every pixel is fresh
+        const unsigned grid = (unsigned)(((g.w + 31) >> 5) * ((g.h + 7) >> 3));
+        clouds_view_reproject_kernel<TS><<<grid, 256, 0, s>>>(t, d_fc, g, d_prev, d_out);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_clouds_view_update(const TexSet& t, const TexSet32* t32, const FrameConsts* d_fc, const ViewUpdateGeom& g, const uint2* d_prev, uint2* d_out, hipStream_t s) {
+    if (g.w < 1 || g.h < 1 || g.w > 8192 || g.h > 8192 || g.pitch_px < (uint32_t)g.w) return hipErrorInvalidValue;
+    if (g.block < 1 || g.block > 8 || g.px < 0 || g.px >= g.block || g.py < 0 || g.py >= g.block) return hipErrorInvalidValue;
+    if ((g.has_history != 0) != (d_prev != nullptr) || (d_prev && g.prev_pitch_px < (uint32_t)g.w)) return hipErrorInvalidValue;
+    if (g.sub_w != (g.px < g.w ? (g.w - g.px + g.block - 1) / g.block : 0) || g.sub_h != (g.py < g.h ? (g.h - g.py + g.block - 1) / g.block : 0)) return hipErrorInvalidValue;
+    return t32 ? launch_view_update_ts(*t32, d_fc, g, d_prev, d_out, s) : launch_view_update_ts(t, d_fc, g, d_prev, d_out, s);
+}
+
+}  // namespace csky

@@ -76,6 +76,11 @@ hipError_t launch_sqrt_shell(const float* d_in, float* d_out, size_t n, hipStrea
 // fp32-coefficient cells.  A plain launch in natural order; g travels as a kernel argument.
 struct RaysGeom;
 hipError_t launch_clouds_rays(const TexSet& t, const TexSet32* t32, const FrameConsts* d_fc, const RaysGeom& g, const float* d_dirs, uint2* d_out, hipStream_t s);
+// the temporal split of a view frame (view_update_core.h): the fresh pixels of g's phase over their sub-grid (no launch where the image has none), then
+// every other pixel of the g.w x g.h image from d_prev (row pitch g.prev_pitch_px pixels; NULL exactly when g.has_history is 0) or, where that frame
+// has none, by the march; no second launch for g.block 1.  The two launches write disjoint texels of d_out.  g travels as a kernel argument.
+struct ViewUpdateGeom;
+hipError_t launch_clouds_view_update(const TexSet& t, const TexSet32* t32, const FrameConsts* d_fc, const ViewUpdateGeom& g, const uint2* d_prev, uint2* d_out, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------ shadow.hip
 // the cloud shadow map (shadow_core.h): sc.w x sc.h halfs into d_out, row pitch sc.pitch_h halfs.  fc: shadow_frame_consts; both blocks travel as

@@ -560,6 +560,52 @@ int csky_render_clouds_view_device(csky_ctx* ctx, const csky_cloud_params* p, co
 int csky_composite_view_frames(csky_ctx* ctx, const csky_composite_params* p, const csky_view* view, const uint16_t* cloud_from,
                                const uint16_t* cloud_to, const uint16_t* sky_from, const uint16_t* sky_to, uint16_t* out_rgba16f);
 
+/* ---- the temporal split of a view frame -------------------------------------------- */
+/* csky_render_clouds_view marches every pixel on every call.  These calls march one pixel of every B x B block (B = block) and take every other
+ * pixel from the previous view frame through the previous camera; a pixel that frame does not cover is marched.  The observer of this model does
+ * not move: a cloud texel is a function of a direction alone, so the reprojection is a pure rotation and needs no depth and no motion vectors.
+ * Inputs: the call's push-constant block, the current view and the previous one, the image size w x h, block B in [1, 8], phase in [0, B * B), the
+ * previous view frame prev (RGBA16F, w x h, its own row pitch) and out.  prev may be NULL: prev_view is then not read (nor its pitch) and the call
+ * has no history.
+ * For pixel (i, j), all in fp32 without contraction, in this order:
+ *   e        exactly csky_render_clouds_view's direction of pixel (i, j) for `view`
+ *   accept   that call's rule.  Not accepted: the texel is (0, 0, 0, 0), no sample, no tap, whatever follows
+ *   fresh    i % B == phase % B  and  j % B == phase / B
+ *   same     prev != NULL and the ten floats of view equal those of prev_view bit for bit (decided once per call)
+ *   history  prev == NULL: none.
+ *            same: the texel prev(i, j), copied bit for bit
+ *            otherwise, with c = prev_view->basis (column-major), th = tan(prev fov_y / 2) and asp = w / h as csky_composite_view computes them:
+ *              qx = (c[0]*e.x + c[1]*e.y) + c[2]*e.z     qy likewise with c[3..5]     qz likewise with c[6..8]
+ *              front = qz < 0;   nx = qx / (-qz);   ny = qy / (-qz)
+ *              u = (nx / (th * asp) + 1) * 0.5;     v = (1 - ny / th) * 0.5
+ *              ux = u * w - 0.5;   uy = v * h - 0.5
+ *              valid = front and 0 <= ux <= w - 1 and 0 <= uy <= h - 1        (NaN fails every comparison)
+ *              valid: the bilinear tap of prev at (ux, uy): x0 = floor(ux), ax = ux - x0, likewise y; per channel
+ *                     lerp(lerp(p00, p10, ax), lerp(p01, p11, ax), ay) with lerp(a, b, f) = a + (b - a) * f, stored as a half (round to nearest even)
+ *   texel    accepted and (fresh or no valid history): marched, exactly the texel csky_render_clouds_view gives this pixel for p and view
+ *            accepted, not fresh, valid history: the history texel
+ * The `same` rule is not a shortcut: with an unmoved camera the formula gives ux = i only to within a few 1e-6, which puts edge pixels just outside
+ * [0, w - 1] (they would be marched on every call) and would blur the rest by one bilinear tap per call.
+ * Consequences:
+ *   - block = 1, or prev = NULL, gives the bytes of csky_render_clouds_view.
+ *   - A still camera fed its own output for B * B calls, with phase running over a permutation of 0 .. B * B - 1, converges to the full view frame
+ *     byte for byte while the parameters do not change.
+ *   - With changing parameters (time, wind, sun) a reprojected pixel is up to B * B - 1 calls old, as in the reference's own split.
+ *   - A tap whose footprint straddles the horizon mixes in the zero texels below it.  The compositor fades to the background there anyway.
+ *   - csky_set_early_out with eps > 0 ends a wavefront by a vote of its lanes: a marched pixel then depends on which rays share its wavefront and is
+ *     no longer the full view's byte for byte.  The default (off) keeps the statements above.
+ * State, ranges and errors are csky_render_clouds_view's.  CSKY_ERR_INVALID also for: block outside [1, 8]; phase outside [0, B * B); a non-NULL prev
+ * with a NULL prev_view or one that is not a valid view; a prev pitch that is no multiple of 8 or < 8 w; prev and out byte ranges that overlap.
+ * Like every rays call it takes no slot of the cloud frames' ring and changes nothing a cloud frame reads. */
+/* Blocking host form: prev (or NULL) and out are h * w * 4 halfs, tightly packed. */
+int csky_render_clouds_view_update(csky_ctx* ctx, const csky_cloud_params* p, const csky_view* view, const csky_view* prev_view_or_NULL, int w, int h,
+                                   int block, int phase, const uint16_t* prev_rgba16f_or_NULL, uint16_t* out_rgba16f);
+/* Device form: asynchronous on hip_stream (the context's own stream if NULL), ordered behind the frame set-up the call enqueues on the context's
+ * stream.  d_prev is read on hip_stream.  Writes the w x h texels of d_out and nothing else, and leaves d_prev as it was. */
+int csky_render_clouds_view_update_device(csky_ctx* ctx, const csky_cloud_params* p, const csky_view* view, const csky_view* prev_view_or_NULL, int w,
+                                          int h, int block, int phase, const void* d_prev_rgba16f_or_NULL, size_t prev_row_pitch_bytes,
+                                          void* d_out_rgba16f, size_t row_pitch_bytes, void* hip_stream);
+
 /* ---- depth and aerial perspective for view frames and ray frames ------------------- */
 /* csky_render_cloud_depth and csky_apply_cloud_aerial above serve the hemisphere frame: both take every pixel's direction from the hemi-octahedral
  * grid.  These calls are the same two steps for the image of a direct march (csky_render_clouds_dirs / _view): the direction of pixel (i, j) of a
