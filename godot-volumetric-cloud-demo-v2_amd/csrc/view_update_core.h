@@ -101,6 +101,16 @@ CSKY_HD ViewUpdateClass view_update_classify(const ViewUpdateGeom& g, int i, int
     return c;
 }
 
+// lerp(a, b, f) = a + (b - a) * f of the definition, its three operations rounded one by one.  Not csky_common.h's lerpf: that header states no
+// contraction mode of its own, so lerpf's multiply and add carry the mode of whoever includes it first, and in the device build they fuse into one
+// fma even when inlined here.  A fused tap differs from the definition in the last bit of about one half in 3000
+// (tests/test_gpu_view_cameras.py).
+CSKY_HD float view_update_lerp(float a, float b, float f) {
+    const float d = b - a;
+    const float m = d * f;
+    return a + m;
+}
+
 // The tap: composite_core.h tap_half_clamp's arithmetic from (ux, uy) on, over an image of `pitch_px` pixels per row, each channel stored with f2h.
 // For a VU_TAP's coordinates the clamps only ever move x1 / y1 from w / h to w - 1 / h - 1.
 CSKY_HD uint2 view_update_tap(const uint2* __restrict__ prev, uint32_t pitch_px, int w, int h, float ux, float uy) {
@@ -114,7 +124,7 @@ CSKY_HD uint2 view_update_tap(const uint2* __restrict__ prev, uint32_t pitch_px,
         const uint32_t wa = k < 2 ? a.x : a.y, wb = k < 2 ? b.x : b.y, wc = k < 2 ? c.x : c.y, wd = k < 2 ? d.x : d.y;
         const int sh = (k & 1) * 16;
         const float fa = h2f((uint16_t)(wa >> sh)), fb = h2f((uint16_t)(wb >> sh)), fc = h2f((uint16_t)(wc >> sh)), fd = h2f((uint16_t)(wd >> sh));
-        o[k] = f2h(lerpf(lerpf(fa, fb, ax), lerpf(fc, fd, ax), ay));
+        o[k] = f2h(view_update_lerp(view_update_lerp(fa, fb, ax), view_update_lerp(fc, fd, ax), ay));
     }
     return pack_half4(o[0], o[1], o[2], o[3]);
 }
