@@ -102,6 +102,11 @@ class View(C.Structure):
     _fields_ = [("basis", C.c_float * 9), ("fov_y_degrees", C.c_float)]
 
 
+class Observer(C.Structure):
+    """csky_observer (include/cloudsky.h): the observer's position relative to the reference's camera, in metres, and the cap on a ray's length."""
+    _fields_ = [("position", C.c_float * 3), ("max_distance", C.c_float)]
+
+
 class CloudStats(C.Structure):
     _fields_ = [("rays", C.c_uint64), ("primary_samples", C.c_uint64), ("incloud_samples", C.c_uint64)]
 
@@ -199,6 +204,12 @@ SYMBOLS = [
     ("csky_render_clouds_view_update", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.POINTER(View), C.POINTER(View), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     ("csky_render_clouds_view_update_device", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.POINTER(View), C.POINTER(View), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                                         C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("csky_render_clouds_view_from", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.POINTER(View), C.POINTER(Observer), C.c_int, C.c_int, C.c_void_p]),
+    ("csky_render_clouds_view_from_device", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.POINTER(View), C.POINTER(Observer), C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                                      C.c_void_p]),
+    ("csky_render_clouds_dirs_from", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.c_int, C.c_int, C.c_void_p, C.POINTER(Observer), C.c_void_p]),
+    ("csky_render_clouds_dirs_from_device", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.c_int, C.c_int, C.c_void_p, C.POINTER(Observer), C.c_void_p, C.c_size_t,
+                                                      C.c_void_p]),
     ("csky_render_cloud_depth_dirs", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     ("csky_render_cloud_depth_dirs_device", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("csky_render_cloud_depth_view", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.POINTER(View), C.c_int, C.c_int, C.c_int, C.c_void_p]),
@@ -372,6 +383,16 @@ def _sky_params(sun_dir, w, h):
 
 def _view(basis, fov_y_degrees):
     return View((C.c_float * 9)(*[float(x) for x in np.asarray(basis, np.float32).T.reshape(-1)]), float(fov_y_degrees))   # column-major basis
+
+
+def _observer(name, position, max_distance):
+    """csky_observer from a position of three numbers and a cap; what the library would refuse for its shape or sign is refused here."""
+    pos = [float(x) for x in np.asarray(position, np.float64).reshape(-1)]
+    if len(pos) != 3 or not all(np.isfinite(pos)):
+        raise ValueError("%s: position must be three finite numbers (metres from the reference's camera)" % name)
+    if not float(max_distance) > 0.0:
+        raise ValueError("%s: max_distance must be > 0 (inf: no cap)" % name)
+    return Observer((C.c_float * 3)(*pos), float(max_distance))
 
 
 def _composite_params(out_w, out_h, cloud_wh, sky_wh, light_dir, blend_amount, sun_disk_scale):
@@ -678,14 +699,15 @@ class Context:
         `out`, a new tensor unless given; out may be `cloud`.  Needs the transmittance LUT and nothing else."""
         return self._apply_rays("apply_cloud_aerial", (), sun, cloud, depth, steps, out, stream)
 
-    def _render_image(self, name, params, mid, shape, out, stream, dirs=None):
-        """The one path of every method that renders an image of `shape` from a push-constant block: csky_<name>(ctx, params, *mid[, dirs], out) for a host
-        image (None: a new one), csky_<name>_device(ctx, params, *mid[, dirs], out, pitch, stream) for a tensor, whose row stride is the pitch.  With `dirs`
-        ([h, w, 3]) the directions decide which of the two it is: `out` must be of their kind, and a missing device `out` is made next to them."""
+    def _render_image(self, name, params, mid, shape, out, stream, dirs=None, after=()):
+        """The one path of every method that renders an image of `shape` from a push-constant block: csky_<name>(ctx, params, *mid[, dirs], *after, out) for a
+        host image (None: a new one), csky_<name>_device(ctx, params, *mid[, dirs], *after, out, pitch, stream) for a tensor, whose row stride is the pitch.  With
+        `dirs` ([h, w, 3]) the directions decide which of the two it is: `out` must be of their kind, and a missing device `out` is made next to them."""
         p = cloud_params(params)
         device = hasattr(out if dirs is None else dirs, "data_ptr")
         if dirs is not None:
             mid += (_dirs_arg(name, dirs, device),)
+        mid += tuple(after)
         if device:
             if out is None:
                 import torch
@@ -715,6 +737,23 @@ class Context:
         contiguous; its row stride is the pitch): asynchronous on `stream`, written in place, returns the tensor.  Needs the noise and a sky LUT."""
         v = _view(basis, fov_y_degrees)
         return self._render_image("render_clouds_view", params, (C.byref(v), int(width), int(height)), (int(height), int(width), 4), out, stream)
+
+    def render_clouds_view_from(self, params, basis, fov_y_degrees, width, height, position, max_distance=float("inf"), out=None, stream=None):
+        """render_clouds_view for an observer who stands at `position` (csky_render_clouds_view_from*, definition: include/cloudsky.h): three numbers,
+        metres from the reference's camera, y up; under, inside or above the cloud layer.  Each ray's first segment through the layer is marched, at
+        most `max_distance` metres from the observer; a ray without one gives a zero texel.  position (0, 0, 0) without a cap gives
+        render_clouds_view's bytes.  Host and device path as there."""
+        name = "render_clouds_view_from"
+        v, o = _view(basis, fov_y_degrees), _observer(name, position, max_distance)
+        return self._render_image(name, params, (C.byref(v), C.byref(o), int(width), int(height)), (int(height), int(width), 4), out, stream)
+
+    def render_clouds_dirs_from(self, params, dirs, position, max_distance=float("inf"), out=None, stream=None):
+        """render_clouds_dirs for an observer who stands at `position` (csky_render_clouds_dirs_from*; see render_clouds_view_from).  A direction may
+        point under the horizon; one whose squared length is outside [0.99, 1.01] gives a zero texel.  Host and device path as render_clouds_dirs."""
+        name = "render_clouds_dirs_from"
+        w, h = _dirs_size(name, dirs)
+        o = _observer(name, position, max_distance)
+        return self._render_image(name, params, (w, h), (h, w, 4), out, stream, dirs=dirs, after=(C.byref(o),))
 
     def render_clouds_view_update(self, params, basis, fov_y_degrees, width, height, block, phase, prev=None, prev_basis=None, prev_fov=None, out=None, stream=None):
         """The temporal split of a view frame (csky_render_clouds_view_update*, definition: include/cloudsky.h): one pixel of every block x block

@@ -17,6 +17,7 @@ import numpy as np
 from . import assets as _assets
 from . import tiling as _tiling
 from ._lib import Context
+from ._lib import _observer
 from ._lib import aerial_shadow_rect as _aerial_shadow_rect
 from .sky_lut import SkyLut
 from .transmittance_lut import TransmittanceLut
@@ -267,15 +268,30 @@ class CloudSky:
         sf, st = (host(t) for t in self.sky_lut.back_texture)   # sky_blend_from/to_texture = the two OLDER ring copies (cloud_sky.gd:147-148)
         return self.ctx.composite_sky(bf, bt, sf, st, self.frame_data.LIGHT_DIRECTION, self.blend_amount, self.sun_disk_scale, out_w, out_h)
 
-    def cloud_view(self, basis, fov_y_degrees=75.0, out_w=1152, out_h=648, aerial=False, aerial_steps=16):
+    def cloud_view(self, basis, fov_y_degrees=75.0, out_w=1152, out_h=648, aerial=False, aerial_steps=16, position=None, max_distance=float("inf")):
         """The clouds of the current frame data marched along the rays of a perspective camera's SCREEN pixels instead of the hemisphere frame's
         (csky_render_clouds_view; the definition: include/cloudsky.h): float16 [out_h, out_w, 4], what the hemisphere frame would store for each
         ray, at the camera's own angular resolution; zero under the horizon.  The block _fill_push_constant() packs, the context's step counts.
         basis as sky_view takes it.  A torch CUDA tensor with device_buffers=True.  Not called by update_sky().
         aerial=True: the air in front of the view's clouds under the current sun, aerial_steps steps per pixel (the view's own depth frame, then
-        csky_apply_cloud_aerial_view; with device_buffers=True the three kernels run back to back on the march stream).  Alpha is unchanged."""
+        csky_apply_cloud_aerial_view; with device_buffers=True the three kernels run back to back on the march stream).  Alpha is unchanged.
+        position: the observer's place, three numbers in metres from the reference's camera (y up; under, inside or above the layer), with
+        max_distance the cap on a ray's length from there (csky_render_clouds_view_from).  None: the reference's observer, the call made without it.
+        The aerial step is the ground observer's: aerial=True with a position is a ValueError."""
+        if position is not None and aerial:
+            raise ValueError("cloud_view: aerial=True is the ground observer's step and takes no position")
         pc = self._fill_push_constant()
         sun = self.frame_data.LIGHT_DIRECTION
+        if position is not None:
+            _observer("cloud_view", position, max_distance)      # refused before a frame is allocated
+            if not self.device_buffers:
+                return self.ctx.render_clouds_view_from(pc, basis, fov_y_degrees, out_w, out_h, position, max_distance)
+            import torch
+            out = torch.empty((int(out_h), int(out_w), 4), dtype=torch.float16, device=torch.device("cuda", self.ctx.device_id))
+            stream, done = self._march_stream()
+            self.ctx.render_clouds_view_from(pc, basis, fov_y_degrees, out_w, out_h, position, max_distance, out=out, stream=stream)
+            done()
+            return out
         if not self.device_buffers:
             cv = self.ctx.render_clouds_view(pc, basis, fov_y_degrees, out_w, out_h)
             if not aerial:

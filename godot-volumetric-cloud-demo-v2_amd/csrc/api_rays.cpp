@@ -1,5 +1,5 @@
 // api_rays.cpp -- the direct cloud march's C ABI (csky_render_clouds_dirs / _view and their _device forms; rays_core.h, cloud_kernels.hip
-// clouds_rays_kernel) and the temporal split of a view frame (csky_render_clouds_view_update*; view_update_core.h).
+// clouds_rays_kernel), the same from an observer's position (the _from forms; observer_core.h, clouds_observer_kernel; §21) and the temporal split of a view frame (csky_render_clouds_view_update*; view_update_core.h).
 // The call reads what a cloud frame reads (noise, sky LUT, the march settings) and writes none of it.  Its frame constants come from the cloud
 // frame's own set-up kernel, enqueued on the context's stream into a block of the call's own: no slot of the frame ring, none of the ring's order,
 // feedback or head state, no stream of its own.  The blocking forms work in the context's stage (host_stage.h).
@@ -7,6 +7,7 @@
 #include <cstring>
 #include "context.h"
 #include "rays_core.h"
+#include "observer_core.h"
 #include "view_update_core.h"
 
 using namespace csky;
@@ -63,22 +64,43 @@ template <class F> int rays_run(csky_ctx* c, const char* fn, const csky_cloud_pa
     return CSKY_OK;
 }
 
-// The dirs and view forms' march.  d_dirs: NULL for the view forms.
+// What the _from forms check beyond rays_check, before it (a bad observer is CSKY_ERR_INVALID whatever the context holds): observer_core.h's rule.
+int observer_check(csky_ctx* c, const char* fn, const csky_observer* obs) {
+    if (!obs) return fail(c, CSKY_ERR_INVALID, "%s: observer is NULL", fn);
+    switch (observer_invalid(obs->position, obs->max_distance)) {
+        case 0: return CSKY_OK;
+        case 1: return fail(c, CSKY_ERR_INVALID, "%s: the observer's position is not finite", fn);
+        case 2: return fail(c, CSKY_ERR_INVALID, "%s: the observer's position[0] and position[2] must be within 1e6 m", fn);
+        case 3: return fail(c, CSKY_ERR_INVALID, "%s: the observer is under the ground", fn);
+        case 4: return fail(c, CSKY_ERR_INVALID, "%s: the observer is more than 100 000 m above the ground", fn);
+        default: return fail(c, CSKY_ERR_INVALID, "%s: max_distance must be > 0 (+inf: no cap)", fn);
+    }
+}
+
+// The dirs and view forms' march.  d_dirs: NULL for the view forms.  obs: NULL for the reference's observer, else checked (the _from forms).
 int rays_launch(csky_ctx* c, const char* fn, const csky_cloud_params* p, const csky_view* view, int w, int h, const float* d_dirs, uint2* d_out, size_t pitch_bytes,
-                hipStream_t s) {
-    const RaysGeom g = rays_geom(view ? view->basis : nullptr, view ? view->fov_y_degrees : 0.0f, w, h, (uint32_t)(pitch_bytes / 8));
+                hipStream_t s, const csky_observer* obs = nullptr) {
+    const float* basis = view ? view->basis : nullptr;
+    const float fov = view ? view->fov_y_degrees : 0.0f;
+    if (obs) {
+        const ObserverGeom g = observer_geom(basis, fov, w, h, (uint32_t)(pitch_bytes / 8), obs->position, obs->max_distance);
+        return rays_run(c, fn, p, s, [&](const TexSet& t, const TexSet32* t32) { return launch_clouds_observer(t, t32, c->d_rays_fc, g, d_dirs, d_out, s); });
+    }
+    const RaysGeom g = rays_geom(basis, fov, w, h, (uint32_t)(pitch_bytes / 8));
     return rays_run(c, fn, p, s, [&](const TexSet& t, const TexSet32* t32) { return launch_clouds_rays(t, t32, c->d_rays_fc, g, d_dirs, d_out, s); });
 }
 
-// The blocking host forms: dirs (NULL for a view) up, the image down, on the context's stream.
-int rays_host(csky_ctx* c, const char* fn, const csky_cloud_params* p, const csky_view* view, bool is_view, int w, int h, const float* dirs, uint16_t* out) {
+// The blocking host forms: dirs (NULL for a view) up, the image down, on the context's stream.  from: a _from form, obs its observer.
+int rays_host(csky_ctx* c, const char* fn, const csky_cloud_params* p, const csky_view* view, bool is_view, int w, int h, const float* dirs, uint16_t* out,
+              bool from = false, const csky_observer* obs = nullptr) {
     if (!out) return fail(c, CSKY_ERR_INVALID, "%s: out is NULL", fn);
     if (!is_view && !dirs) return fail(c, CSKY_ERR_INVALID, "%s: dirs_xyz is NULL", fn);
-    int rc; if ((rc = rays_check(c, fn, p, view, is_view, w, h, (w >= 1 && w <= 8192) ? (size_t)w * 8 : 8)) || (rc = bind(c))) return rc;
+    int rc; if (from && (rc = observer_check(c, fn, obs))) return rc;
+    if ((rc = rays_check(c, fn, p, view, is_view, w, h, (w >= 1 && w <= 8192) ? (size_t)w * 8 : 8)) || (rc = bind(c))) return rc;
     const size_t n = (size_t)w * h, db = is_view ? 0 : n * 3 * sizeof(float);
     HostCall hc = host_call(c, fn, {db, n * 8});
     hc.up(0, dirs, db);
-    hc.step([&] { return rays_launch(c, fn, p, view, w, h, is_view ? nullptr : hc.at<float>(0), hc.at<uint2>(1), (size_t)w * 8, c->stream); });
+    hc.step([&] { return rays_launch(c, fn, p, view, w, h, is_view ? nullptr : hc.at<float>(0), hc.at<uint2>(1), (size_t)w * 8, c->stream, obs); });
     hc.down(out, 1, n * 8);
     return hc.finish();
 }
@@ -165,6 +187,37 @@ int csky_render_clouds_view_device(csky_ctx* c, const csky_cloud_params* p, cons
     if (!d_out) return fail(c, CSKY_ERR_INVALID, "%s: d_out is NULL", fn);
     int rc; if ((rc = rays_check(c, fn, p, view, true, w, h, pitch)) || (rc = bind(c))) return rc;
     return rays_launch(c, fn, p, view, w, h, nullptr, static_cast<uint2*>(d_out), pitch, stream_of(c, hip_stream));
+}
+
+// ---- the same from an observer's position (observer_core.h)
+int csky_render_clouds_dirs_from(csky_ctx* c, const csky_cloud_params* p, int w, int h, const float* dirs, const csky_observer* obs, uint16_t* out) {
+    const char* fn = "csky_render_clouds_dirs_from";
+    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "%s: ctx is NULL", fn);
+    return rays_host(c, fn, p, nullptr, false, w, h, dirs, out, true, obs);
+}
+
+int csky_render_clouds_view_from(csky_ctx* c, const csky_cloud_params* p, const csky_view* view, const csky_observer* obs, int w, int h, uint16_t* out) {
+    const char* fn = "csky_render_clouds_view_from";
+    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "%s: ctx is NULL", fn);
+    return rays_host(c, fn, p, view, true, w, h, nullptr, out, true, obs);
+}
+
+int csky_render_clouds_dirs_from_device(csky_ctx* c, const csky_cloud_params* p, int w, int h, const void* d_dirs, const csky_observer* obs, void* d_out, size_t pitch,
+                                        void* hip_stream) {
+    const char* fn = "csky_render_clouds_dirs_from_device";
+    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "%s: ctx is NULL", fn);
+    if (!d_dirs || !d_out) return fail(c, CSKY_ERR_INVALID, "%s: d_dirs_xyz or d_out is NULL", fn);
+    int rc; if ((rc = observer_check(c, fn, obs)) || (rc = rays_check(c, fn, p, nullptr, false, w, h, pitch)) || (rc = bind(c))) return rc;
+    return rays_launch(c, fn, p, nullptr, w, h, static_cast<const float*>(d_dirs), static_cast<uint2*>(d_out), pitch, stream_of(c, hip_stream), obs);
+}
+
+int csky_render_clouds_view_from_device(csky_ctx* c, const csky_cloud_params* p, const csky_view* view, const csky_observer* obs, int w, int h, void* d_out, size_t pitch,
+                                        void* hip_stream) {
+    const char* fn = "csky_render_clouds_view_from_device";
+    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "%s: ctx is NULL", fn);
+    if (!d_out) return fail(c, CSKY_ERR_INVALID, "%s: d_out is NULL", fn);
+    int rc; if ((rc = observer_check(c, fn, obs)) || (rc = rays_check(c, fn, p, view, true, w, h, pitch)) || (rc = bind(c))) return rc;
+    return rays_launch(c, fn, p, view, w, h, nullptr, static_cast<uint2*>(d_out), pitch, stream_of(c, hip_stream), obs);
 }
 
 }  // extern "C"

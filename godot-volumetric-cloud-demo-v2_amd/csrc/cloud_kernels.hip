@@ -286,7 +286,9 @@ __device__ __forceinline__ void light_march_terms(const TS& T, const FrameConsts
 // samples in the same order either way (a latched ray's were never queued), so flushes, latch tests and the stored halfs are those of TALLY = true
 // (tests/tilewalk emulates both per tile; tests/test_gpu_latched_rays.py compares the frames).  MarchOut::incloud is 0 and must not be read.
 // CT: the cloud-type mode of the frame as a compile-time value (cloud_core.h density_height_gradient); 0 reads fc.ct_mode per evaluation.
-template <bool WHOLE, bool TALLY, int CT = 0, class TS>
+// RISING: every ray of the call starts on the inner shell and runs outwards (every caller but clouds_observer_kernel).  It guards the early end below and
+// nothing else; without it the wavefront ends once no lane is live, which needs no assumption about the rays.
+template <bool WHOLE, bool TALLY, int CT = 0, class TS, bool RISING = true>
 __device__ __forceinline__ MarchOut march_compact(const TS& T, const FrameConsts& fc, Ray ray, float* __restrict__ q, int step_begin, int step_end) {
     constexpr bool SAT = WHOLE && !TS::cell32;
     constexpr bool DEAD = SAT && !TALLY;                      // a latched ray stops marching
@@ -346,7 +348,11 @@ __device__ __forceinline__ MarchOut march_compact(const TS& T, const FrameConsts
             // tests/test_hostsim_core.py), so once EVERY live ray of the wavefront is above the height window
             // (density() == 0 there, cloud_core.h) all remaining samples are 0 too.  Checked every 4th step: one compare + ballot.
             // 21 % of the wave-steps of the headline view lie above the window (tools/stage_trace).
-            if ((i & 3) == 3 && __builtin_amdgcn_ballot_w64(below_top) == 0ull) end = i + 1;
+            if constexpr (RISING) {
+                if ((i & 3) == 3 && __builtin_amdgcn_ballot_w64(below_top) == 0ull) end = i + 1;
+            } else {                                         // rays that descend, or dip and rise: a lane above the window may come back into it
+                if ((i & 3) == 3 && __builtin_amdgcn_ballot_w64(live) == 0ull) end = i + 1;
+            }
             const unsigned long long m = __builtin_amdgcn_ballot_w64(have);
             if (m != 0ull) {
                 const int slot = count + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
@@ -1083,6 +1089,56 @@ hipError_t launch_clouds_view_update(const TexSet& t, const TexSet32* t32, const
     if ((g.has_history != 0) != (d_prev != nullptr) || (d_prev && g.prev_pitch_px < (uint32_t)g.w)) return hipErrorInvalidValue;
     if (g.sub_w != (g.px < g.w ? (g.w - g.px + g.block - 1) / g.block : 0) || g.sub_h != (g.py < g.h ? (g.h - g.py + g.block - 1) / g.block : 0)) return hipErrorInvalidValue;
     return t32 ? launch_view_update_ts(*t32, d_fc, g, d_prev, d_out, s) : launch_view_update_ts(t, d_fc, g, d_prev, d_out, s);
+}
+
+}  // namespace csky
+
+// ---- the direct march from an observer's position -------------------------------------------------------------------
+// clouds_rays_kernel with another front end: observer_core.h observer_ray makes the lane's Ray from its direction AND the observer's position (under,
+// inside or above the layer; the first segment through the layer, capped).  The same shape: one pixel per lane, an 8x8 tile per wavefront, four
+// tiles per workgroup, the same LDS queue and launch bound, a plain launch in natural order.  march_compact<true, false, 0, TS, false>: these rays
+// descend, or dip and rise, so the wavefront's early end is "no lane is live" and not "every lane is above the window".
+#include "observer_core.h"
+#pragma clang fp contract(off)   // (observer_core.h ends with contraction on, like rays_core.h)
+
+namespace csky {
+
+// SRC 0: directions from `dirs` ([H][W][3] floats, tightly packed); 1: the view of G.g (composite_eyedir, view_mode 1)
+template <int SRC, class TS>
+__global__ __launch_bounds__(256, CSKY_COMPACT_WAVES) void clouds_observer_kernel(TS T, const FrameConsts* __restrict__ fcp, ObserverGeom G, const float* __restrict__ dirs,
+                                                                                  uint2* __restrict__ out) {
+    __shared__ float lds[4][CQ_FLOATS];
+    const int tiles_x = (G.g.w + 31) >> 5;
+    const int slab = (int)blockIdx.x / tiles_x, bx = (int)blockIdx.x - slab * tiles_x;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int gx = bx * 32 + wave * 8 + (lane & 7);
+    const int gy = slab * 8 + (lane >> 3);
+    const bool valid = gx < G.g.w && gy < G.g.h;
+    const FrameConsts& fc = *fcp;
+    T.detail_lds = nullptr;                                    // compile-time constant here: the LDS tap path folds away
+    float ex = 0.0f, ey = 0.0f, ez = 0.0f;                     // (0, 0, 0) fails observer_accept
+    if constexpr (SRC == 0) {
+        if (valid) { const float* __restrict__ d = dirs + ((size_t)gy * (size_t)G.g.w + (size_t)gx) * 3; ex = d[0]; ey = d[1]; ez = d[2]; }
+    } else {
+        rays_view_dir(G.g, valid ? gx : 0, valid ? gy : 0, ex, ey, ez);
+    }
+    Ray ray = observer_ray(fc, G, ex, ey, ez);
+    if (!valid) ray.above = false;
+    const MarchOut o = march_compact<true, false, 0, TS, false>(T, fc, ray, &lds[wave][0], 0, fc.primary_steps);
+    if (valid) out[(size_t)gy * G.g.pitch_px + gx] = pack_half4(f2h(o.r), f2h(o.g), f2h(o.b), f2h(o.a));   // store_pixel's packing
+}
+
+hipError_t launch_clouds_observer(const TexSet& t, const TexSet32* t32, const FrameConsts* d_fc, const ObserverGeom& g, const float* d_dirs, uint2* d_out, hipStream_t s) {
+    if (g.g.w < 1 || g.g.h < 1 || g.g.w > 8192 || g.g.h > 8192 || g.g.pitch_px < (uint32_t)g.g.w) return hipErrorInvalidValue;
+    const unsigned grid = (unsigned)(((g.g.w + 31) >> 5) * ((g.g.h + 7) >> 3));
+    if (t32) {
+        if (d_dirs) clouds_observer_kernel<0, TexSet32><<<grid, 256, 0, s>>>(*t32, d_fc, g, d_dirs, d_out);
+        else clouds_observer_kernel<1, TexSet32><<<grid, 256, 0, s>>>(*t32, d_fc, g, d_dirs, d_out);
+    } else {
+        if (d_dirs) clouds_observer_kernel<0, TexSet><<<grid, 256, 0, s>>>(t, d_fc, g, d_dirs, d_out);
+        else clouds_observer_kernel<1, TexSet><<<grid, 256, 0, s>>>(t, d_fc, g, d_dirs, d_out);
+    }
+    return hipGetLastError();
 }
 
 }  // namespace csky

@@ -81,6 +81,10 @@ hipError_t launch_clouds_rays(const TexSet& t, const TexSet32* t32, const FrameC
 // has none, by the march; no second launch for g.block 1.  The two launches write disjoint texels of d_out.  g travels as a kernel argument.
 struct ViewUpdateGeom;
 hipError_t launch_clouds_view_update(const TexSet& t, const TexSet32* t32, const FrameConsts* d_fc, const ViewUpdateGeom& g, const uint2* d_prev, uint2* d_out, hipStream_t s);
+// the direct march from an observer's position (observer_core.h): launch_clouds_rays for the rays of g.g seen from g.o, each ray's first segment
+// through the layer capped at g.max_dist.  g travels as a kernel argument.
+struct ObserverGeom;
+hipError_t launch_clouds_observer(const TexSet& t, const TexSet32* t32, const FrameConsts* d_fc, const ObserverGeom& g, const float* d_dirs, uint2* d_out, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------ shadow.hip
 // the cloud shadow map (shadow_core.h): sc.w x sc.h halfs into d_out, row pitch sc.pitch_h halfs.  fc: shadow_frame_consts; both blocks travel as

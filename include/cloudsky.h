@@ -596,7 +596,8 @@ int csky_composite_view_frames(csky_ctx* ctx, const csky_composite_params* p, co
  *     no longer the full view's byte for byte.  The default (off) keeps the statements above.
  * State, ranges and errors are csky_render_clouds_view's.  CSKY_ERR_INVALID also for: block outside [1, 8]; phase outside [0, B * B); a non-NULL prev
  * with a NULL prev_view or one that is not a valid view; a prev pitch that is no multiple of 8 or < 8 w; prev and out byte ranges that overlap.
- * Like every rays call it takes no slot of the cloud frames' ring and changes nothing a cloud frame reads. */
+ * Like every rays call it takes no slot of the cloud frames' ring and changes nothing a cloud frame reads.
+ * The reprojection assumes the fixed observer: it has no counterpart for csky_render_clouds_view_from, whose observer may move between calls. */
 /* Blocking host form: prev (or NULL) and out are h * w * 4 halfs, tightly packed. */
 int csky_render_clouds_view_update(csky_ctx* ctx, const csky_cloud_params* p, const csky_view* view, const csky_view* prev_view_or_NULL, int w, int h,
                                    int block, int phase, const uint16_t* prev_rgba16f_or_NULL, uint16_t* out_rgba16f);
@@ -605,6 +606,47 @@ int csky_render_clouds_view_update(csky_ctx* ctx, const csky_cloud_params* p, co
 int csky_render_clouds_view_update_device(csky_ctx* ctx, const csky_cloud_params* p, const csky_view* view, const csky_view* prev_view_or_NULL, int w,
                                           int h, int block, int phase, const void* d_prev_rgba16f_or_NULL, size_t prev_row_pitch_bytes,
                                           void* d_out_rgba16f, size_t row_pitch_bytes, void* hip_stream);
+
+/* ---- the direct cloud march from an observer's position ---------------------------- */
+/* Every call above sees the clouds from clouds.glsl's camPos = (0, g_radius, 0).  These calls are csky_render_clouds_view / _dirs for an observer
+ * who stands elsewhere: on a hill, inside the layer, above it looking down.  The march is the same; only the ray's set-up differs.
+ *   position      metres, relative to the reference's camera, in the reference's axes (y up).  The world point is
+ *                 o = (position[0], G_RADIUS + position[1], position[2]) with G_RADIUS = 6 000 000, formed once on the host in fp32.
+ *   max_distance  metres along the ray, measured from the observer; +inf means no cap.  A level ray from inside the layer stays inside it for up
+ *                 to about 350 km: N steps over that say little about the clouds close by.
+ * For pixel (i, j), N = the context's primary steps, B = 6 001 500 and T = 6 004 000 the layer's shells; fp32 without contraction, in this order:
+ *   e        the direct march's direction (the view's EYEDIR, or dirs[j * W + i] as given)
+ *   accept   0.99 <= (e.x*e.x + e.y*e.y) + e.z*e.z <= 1.01        (the direct march's rule WITHOUT its e.y > 0; NaN fails)
+ *   isect(r) a = e.e;  b = 2*(e.x*o.x + e.y*o.y + e.z*o.z);  c = (o.x*o.x + o.y*o.y + o.z*o.z) - r*r      (clouds.glsl:97-105 with pos = o)
+ *            D = b*b - 4*a*c;  d = sqrtf(D);  near = fminf(-b-d, -b+d)/(2a);  far = fmaxf(-b-d, -b+d)/(2a)
+ *   where    cb = c(B), ct = c(T):   below: cb < 0;   above: ct > 0;   inside: otherwise
+ *   segment  below : blocked = b <= 0 and D(G_RADIUS) >= 0 -> no segment;   else t0 = far(B), t1 = far(T)
+ *            inside: t0 = 0;  t1 = (b < 0 and D(B) >= 0) ? near(B) : far(T)
+ *            above : no segment unless b < 0 and D(T) >= 0;  t0 = near(T);  t1 = D(B) >= 0 ? near(B) : far(T)
+ *   cap      t1 = fminf(t1, max_distance)
+ *   marched  accepted, a segment, and t1 > t0  (NaN fails).  Otherwise the texel is (0, 0, 0, 0) and the ray takes no sample
+ *   ray      start = o + e*t0, end = o + e*t1; shelldist = |end - start|; raystep = e * shelldist / N; ss = |raystep|; dir = raystep / ss; p = start
+ *   texel    march() of clouds.glsl:139-215 on that ray: N samples, the first one full step past `start`, L.rgb, alpha, four halves
+ * Only the first segment through the layer is marched: a ray from above that leaves through the bottom, or a tangent ray that leaves through the
+ * top, does not re-enter.  With position = (0, 0, 0) and max_distance = +inf the calls give the bytes of csky_render_clouds_view / _dirs.
+ * Limits: the frame constants (sun, ambient and ground colours from the sky LUT) stay those of the ground observer, the atmosphere LUT's eye does
+ * not move; there is no planet shadow; the depth frame, the aerial step, the temporal split and csky_composite_view_frames (whose horizon and
+ * ground line are the ground observer's) have no _from form.
+ * State, ranges and errors are csky_render_clouds_view's / _dirs'.  CSKY_ERR_INVALID also, before the context's state is looked at, for: a NULL
+ * observer; a non-finite position; |position[0]| or |position[2]| above 1e6; |o| (fp32) below G_RADIUS or above G_RADIUS + 100 000; a
+ * max_distance that is not > 0 (NaN included).  Like every rays call they take no slot of the cloud frames' ring and change nothing a cloud
+ * frame reads. */
+typedef struct { float position[3]; float max_distance; } csky_observer;
+/* Blocking host forms. */
+int csky_render_clouds_view_from(csky_ctx* ctx, const csky_cloud_params* p, const csky_view* view, const csky_observer* observer, int w, int h,
+                                 uint16_t* out_rgba16f);
+int csky_render_clouds_dirs_from(csky_ctx* ctx, const csky_cloud_params* p, int w, int h, const float* dirs_xyz, const csky_observer* observer,
+                                 uint16_t* out_rgba16f);
+/* Device forms: as csky_render_clouds_view_device / _dirs_device. */
+int csky_render_clouds_view_from_device(csky_ctx* ctx, const csky_cloud_params* p, const csky_view* view, const csky_observer* observer, int w, int h,
+                                        void* d_out_rgba16f, size_t row_pitch_bytes, void* hip_stream);
+int csky_render_clouds_dirs_from_device(csky_ctx* ctx, const csky_cloud_params* p, int w, int h, const void* d_dirs_xyz, const csky_observer* observer,
+                                        void* d_out_rgba16f, size_t row_pitch_bytes, void* hip_stream);
 
 /* ---- depth and aerial perspective for view frames and ray frames ------------------- */
 /* csky_render_cloud_depth and csky_apply_cloud_aerial above serve the hemisphere frame: both take every pixel's direction from the hemi-octahedral
