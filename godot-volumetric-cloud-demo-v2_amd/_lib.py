@@ -107,6 +107,14 @@ class Observer(C.Structure):
     _fields_ = [("position", C.c_float * 3), ("max_distance", C.c_float)]
 
 
+class SceneDepth(C.Structure):
+    """csky_scene_depth (include/cloudsky.h): a float32 depth buffer of the host's scene, its row pitch in bytes and the kind of its texels."""
+    _fields_ = [("texels", C.c_void_p), ("pitch_bytes", C.c_size_t), ("kind", C.c_int)]
+
+
+DEPTH_KINDS = {"distance": 0, "view_z": 1}           # CSKY_DEPTH_DISTANCE, CSKY_DEPTH_VIEW_Z
+
+
 class CloudStats(C.Structure):
     _fields_ = [("rays", C.c_uint64), ("primary_samples", C.c_uint64), ("incloud_samples", C.c_uint64)]
 
@@ -210,6 +218,14 @@ SYMBOLS = [
     ("csky_render_clouds_dirs_from", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.c_int, C.c_int, C.c_void_p, C.POINTER(Observer), C.c_void_p]),
     ("csky_render_clouds_dirs_from_device", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.c_int, C.c_int, C.c_void_p, C.POINTER(Observer), C.c_void_p, C.c_size_t,
                                                       C.c_void_p]),
+    ("csky_render_clouds_view_from_depth", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.POINTER(View), C.POINTER(Observer), C.c_int, C.c_int, C.POINTER(SceneDepth),
+                                                     C.c_void_p]),
+    ("csky_render_clouds_view_from_depth_device", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.POINTER(View), C.POINTER(Observer), C.c_int, C.c_int, C.POINTER(SceneDepth),
+                                                            C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("csky_render_clouds_dirs_from_depth", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.c_int, C.c_int, C.c_void_p, C.POINTER(Observer), C.POINTER(SceneDepth),
+                                                     C.c_void_p]),
+    ("csky_render_clouds_dirs_from_depth_device", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.c_int, C.c_int, C.c_void_p, C.POINTER(Observer), C.POINTER(SceneDepth),
+                                                            C.c_void_p, C.c_size_t, C.c_void_p]),
     ("csky_render_cloud_depth_dirs", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     ("csky_render_cloud_depth_dirs_device", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("csky_render_cloud_depth_view", C.c_int, [C.c_void_p, C.POINTER(CloudParams), C.POINTER(View), C.c_int, C.c_int, C.c_int, C.c_void_p]),
@@ -393,6 +409,29 @@ def _observer(name, position, max_distance):
     if not float(max_distance) > 0.0:
         raise ValueError("%s: max_distance must be > 0 (inf: no cap)" % name)
     return Observer((C.c_float * 3)(*pos), float(max_distance))
+
+
+def _scene_depth(name, depth, depth_kind, w, h, is_view):
+    """(csky_scene_depth, whether it lies on the device) from a float32 [h, w] depth buffer: a numpy array (the host forms) or a torch tensor (the
+    device forms), its texels contiguous and its row stride the pitch.  Nothing is converted or copied: the struct points into `depth`."""
+    if depth_kind not in DEPTH_KINDS:
+        raise ValueError("%s: depth_kind must be one of %s" % (name, sorted(DEPTH_KINDS)))
+    if depth_kind == "view_z" and not is_view:
+        raise ValueError("%s: a view_z depth needs a camera: the dirs form takes distances along its rays" % name)
+    device = hasattr(depth, "data_ptr")
+    shape = (int(h), int(w))
+    if device:
+        import torch
+        ok = depth.dtype == torch.float32 and tuple(depth.shape) == shape
+        stride, ptr = (tuple(depth.stride()), int(depth.data_ptr())) if ok else ((0, 0), 0)
+    else:
+        ok = isinstance(depth, np.ndarray) and depth.dtype == np.float32 and depth.shape == shape
+        stride, ptr = (tuple(s // 4 if s % 4 == 0 else 0 for s in depth.strides), depth.ctypes.data) if ok else ((0, 0), 0)
+    ok = ok and (shape[1] == 1 or stride[1] == 1) and (shape[0] == 1 or stride[0] >= shape[1])
+    if not ok:
+        raise ValueError("%s: depth must be a float32 %s array (or torch tensor on the GPU) whose texels are contiguous, its row stride the pitch" % (name, shape))
+    pitch = stride[0] * 4 if shape[0] > 1 else shape[1] * 4
+    return SceneDepth(C.c_void_p(ptr), pitch, DEPTH_KINDS[depth_kind]), device
 
 
 def _composite_params(out_w, out_h, cloud_wh, sky_wh, light_dir, blend_amount, sun_disk_scale):
@@ -754,6 +793,38 @@ class Context:
         w, h = _dirs_size(name, dirs)
         o = _observer(name, position, max_distance)
         return self._render_image(name, params, (w, h), (h, w, 4), out, stream, dirs=dirs, after=(C.byref(o),))
+
+    def render_clouds_view_from_depth(self, params, basis, fov_y_degrees, width, height, position, depth, depth_kind="distance", max_distance=float("inf"), out=None,
+                                      stream=None):
+        """render_clouds_view_from behind the host's scene (csky_render_clouds_view_from_depth*, definition: include/cloudsky.h): `depth` is a float32
+        [height, width] buffer in metres, along each pixel's ray from the observer (depth_kind "distance") or along the camera's forward axis
+        ("view_z", a rasteriser's linear depth).  Each ray ends at its pixel's depth as well as at max_distance: the frame holds the cloud in front
+        of the geometry.  inf: nothing in the way; 0, negatives and NaN: geometry at the lens, a zero texel.  The kind of `depth` selects the path:
+        a numpy array the host path (out None or a numpy float16 array; blocks, returns numpy), a float32 torch tensor on this context's GPU whose
+        texels are contiguous, its row stride the pitch, the device path (out as render_clouds_view's or None for a new tensor; asynchronous on
+        `stream`).  depth and out must not overlap."""
+        name = "render_clouds_view_from_depth"
+        shape = (int(height), int(width), 4)
+        v, o = _view(basis, fov_y_degrees), _observer(name, position, max_distance)
+        d, device = _scene_depth(name, depth, depth_kind, width, height, True)
+        if out is not None and hasattr(out, "data_ptr") != device:
+            raise ValueError("%s: depth and out must both be numpy arrays or both be tensors on the GPU" % name)
+        if device and out is None:
+            import torch
+            out = torch.empty(shape, dtype=torch.float16, device=depth.device)
+        return self._render_image(name, params, (C.byref(v), C.byref(o), int(width), int(height), C.byref(d)), shape, out, stream)
+
+    def render_clouds_dirs_from_depth(self, params, dirs, position, depth, depth_kind="distance", max_distance=float("inf"), out=None, stream=None):
+        """render_clouds_dirs_from behind the host's scene (csky_render_clouds_dirs_from_depth*; see render_clouds_view_from_depth): `depth` is a
+        float32 [h, w] buffer of metres along each of the caller's rays; "distance" is its only kind.  dirs and depth are both numpy arrays (the
+        host path) or both tensors on this context's GPU (the device path)."""
+        name = "render_clouds_dirs_from_depth"
+        w, h = _dirs_size(name, dirs)
+        o = _observer(name, position, max_distance)
+        d, device = _scene_depth(name, depth, depth_kind, w, h, False)
+        if hasattr(dirs, "data_ptr") != device:
+            raise ValueError("%s: dirs and depth must both be numpy arrays or both be tensors on the GPU" % name)
+        return self._render_image(name, params, (w, h), (h, w, 4), out, stream, dirs=dirs, after=(C.byref(o), C.byref(d)))
 
     def render_clouds_view_update(self, params, basis, fov_y_degrees, width, height, block, phase, prev=None, prev_basis=None, prev_fov=None, out=None, stream=None):
         """The temporal split of a view frame (csky_render_clouds_view_update*, definition: include/cloudsky.h): one pixel of every block x block

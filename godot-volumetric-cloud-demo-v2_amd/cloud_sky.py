@@ -18,6 +18,7 @@ from . import assets as _assets
 from . import tiling as _tiling
 from ._lib import Context
 from ._lib import _observer
+from ._lib import _scene_depth
 from ._lib import aerial_shadow_rect as _aerial_shadow_rect
 from .sky_lut import SkyLut
 from .transmittance_lut import TransmittanceLut
@@ -268,7 +269,8 @@ class CloudSky:
         sf, st = (host(t) for t in self.sky_lut.back_texture)   # sky_blend_from/to_texture = the two OLDER ring copies (cloud_sky.gd:147-148)
         return self.ctx.composite_sky(bf, bt, sf, st, self.frame_data.LIGHT_DIRECTION, self.blend_amount, self.sun_disk_scale, out_w, out_h)
 
-    def cloud_view(self, basis, fov_y_degrees=75.0, out_w=1152, out_h=648, aerial=False, aerial_steps=16, position=None, max_distance=float("inf")):
+    def cloud_view(self, basis, fov_y_degrees=75.0, out_w=1152, out_h=648, aerial=False, aerial_steps=16, position=None, max_distance=float("inf"), scene_depth=None,
+                   depth_kind="distance"):
         """The clouds of the current frame data marched along the rays of a perspective camera's SCREEN pixels instead of the hemisphere frame's
         (csky_render_clouds_view; the definition: include/cloudsky.h): float16 [out_h, out_w, 4], what the hemisphere frame would store for each
         ray, at the camera's own angular resolution; zero under the horizon.  The block _fill_push_constant() packs, the context's step counts.
@@ -277,19 +279,31 @@ class CloudSky:
         csky_apply_cloud_aerial_view; with device_buffers=True the three kernels run back to back on the march stream).  Alpha is unchanged.
         position: the observer's place, three numbers in metres from the reference's camera (y up; under, inside or above the layer), with
         max_distance the cap on a ray's length from there (csky_render_clouds_view_from).  None: the reference's observer, the call made without it.
-        The aerial step is the ground observer's: aerial=True with a position is a ValueError."""
-        if position is not None and aerial:
-            raise ValueError("cloud_view: aerial=True is the ground observer's step and takes no position")
+        The aerial step is the ground observer's: aerial=True with a position is a ValueError.
+        scene_depth: the host's scene in front of the camera, float32 [out_h, out_w] metres along each pixel's ray (depth_kind "distance") or along
+        the camera's forward axis ("view_z"): each ray ends at its pixel's depth, so the frame holds the cloud in front of the geometry
+        (csky_render_clouds_view_from_depth).  A numpy array without device_buffers, a torch CUDA tensor with them.  Beside it position=None
+        means (0, 0, 0); aerial=True is refused as beside a position."""
+        if (position is not None or scene_depth is not None) and aerial:
+            raise ValueError("cloud_view: aerial=True is the ground observer's step and takes no position and no scene depth")
+        if scene_depth is not None and position is None:
+            position = (0.0, 0.0, 0.0)
         pc = self._fill_push_constant()
         sun = self.frame_data.LIGHT_DIRECTION
         if position is not None:
             _observer("cloud_view", position, max_distance)      # refused before a frame is allocated
+            if scene_depth is not None:
+                if _scene_depth("cloud_view", scene_depth, depth_kind, out_w, out_h, True)[1] != bool(self.device_buffers):
+                    raise ValueError("cloud_view: scene_depth must be a numpy array without device_buffers and a tensor on the GPU with them")
+                march, extra = self.ctx.render_clouds_view_from_depth, (scene_depth, depth_kind, max_distance)
+            else:
+                march, extra = self.ctx.render_clouds_view_from, (max_distance,)
             if not self.device_buffers:
-                return self.ctx.render_clouds_view_from(pc, basis, fov_y_degrees, out_w, out_h, position, max_distance)
+                return march(pc, basis, fov_y_degrees, out_w, out_h, position, *extra)
             import torch
             out = torch.empty((int(out_h), int(out_w), 4), dtype=torch.float16, device=torch.device("cuda", self.ctx.device_id))
             stream, done = self._march_stream()
-            self.ctx.render_clouds_view_from(pc, basis, fov_y_degrees, out_w, out_h, position, max_distance, out=out, stream=stream)
+            march(pc, basis, fov_y_degrees, out_w, out_h, position, *extra, out=out, stream=stream)
             done()
             return out
         if not self.device_buffers:

@@ -1,5 +1,6 @@
 // api_rays.cpp -- the direct cloud march's C ABI (csky_render_clouds_dirs / _view and their _device forms; rays_core.h, cloud_kernels.hip
-// clouds_rays_kernel), the same from an observer's position (the _from forms; observer_core.h, clouds_observer_kernel; §21) and the temporal split of a view frame (csky_render_clouds_view_update*; view_update_core.h).
+// clouds_rays_kernel), the same from an observer's position (the _from forms; observer_core.h, clouds_observer_kernel; §21), that behind a per-pixel scene depth (the
+// _from_depth forms; scene_depth_core.h, clouds_observer_depth_kernel; §22) and the temporal split of a view frame (csky_render_clouds_view_update*; view_update_core.h).
 // The call reads what a cloud frame reads (noise, sky LUT, the march settings) and writes none of it.  Its frame constants come from the cloud
 // frame's own set-up kernel, enqueued on the context's stream into a block of the call's own: no slot of the frame ring, none of the ring's order,
 // feedback or head state, no stream of its own.  The blocking forms work in the context's stage (host_stage.h).
@@ -8,6 +9,7 @@
 #include "context.h"
 #include "rays_core.h"
 #include "observer_core.h"
+#include "scene_depth_core.h"
 #include "view_update_core.h"
 
 using namespace csky;
@@ -132,6 +134,59 @@ int update_launch(csky_ctx* c, const char* fn, const csky_cloud_params* p, const
     return rays_run(c, fn, p, s, [&](const TexSet& t, const TexSet32* t32) { return launch_clouds_view_update(t, t32, c->d_rays_fc, g, d_prev, d_out, s); });
 }
 
+// ---- the observer's march behind a per-pixel scene depth (scene_depth_core.h)
+// What the _from_depth forms check beyond observer_check and rays_check, before them: scene_depth_core.h's rule.  out, pitch: the device forms' image (the
+// overlap test); NULL for the host forms, whose depth is staged.
+int depth_check(csky_ctx* c, const char* fn, const csky_scene_depth* depth, bool is_view, bool host_form, int w, int h, const void* out, size_t pitch) {
+    if (!depth) return fail(c, CSKY_ERR_INVALID, "%s: depth is NULL", fn);
+    switch (scene_depth_invalid((uintptr_t)depth->texels, depth->pitch_bytes, depth->kind, is_view, host_form, w, h, (uintptr_t)out, pitch)) {
+        case 0: return CSKY_OK;
+        case 1: return fail(c, CSKY_ERR_INVALID, "%s: depth->texels is NULL", fn);
+        case 2: return fail(c, CSKY_ERR_INVALID, "%s: depth->kind must be CSKY_DEPTH_DISTANCE or CSKY_DEPTH_VIEW_Z", fn);
+        case 3: return fail(c, CSKY_ERR_INVALID, "%s: CSKY_DEPTH_VIEW_Z needs a view: the dirs forms take CSKY_DEPTH_DISTANCE only", fn);
+        case 4: return fail(c, CSKY_ERR_INVALID, "%s: the depth buffer's row pitch must be a multiple of 4 and >= 4 * w", fn);
+        default: return fail(c, CSKY_ERR_INVALID, "%s: the depth buffer and out overlap", fn);
+    }
+}
+
+// The march of a _from_depth form, for arguments the checks have passed.  d_dirs: NULL for the view forms.  d_depth, depth_pitch (bytes): on the device.
+int depth_launch(csky_ctx* c, const char* fn, const csky_cloud_params* p, const csky_view* view, int w, int h, const float* d_dirs, const csky_observer* obs, const float* d_depth,
+                 size_t depth_pitch, int kind, uint2* d_out, size_t pitch_bytes, hipStream_t s) {
+    const SceneDepthGeom g = scene_depth_geom(view ? view->basis : nullptr, view ? view->fov_y_degrees : 0.0f, w, h, (uint32_t)(pitch_bytes / 8), obs->position, obs->max_distance,
+                                              (uint32_t)(depth_pitch / 4), kind);
+    return rays_run(c, fn, p, s, [&](const TexSet& t, const TexSet32* t32) { return launch_clouds_observer_depth(t, t32, c->d_rays_fc, g, d_dirs, d_depth, d_out, s); });
+}
+
+// The blocking host forms: dirs (NULL for a view) and the depth buffer up, the image down, on the context's stream.  A pitched depth buffer goes up
+// as it lies, its pitch with it.
+int depth_host(csky_ctx* c, const char* fn, const csky_cloud_params* p, const csky_view* view, bool is_view, int w, int h, const float* dirs, const csky_observer* obs,
+               const csky_scene_depth* depth, uint16_t* out) {
+    if (!out) return fail(c, CSKY_ERR_INVALID, "%s: out is NULL", fn);
+    if (!is_view && !dirs) return fail(c, CSKY_ERR_INVALID, "%s: dirs_xyz is NULL", fn);
+    int rc;
+    if ((rc = depth_check(c, fn, depth, is_view, true, w, h, nullptr, 0)) || (rc = observer_check(c, fn, obs)) ||
+        (rc = rays_check(c, fn, p, view, is_view, w, h, (w >= 1 && w <= 8192) ? (size_t)w * 8 : 8)) || (rc = bind(c))) return rc;
+    const size_t n = (size_t)w * h, db = is_view ? 0 : n * 3 * sizeof(float);
+    const size_t dp = depth->pitch_bytes ? depth->pitch_bytes : (size_t)w * 4, zb = (size_t)(h - 1) * dp + (size_t)w * 4;
+    HostCall hc = host_call(c, fn, {db, zb, n * 8});
+    hc.up(0, dirs, db);
+    hc.up(1, depth->texels, zb);
+    hc.step([&] { return depth_launch(c, fn, p, view, w, h, is_view ? nullptr : hc.at<float>(0), obs, hc.at<float>(1), dp, depth->kind, hc.at<uint2>(2), (size_t)w * 8, c->stream); });
+    hc.down(out, 2, n * 8);
+    return hc.finish();
+}
+
+int depth_device(csky_ctx* c, const char* fn, const csky_cloud_params* p, const csky_view* view, bool is_view, int w, int h, const void* d_dirs, const csky_observer* obs,
+                 const csky_scene_depth* depth, void* d_out, size_t pitch, void* hip_stream) {
+    if (!d_out) return fail(c, CSKY_ERR_INVALID, "%s: d_out is NULL", fn);
+    if (!is_view && !d_dirs) return fail(c, CSKY_ERR_INVALID, "%s: d_dirs_xyz is NULL", fn);
+    int rc;
+    if ((rc = depth_check(c, fn, depth, is_view, false, w, h, d_out, pitch)) || (rc = observer_check(c, fn, obs)) || (rc = rays_check(c, fn, p, view, is_view, w, h, pitch)) ||
+        (rc = bind(c))) return rc;
+    return depth_launch(c, fn, p, view, w, h, is_view ? nullptr : static_cast<const float*>(d_dirs), obs, static_cast<const float*>(depth->texels), depth->pitch_bytes,
+                        depth->kind, static_cast<uint2*>(d_out), pitch, stream_of(c, hip_stream));
+}
+
 }  // namespace
 
 extern "C" {
@@ -218,6 +273,35 @@ int csky_render_clouds_view_from_device(csky_ctx* c, const csky_cloud_params* p,
     if (!d_out) return fail(c, CSKY_ERR_INVALID, "%s: d_out is NULL", fn);
     int rc; if ((rc = observer_check(c, fn, obs)) || (rc = rays_check(c, fn, p, view, true, w, h, pitch)) || (rc = bind(c))) return rc;
     return rays_launch(c, fn, p, view, w, h, nullptr, static_cast<uint2*>(d_out), pitch, stream_of(c, hip_stream), obs);
+}
+
+// ---- the same behind a per-pixel scene depth (scene_depth_core.h)
+int csky_render_clouds_view_from_depth(csky_ctx* c, const csky_cloud_params* p, const csky_view* view, const csky_observer* obs, int w, int h, const csky_scene_depth* depth,
+                                       uint16_t* out) {
+    const char* fn = "csky_render_clouds_view_from_depth";
+    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "%s: ctx is NULL", fn);
+    return depth_host(c, fn, p, view, true, w, h, nullptr, obs, depth, out);
+}
+
+int csky_render_clouds_dirs_from_depth(csky_ctx* c, const csky_cloud_params* p, int w, int h, const float* dirs, const csky_observer* obs, const csky_scene_depth* depth,
+                                       uint16_t* out) {
+    const char* fn = "csky_render_clouds_dirs_from_depth";
+    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "%s: ctx is NULL", fn);
+    return depth_host(c, fn, p, nullptr, false, w, h, dirs, obs, depth, out);
+}
+
+int csky_render_clouds_view_from_depth_device(csky_ctx* c, const csky_cloud_params* p, const csky_view* view, const csky_observer* obs, int w, int h,
+                                              const csky_scene_depth* depth, void* d_out, size_t pitch, void* hip_stream) {
+    const char* fn = "csky_render_clouds_view_from_depth_device";
+    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "%s: ctx is NULL", fn);
+    return depth_device(c, fn, p, view, true, w, h, nullptr, obs, depth, d_out, pitch, hip_stream);
+}
+
+int csky_render_clouds_dirs_from_depth_device(csky_ctx* c, const csky_cloud_params* p, int w, int h, const void* d_dirs, const csky_observer* obs,
+                                              const csky_scene_depth* depth, void* d_out, size_t pitch, void* hip_stream) {
+    const char* fn = "csky_render_clouds_dirs_from_depth_device";
+    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "%s: ctx is NULL", fn);
+    return depth_device(c, fn, p, nullptr, false, w, h, d_dirs, obs, depth, d_out, pitch, hip_stream);
 }
 
 }  // extern "C"

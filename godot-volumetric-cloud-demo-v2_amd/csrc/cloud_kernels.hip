@@ -1142,3 +1142,61 @@ hipError_t launch_clouds_observer(const TexSet& t, const TexSet32* t32, const Fr
 }
 
 }  // namespace csky
+
+// ---- the observer's march behind a per-pixel scene depth -------------------------------------------------------------
+// clouds_observer_kernel with one more input: scene_depth_core.h scene_depth_ray ends the lane's segment at its own pixel's depth texel (metres along
+// the ray, or along the camera's forward axis) as well as at the frame's max_distance.  The same shape: one pixel per lane, an 8x8 tile per wavefront,
+// four tiles per workgroup, the same LDS queue and launch bound, a plain launch in natural order, march_compact<true, false, 0, TS, false>.  A lane
+// inside the image makes one 4-byte load of its texel (a row of a tile is eight consecutive floats); a lane outside it loads nothing.  A wavefront
+// whose lanes are all occluded returns at march_compact's first ballot.
+#include "scene_depth_core.h"
+#pragma clang fp contract(off)   // (scene_depth_core.h ends with contraction on, like observer_core.h)
+
+namespace csky {
+
+// SRC as clouds_observer_kernel's.  KIND: DEPTH_DISTANCE or DEPTH_VIEW_Z (view form only), compiled in: the distance form has no dot product or divide.
+// depth: G.og.g.h rows of G.og.g.w floats, G.depth_pitch floats apart; it does not overlap out.
+template <int SRC, int KIND, class TS>
+__global__ __launch_bounds__(256, CSKY_COMPACT_WAVES) void clouds_observer_depth_kernel(TS T, const FrameConsts* __restrict__ fcp, SceneDepthGeom G, const float* __restrict__ dirs,
+                                                                                        const float* __restrict__ depth, uint2* __restrict__ out) {
+    __shared__ float lds[4][CQ_FLOATS];
+    const int tiles_x = (G.og.g.w + 31) >> 5;
+    const int slab = (int)blockIdx.x / tiles_x, bx = (int)blockIdx.x - slab * tiles_x;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int gx = bx * 32 + wave * 8 + (lane & 7);
+    const int gy = slab * 8 + (lane >> 3);
+    const bool valid = gx < G.og.g.w && gy < G.og.g.h;
+    const FrameConsts& fc = *fcp;
+    T.detail_lds = nullptr;                                    // compile-time constant here: the LDS tap path folds away
+    float z = 0.0f;                                            // 0 is no valid texel
+    if (valid) z = depth[(size_t)gy * G.depth_pitch + gx];
+    float ex = 0.0f, ey = 0.0f, ez = 0.0f;                     // (0, 0, 0) fails observer_accept
+    if constexpr (SRC == 0) {
+        if (valid) { const float* __restrict__ d = dirs + ((size_t)gy * (size_t)G.og.g.w + (size_t)gx) * 3; ex = d[0]; ey = d[1]; ez = d[2]; }
+    } else {
+        rays_view_dir(G.og.g, valid ? gx : 0, valid ? gy : 0, ex, ey, ez);
+    }
+    Ray ray = scene_depth_ray_k<KIND>(fc, G.og, ex, ey, ez, z);
+    if (!valid) ray.above = false;
+    const MarchOut o = march_compact<true, false, 0, TS, false>(T, fc, ray, &lds[wave][0], 0, fc.primary_steps);
+    if (valid) out[(size_t)gy * G.og.g.pitch_px + gx] = pack_half4(f2h(o.r), f2h(o.g), f2h(o.b), f2h(o.a));   // store_pixel's packing
+}
+
+template <class TS>
+static hipError_t launch_observer_depth_ts(const TS& t, const FrameConsts* d_fc, const SceneDepthGeom& g, const float* d_dirs, const float* d_depth, uint2* d_out, hipStream_t s) {
+    const unsigned grid = (unsigned)(((g.og.g.w + 31) >> 5) * ((g.og.g.h + 7) >> 3));
+    if (d_dirs) clouds_observer_depth_kernel<0, DEPTH_DISTANCE, TS><<<grid, 256, 0, s>>>(t, d_fc, g, d_dirs, d_depth, d_out);
+    else if (g.kind == DEPTH_VIEW_Z) clouds_observer_depth_kernel<1, DEPTH_VIEW_Z, TS><<<grid, 256, 0, s>>>(t, d_fc, g, d_dirs, d_depth, d_out);
+    else clouds_observer_depth_kernel<1, DEPTH_DISTANCE, TS><<<grid, 256, 0, s>>>(t, d_fc, g, d_dirs, d_depth, d_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_clouds_observer_depth(const TexSet& t, const TexSet32* t32, const FrameConsts* d_fc, const SceneDepthGeom& g, const float* d_dirs, const float* d_depth,
+                                        uint2* d_out, hipStream_t s) {
+    if (g.og.g.w < 1 || g.og.g.h < 1 || g.og.g.w > 8192 || g.og.g.h > 8192 || g.og.g.pitch_px < (uint32_t)g.og.g.w) return hipErrorInvalidValue;
+    if (!d_depth || g.depth_pitch < (uint32_t)g.og.g.w) return hipErrorInvalidValue;
+    if ((g.kind != DEPTH_DISTANCE && g.kind != DEPTH_VIEW_Z) || (g.kind == DEPTH_VIEW_Z && d_dirs)) return hipErrorInvalidValue;
+    return t32 ? launch_observer_depth_ts(*t32, d_fc, g, d_dirs, d_depth, d_out, s) : launch_observer_depth_ts(t, d_fc, g, d_dirs, d_depth, d_out, s);
+}
+
+}  // namespace csky

@@ -85,6 +85,12 @@ hipError_t launch_clouds_view_update(const TexSet& t, const TexSet32* t32, const
 // through the layer capped at g.max_dist.  g travels as a kernel argument.
 struct ObserverGeom;
 hipError_t launch_clouds_observer(const TexSet& t, const TexSet32* t32, const FrameConsts* d_fc, const ObserverGeom& g, const float* d_dirs, uint2* d_out, hipStream_t s);
+// the same behind a per-pixel scene depth (scene_depth_core.h): each ray also ends at its pixel's texel of d_depth (g.og.g.h rows of g.og.g.w floats,
+// g.depth_pitch floats apart, metres along the ray or, g.kind DEPTH_VIEW_Z and a view only, along the camera's forward axis).  d_depth does not
+// overlap d_out.  g travels as a kernel argument.
+struct SceneDepthGeom;
+hipError_t launch_clouds_observer_depth(const TexSet& t, const TexSet32* t32, const FrameConsts* d_fc, const SceneDepthGeom& g, const float* d_dirs, const float* d_depth,
+                                        uint2* d_out, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------ shadow.hip
 // the cloud shadow map (shadow_core.h): sc.w x sc.h halfs into d_out, row pitch sc.pitch_h halfs.  fc: shadow_frame_consts; both blocks travel as

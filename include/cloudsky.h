@@ -648,6 +648,51 @@ int csky_render_clouds_view_from_device(csky_ctx* ctx, const csky_cloud_params* 
 int csky_render_clouds_dirs_from_device(csky_ctx* ctx, const csky_cloud_params* p, int w, int h, const void* d_dirs_xyz, const csky_observer* observer,
                                         void* d_out_rgba16f, size_t row_pitch_bytes, void* hip_stream);
 
+/* ---- the observer's march behind a per-pixel scene depth ---------------------------- */
+/* The _from forms end every ray of a frame at one max_distance.  A host with such a camera has a scene in front of it: a mountain that stands into
+ * the layer, a wing, the terrain under an aircraft.  These calls are the _from forms with a depth buffer of that scene: each ray ends at its own
+ * pixel's depth as well, so the frame holds the cloud IN FRONT of the geometry and none of the cloud behind it.
+ *   texels       h rows of w float32, metres.  A host pointer in the blocking forms, a device pointer in the _device forms.
+ *   pitch_bytes  the row pitch: a multiple of 4 and >= 4 * w.  In the blocking forms 0 means tight (4 * w).
+ *   kind         CSKY_DEPTH_DISTANCE: metres along the pixel's ray from the observer.  CSKY_DEPTH_VIEW_Z: metres along the camera's forward
+ *                axis, the linear depth a rasteriser has; view forms only.
+ * For pixel (i, j), fp32 without contraction, in this order; everything not named here is the _from forms' definition above, unchanged:
+ *   e, accept, isect, segment      the _from forms'
+ *   z        texels[j][i]
+ *   d        kind 0:  d = z
+ *            kind 1:  f = -((cam[6]*e.x + cam[7]*e.y) + cam[8]*e.z)      cam = csky_view.basis, column-major (cam[6..8]: the back axis)
+ *                     d = z / f;   the texel is not valid unless f > 0
+ *   valid    z > 0 and d > 0      (NaN, 0, -0, negatives and -inf fail: geometry at the lens; +inf: nothing in the way)
+ *   cap      t1 = fminf(fminf(t1, max_distance), d)
+ *   marched  accepted, a segment, valid, t1 > t0, |end - start|^2 >= 2^-102 and |raystep|^2 >= 2^-102     (the two sums of three squares whose
+ *            roots are shelldist and ss, as the _from forms compute them; the first implies shelldist > 0)
+ *   ray, texel   the _from forms', from t0 and the capped t1
+ * The last two clauses: world positions are near 6e6 m, where fp32 has a quantum of 0.5 m.  Along every silhouette inside the layer a depth buffer
+ * holds pixels whose depth is within that quantum of t0; there end == start, ss = 0 and dir = 0 / 0.  shelldist > 0 alone does not exclude it (from
+ * an observer on the axis inside the layer a depth of 1e-22 m has shelldist > 0 and still ss = 0), so both roots must take an argument a float
+ * square root resolves: shelldist >= 4.4e-16 m.  Such a pixel is not marched: a zero texel.
+ * The cap RE-SPACES the N samples over the shortened segment, exactly as max_distance does: the sample positions of the uncapped ray are not
+ * kept and truncated.  A marched pixel's texel depends on its own direction and its own depth only (csky_set_early_out off, the default), so:
+ * a buffer of +inf gives the bytes of the _from forms; a buffer of one constant c (kind 0) those of the _from forms with
+ * max_distance = fminf(max_distance, c).
+ * Texel values are never a call error: they are the per-pixel rule above.  State, ranges and errors are the _from forms'.  CSKY_ERR_INVALID also,
+ * before the observer and the context's state are looked at, for: a NULL depth or texels; a kind outside {0, 1}; CSKY_DEPTH_VIEW_Z on a dirs form;
+ * a pitch that is no multiple of 4 or below 4 * w; in the _device forms, byte ranges of the depth buffer and of out that overlap.  The calls read
+ * the depth buffer and never write it.  Depth formats other than float32, reversed or non-linear depth have no form. */
+enum { CSKY_DEPTH_DISTANCE = 0, CSKY_DEPTH_VIEW_Z = 1 };
+typedef struct { const void* texels; size_t pitch_bytes; int kind; } csky_scene_depth;
+/* Blocking host forms. */
+int csky_render_clouds_view_from_depth(csky_ctx* ctx, const csky_cloud_params* p, const csky_view* view, const csky_observer* observer, int w, int h,
+                                       const csky_scene_depth* depth, uint16_t* out_rgba16f);
+int csky_render_clouds_dirs_from_depth(csky_ctx* ctx, const csky_cloud_params* p, int w, int h, const float* dirs_xyz, const csky_observer* observer,
+                                       const csky_scene_depth* depth, uint16_t* out_rgba16f);
+/* Device forms: as csky_render_clouds_view_from_device / _dirs_from_device. */
+int csky_render_clouds_view_from_depth_device(csky_ctx* ctx, const csky_cloud_params* p, const csky_view* view, const csky_observer* observer, int w,
+                                              int h, const csky_scene_depth* depth, void* d_out_rgba16f, size_t row_pitch_bytes, void* hip_stream);
+int csky_render_clouds_dirs_from_depth_device(csky_ctx* ctx, const csky_cloud_params* p, int w, int h, const void* d_dirs_xyz,
+                                              const csky_observer* observer, const csky_scene_depth* depth, void* d_out_rgba16f,
+                                              size_t row_pitch_bytes, void* hip_stream);
+
 /* ---- depth and aerial perspective for view frames and ray frames ------------------- */
 /* csky_render_cloud_depth and csky_apply_cloud_aerial above serve the hemisphere frame: both take every pixel's direction from the hemi-octahedral
  * grid.  These calls are the same two steps for the image of a direct march (csky_render_clouds_dirs / _view): the direction of pixel (i, j) of a
