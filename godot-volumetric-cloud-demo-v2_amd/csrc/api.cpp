@@ -111,10 +111,11 @@ int csky_create(csky_ctx** out, int device_id) {
     c->device = device_id;
     // a step that fails leaves its text in the half-built context: hand it to the caller's thread, release what was made
     if (const int rc = create_resources(c)) { fail(nullptr, rc, "csky_create: %s", c->err); csky_destroy(c); return rc; }
-    { int cus = 0; (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_id); c->resident_wgs = (cus > 0 ? cus : 256) * cloud_resident_workgroups_per_cu(); }
+    { int cus = 0; (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_id); cus = cus > 0 ? cus : 256;
+      c->resident_wgs = cus * cloud_resident_workgroups_per_cu(); c->resident_wgs_slim = cus * cloud_resident_workgroups_per_cu_slim(); }
     // A/B switch (CSKY_PERSISTENT; the A/B of profiles/r02/persistent_launch_ab.txt): 0 = never, 1 = the policy of clouds_dev (default), 2 = every whole-ray launch
     if (const char* pe = getenv("CSKY_PERSISTENT")) c->persistent = atoi(pe);
-    if (const char* pe = getenv("CSKY_PERSISTENT_WGS")) { const int n = atoi(pe); if (n > 0) c->resident_wgs = n; }
+    if (const char* pe = getenv("CSKY_PERSISTENT_WGS")) { const int n = atoi(pe); if (n > 0) c->resident_wgs = c->resident_wgs_slim = n; }
     *out = c;
     return CSKY_OK;
 }

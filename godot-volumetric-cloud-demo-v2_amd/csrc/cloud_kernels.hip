@@ -176,6 +176,25 @@ __device__ __forceinline__ MarchOut march_queue(const TexSet& T, const FrameCons
 constexpr int CQ_CAP = 128;                                  // a flush is taken as soon as 64 samples are queued: count <= 63 + 64
 constexpr int CQ_STEPS = 66;                                 // steps-with-events between flushes: <= 1 carried + 64 (>= 1 event each)
 constexpr int CQ_FLOATS = 5 * CQ_CAP + CQ_CAP / 4 + 3 * CQ_STEPS + 2 + 128 + 320;   // pos(3) t hf (after the light march: D(3) q dt) | owner lane (bytes) | per-step mask lo/hi + base | in-cloud tally | per-ray ss, phase | per-ray T, alpha, L between flushes = 5.2 KB per wavefront
+// The SLIM layout (march_compact<.., SLIM = true>: the specialised persistent forms only, so that eight of their workgroups fit a CU's LDS).  Same samples,
+// same order, same flushes; two arrays go:
+//   * st_base[CQ_STEPS]: a step's first slot is the previous step's plus the popcount of its mask, and the replay holds the mask as a scalar pair anyway;
+//   * ev_hf[64 .. CQ_CAP): a flush evaluates slots 0..63 only, so a sample queued at slot >= 64 is never read there: it is carried to the front first.  The
+//     carry recomputes its height fraction from the queued position (the same function of the same three floats as step A: the same bits), once per
+//     carried flush with all its lanes at once, not once per queued sample.
+constexpr int CQ_HF_SLIM = 64;
+// the first slot of the replayed step s: read from st_base, or (SLIM) counted up from the masks of the steps before it (the carried step, or the first
+// one after an empty queue, starts at 0).  Two types, so that the wide layout's replay is the code it was.
+template <bool SLIM> struct ReplayBase {
+    __device__ __forceinline__ int first(const unsigned* __restrict__ st_base, int s) const { return (int)st_base[s]; }
+    __device__ __forceinline__ void next(unsigned, unsigned) {}
+};
+template <> struct ReplayBase<true> {
+    int base = 0;
+    __device__ __forceinline__ int first(const unsigned* __restrict__, int) const { return base; }
+    __device__ __forceinline__ void next(unsigned lo, unsigned hi) { base += __builtin_popcount(lo) + __builtin_popcount(hi); }
+};
+constexpr int CQ_FLOATS_SLIM = 4 * CQ_CAP + CQ_HF_SLIM + CQ_CAP / 4 + 2 * CQ_STEPS + 2 + 128 + 320;   // 4 760 bytes per wavefront
 
 #ifndef CSKY_EAGER_LIGHT
 #define CSKY_EAGER_LIGHT 1
@@ -288,7 +307,8 @@ __device__ __forceinline__ void light_march_terms(const TS& T, const FrameConsts
 // CT: the cloud-type mode of the frame as a compile-time value (cloud_core.h density_height_gradient); 0 reads fc.ct_mode per evaluation.
 // RISING: every ray of the call starts on the inner shell and runs outwards (every caller but clouds_observer_kernel).  It guards the early end below and
 // nothing else; without it the wavefront ends once no lane is live, which needs no assumption about the rays.
-template <bool WHOLE, bool TALLY, int CT = 0, class TS, bool RISING = true>
+// SLIM: the queue has the CQ_FLOATS_SLIM layout (above).
+template <bool WHOLE, bool TALLY, int CT = 0, class TS, bool RISING = true, bool SLIM = false>
 __device__ __forceinline__ MarchOut march_compact(const TS& T, const FrameConsts& fc, Ray ray, float* __restrict__ q, int step_begin, int step_end) {
     constexpr bool SAT = WHOLE && !TS::cell32;
     constexpr bool DEAD = SAT && !TALLY;                      // a latched ray stops marching
@@ -296,11 +316,12 @@ __device__ __forceinline__ MarchOut march_compact(const TS& T, const FrameConsts
     float* __restrict__ ev_py = q + CQ_CAP;
     float* __restrict__ ev_pz = q + 2 * CQ_CAP;
     float* __restrict__ ev_t = q + 3 * CQ_CAP;
-    float* __restrict__ ev_hf = q + 4 * CQ_CAP;
-    unsigned char* __restrict__ ev_owner = reinterpret_cast<unsigned char*>(q + 5 * CQ_CAP);   // the sample's owner lane: its step length and phase value are read from ray_ss / ray_ph
-    unsigned* __restrict__ st_lo = reinterpret_cast<unsigned*>(q + 5 * CQ_CAP + CQ_CAP / 4);  // [CQ_STEPS]
+    float* __restrict__ ev_hf = q + 4 * CQ_CAP;                 // [CQ_CAP], SLIM: [CQ_HF_SLIM]
+    constexpr int HF_CAP = SLIM ? CQ_HF_SLIM : CQ_CAP;
+    unsigned char* __restrict__ ev_owner = reinterpret_cast<unsigned char*>(q + (4 * CQ_CAP + HF_CAP));   // the sample's owner lane: its step length and phase value are read from ray_ss / ray_ph
+    unsigned* __restrict__ st_lo = reinterpret_cast<unsigned*>(q + (4 * CQ_CAP + HF_CAP) + CQ_CAP / 4);  // [CQ_STEPS]
     unsigned* __restrict__ st_hi = st_lo + CQ_STEPS;
-    unsigned* __restrict__ st_base = st_hi + CQ_STEPS;
+    unsigned* __restrict__ st_base = st_hi + CQ_STEPS;          // [CQ_STEPS], SLIM: absent (derived in the replay)
 
     MarchOut o; o.r = o.g = o.b = o.a = 0.0f; o.t = 1.0f; o.incloud = 0;
     const int lane = threadIdx.x & 63;
@@ -312,7 +333,7 @@ __device__ __forceinline__ MarchOut march_compact(const TS& T, const FrameConsts
     int count = 0, cs = 0;                                    // queued samples / steps owning them (uniform)
     bool latched = false;                                     // saturation skip: this lane's ray is saturated (SAT && TALLY only: a DEAD ray is `!live`)
     unsigned skipped = 0u;                                    // in-cloud samples of latched rays, counted and not queued (uniform; TALLY only)
-    unsigned* __restrict__ tally = st_base + CQ_STEPS;          // in-cloud samples composited by this wavefront, kept in LDS (round 4: neither a per-lane accumulator register
+    unsigned* __restrict__ tally = st_base + (SLIM ? 0 : CQ_STEPS);   // in-cloud samples composited by this wavefront, kept in LDS (round 4: neither a per-lane accumulator register
     if constexpr (TALLY) { if (lane == 0) tally[0] = 0u; }    // in the march loops nor a scalar one in the SGPR-starved persistent form; one ds_add per flush)
     // the two per-ray constants a queued sample carries (step length, phase value) live in LDS, not in registers held across the whole march: the
     // persistent form had spilled `phase` to scratch and re-loaded it, behind a vmcnt(0), at every step with an in-cloud sample (round 4 census)
@@ -356,8 +377,13 @@ __device__ __forceinline__ MarchOut march_compact(const TS& T, const FrameConsts
             const unsigned long long m = __builtin_amdgcn_ballot_w64(have);
             if (m != 0ull) {
                 const int slot = count + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+                if constexpr (SLIM) {
+                    if (have) { ev_px[slot] = px; ev_py[slot] = py; ev_pz[slot] = pz; ev_t[slot] = t; ev_owner[slot] = (unsigned char)lane; if (slot < CQ_HF_SLIM) ev_hf[slot] = hf; }
+                    if (lane == 0) { st_lo[cs] = (unsigned)m; st_hi[cs] = (unsigned)(m >> 32); }
+                } else {
                 if (have) { ev_px[slot] = px; ev_py[slot] = py; ev_pz[slot] = pz; ev_t[slot] = t; ev_hf[slot] = hf; ev_owner[slot] = (unsigned char)lane; }
                 if (lane == 0) { st_lo[cs] = (unsigned)m; st_hi[cs] = (unsigned)(m >> 32); st_base[cs] = (unsigned)count; }
+                }
                 count += __popcll(m);
                 cs++;
             }
@@ -382,11 +408,13 @@ __device__ __forceinline__ MarchOut march_compact(const TS& T, const FrameConsts
         wave_lds_fence();
         // ---- C: replay the steps in order; owners of evaluated samples (slot < n) composite (:207-210)
         float Tr = acc[lane], alpha = acc[64 + lane], Lr = acc[128 + lane], Lg = acc[192 + lane], Lb = acc[256 + lane];
+        ReplayBase<SLIM> sb;
         for (int s = 0; s < cs; s++) {
             // the step's lane mask is wave-uniform: as a scalar pair it IS the execution mask of the owners (inverse ballot: no per-lane bit test)
             const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)st_lo[s]), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)st_hi[s]);
             const bool mine = __builtin_amdgcn_inverse_ballot_w64(((unsigned long long)hi << 32) | lo);
-            const int slot = (int)st_base[s] + (int)__builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo, 0u));
+            const int slot = sb.first(st_base, s) + (int)__builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo, 0u));
+            sb.next(lo, hi);
             if (mine && slot < n) {
                 composite_sample(ev_hf[slot], ev_t[slot], ev_px[slot], ev_py[slot], ev_pz[slot], Tr, alpha, Lr, Lg, Lb);
             }
@@ -415,10 +443,15 @@ __device__ __forceinline__ MarchOut march_compact(const TS& T, const FrameConsts
         const int rem = count - n;
         if (rem > 0) {
             float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f, a4 = 0.0f; unsigned char a5 = 0;
+            if constexpr (SLIM) {                            // rem > 0: n == 64 == CQ_HF_SLIM, every carried sample lies where no height fraction was stored
+                if (lane < rem) { a0 = ev_px[n + lane]; a1 = ev_py[n + lane]; a2 = ev_pz[n + lane]; a3 = ev_t[n + lane]; a5 = ev_owner[n + lane]; a4 = height_fraction(length3_shell(a0, a1, a2)); }
+            } else {
             if (lane < rem) { a0 = ev_px[n + lane]; a1 = ev_py[n + lane]; a2 = ev_pz[n + lane]; a3 = ev_t[n + lane]; a4 = ev_hf[n + lane]; a5 = ev_owner[n + lane]; }
+            }
             wave_lds_fence();
             if (lane < rem) { ev_px[lane] = a0; ev_py[lane] = a1; ev_pz[lane] = a2; ev_t[lane] = a3; ev_hf[lane] = a4; ev_owner[lane] = a5; }
-            if (lane == 0) { st_lo[0] = (unsigned)carry; st_hi[0] = (unsigned)(carry >> 32); st_base[0] = 0u; }
+            if constexpr (SLIM) { if (lane == 0) { st_lo[0] = (unsigned)carry; st_hi[0] = (unsigned)(carry >> 32); } }
+            else { if (lane == 0) { st_lo[0] = (unsigned)carry; st_hi[0] = (unsigned)(carry >> 32); st_base[0] = 0u; } }
             wave_lds_fence();
             count = rem; cs = 1;
         } else {
@@ -643,8 +676,14 @@ __global__ __launch_bounds__(1024) void clouds_kernel_lds(TexSet T, const FrameC
 #define CSKY_COMPACT_WAVES 7   // waves/SIMD asked of the "compact" variant.  With the eager light-march fetches (three gathers of a sample in flight
                                // together) 7 waves x 72 VGPRs beat 8 waves x 64 VGPRs + spills: whole frame 1.83 -> 1.80 ms, 1/4 frame 0.49 -> 0.48
 #endif
+#ifndef CSKY_PERSISTENT_SLIM_WAVES
+#define CSKY_PERSISTENT_SLIM_WAVES 8   // waves/SIMD asked of the specialised persistent forms (clouds_kernel_persistent<3, false, 1 | 2>) alone: 64 VGPRs without a
+                                       // VGPR spill since round 22's straight-line light march, and the slim queue (CQ_FLOATS_SLIM) lets eight workgroups share a CU's LDS
+#endif
+// which persistent instantiations those are
+constexpr bool persistent_slim(int variant, bool tally, int ct) { return variant == 3 && !tally && ct != 0; }
 // One workgroup's footprint (4 tiles / SEG): `logical` = slab * tiles_x + bx, `rec` = its position in the launch order (the persistent form: its cost-feedback slot).
-template <int VARIANT, int SEG, class TS = TexSet, bool TALLY = true, int CT = 0>
+template <int VARIANT, int SEG, class TS = TexSet, bool TALLY = true, int CT = 0, bool SLIM = false>
 __device__ __forceinline__ void render_block(TS T, const FrameConsts* __restrict__ fcp, const RenderGeom& G, const uint32_t logical, const uint32_t rec,
                                              uint2* __restrict__ out, unsigned long long* __restrict__ stats, uint32_t* __restrict__ wg_cost, const int tile_of_wave = -1) {
     constexpr int BW = 32 / SEG;                               // workgroup footprint width in pixels
@@ -671,9 +710,10 @@ __device__ __forceinline__ void render_block(TS T, const FrameConsts* __restrict
         static_assert(SEG == 1, "the lock-step reference variant marches whole rays");
         o = march(T, fc, ray);
     } else {
-        __shared__ float lds[4][VARIANT == 3 ? CQ_FLOATS : Q_FLOATS];
+        static_assert(!SLIM || (VARIANT == 3 && SEG == 1), "the slim queue is the compact whole-ray march's");
+        __shared__ float lds[4][VARIANT == 3 ? (SLIM ? CQ_FLOATS_SLIM : CQ_FLOATS) : Q_FLOATS];
         const int s0 = (fc.primary_steps * seg) / SEG, s1 = (fc.primary_steps * (seg + 1)) / SEG;
-        if constexpr (VARIANT == 3) o = march_compact<SEG == 1, TALLY, CT>(T, fc, ray, &lds[wave][0], s0, s1);
+        if constexpr (VARIANT == 3) o = march_compact<SEG == 1, TALLY, CT, TS, true, SLIM>(T, fc, ray, &lds[wave][0], s0, s1);
         else o = march_queue(T, fc, ray, &lds[wave][0], s0, s1);
         if constexpr (SEG > 1) {
             __shared__ float comb[4][5][64];
@@ -735,7 +775,7 @@ __global__ __launch_bounds__(256, VARIANT == 3 ? CSKY_COMPACT_WAVES : 7) void cl
 //   * CT: the cloud-type mode the frame set-up wrote into *fcp (launch_clouds picks the instantiation from the same value), 0 for a mixed map or
 //     csky_set_height_window(0): the march reads the mode from the frame constants as every other kernel does.
 template <int VARIANT, bool TALLY = true, int CT = 0>
-__global__ __launch_bounds__(256, VARIANT == 3 ? CSKY_COMPACT_WAVES : 7) void clouds_kernel_persistent(TexSet T, const FrameConsts* __restrict__ fcp, RenderGeom G,
+__global__ __launch_bounds__(256, persistent_slim(VARIANT, TALLY, CT) ? CSKY_PERSISTENT_SLIM_WAVES : VARIANT == 3 ? CSKY_COMPACT_WAVES : 7) void clouds_kernel_persistent(TexSet T, const FrameConsts* __restrict__ fcp, RenderGeom G,
         const uint32_t* __restrict__ order, const uint32_t n_items, uint32_t* __restrict__ heads, uint2* __restrict__ out, unsigned long long* __restrict__ stats,
         uint32_t* __restrict__ wg_cost) {
     unsigned xcc;
@@ -748,6 +788,10 @@ __global__ __launch_bounds__(256, VARIANT == 3 ? CSKY_COMPACT_WAVES : 7) void cl
     // a barrier of its own, and lost: docs/EXPERIMENTS.md §5).  Staged from the set THIS launch was given: a rebind needs no care.
     static_assert(VARIANT == 3, "the persistent form exists for the compact march only: its light march is the one that reads the table");
     __shared__ __attribute__((aligned(16))) uint4 det_small[TexSetSmallDetail::SMALL_DETAIL_CELLS];
+    constexpr bool SLIM = persistent_slim(VARIANT, TALLY, CT);
+    // eight workgroups per CU: four queues, the nine ticket words and the table within an eighth of the CU's 160 KB
+    static_assert(!SLIM || 4 * CQ_FLOATS_SLIM * sizeof(float) + 9 * sizeof(uint32_t) + sizeof(det_small) <= 163840 / CSKY_PERSISTENT_SLIM_WAVES,
+                  "the specialised persistent forms no longer fit eight workgroups into a CU's LDS");
     if (threadIdx.x < (unsigned)TexSetSmallDetail::SMALL_DETAIL_CELLS) det_small[threadIdx.x] = T.detail[detail_level_offset(TexSetSmallDetail::SMALL_DETAIL_FIRST) + threadIdx.x];
     __syncthreads();
     const bool lane0 = (threadIdx.x & 63) == 0;
@@ -796,7 +840,7 @@ __global__ __launch_bounds__(256, VARIANT == 3 ? CSKY_COMPACT_WAVES : 7) void cl
             TexSetSmallDetail Ts;
             static_cast<TexSet&>(Ts) = T;
             Ts.det_small = (SmallDetailTable)det_small;                        // generic -> LDS: a C-style cast is the only one that may change the address space
-            render_block<VARIANT, 1, TexSetSmallDetail, TALLY, CT>(Ts, fcp, G, logical, rec, out, stats, wg_cost, tile);
+            render_block<VARIANT, 1, TexSetSmallDetail, TALLY, CT, SLIM>(Ts, fcp, G, logical, rec, out, stats, wg_cost, tile);
         }
     }
 }
@@ -898,12 +942,24 @@ hipError_t launch_sqrt_shell(const float* d_in, float* d_out, size_t n, hipStrea
 
 static const char* const kVariantNames[] = {"lockstep", "queue", "queue-lds", "compact"};
 int cloud_resident_workgroups_per_cu() { return CSKY_COMPACT_WAVES; }
+int cloud_resident_workgroups_per_cu_slim() {
+    // what the runtime says the current device holds of each of the two forms, the launch bound at the most: a workgroup that is not resident only waits
+    // its turn (no workgroup of a persistent launch waits for another), but a grid that is too large wastes the launch's tail
+    int per_cu = CSKY_PERSISTENT_SLIM_WAVES;
+    const void* const forms[2] = {reinterpret_cast<const void*>(&clouds_kernel_persistent<3, false, 1>), reinterpret_cast<const void*>(&clouds_kernel_persistent<3, false, 2>)};
+    for (const void* f : forms) {
+        int n = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, f, 256, 0) != hipSuccess || n <= 0) { (void)hipGetLastError(); n = CSKY_COMPACT_WAVES; }
+        if (n < per_cu) per_cu = n;
+    }
+    return per_cu;
+}
 int cloud_variant_count() { return (int)(sizeof(kVariantNames) / sizeof(kVariantNames[0])); }
 const char* cloud_variant_name(int v) { return (v >= 0 && v < cloud_variant_count()) ? kVariantNames[v] : nullptr; }
 
 hipError_t launch_clouds(int variant, int seg, const TexSet& t, const FrameConsts* d_fc, const RenderGeom& g, const uint32_t* d_order, int grid,
                          uint2* d_out, unsigned long long* d_stats, uint32_t* d_wg_cost, hipStream_t s, uint32_t* d_heads, int resident, const TexSet32* t32, bool census_lean,
-                         int ct_mode) {
+                         int ct_mode, int resident_slim) {
     if (grid <= 0) return hipSuccess;
     if (ct_mode < 0 || ct_mode > 2) return hipErrorInvalidValue;
     // the in-cloud count has a reader only when the launch was given somewhere to put it: without one the whole-ray compact kernel runs in the form whose
@@ -917,8 +973,9 @@ hipError_t launch_clouds(int variant, int seg, const TexSet& t, const FrameConst
     if (d_heads && variant == 3 && seg == 1) {                 // persistent form, see clouds_kernel_persistent
         // the instantiation of the frame's cloud-type mode: ct_mode is what the set-up of d_fc was given (clouds_launch.cpp setup_args), so the compiled-in
         // branch is the one the generic form would take on fc.ct_mode
-        const unsigned n = (unsigned)(grid < resident ? grid : resident);
         const auto go = [&](auto tl, auto ct) {
+            const int res = persistent_slim(3, decltype(tl)::value, decltype(ct)::value) && resident_slim > 0 ? resident_slim : resident;   // the instantiation's own resident count
+            const unsigned n = (unsigned)(grid < res ? grid : res);
             clouds_kernel_persistent<3, decltype(tl)::value, decltype(ct)::value><<<n, 256, 0, s>>>(t, d_fc, g, d_order, (uint32_t)grid, d_heads, d_out, d_stats, d_wg_cost);
         };
         const auto with_mode = [&](auto tl) {

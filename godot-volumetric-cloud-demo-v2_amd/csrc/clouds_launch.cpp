@@ -120,7 +120,7 @@ int clouds_dev(csky_ctx* c, const csky_cloud_params* p, int tile_w, const csky_b
     // serial chains, not idle slots; the next frame fills it.)
     {   // a failed persistent launch may leave the slot's pop counters armed: re-zero them so that the next launch on this slot starts clean
         const hipError_t le = launch_clouds(pl.variant, pl.seg, texset(c), ring.fc(), g, order, grid, d_out, d_stats, cost, s, heads, c->resident_wgs, t32p, c->census_lean,
-                                                setup_args(c, cp).ct_mode);
+                                                setup_args(c, cp).ct_mode, c->resident_wgs_slim);
         if (le != hipSuccess) { if (heads) (void)hipMemsetAsync(heads, 0, 16 * sizeof(uint32_t), s); return fail(c, CSKY_ERR_HIP, "cloud kernel launch failed: %s", hipGetErrorString(le)); }
     }
     if (kt) HIPCHK(c, hipEventRecord(kt[1], s));

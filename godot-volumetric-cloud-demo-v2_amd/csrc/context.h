@@ -233,6 +233,7 @@ struct csky_ctx {
     int frames_in_flight = 1;                         // csky_set_frames_in_flight: the caller alternates that many streams
     int frames_overlapping = 1;                       // how many of them the hardware queues in effect can keep apart: the launch policy's hint (clouds_dev)
     int persistent = 1; int resident_wgs = 0;         // the persistent launch form: allowed; workgroups resident at once
+    int resident_wgs_slim = 0;                        // ... of the forms that run eight workgroups per CU (kernels.h cloud_resident_workgroups_per_cu_slim)
     csky::TimingPool kt;                              // csky_set_kernel_timing
     // radiance cubemap (csky_render_radiance*, csky_prefilter_cube): source-record table and block cones, grow-only.  `rad` is the snapshot
     // of the last layer-0 call, which later calls filter from; csky_prefilter_cube works in `rad_pf` and leaves the snapshot alone

@@ -57,9 +57,12 @@ hipError_t launch_bake32(const uint8_t* d_large_chain, const uint8_t* d_small_ch
 hipError_t launch_clouds(int variant, int seg, const TexSet& t, const FrameConsts* d_fc, const RenderGeom& g, const uint32_t* d_order, int grid,
                          uint2* d_out, unsigned long long* d_stats, uint32_t* d_wg_cost, hipStream_t s, uint32_t* d_heads = nullptr, int resident = 0,
                          const TexSet32* t32 = nullptr, bool census_lean = false,    // t32: march on the exact fp32-coefficient cells (variant 3, seg 1 only)
-                         int ct_mode = 0);   // the SetupArgs::ct_mode *d_fc was set up with: a persistent launch runs the march compiled for that mode (0: the generic one)
+                         int ct_mode = 0,    // the SetupArgs::ct_mode *d_fc was set up with: a persistent launch runs the march compiled for that mode (0: the generic one)
+                         int resident_slim = 0);   // `resident` of the specialised persistent forms without a tally (0: `resident`)
 // resident 256-thread workgroups per CU of the "compact" kernel (its launch bound): the size of a persistent launch
 int cloud_resident_workgroups_per_cu();
+// the same for the persistent forms with a compiled-in cloud-type mode and no tally, asked of the runtime for the current device (at most their launch bound)
+int cloud_resident_workgroups_per_cu_slim();
 int cloud_variant_count();
 const char* cloud_variant_name(int v);
 // next launch's workgroup order from this launch's per-workgroup costs, heaviest first.  d_cost[n] and d_scratch[2048] must be zero
