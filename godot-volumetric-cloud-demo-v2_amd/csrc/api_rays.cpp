@@ -79,33 +79,8 @@ int observer_check(csky_ctx* c, const char* fn, const csky_observer* obs) {
     }
 }
 
-// The dirs and view forms' march.  d_dirs: NULL for the view forms.  obs: NULL for the reference's observer, else checked (the _from forms).
-int rays_launch(csky_ctx* c, const char* fn, const csky_cloud_params* p, const csky_view* view, int w, int h, const float* d_dirs, uint2* d_out, size_t pitch_bytes,
-                hipStream_t s, const csky_observer* obs = nullptr) {
-    const float* basis = view ? view->basis : nullptr;
-    const float fov = view ? view->fov_y_degrees : 0.0f;
-    if (obs) {
-        const ObserverGeom g = observer_geom(basis, fov, w, h, (uint32_t)(pitch_bytes / 8), obs->position, obs->max_distance);
-        return rays_run(c, fn, p, s, [&](const TexSet& t, const TexSet32* t32) { return launch_clouds_observer(t, t32, c->d_rays_fc, g, d_dirs, d_out, s); });
-    }
-    const RaysGeom g = rays_geom(basis, fov, w, h, (uint32_t)(pitch_bytes / 8));
-    return rays_run(c, fn, p, s, [&](const TexSet& t, const TexSet32* t32) { return launch_clouds_rays(t, t32, c->d_rays_fc, g, d_dirs, d_out, s); });
-}
-
-// The blocking host forms: dirs (NULL for a view) up, the image down, on the context's stream.  from: a _from form, obs its observer.
-int rays_host(csky_ctx* c, const char* fn, const csky_cloud_params* p, const csky_view* view, bool is_view, int w, int h, const float* dirs, uint16_t* out,
-              bool from = false, const csky_observer* obs = nullptr) {
-    if (!out) return fail(c, CSKY_ERR_INVALID, "%s: out is NULL", fn);
-    if (!is_view && !dirs) return fail(c, CSKY_ERR_INVALID, "%s: dirs_xyz is NULL", fn);
-    int rc; if (from && (rc = observer_check(c, fn, obs))) return rc;
-    if ((rc = rays_check(c, fn, p, view, is_view, w, h, (w >= 1 && w <= 8192) ? (size_t)w * 8 : 8)) || (rc = bind(c))) return rc;
-    const size_t n = (size_t)w * h, db = is_view ? 0 : n * 3 * sizeof(float);
-    HostCall hc = host_call(c, fn, {db, n * 8});
-    hc.up(0, dirs, db);
-    hc.step([&] { return rays_launch(c, fn, p, view, w, h, is_view ? nullptr : hc.at<float>(0), hc.at<uint2>(1), (size_t)w * 8, c->stream, obs); });
-    hc.down(out, 1, n * 8);
-    return hc.finish();
-}
+// The row pitch of a blocking form's image, whose rows are packed; for a width rays_check refuses, one that passes every check in front of it.
+size_t tight_pitch(int w) { return (w >= 1 && w <= 8192) ? (size_t)w * 8 : 8; }
 
 // ---- the temporal split of a view frame (view_update_core.h)
 // What the update forms check beyond rays_check, before it (a bad argument is CSKY_ERR_INVALID whatever the context holds).  prev / out: device
@@ -123,6 +98,16 @@ int update_check(csky_ctx* c, const char* fn, const csky_view* prev_view, int w,
     const size_t na = (size_t)(h - 1) * prev_pitch + (size_t)w * 8, nb = (size_t)(h - 1) * pitch + (size_t)w * 8;
     if (a < b + nb && b < a + na) return fail(c, CSKY_ERR_INVALID, "%s: the previous frame and out overlap", fn);
     return CSKY_OK;
+}
+
+// What both update forms do before their work: the checks in the C ABI's order, then bind.
+int update_begin(csky_ctx* c, const char* fn, bool host_form, const csky_cloud_params* p, const csky_view* view, const csky_view* prev_view, int w, int h, int block, int phase,
+                 const void* prev, size_t prev_pitch, const void* out, size_t pitch) {
+    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "%s: ctx is NULL", fn);
+    if (!out) return fail(c, CSKY_ERR_INVALID, host_form ? "%s: out is NULL" : "%s: d_out is NULL", fn);
+    int rc;
+    if ((rc = update_check(c, fn, prev_view, w, h, block, phase, prev, prev_pitch, out, pitch)) || (rc = rays_check(c, fn, p, view, true, w, h, pitch))) return rc;
+    return bind(c);
 }
 
 // The update's two launches, one timing pair around both.  d_prev: NULL without history (prev_view is then not read).
@@ -149,42 +134,71 @@ int depth_check(csky_ctx* c, const char* fn, const csky_scene_depth* depth, bool
     }
 }
 
-// The march of a _from_depth form, for arguments the checks have passed.  d_dirs: NULL for the view forms.  d_depth, depth_pitch (bytes): on the device.
-int depth_launch(csky_ctx* c, const char* fn, const csky_cloud_params* p, const csky_view* view, int w, int h, const float* d_dirs, const csky_observer* obs, const float* d_depth,
-                 size_t depth_pitch, int kind, uint2* d_out, size_t pitch_bytes, hipStream_t s) {
-    const SceneDepthGeom g = scene_depth_geom(view ? view->basis : nullptr, view ? view->fov_y_degrees : 0.0f, w, h, (uint32_t)(pitch_bytes / 8), obs->position, obs->max_distance,
-                                              (uint32_t)(depth_pitch / 4), kind);
-    return rays_run(c, fn, p, s, [&](const TexSet& t, const TexSet32* t32) { return launch_clouds_observer_depth(t, t32, c->d_rays_fc, g, d_dirs, d_depth, d_out, s); });
+// ---- the twelve forms that are not an update: one description, one host path, one device path
+// What an entry point says of its call.  `form` names the arguments the form has, so that a NULL one is an error; the pointer of an argument the form
+// does not have is NULL.  dirs: on the host for a blocking form, on the device for a _device form.
+enum : int { RAYS_VIEW = 1, RAYS_FROM = 2, RAYS_DEPTH = 4 };   // a view, not dirs; an observer; a scene depth behind that observer
+struct RaysCall {
+    const char* fn;
+    int form;
+    const csky_cloud_params* p;
+    const csky_view* view;
+    int w, h;
+    const void* dirs;
+    const csky_observer* obs;
+    const csky_scene_depth* depth;
+};
+
+// The checks of a call, in the order the C ABI promises (a bad argument is CSKY_ERR_INVALID whatever the context holds), then bind.  out, pitch: the
+// image of either path; a blocking form's depth buffer is staged, so it cannot overlap out.
+int rays_call_check(csky_ctx* c, const RaysCall& k, bool host_form, const void* out, size_t pitch) {
+    const bool is_view = k.form & RAYS_VIEW;
+    if (!out) return fail(c, CSKY_ERR_INVALID, host_form ? "%s: out is NULL" : "%s: d_out is NULL", k.fn);
+    if (!is_view && !k.dirs) return fail(c, CSKY_ERR_INVALID, host_form ? "%s: dirs_xyz is NULL" : "%s: d_dirs_xyz is NULL", k.fn);
+    int rc;
+    if ((k.form & RAYS_DEPTH) && (rc = depth_check(c, k.fn, k.depth, is_view, host_form, k.w, k.h, host_form ? nullptr : out, host_form ? 0 : pitch))) return rc;
+    if ((k.form & RAYS_FROM) && (rc = observer_check(c, k.fn, k.obs))) return rc;
+    if ((rc = rays_check(c, k.fn, k.p, k.view, is_view, k.w, k.h, pitch))) return rc;
+    return bind(c);
 }
 
-// The blocking host forms: dirs (NULL for a view) and the depth buffer up, the image down, on the context's stream.  A pitched depth buffer goes up
+// The march of a call the checks have passed, on stream s: the launcher of what the description holds.  d_dirs (NULL for a view), d_depth and its
+// pitch in bytes (a _from_depth form's), d_out: on the device.
+int rays_launch(csky_ctx* c, const RaysCall& k, const float* d_dirs, const float* d_depth, size_t depth_pitch, uint2* d_out, size_t pitch_bytes, hipStream_t s) {
+    const float* basis = k.view ? k.view->basis : nullptr;
+    const float fov = k.view ? k.view->fov_y_degrees : 0.0f;
+    const uint32_t pitch_px = (uint32_t)(pitch_bytes / 8);
+    return rays_run(c, k.fn, k.p, s, [&](const TexSet& t, const TexSet32* t32) {
+        if (k.form & RAYS_DEPTH) return launch_clouds_observer_depth(t, t32, c->d_rays_fc, scene_depth_geom(basis, fov, k.w, k.h, pitch_px, k.obs->position, k.obs->max_distance,
+                                                                                               (uint32_t)(depth_pitch / 4), k.depth->kind), d_dirs, d_depth, d_out, s);
+        if (k.form & RAYS_FROM) return launch_clouds_observer(t, t32, c->d_rays_fc, observer_geom(basis, fov, k.w, k.h, pitch_px, k.obs->position, k.obs->max_distance), d_dirs, d_out, s);
+        return launch_clouds_rays(t, t32, c->d_rays_fc, rays_geom(basis, fov, k.w, k.h, pitch_px), d_dirs, d_out, s);
+    });
+}
+
+// The blocking forms: dirs and the depth buffer (where the form has them) up, the image down, on the context's stream.  A pitched depth buffer goes up
 // as it lies, its pitch with it.
-int depth_host(csky_ctx* c, const char* fn, const csky_cloud_params* p, const csky_view* view, bool is_view, int w, int h, const float* dirs, const csky_observer* obs,
-               const csky_scene_depth* depth, uint16_t* out) {
-    if (!out) return fail(c, CSKY_ERR_INVALID, "%s: out is NULL", fn);
-    if (!is_view && !dirs) return fail(c, CSKY_ERR_INVALID, "%s: dirs_xyz is NULL", fn);
-    int rc;
-    if ((rc = depth_check(c, fn, depth, is_view, true, w, h, nullptr, 0)) || (rc = observer_check(c, fn, obs)) ||
-        (rc = rays_check(c, fn, p, view, is_view, w, h, (w >= 1 && w <= 8192) ? (size_t)w * 8 : 8)) || (rc = bind(c))) return rc;
-    const size_t n = (size_t)w * h, db = is_view ? 0 : n * 3 * sizeof(float);
-    const size_t dp = depth->pitch_bytes ? depth->pitch_bytes : (size_t)w * 4, zb = (size_t)(h - 1) * dp + (size_t)w * 4;
-    HostCall hc = host_call(c, fn, {db, zb, n * 8});
-    hc.up(0, dirs, db);
-    hc.up(1, depth->texels, zb);
-    hc.step([&] { return depth_launch(c, fn, p, view, w, h, is_view ? nullptr : hc.at<float>(0), obs, hc.at<float>(1), dp, depth->kind, hc.at<uint2>(2), (size_t)w * 8, c->stream); });
+int rays_host(csky_ctx* c, const RaysCall& k, uint16_t* out) {
+    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "%s: ctx is NULL", k.fn);
+    if (const int rc = rays_call_check(c, k, true, out, tight_pitch(k.w))) return rc;
+    const bool has_depth = k.form & RAYS_DEPTH;
+    const size_t n = (size_t)k.w * k.h, db = (k.form & RAYS_VIEW) ? 0 : n * 3 * sizeof(float);
+    const size_t dp = !has_depth ? 0 : k.depth->pitch_bytes ? k.depth->pitch_bytes : (size_t)k.w * 4, zb = has_depth ? (size_t)(k.h - 1) * dp + (size_t)k.w * 4 : 0;
+    HostCall hc = host_call(c, k.fn, {db, zb, n * 8});            // a region of 0 bytes takes nothing
+    hc.up(0, k.dirs, db);
+    hc.up(1, has_depth ? k.depth->texels : nullptr, zb);
+    hc.step([&] { return rays_launch(c, k, db ? hc.at<float>(0) : nullptr, hc.at<float>(1), dp, hc.at<uint2>(2), (size_t)k.w * 8, c->stream); });
     hc.down(out, 2, n * 8);
     return hc.finish();
 }
 
-int depth_device(csky_ctx* c, const char* fn, const csky_cloud_params* p, const csky_view* view, bool is_view, int w, int h, const void* d_dirs, const csky_observer* obs,
-                 const csky_scene_depth* depth, void* d_out, size_t pitch, void* hip_stream) {
-    if (!d_out) return fail(c, CSKY_ERR_INVALID, "%s: d_out is NULL", fn);
-    if (!is_view && !d_dirs) return fail(c, CSKY_ERR_INVALID, "%s: d_dirs_xyz is NULL", fn);
-    int rc;
-    if ((rc = depth_check(c, fn, depth, is_view, false, w, h, d_out, pitch)) || (rc = observer_check(c, fn, obs)) || (rc = rays_check(c, fn, p, view, is_view, w, h, pitch)) ||
-        (rc = bind(c))) return rc;
-    return depth_launch(c, fn, p, view, w, h, is_view ? nullptr : static_cast<const float*>(d_dirs), obs, static_cast<const float*>(depth->texels), depth->pitch_bytes,
-                        depth->kind, static_cast<uint2*>(d_out), pitch, stream_of(c, hip_stream));
+// The _device forms: the caller's pointers, pitch and stream.
+int rays_device(csky_ctx* c, const RaysCall& k, void* d_out, size_t pitch, void* hip_stream) {
+    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "%s: ctx is NULL", k.fn);
+    if (const int rc = rays_call_check(c, k, false, d_out, pitch)) return rc;
+    const bool has_depth = k.form & RAYS_DEPTH;
+    return rays_launch(c, k, static_cast<const float*>(k.dirs), has_depth ? static_cast<const float*>(k.depth->texels) : nullptr, has_depth ? k.depth->pitch_bytes : 0,
+                       static_cast<uint2*>(d_out), pitch, stream_of(c, hip_stream));
 }
 
 }  // namespace
@@ -194,10 +208,8 @@ extern "C" {
 int csky_render_clouds_view_update(csky_ctx* c, const csky_cloud_params* p, const csky_view* view, const csky_view* prev_view, int w, int h, int block, int phase,
                                    const uint16_t* prev, uint16_t* out) {
     const char* fn = "csky_render_clouds_view_update";
-    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "%s: ctx is NULL", fn);
-    if (!out) return fail(c, CSKY_ERR_INVALID, "%s: out is NULL", fn);
-    const size_t tight = (w >= 1 && w <= 8192) ? (size_t)w * 8 : 8;
-    int rc; if ((rc = update_check(c, fn, prev_view, w, h, block, phase, prev, tight, out, tight)) || (rc = rays_check(c, fn, p, view, true, w, h, tight)) || (rc = bind(c))) return rc;
+    const size_t tight = tight_pitch(w);
+    if (const int rc = update_begin(c, fn, true, p, view, prev_view, w, h, block, phase, prev, tight, out, tight)) return rc;
     const size_t n = (size_t)w * h, pb = prev ? n * 8 : 0;
     HostCall hc = host_call(c, fn, {pb, n * 8});
     hc.up(0, prev, pb);
@@ -209,99 +221,65 @@ int csky_render_clouds_view_update(csky_ctx* c, const csky_cloud_params* p, cons
 int csky_render_clouds_view_update_device(csky_ctx* c, const csky_cloud_params* p, const csky_view* view, const csky_view* prev_view, int w, int h, int block, int phase,
                                           const void* d_prev, size_t prev_pitch, void* d_out, size_t pitch, void* hip_stream) {
     const char* fn = "csky_render_clouds_view_update_device";
-    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "%s: ctx is NULL", fn);
-    if (!d_out) return fail(c, CSKY_ERR_INVALID, "%s: d_out is NULL", fn);
-    int rc; if ((rc = update_check(c, fn, prev_view, w, h, block, phase, d_prev, prev_pitch, d_out, pitch)) || (rc = rays_check(c, fn, p, view, true, w, h, pitch)) || (rc = bind(c))) return rc;
+    if (const int rc = update_begin(c, fn, false, p, view, prev_view, w, h, block, phase, d_prev, prev_pitch, d_out, pitch)) return rc;
     return update_launch(c, fn, p, view, prev_view, w, h, block, phase, static_cast<const uint2*>(d_prev), prev_pitch, static_cast<uint2*>(d_out), pitch, stream_of(c, hip_stream));
 }
 
+// RaysCall: {fn, form, params, view, w, h, dirs, observer, depth}
 int csky_render_clouds_dirs(csky_ctx* c, const csky_cloud_params* p, int w, int h, const float* dirs, uint16_t* out) {
-    const char* fn = "csky_render_clouds_dirs";
-    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "%s: ctx is NULL", fn);
-    return rays_host(c, fn, p, nullptr, false, w, h, dirs, out);
+    return rays_host(c, {"csky_render_clouds_dirs", 0, p, nullptr, w, h, dirs, nullptr, nullptr}, out);
 }
 
 int csky_render_clouds_view(csky_ctx* c, const csky_cloud_params* p, const csky_view* view, int w, int h, uint16_t* out) {
-    const char* fn = "csky_render_clouds_view";
-    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "%s: ctx is NULL", fn);
-    return rays_host(c, fn, p, view, true, w, h, nullptr, out);
+    return rays_host(c, {"csky_render_clouds_view", RAYS_VIEW, p, view, w, h, nullptr, nullptr, nullptr}, out);
 }
 
 int csky_render_clouds_dirs_device(csky_ctx* c, const csky_cloud_params* p, int w, int h, const void* d_dirs, void* d_out, size_t pitch, void* hip_stream) {
-    const char* fn = "csky_render_clouds_dirs_device";
-    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "%s: ctx is NULL", fn);
-    if (!d_dirs || !d_out) return fail(c, CSKY_ERR_INVALID, "%s: d_dirs_xyz or d_out is NULL", fn);
-    int rc; if ((rc = rays_check(c, fn, p, nullptr, false, w, h, pitch)) || (rc = bind(c))) return rc;
-    return rays_launch(c, fn, p, nullptr, w, h, static_cast<const float*>(d_dirs), static_cast<uint2*>(d_out), pitch,
-                       stream_of(c, hip_stream));
+    return rays_device(c, {"csky_render_clouds_dirs_device", 0, p, nullptr, w, h, d_dirs, nullptr, nullptr}, d_out, pitch, hip_stream);
 }
 
 int csky_render_clouds_view_device(csky_ctx* c, const csky_cloud_params* p, const csky_view* view, int w, int h, void* d_out, size_t pitch, void* hip_stream) {
-    const char* fn = "csky_render_clouds_view_device";
-    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "%s: ctx is NULL", fn);
-    if (!d_out) return fail(c, CSKY_ERR_INVALID, "%s: d_out is NULL", fn);
-    int rc; if ((rc = rays_check(c, fn, p, view, true, w, h, pitch)) || (rc = bind(c))) return rc;
-    return rays_launch(c, fn, p, view, w, h, nullptr, static_cast<uint2*>(d_out), pitch, stream_of(c, hip_stream));
+    return rays_device(c, {"csky_render_clouds_view_device", RAYS_VIEW, p, view, w, h, nullptr, nullptr, nullptr}, d_out, pitch, hip_stream);
 }
 
 // ---- the same from an observer's position (observer_core.h)
 int csky_render_clouds_dirs_from(csky_ctx* c, const csky_cloud_params* p, int w, int h, const float* dirs, const csky_observer* obs, uint16_t* out) {
-    const char* fn = "csky_render_clouds_dirs_from";
-    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "%s: ctx is NULL", fn);
-    return rays_host(c, fn, p, nullptr, false, w, h, dirs, out, true, obs);
+    return rays_host(c, {"csky_render_clouds_dirs_from", RAYS_FROM, p, nullptr, w, h, dirs, obs, nullptr}, out);
 }
 
 int csky_render_clouds_view_from(csky_ctx* c, const csky_cloud_params* p, const csky_view* view, const csky_observer* obs, int w, int h, uint16_t* out) {
-    const char* fn = "csky_render_clouds_view_from";
-    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "%s: ctx is NULL", fn);
-    return rays_host(c, fn, p, view, true, w, h, nullptr, out, true, obs);
+    return rays_host(c, {"csky_render_clouds_view_from", RAYS_VIEW | RAYS_FROM, p, view, w, h, nullptr, obs, nullptr}, out);
 }
 
 int csky_render_clouds_dirs_from_device(csky_ctx* c, const csky_cloud_params* p, int w, int h, const void* d_dirs, const csky_observer* obs, void* d_out, size_t pitch,
                                         void* hip_stream) {
-    const char* fn = "csky_render_clouds_dirs_from_device";
-    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "%s: ctx is NULL", fn);
-    if (!d_dirs || !d_out) return fail(c, CSKY_ERR_INVALID, "%s: d_dirs_xyz or d_out is NULL", fn);
-    int rc; if ((rc = observer_check(c, fn, obs)) || (rc = rays_check(c, fn, p, nullptr, false, w, h, pitch)) || (rc = bind(c))) return rc;
-    return rays_launch(c, fn, p, nullptr, w, h, static_cast<const float*>(d_dirs), static_cast<uint2*>(d_out), pitch, stream_of(c, hip_stream), obs);
+    return rays_device(c, {"csky_render_clouds_dirs_from_device", RAYS_FROM, p, nullptr, w, h, d_dirs, obs, nullptr}, d_out, pitch, hip_stream);
 }
 
 int csky_render_clouds_view_from_device(csky_ctx* c, const csky_cloud_params* p, const csky_view* view, const csky_observer* obs, int w, int h, void* d_out, size_t pitch,
                                         void* hip_stream) {
-    const char* fn = "csky_render_clouds_view_from_device";
-    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "%s: ctx is NULL", fn);
-    if (!d_out) return fail(c, CSKY_ERR_INVALID, "%s: d_out is NULL", fn);
-    int rc; if ((rc = observer_check(c, fn, obs)) || (rc = rays_check(c, fn, p, view, true, w, h, pitch)) || (rc = bind(c))) return rc;
-    return rays_launch(c, fn, p, view, w, h, nullptr, static_cast<uint2*>(d_out), pitch, stream_of(c, hip_stream), obs);
+    return rays_device(c, {"csky_render_clouds_view_from_device", RAYS_VIEW | RAYS_FROM, p, view, w, h, nullptr, obs, nullptr}, d_out, pitch, hip_stream);
 }
 
 // ---- the same behind a per-pixel scene depth (scene_depth_core.h)
 int csky_render_clouds_view_from_depth(csky_ctx* c, const csky_cloud_params* p, const csky_view* view, const csky_observer* obs, int w, int h, const csky_scene_depth* depth,
                                        uint16_t* out) {
-    const char* fn = "csky_render_clouds_view_from_depth";
-    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "%s: ctx is NULL", fn);
-    return depth_host(c, fn, p, view, true, w, h, nullptr, obs, depth, out);
+    return rays_host(c, {"csky_render_clouds_view_from_depth", RAYS_VIEW | RAYS_FROM | RAYS_DEPTH, p, view, w, h, nullptr, obs, depth}, out);
 }
 
 int csky_render_clouds_dirs_from_depth(csky_ctx* c, const csky_cloud_params* p, int w, int h, const float* dirs, const csky_observer* obs, const csky_scene_depth* depth,
                                        uint16_t* out) {
-    const char* fn = "csky_render_clouds_dirs_from_depth";
-    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "%s: ctx is NULL", fn);
-    return depth_host(c, fn, p, nullptr, false, w, h, dirs, obs, depth, out);
+    return rays_host(c, {"csky_render_clouds_dirs_from_depth", RAYS_FROM | RAYS_DEPTH, p, nullptr, w, h, dirs, obs, depth}, out);
 }
 
 int csky_render_clouds_view_from_depth_device(csky_ctx* c, const csky_cloud_params* p, const csky_view* view, const csky_observer* obs, int w, int h,
                                               const csky_scene_depth* depth, void* d_out, size_t pitch, void* hip_stream) {
-    const char* fn = "csky_render_clouds_view_from_depth_device";
-    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "%s: ctx is NULL", fn);
-    return depth_device(c, fn, p, view, true, w, h, nullptr, obs, depth, d_out, pitch, hip_stream);
+    return rays_device(c, {"csky_render_clouds_view_from_depth_device", RAYS_VIEW | RAYS_FROM | RAYS_DEPTH, p, view, w, h, nullptr, obs, depth}, d_out, pitch, hip_stream);
 }
 
 int csky_render_clouds_dirs_from_depth_device(csky_ctx* c, const csky_cloud_params* p, int w, int h, const void* d_dirs, const csky_observer* obs,
                                               const csky_scene_depth* depth, void* d_out, size_t pitch, void* hip_stream) {
-    const char* fn = "csky_render_clouds_dirs_from_depth_device";
-    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "%s: ctx is NULL", fn);
-    return depth_device(c, fn, p, nullptr, false, w, h, d_dirs, obs, depth, d_out, pitch, hip_stream);
+    return rays_device(c, {"csky_render_clouds_dirs_from_depth_device", RAYS_FROM | RAYS_DEPTH, p, nullptr, w, h, d_dirs, obs, depth}, d_out, pitch, hip_stream);
 }
 
 }  // extern "C"

@@ -30,8 +30,8 @@ template <int TLUT> __global__ __launch_bounds__(256) void cloud_aerial_kernel(c
     if (p.valid) out[at] = c;
 }
 
-// The same step on a ray frame (view_depth_core.h cloud_aerial_dir).  SRC 0: directions from `dirs` ([H][W][3] floats, tightly
-// packed); 1: the view of G (rays_core.h rays_view_dir).  A pixel whose direction the march would not have taken passes like one without a cloud.
+// The same step on a ray frame (view_depth_core.h cloud_aerial_dir).  SRC (rays_core.h rays_lane_dir) 0: directions from `dirs`
+// ([H][W][3] floats, tightly packed); 1: the view of G.  A pixel whose direction the march would not have taken passes like one without a cloud.
 template <int SRC, int TLUT> __global__ __launch_bounds__(256) void cloud_aerial_rays_kernel(const CloudAerialGeom g, const RaysGeom G, const float* __restrict__ dirs,
                                                                                               const float4* __restrict__ trans, int tw, int th, const uint2* cloud,
                                                                                               const uint2* depth, uint2* out) {
@@ -39,13 +39,9 @@ template <int SRC, int TLUT> __global__ __launch_bounds__(256) void cloud_aerial
     const size_t at = (size_t)(p.valid ? p.j : 0) * (size_t)g.w + (size_t)(p.valid ? p.i : 0);
     uint2 c, z;
     c.x = c.y = z.x = z.y = 0u;
-    float ex = 0.0f, ey = 0.0f, ez = 0.0f;                     // (0, 0, 0) fails rays_accept
+    float ex, ey, ez;
     if (p.valid) { c = cloud[at]; z = depth[at]; }
-    if constexpr (SRC == 0) {
-        if (p.valid) { const float* __restrict__ d = dirs + at * 3; ex = d[0]; ey = d[1]; ez = d[2]; }
-    } else {
-        rays_view_dir(G, p.valid ? p.i : 0, p.valid ? p.j : 0, ex, ey, ez);
-    }
+    rays_lane_dir<SRC>(G, dirs, p, ex, ey, ez);   // G.w x G.h = g.w x g.h (launch_cloud_aerial_rays)
     const bool work = p.valid && !cloud_aerial_dir_passes(c, z, ex, ey, ez);
     if (__builtin_amdgcn_ballot_w64(work) == 0ull) {           // clear sky, or a tile under the horizon
         if (p.valid) out[at] = c;

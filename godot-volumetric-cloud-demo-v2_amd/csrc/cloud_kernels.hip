@@ -7,6 +7,12 @@
 //   lpt_*_kernel, static_order_kernel               : the launch orders
 //   interleave_bands_kernel, sqrt_shell_kernel      : the band interleave of a gathered frame (what becomes of the bands these kernels
 //                                                     write when N ranks split a frame) and the test hook of cloud_core.h::sqrt_shell
+//   march_store and the direct march                : whole rays of a W x H image in natural order, one pixel per lane; each kernel is a lane pixel,
+//                                                     a direction, its own ray maker and the shared tail march_store:
+//     clouds_rays_kernel<SRC, TS>                   :   caller-given directions or a camera view, from the reference's observer (§17)
+//     clouds_view_fresh_kernel / _reproject_kernel  :   the temporal split of a view frame: the fresh sub-grid; history taps and holes (§20)
+//     clouds_observer_kernel<SRC, TS>               :   the same rays from an observer's position (§21)
+//     clouds_observer_depth_kernel<SRC, KIND, TS>   :   those behind a per-pixel scene depth (§22)
 //
 // No MFMA anywhere: the path is fetch/latency-bound gather + fp32 VALU, not a contraction.
 // What was built here, measured and removed again is recorded in docs/EXPERIMENTS.md §5.
@@ -1019,46 +1025,43 @@ hipError_t launch_clouds(int variant, int seg, const TexSet& t, const FrameConst
 // side per workgroup (32 x 8 pixels), march_compact<true, false> (whole rays, no tally: nobody reads a count here) on the frame constants the cloud
 // frame's own set-up kernel wrote.  A plain launch in natural order: workgroup b is footprint b, row-major.  Lanes outside the image and lanes whose
 // direction fails rays_core.h rays_accept do not march (`above = false`): they take no sample and compute no texture address; the latter store zeros.
+//
+// Every kernel from here to the end of the file is this one with another front end, and is written as: the lane's pixel (csky_common.h tile_pixel),
+// its direction (rays_core.h rays_lane_dir, or the update's view_update_dir), the kernel's own ray maker, march_store.
 #include "rays_core.h"
 #pragma clang fp contract(off)   // (rays_core.h ends with contraction on, like cloud_core.h)
 
 namespace csky {
 
-// SRC 0: directions from `dirs` ([H][W][3] floats, tightly packed); 1: the view of G (composite_eyedir, view_mode 1)
+// The shared tail.  The lanes with `marches` run `ray` whole through march_compact on their wavefront's quarter of the workgroup's queues and store
+// the texel at pixel (i, j) of `out` (store_pixel's packing); the others take no sample, compute no texture address and store nothing.  The queues
+// are this function's: a kernel that ends here has no other LDS.  RISING: march_compact's.
+template <bool RISING, class TS>
+__device__ __forceinline__ void march_store(TS T, const FrameConsts& fc, Ray ray, bool marches, int wave, uint2* __restrict__ out, uint32_t pitch_px, int i, int j) {
+    __shared__ float lds[4][CQ_FLOATS];
+    T.detail_lds = nullptr;                                    // compile-time constant here: the LDS tap path folds away
+    if (!marches) ray.above = false;
+    const MarchOut o = march_compact<true, false, 0, TS, RISING>(T, fc, ray, &lds[wave][0], 0, fc.primary_steps);
+    if (marches) out[(size_t)j * pitch_px + i] = pack_half4(f2h(o.r), f2h(o.g), f2h(o.b), f2h(o.a));
+}
+
+// SRC: rays_lane_dir's (0: directions from `dirs`; 1: the view of G)
 template <int SRC, class TS>
 __global__ __launch_bounds__(256, CSKY_COMPACT_WAVES) void clouds_rays_kernel(TS T, const FrameConsts* __restrict__ fcp, RaysGeom G, const float* __restrict__ dirs,
                                                                               uint2* __restrict__ out) {
-    __shared__ float lds[4][CQ_FLOATS];
-    const int tiles_x = (G.w + 31) >> 5;                       // csky_common.h tile_pixel's arithmetic, kept as its own copy (through that function this kernel's code is not the parent's)
-    const int slab = (int)blockIdx.x / tiles_x, bx = (int)blockIdx.x - slab * tiles_x;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int gx = bx * 32 + wave * 8 + (lane & 7);
-    const int gy = slab * 8 + (lane >> 3);
-    const bool valid = gx < G.w && gy < G.h;
-    const FrameConsts& fc = *fcp;
-    T.detail_lds = nullptr;                                    // compile-time constant here: the LDS tap path folds away
-    float ex = 0.0f, ey = 0.0f, ez = 0.0f;                     // (0, 0, 0) fails rays_accept
-    if constexpr (SRC == 0) {
-        if (valid) { const float* __restrict__ d = dirs + ((size_t)gy * (size_t)G.w + (size_t)gx) * 3; ex = d[0]; ey = d[1]; ez = d[2]; }
-    } else {
-        rays_view_dir(G, valid ? gx : 0, valid ? gy : 0, ex, ey, ez);
-    }
-    Ray ray = rays_ray(fc, ex, ey, ez);
-    if (!valid) ray.above = false;
-    const MarchOut o = march_compact<true, false>(T, fc, ray, &lds[wave][0], 0, fc.primary_steps);
-    if (valid) out[(size_t)gy * G.pitch_px + gx] = pack_half4(f2h(o.r), f2h(o.g), f2h(o.b), f2h(o.a));   // store_pixel's packing
+    const TilePixel p = tile_pixel(G.w, G.h);
+    float ex, ey, ez;
+    rays_lane_dir<SRC>(G, dirs, p, ex, ey, ez);
+    march_store<true>(T, *fcp, rays_ray(*fcp, ex, ey, ez), p.valid, p.wave, out, G.pitch_px, p.i, p.j);
 }
 
 hipError_t launch_clouds_rays(const TexSet& t, const TexSet32* t32, const FrameConsts* d_fc, const RaysGeom& g, const float* d_dirs, uint2* d_out, hipStream_t s) {
-    if (g.w < 1 || g.h < 1 || g.w > 8192 || g.h > 8192 || g.pitch_px < (uint32_t)g.w) return hipErrorInvalidValue;
-    const unsigned grid = (unsigned)(((g.w + 31) >> 5) * ((g.h + 7) >> 3));
-    if (t32) {
-        if (d_dirs) clouds_rays_kernel<0, TexSet32><<<grid, 256, 0, s>>>(*t32, d_fc, g, d_dirs, d_out);
-        else clouds_rays_kernel<1, TexSet32><<<grid, 256, 0, s>>>(*t32, d_fc, g, d_dirs, d_out);
-    } else {
-        if (d_dirs) clouds_rays_kernel<0, TexSet><<<grid, 256, 0, s>>>(t, d_fc, g, d_dirs, d_out);
-        else clouds_rays_kernel<1, TexSet><<<grid, 256, 0, s>>>(t, d_fc, g, d_dirs, d_out);
-    }
+    if (!rays_geom_ok(g)) return hipErrorInvalidValue;
+    const unsigned grid = (unsigned)tile_grid(g.w, g.h);
+    with_texset(t, t32, [&](const auto& ts) {
+        if (d_dirs) clouds_rays_kernel<0><<<grid, 256, 0, s>>>(ts, d_fc, g, d_dirs, d_out);
+        else clouds_rays_kernel<1><<<grid, 256, 0, s>>>(ts, d_fc, g, d_dirs, d_out);
+    });
     return hipGetLastError();
 }
 
@@ -1074,26 +1077,15 @@ hipError_t launch_clouds_rays(const TexSet& t, const TexSet32* t32, const FrameC
 
 namespace csky {
 
-// The fresh pixels, run over the SUB-GRID: lane (gx, gy) of G.sub_w x G.sub_h marches pixel (gx * B + px, gy * B + py) and stores there.  The
+// The fresh pixels, run over the SUB-GRID: lane (p.i, p.j) of G.sub_w x G.sub_h marches pixel (p.i * B + px, p.j * B + py) and stores there.  The
 // fresh rays fill whole 8x8 tiles: a wavefront of 64 fresh rays, not 4 lanes of every wavefront of the image.
 template <class TS>
 __global__ __launch_bounds__(256, CSKY_COMPACT_WAVES) void clouds_view_fresh_kernel(TS T, const FrameConsts* __restrict__ fcp, ViewUpdateGeom G, uint2* __restrict__ out) {
-    __shared__ float lds[4][CQ_FLOATS];
-    const int tiles_x = (G.sub_w + 31) >> 5;
-    const int slab = (int)blockIdx.x / tiles_x, bx = (int)blockIdx.x - slab * tiles_x;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int gx = bx * 32 + wave * 8 + (lane & 7);
-    const int gy = slab * 8 + (lane >> 3);
-    const bool valid = gx < G.sub_w && gy < G.sub_h;
-    const int i = valid ? gx * G.block + G.px : 0, j = valid ? gy * G.block + G.py : 0;   // < G.w, G.h by the sub-grid's size
-    const FrameConsts& fc = *fcp;
-    T.detail_lds = nullptr;                                    // compile-time constant here: the LDS tap path folds away
+    const TilePixel p = tile_pixel(G.sub_w, G.sub_h);
+    const int i = p.valid ? p.i * G.block + G.px : 0, j = p.valid ? p.j * G.block + G.py : 0;   // < G.w, G.h by the sub-grid's size
     float ex, ey, ez;
     view_update_dir(G, i, j, ex, ey, ez);
-    Ray ray = rays_ray(fc, ex, ey, ez);
-    if (!valid) ray.above = false;
-    const MarchOut o = march_compact<true, false>(T, fc, ray, &lds[wave][0], 0, fc.primary_steps);
-    if (valid) out[(size_t)j * G.pitch_px + i] = pack_half4(f2h(o.r), f2h(o.g), f2h(o.b), f2h(o.a));
+    march_store<true>(T, *fcp, rays_ray(*fcp, ex, ey, ez), p.valid, p.wave, out, G.pitch_px, i, j);
 }
 
 // Every other pixel, one per lane over the full image.  A lane that is not fresh stores zeros (not accepted), its history texel, or is a hole.  A
@@ -1102,50 +1094,31 @@ __global__ __launch_bounds__(256, CSKY_COMPACT_WAVES) void clouds_view_fresh_ker
 template <class TS>
 __global__ __launch_bounds__(256, CSKY_COMPACT_WAVES) void clouds_view_reproject_kernel(TS T, const FrameConsts* __restrict__ fcp, ViewUpdateGeom G,
                                                                                         const uint2* __restrict__ prev, uint2* __restrict__ out) {
-    __shared__ float lds[4][CQ_FLOATS];
-    const int tiles_x = (G.w + 31) >> 5;
-    const int slab = (int)blockIdx.x / tiles_x, bx = (int)blockIdx.x - slab * tiles_x;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int gx = bx * 32 + wave * 8 + (lane & 7);
-    const int gy = slab * 8 + (lane >> 3);
-    const bool valid = gx < G.w && gy < G.h;
-    const FrameConsts& fc = *fcp;
-    T.detail_lds = nullptr;
+    const TilePixel p = tile_pixel(G.w, G.h);
     float ex, ey, ez;
-    view_update_dir(G, valid ? gx : 0, valid ? gy : 0, ex, ey, ez);
-    const ViewUpdateClass c = view_update_classify(G, gx, gy, ex, ey, ez);
-    const int kind = valid ? c.kind : VU_FRESH;                // a lane outside the image stores nothing, like a fresh one
-    uint2* __restrict__ dst = out + ((size_t)gy * G.pitch_px + gx);
+    view_update_dir(G, p.valid ? p.i : 0, p.valid ? p.j : 0, ex, ey, ez);
+    const ViewUpdateClass c = view_update_classify(G, p.i, p.j, ex, ey, ez);
+    const int kind = p.valid ? c.kind : VU_FRESH;              // a lane outside the image stores nothing, like a fresh one
+    uint2* __restrict__ dst = out + ((size_t)p.j * G.pitch_px + p.i);
     if (kind == VU_ZERO) { uint2 z; z.x = 0u; z.y = 0u; *dst = z; }
-    else if (kind == VU_COPY) *dst = prev[(size_t)gy * G.prev_pitch_px + gx];
+    else if (kind == VU_COPY) *dst = prev[(size_t)p.j * G.prev_pitch_px + p.i];
     else if (kind == VU_TAP) *dst = view_update_tap(prev, G.prev_pitch_px, G.w, G.h, c.ux, c.uy);
     const bool hole = kind == VU_HOLE;
     if (__builtin_amdgcn_ballot_w64(hole) == 0ull) return;
-    Ray ray = rays_ray(fc, hole ? ex : 0.0f, hole ? ey : 0.0f, hole ? ez : 0.0f);   // (0, 0, 0) fails rays_accept: no sample, no address
-    if (!hole) ray.above = false;
-    const MarchOut o = march_compact<true, false>(T, fc, ray, &lds[wave][0], 0, fc.primary_steps);
-    if (hole) *dst = pack_half4(f2h(o.r), f2h(o.g), f2h(o.b), f2h(o.a));
-}
-
-template <class TS>
-static hipError_t launch_view_update_ts(const TS& t, const FrameConsts* d_fc, const ViewUpdateGeom& g, const uint2* d_prev, uint2* d_out, hipStream_t s) {
-    if (g.sub_w > 0 && g.sub_h > 0) {
-        const unsigned fresh = (unsigned)(((g.sub_w + 31) >> 5) * ((g.sub_h + 7) >> 3));
-        clouds_view_fresh_kernel<TS><<<fresh, 256, 0, s>>>(t, d_fc, g, d_out);
-    }
-    if (g.block > 1) {                                          // B = 1: every pixel is fresh
-        const unsigned grid = (unsigned)(((g.w + 31) >> 5) * ((g.h + 7) >> 3));
-        clouds_view_reproject_kernel<TS><<<grid, 256, 0, s>>>(t, d_fc, g, d_prev, d_out);
-    }
-    return hipGetLastError();
+    // (0, 0, 0) fails rays_accept: no sample, no address
+    march_store<true>(T, *fcp, rays_ray(*fcp, hole ? ex : 0.0f, hole ? ey : 0.0f, hole ? ez : 0.0f), hole, p.wave, out, G.pitch_px, p.i, p.j);
 }
 
 hipError_t launch_clouds_view_update(const TexSet& t, const TexSet32* t32, const FrameConsts* d_fc, const ViewUpdateGeom& g, const uint2* d_prev, uint2* d_out, hipStream_t s) {
-    if (g.w < 1 || g.h < 1 || g.w > 8192 || g.h > 8192 || g.pitch_px < (uint32_t)g.w) return hipErrorInvalidValue;
+    if (!rays_geom_ok(g)) return hipErrorInvalidValue;
     if (g.block < 1 || g.block > 8 || g.px < 0 || g.px >= g.block || g.py < 0 || g.py >= g.block) return hipErrorInvalidValue;
     if ((g.has_history != 0) != (d_prev != nullptr) || (d_prev && g.prev_pitch_px < (uint32_t)g.w)) return hipErrorInvalidValue;
     if (g.sub_w != (g.px < g.w ? (g.w - g.px + g.block - 1) / g.block : 0) || g.sub_h != (g.py < g.h ? (g.h - g.py + g.block - 1) / g.block : 0)) return hipErrorInvalidValue;
-    return t32 ? launch_view_update_ts(*t32, d_fc, g, d_prev, d_out, s) : launch_view_update_ts(t, d_fc, g, d_prev, d_out, s);
+    with_texset(t, t32, [&](const auto& ts) {
+        if (g.sub_w > 0 && g.sub_h > 0) clouds_view_fresh_kernel<<<tile_grid(g.sub_w, g.sub_h), 256, 0, s>>>(ts, d_fc, g, d_out);
+        if (g.block > 1) clouds_view_reproject_kernel<<<tile_grid(g.w, g.h), 256, 0, s>>>(ts, d_fc, g, d_prev, d_out);   // B = 1: every pixel is fresh
+    });
+    return hipGetLastError();
 }
 
 }  // namespace csky
@@ -1160,41 +1133,23 @@ hipError_t launch_clouds_view_update(const TexSet& t, const TexSet32* t32, const
 
 namespace csky {
 
-// SRC 0: directions from `dirs` ([H][W][3] floats, tightly packed); 1: the view of G.g (composite_eyedir, view_mode 1)
+// SRC: rays_lane_dir's, on G.g
 template <int SRC, class TS>
 __global__ __launch_bounds__(256, CSKY_COMPACT_WAVES) void clouds_observer_kernel(TS T, const FrameConsts* __restrict__ fcp, ObserverGeom G, const float* __restrict__ dirs,
                                                                                   uint2* __restrict__ out) {
-    __shared__ float lds[4][CQ_FLOATS];
-    const int tiles_x = (G.g.w + 31) >> 5;
-    const int slab = (int)blockIdx.x / tiles_x, bx = (int)blockIdx.x - slab * tiles_x;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int gx = bx * 32 + wave * 8 + (lane & 7);
-    const int gy = slab * 8 + (lane >> 3);
-    const bool valid = gx < G.g.w && gy < G.g.h;
-    const FrameConsts& fc = *fcp;
-    T.detail_lds = nullptr;                                    // compile-time constant here: the LDS tap path folds away
-    float ex = 0.0f, ey = 0.0f, ez = 0.0f;                     // (0, 0, 0) fails observer_accept
-    if constexpr (SRC == 0) {
-        if (valid) { const float* __restrict__ d = dirs + ((size_t)gy * (size_t)G.g.w + (size_t)gx) * 3; ex = d[0]; ey = d[1]; ez = d[2]; }
-    } else {
-        rays_view_dir(G.g, valid ? gx : 0, valid ? gy : 0, ex, ey, ez);
-    }
-    Ray ray = observer_ray(fc, G, ex, ey, ez);
-    if (!valid) ray.above = false;
-    const MarchOut o = march_compact<true, false, 0, TS, false>(T, fc, ray, &lds[wave][0], 0, fc.primary_steps);
-    if (valid) out[(size_t)gy * G.g.pitch_px + gx] = pack_half4(f2h(o.r), f2h(o.g), f2h(o.b), f2h(o.a));   // store_pixel's packing
+    const TilePixel p = tile_pixel(G.g.w, G.g.h);
+    float ex, ey, ez;
+    rays_lane_dir<SRC>(G.g, dirs, p, ex, ey, ez);
+    march_store<false>(T, *fcp, observer_ray(*fcp, G, ex, ey, ez), p.valid, p.wave, out, G.g.pitch_px, p.i, p.j);
 }
 
 hipError_t launch_clouds_observer(const TexSet& t, const TexSet32* t32, const FrameConsts* d_fc, const ObserverGeom& g, const float* d_dirs, uint2* d_out, hipStream_t s) {
-    if (g.g.w < 1 || g.g.h < 1 || g.g.w > 8192 || g.g.h > 8192 || g.g.pitch_px < (uint32_t)g.g.w) return hipErrorInvalidValue;
-    const unsigned grid = (unsigned)(((g.g.w + 31) >> 5) * ((g.g.h + 7) >> 3));
-    if (t32) {
-        if (d_dirs) clouds_observer_kernel<0, TexSet32><<<grid, 256, 0, s>>>(*t32, d_fc, g, d_dirs, d_out);
-        else clouds_observer_kernel<1, TexSet32><<<grid, 256, 0, s>>>(*t32, d_fc, g, d_dirs, d_out);
-    } else {
-        if (d_dirs) clouds_observer_kernel<0, TexSet><<<grid, 256, 0, s>>>(t, d_fc, g, d_dirs, d_out);
-        else clouds_observer_kernel<1, TexSet><<<grid, 256, 0, s>>>(t, d_fc, g, d_dirs, d_out);
-    }
+    if (!rays_geom_ok(g.g)) return hipErrorInvalidValue;
+    const unsigned grid = (unsigned)tile_grid(g.g.w, g.g.h);
+    with_texset(t, t32, [&](const auto& ts) {
+        if (d_dirs) clouds_observer_kernel<0><<<grid, 256, 0, s>>>(ts, d_fc, g, d_dirs, d_out);
+        else clouds_observer_kernel<1><<<grid, 256, 0, s>>>(ts, d_fc, g, d_dirs, d_out);
+    });
     return hipGetLastError();
 }
 
@@ -1211,49 +1166,37 @@ hipError_t launch_clouds_observer(const TexSet& t, const TexSet32* t32, const Fr
 
 namespace csky {
 
-// SRC as clouds_observer_kernel's.  KIND: DEPTH_DISTANCE or DEPTH_VIEW_Z (view form only), compiled in: the distance form has no dot product or divide.
+// SRC as clouds_observer_kernel's (0: directions from `dirs`, [H][W][3] floats; 1: the view of G.og.g).  KIND: DEPTH_DISTANCE or DEPTH_VIEW_Z (view form only), compiled in: the distance form has no dot product or divide.
 // depth: G.og.g.h rows of G.og.g.w floats, G.depth_pitch floats apart; it does not overlap out.
 template <int SRC, int KIND, class TS>
 __global__ __launch_bounds__(256, CSKY_COMPACT_WAVES) void clouds_observer_depth_kernel(TS T, const FrameConsts* __restrict__ fcp, SceneDepthGeom G, const float* __restrict__ dirs,
                                                                                         const float* __restrict__ depth, uint2* __restrict__ out) {
-    __shared__ float lds[4][CQ_FLOATS];
-    const int tiles_x = (G.og.g.w + 31) >> 5;
-    const int slab = (int)blockIdx.x / tiles_x, bx = (int)blockIdx.x - slab * tiles_x;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int gx = bx * 32 + wave * 8 + (lane & 7);
-    const int gy = slab * 8 + (lane >> 3);
-    const bool valid = gx < G.og.g.w && gy < G.og.g.h;
-    const FrameConsts& fc = *fcp;
-    T.detail_lds = nullptr;                                    // compile-time constant here: the LDS tap path folds away
+    const TilePixel p = tile_pixel(G.og.g.w, G.og.g.h);
     float z = 0.0f;                                            // 0 is no valid texel
-    if (valid) z = depth[(size_t)gy * G.depth_pitch + gx];
+    if (p.valid) z = depth[(size_t)p.j * G.depth_pitch + p.i];
+    // rays_lane_dir<SRC>(G.og.g, dirs, p, ...), kept as its own copy: through that function the view forms of this kernel are the parent's
+    // instructions in another order, and that order missed the timing rule on two of tools/scene_depth_profile.py's eight lines
     float ex = 0.0f, ey = 0.0f, ez = 0.0f;                     // (0, 0, 0) fails observer_accept
     if constexpr (SRC == 0) {
-        if (valid) { const float* __restrict__ d = dirs + ((size_t)gy * (size_t)G.og.g.w + (size_t)gx) * 3; ex = d[0]; ey = d[1]; ez = d[2]; }
+        if (p.valid) { const float* __restrict__ d = dirs + ((size_t)p.j * (size_t)G.og.g.w + (size_t)p.i) * 3; ex = d[0]; ey = d[1]; ez = d[2]; }
     } else {
-        rays_view_dir(G.og.g, valid ? gx : 0, valid ? gy : 0, ex, ey, ez);
+        rays_view_dir(G.og.g, p.valid ? p.i : 0, p.valid ? p.j : 0, ex, ey, ez);
     }
-    Ray ray = scene_depth_ray_k<KIND>(fc, G.og, ex, ey, ez, z);
-    if (!valid) ray.above = false;
-    const MarchOut o = march_compact<true, false, 0, TS, false>(T, fc, ray, &lds[wave][0], 0, fc.primary_steps);
-    if (valid) out[(size_t)gy * G.og.g.pitch_px + gx] = pack_half4(f2h(o.r), f2h(o.g), f2h(o.b), f2h(o.a));   // store_pixel's packing
-}
-
-template <class TS>
-static hipError_t launch_observer_depth_ts(const TS& t, const FrameConsts* d_fc, const SceneDepthGeom& g, const float* d_dirs, const float* d_depth, uint2* d_out, hipStream_t s) {
-    const unsigned grid = (unsigned)(((g.og.g.w + 31) >> 5) * ((g.og.g.h + 7) >> 3));
-    if (d_dirs) clouds_observer_depth_kernel<0, DEPTH_DISTANCE, TS><<<grid, 256, 0, s>>>(t, d_fc, g, d_dirs, d_depth, d_out);
-    else if (g.kind == DEPTH_VIEW_Z) clouds_observer_depth_kernel<1, DEPTH_VIEW_Z, TS><<<grid, 256, 0, s>>>(t, d_fc, g, d_dirs, d_depth, d_out);
-    else clouds_observer_depth_kernel<1, DEPTH_DISTANCE, TS><<<grid, 256, 0, s>>>(t, d_fc, g, d_dirs, d_depth, d_out);
-    return hipGetLastError();
+    march_store<false>(T, *fcp, scene_depth_ray_k<KIND>(*fcp, G.og, ex, ey, ez, z), p.valid, p.wave, out, G.og.g.pitch_px, p.i, p.j);
 }
 
 hipError_t launch_clouds_observer_depth(const TexSet& t, const TexSet32* t32, const FrameConsts* d_fc, const SceneDepthGeom& g, const float* d_dirs, const float* d_depth,
                                         uint2* d_out, hipStream_t s) {
-    if (g.og.g.w < 1 || g.og.g.h < 1 || g.og.g.w > 8192 || g.og.g.h > 8192 || g.og.g.pitch_px < (uint32_t)g.og.g.w) return hipErrorInvalidValue;
+    if (!rays_geom_ok(g.og.g)) return hipErrorInvalidValue;
     if (!d_depth || g.depth_pitch < (uint32_t)g.og.g.w) return hipErrorInvalidValue;
     if ((g.kind != DEPTH_DISTANCE && g.kind != DEPTH_VIEW_Z) || (g.kind == DEPTH_VIEW_Z && d_dirs)) return hipErrorInvalidValue;
-    return t32 ? launch_observer_depth_ts(*t32, d_fc, g, d_dirs, d_depth, d_out, s) : launch_observer_depth_ts(t, d_fc, g, d_dirs, d_depth, d_out, s);
+    const unsigned grid = (unsigned)tile_grid(g.og.g.w, g.og.g.h);
+    with_texset(t, t32, [&](const auto& ts) {
+        if (d_dirs) clouds_observer_depth_kernel<0, DEPTH_DISTANCE><<<grid, 256, 0, s>>>(ts, d_fc, g, d_dirs, d_depth, d_out);
+        else if (g.kind == DEPTH_VIEW_Z) clouds_observer_depth_kernel<1, DEPTH_VIEW_Z><<<grid, 256, 0, s>>>(ts, d_fc, g, d_dirs, d_depth, d_out);
+        else clouds_observer_depth_kernel<1, DEPTH_DISTANCE><<<grid, 256, 0, s>>>(ts, d_fc, g, d_dirs, d_depth, d_out);
+    });
+    return hipGetLastError();
 }
 
 }  // namespace csky

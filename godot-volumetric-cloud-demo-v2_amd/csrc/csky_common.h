@@ -184,7 +184,7 @@ CSKY_HD uint2 pack_half4(uint16_t hx, uint16_t hy, uint16_t hz, uint16_t hw) {  
 // wavefronts' 8x8 tiles side by side (lane = ly*8 + lx), the cloud kernel's footprint.  A ragged image masks the lanes of its partial tiles (`valid`).
 CSKY_HD int tile_grid(int w, int h) { return ((w + 31) >> 5) * ((h + 7) >> 3); }   // <= 256 x 1024 for the largest image
 #if defined(__HIPCC__)
-struct TilePixel { int i, j; bool valid; };
+struct TilePixel { int i, j; bool valid; int wave; };   // wave: the lane's wavefront of the workgroup, i.e. which of the four tiles
 CSKY_D TilePixel tile_pixel(int w, int h) {
     const int tiles_x = (w + 31) >> 5;
     const int slab = (int)blockIdx.x / tiles_x, bx = (int)blockIdx.x - slab * tiles_x;
@@ -193,6 +193,7 @@ CSKY_D TilePixel tile_pixel(int w, int h) {
     p.i = bx * 32 + wave * 8 + (lane & 7);
     p.j = slab * 8 + (lane >> 3);
     p.valid = p.i < w && p.j < h;
+    p.wave = wave;
     return p;
 }
 #endif

@@ -7,6 +7,10 @@
 
 namespace csky {
 
+// f(the texture set a launch marches on, as its own type): *t32, the exact fp32-coefficient cells, when there is one, else t.  A generic lambda
+// instantiates its kernel once per type; every launcher that takes (t, t32) and runs the same kernel on either goes through here.
+template <class F> inline void with_texset(const TexSet& t, const TexSet32* t32, F&& f) { if (t32) f(*t32); else f(t); }
+
 // ------------------------------------------------------------------------------------------------ lut_kernels.hip
 // transmittance-lut.glsl main(): writes the RGBA16F image and a float4 copy of the fp16-ROUNDED values
 // (what a sampler would read back), so later kernels sample floats without per-tap half unpacking.

@@ -4,7 +4,8 @@
 // march's Ray from a direction the caller gives (a buffer of directions, or a camera view through composite_core.h's composite_eyedir) instead of from
 // a grid pixel, with cloud_core.h ray_from_dir: the half of ray_setup behind the pixel's direction, so a grid pixel's own direction gives its own ray.
 //
-// Host+device (CSKY_HD) like cloud_core.h: tests/rays_host runs this per-lane code on a CPU.  The product instantiates it inside cloud_kernels.hip only.
+// Host+device (CSKY_HD) like cloud_core.h: tests/rays_host runs this per-lane code on a CPU.  The product instantiates it inside cloud_kernels.hip,
+// depth.hip and cloud_aerial.hip; rays_lane_dir at the end is device-only (it takes csky_common.h's TilePixel).
 #pragma once
 #include "cloud_core.h"
 #include "composite_core.h"
@@ -51,6 +52,10 @@ CSKY_HD RaysGeom rays_geom(const float* basis, float fov_y_degrees, int w, int h
     return g;
 }
 
+// What every launcher of the direct march asks of its geometry block (a RaysGeom, or a block that carries the same three fields): the image's size
+// range, and a row pitch that holds a row.
+template <class G> CSKY_HD bool rays_geom_ok(const G& g) { return g.w >= 1 && g.h >= 1 && g.w <= 8192 && g.h <= 8192 && g.pitch_px >= (uint32_t)g.w; }
+
 // EYEDIR of pixel (i, j) of the view g: composite_eyedir, which reads these fields of its argument block and no other.  (view_mode is 1 in a way the
 // compiler sees: the panorama and cube-face branches fold away.)
 CSKY_HD void rays_view_dir(const RaysGeom& g, int i, int j, float& ex, float& ey, float& ez) {
@@ -73,6 +78,21 @@ CSKY_HD Ray rays_ray(const FrameConsts& fc, float dx, float dy, float dz) {
     Ray r = ray_from_dir(fc, ok ? dx : 0.0f, ok ? dy : 0.0f, ok ? dz : 0.0f);
     return r;
 }
+
+#if defined(__HIPCC__)
+// The direction of the lane's pixel p (csky_common.h tile_pixel) of a ray frame: the one direction source of every kernel that takes one
+// (cloud_kernels.hip, depth.hip, cloud_aerial.hip).  SRC 0: from `dirs` ([g.h][g.w][3] floats, tightly packed, three dword loads); a lane outside the
+// image loads nothing and gets (0, 0, 0), which fails rays_accept and observer_accept.  SRC 1: the view of g (rays_view_dir; dirs is not read); a lane
+// outside the image gets pixel (0, 0)'s direction, and its caller keeps it from marching and storing.
+template <int SRC> CSKY_D void rays_lane_dir(const RaysGeom& g, const float* __restrict__ dirs, const TilePixel& p, float& ex, float& ey, float& ez) {
+    if constexpr (SRC == 0) {
+        ex = 0.0f; ey = 0.0f; ez = 0.0f;
+        if (p.valid) { const float* __restrict__ d = dirs + ((size_t)p.j * (size_t)g.w + (size_t)p.i) * 3; ex = d[0]; ey = d[1]; ez = d[2]; }
+    } else {
+        rays_view_dir(g, p.valid ? p.i : 0, p.valid ? p.j : 0, ex, ey, ez);
+    }
+}
+#endif
 
 #pragma clang fp contract(fast)
 

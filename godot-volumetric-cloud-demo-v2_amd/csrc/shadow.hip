@@ -22,8 +22,7 @@ __global__ __launch_bounds__(256) void shadow_kernel(TS T, const FrameConsts fc,
 
 hipError_t launch_cloud_shadow(const TexSet& t, const TexSet32* t32, const FrameConsts& fc, const ShadowConsts& sc, uint16_t* d_out, hipStream_t s) {
     const int grid = tile_grid(sc.w, sc.h);
-    if (t32) shadow_kernel<TexSet32><<<grid, 256, 0, s>>>(*t32, fc, sc, d_out);
-    else shadow_kernel<TexSet><<<grid, 256, 0, s>>>(t, fc, sc, d_out);
+    with_texset(t, t32, [&](const auto& ts) { shadow_kernel<<<grid, 256, 0, s>>>(ts, fc, sc, d_out); });
     return hipGetLastError();
 }
 
