@@ -125,6 +125,13 @@ class ShapeNoiseParams(C.Structure):
                 ("centre", C.c_float), ("contrast", C.c_float), ("offset", C.c_float)]
 
 
+class WeatherParams(C.Structure):
+    """csky_weather_params (include/cloudsky.h): the knobs of the weather-map generator."""
+    _fields_ = [("coverage_freq", C.c_int32), ("coverage_octaves", C.c_int32), ("type_freq", C.c_int32), ("type_octaves", C.c_int32), ("phase", C.c_float),
+                ("coverage_gain", C.c_float), ("dilate", C.c_float), ("coverage_centre", C.c_float), ("coverage_contrast", C.c_float),
+                ("coverage_offset", C.c_float), ("coverage_floor", C.c_float), ("type_mean", C.c_float), ("type_spread", C.c_float)]
+
+
 MULTI_STATS_MAX = 16
 
 
@@ -144,6 +151,37 @@ def shape_noise_params(**knobs):
             raise TypeError("unknown shape-noise knob %r" % k)
         setattr(p, k, v)
     return p
+
+
+def weather_params(**knobs):
+    """The weather generator's defaults with the given fields replaced."""
+    p = WeatherParams()
+    lib().csky_weather_default_params(C.byref(p))
+    for k, v in knobs.items():
+        if k not in dict(WeatherParams._fields_):
+            raise TypeError("unknown weather knob %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+WEATHER_SHAPE = (512, 512, 3)
+
+
+def _weather_arg(name, weather, device_id):
+    """The weather map a rebind takes: a numpy uint8 [512, 512, 3] array (-> its pointer, False) or a contiguous uint8 tensor of that shape on the
+    context's GPU (-> its pointer, True).  Anything else is refused here, before any library call."""
+    if isinstance(weather, np.ndarray):
+        if weather.shape != WEATHER_SHAPE or weather.dtype != np.uint8 or not weather.flags.c_contiguous:
+            raise ValueError("%s: a host weather map is a contiguous uint8 [512, 512, 3] array" % name)
+        return _ptr(weather), False
+    if hasattr(weather, "data_ptr"):
+        import torch
+        dev = getattr(weather, "device", None)
+        index = dev.index if dev is not None and dev.index is not None else (torch.cuda.current_device() if dev is not None and dev.type == "cuda" else None)
+        if tuple(weather.shape) != WEATHER_SHAPE or weather.dtype != torch.uint8 or not weather.is_contiguous() or dev is None or dev.type != "cuda" or index != device_id:
+            raise ValueError("%s: a device weather map is a contiguous uint8 [512, 512, 3] tensor on cuda:%d" % (name, device_id))
+        return C.c_void_p(int(weather.data_ptr())), True
+    raise ValueError("%s: weather must be a numpy uint8 [512, 512, 3] array or a torch tensor of that shape on the GPU" % name)
 
 
 # every symbol include/cloudsky.h and include/cloudsky_internal.h declare: (name, restype, argtypes); INTERNAL names the second header's (the lab bench)
@@ -278,6 +316,13 @@ SYMBOLS = [
     ("csky_check_shape_noise_params", C.c_int, [C.c_void_p, C.c_int]),
     ("csky_generate_shape_noise_tuned", C.c_int, [C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]),
     ("csky_generate_shape_noise_tuned_device", C.c_int, [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]),
+    ("csky_set_weather", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("csky_set_weather_device", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("csky_set_weather_generated", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    ("csky_weather_default_params", None, [C.c_void_p]),
+    ("csky_check_weather_params", C.c_int, [C.c_void_p]),
+    ("csky_generate_weather", C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p]),
+    ("csky_generate_weather_device", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     ("csky_generate_detail_noise", C.c_int, [C.c_uint32, C.c_int, C.c_void_p]),
     ("csky_generate_detail_noise_device", C.c_int, [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]),
     ("csky_build_mips_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
@@ -550,6 +595,30 @@ class Context:
         if a.size != self._L.csky_mip_offset(128, 8, 4) or b.size != self._L.csky_mip_offset(32, 6, 3) or c.size != 512 * 512 * 3:
             raise ValueError("set_noise_mips: expected the 8-level 128^3 RGBA8 chain, the 6-level 32^3 RGB8 chain, 512^2 RGB8")
         self._chk(self._L.csky_set_noise_mips(self._h, _ptr(a), _ptr(b), _ptr(c)))
+
+    def set_weather(self, weather):
+        """The weather map alone, in a context that set_noise has bound: a numpy uint8 [512, 512, 3] array (csky_set_weather) or a contiguous uint8
+        tensor of that shape on this context's GPU (csky_set_weather_device, only read).  Afterwards the context is as if set_noise had been given
+        this map; the shape and detail volumes, the LUTs and the cell format are untouched."""
+        ptr, device = _weather_arg("set_weather", weather, self.device_id)
+        self._chk((self._L.csky_set_weather_device if device else self._L.csky_set_weather)(self._h, ptr))
+
+    def set_weather_generated(self, seed=1, **knobs):
+        """csky_set_weather_generated: the map of generate_weather(seed, **knobs) made on the GPU in the context's own buffer and bound (knobs: WeatherParams fields)."""
+        p = weather_params(**knobs)
+        self._chk(self._L.csky_set_weather_generated(self._h, int(seed), C.byref(p)))
+
+    def generate_weather(self, seed=1, device=True, **knobs):
+        """A generated weather map, uint8 [512, 512, 3]: the HIP kernel (device=True) or the host generator; byte-identical (knobs: WeatherParams fields)."""
+        p = weather_params(**knobs)
+        out = np.zeros(WEATHER_SHAPE, np.uint8)
+        if device:
+            self._chk(self._L.csky_generate_weather_device(self._h, int(seed), C.byref(p), _ptr(out)))
+        else:
+            rc = self._L.csky_generate_weather(int(seed), C.byref(p), _ptr(out))
+            if rc != OK:
+                raise CloudSkyError(rc, (self._L.csky_assets_last_error() or b"").decode())
+        return out
 
     def encode_bc7(self, images, quality=0):
         """csky_encode_bc7[_quality]: [n, h, w, 4] (or [h, w, 4]) uint8 -> [n, ceil(h/4), ceil(w/4), 16] uint8 BC7 blocks, encoded on the GPU

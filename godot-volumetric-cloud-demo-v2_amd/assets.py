@@ -71,6 +71,21 @@ def generate_detail_noise(seed=1, n=32):
     return vol
 
 
+def weather_default_params():
+    """The weather generator's defaults as a dict (the fields of _lib.WeatherParams, include/cloudsky.h csky_weather_params)."""
+    p = _lib.weather_params()
+    return {k: getattr(p, k) for k, _ in _lib.WeatherParams._fields_}
+
+
+def generate_weather(seed=1, **knobs):
+    """A generated weather map in the role of weather.bmp: uint8 [512, 512, 3], R = cloud type, G = 0, B = coverage; tileable, evolving smoothly in
+    the knob `phase` (period 1).  knobs: fields of _lib.WeatherParams; none = the calibration on the shipped map's statistics."""
+    out = np.zeros(_lib.WEATHER_SHAPE, np.uint8)
+    p = _lib.weather_params(**knobs)
+    _chk(_lib.lib().csky_generate_weather(int(seed), C.byref(p), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
 def build_mips(level0, levels):
     level0 = np.ascontiguousarray(level0, np.uint8)
     n, ch = level0.shape[0], level0.shape[3]

@@ -128,6 +128,22 @@ class CloudSky:
         self.ctx.set_noise(large, small, weather)                              # _create_noise_uniform_set, :298-341
         self.update_performance()
 
+    def set_weather(self, weather=None, *, seed=None, **knobs):
+        """Replace the weather map alone (cloud type in R, coverage in B) between two passes: `weather` is a numpy uint8 [512, 512, 3] array or a
+        contiguous uint8 CUDA tensor of that shape on the context's device (csky_set_weather / csky_set_weather_device); or, with `seed`, the map of
+        assets.generate_weather(seed, **knobs) generated on the GPU (csky_set_weather_generated).  The call waits for the device; tiles marched
+        before it are of the old map, later ones of the new: the textures change over one tile at a time, as they do when the sun moves
+        (request_full_sky_init() for a cut).  The temporal split's history is dropped."""
+        if (weather is None) == (seed is None):
+            raise ValueError("set_weather: give a weather map or a seed")
+        if weather is not None:
+            if knobs:
+                raise ValueError("set_weather: generator knobs go with a seed, not with a map")
+            self.ctx.set_weather(weather)
+        else:
+            self.ctx.set_weather_generated(seed, **knobs)
+        self._temporal = None
+
     # ---- clouds_sky.tres:11-18 ----------------------------------------------------------------------------
     @classmethod
     def from_default_resource(cls, **kw):

@@ -204,6 +204,84 @@ int csky_set_noise_mips(csky_ctx* c, const uint8_t* large_chain_rgba8, const uin
     return set_noise(c, large_chain_rgba8, small_chain_rgb8, weather_rgb8, true);
 }
 
+// ---- the weather map alone (include/cloudsky.h).  Where the 8-bit map comes from: host memory, memory of this device, or the
+// generator kernel writing into the context's own buffer.
+namespace {
+struct WeatherSource { const void* host; const void* dev; const WeatherNoiseParams* gen; uint32_t seed; };
+
+// the bake itself: d_raw_weather filled, the cells of both formats the context marches on rebuilt, the range read back.  Every buffer exists (have())
+int bake_weather(csky_ctx* c, const WeatherSource& src, WeatherRange& range) {
+    NoiseSet& n = c->noise;
+    hipStream_t s = c->stream;
+    struct { unsigned long long inexact; int range[3]; int pad; } meta = {0ull, {255, 0, 0}, 0};   // the bake's counters, as in set_noise; a weather cell never adds to inexact
+    HIPCHK(c, hipMemcpyAsync(n.d_bake_meta, &meta, sizeof meta, hipMemcpyHostToDevice, s));
+    if (src.gen) {
+        const Event* kt = nullptr;                              // timing pair of the generator's launch (csky_set_kernel_timing)
+        int rc; if (c->kt.on && (rc = c->kt.next_pair(c, kt))) return rc;
+        if (kt) HIPCHK(c, hipEventRecord(kt[0], s));
+        HIPCHK(c, launch_weather_noise(src.seed, *src.gen, n.d_raw_weather, s));
+        if (kt) HIPCHK(c, hipEventRecord(kt[1], s));
+    } else if (src.dev) {
+        HIPCHK(c, hipMemcpyAsync(n.d_raw_weather, src.dev, RAW_WEATHER, hipMemcpyDeviceToDevice, s));
+    } else {
+        HIPCHK(c, hipMemcpyAsync(n.d_raw_weather, src.host, RAW_WEATHER, hipMemcpyHostToDevice, s));
+    }
+    HIPCHK(c, launch_bake_weather(n.d_raw_weather, n.d_weather, reinterpret_cast<unsigned long long*>(n.d_bake_meta.get()), reinterpret_cast<int*>(n.d_bake_meta + 8), s));
+    if (n.st.cell32()) HIPCHK(c, launch_bake_weather32(n.d_raw_weather, n.d_weather32, s));
+    HIPCHK(c, hipMemcpyAsync(&meta, n.d_bake_meta, sizeof meta, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (meta.inexact) return fail(c, CSKY_ERR_INVALID, "internal: a weather cell's coefficients do not fit fp16");
+    range = WeatherRange{meta.range[0], meta.range[1], meta.range[2]};
+    return CSKY_OK;
+}
+
+// arguments are valid when this is called; `name` is the entry point's
+int set_weather(csky_ctx* c, const char* name, const WeatherSource& src) {
+    if (!c->noise.st.have()) return fail(c, CSKY_ERR_STATE, "%s: csky_set_noise has not been called", name);
+    int rc; if ((rc = bind(c))) return rc;
+    HIPCHK(c, hipDeviceSynchronize());                        // frames reading the old cells may be in flight on caller streams; a device source has been produced after this
+    WeatherRange range;
+    if ((rc = bake_weather(c, src, range))) { c->noise.st.begin_rebind(); return rc; }   // half-baked cells are not marched: nothing bound until a csky_set_noise* succeeds
+    c->noise.st.reweathered(range);
+    return CSKY_OK;
+}
+}  // namespace
+
+int csky_set_weather(csky_ctx* c, const uint8_t* weather_rgb8) {
+    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "csky_set_weather: ctx is NULL");
+    if (!weather_rgb8) return fail(c, CSKY_ERR_INVALID, "csky_set_weather: NULL texture pointer");
+    return set_weather(c, "csky_set_weather", WeatherSource{weather_rgb8, nullptr, nullptr, 0});
+}
+int csky_set_weather_device(csky_ctx* c, const void* d_weather_rgb8) {
+    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "csky_set_weather_device: ctx is NULL");
+    if (!d_weather_rgb8) return fail(c, CSKY_ERR_INVALID, "csky_set_weather_device: NULL texture pointer");
+    return set_weather(c, "csky_set_weather_device", WeatherSource{nullptr, d_weather_rgb8, nullptr, 0});
+}
+int csky_set_weather_generated(csky_ctx* c, uint32_t seed, const csky_weather_params* params) {
+    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "csky_set_weather_generated: ctx is NULL");
+    WeatherNoiseParams P = weather_noise_defaults();
+    if (params) {
+        if (csky_check_weather_params(params)) return fail(c, CSKY_ERR_INVALID, "csky_set_weather_generated: %s", csky_assets_last_error());
+        memcpy(&P, params, sizeof P);
+    }
+    return set_weather(c, "csky_set_weather_generated", WeatherSource{nullptr, nullptr, &P, seed});
+}
+int csky_generate_weather_device(csky_ctx* c, uint32_t seed, const csky_weather_params* params, uint8_t* out_rgb8) {
+    if (!c) return fail(nullptr, CSKY_ERR_INVALID, "csky_generate_weather_device: ctx is NULL");
+    if (!out_rgb8) return fail(c, CSKY_ERR_INVALID, "csky_generate_weather_device: out is NULL");
+    WeatherNoiseParams P = weather_noise_defaults();
+    if (params) {
+        if (csky_check_weather_params(params)) return fail(c, CSKY_ERR_INVALID, "csky_generate_weather_device: %s", csky_assets_last_error());
+        memcpy(&P, params, sizeof P);
+    }
+    int rc; if ((rc = bind(c))) return rc;
+    DevBuf<uint8_t> d; if ((rc = d.alloc(c, RAW_WEATHER))) return rc;
+    HIPCHK(c, launch_weather_noise(seed, P, d, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out_rgb8, d, RAW_WEATHER, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return CSKY_OK;
+}
+
 int csky_read_baked_texture(csky_ctx* c, int which, void* out, size_t capacity, size_t* bytes) {
     if (!c || !bytes) return fail(c, CSKY_ERR_INVALID, "csky_read_baked_texture: NULL argument");
     if (!c->noise.st.have()) return fail(c, CSKY_ERR_STATE, "csky_read_baked_texture: csky_set_noise has not been called");

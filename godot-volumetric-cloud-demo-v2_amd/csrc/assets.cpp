@@ -27,6 +27,9 @@ void shape_rows(uint32_t seed, int n, csky::ShapeNoiseParams P, int z0, int z1, 
     for (int z = z0; z < z1; z++) for (int y = 0; y < n; y++) for (int x = 0; x < n; x++)
         csky::shape_voxel(seed, n, x, y, z, P, out + ((((size_t)z * n + y) * n + x) * 4));
 }
+void weather_rows(uint32_t seed, csky::WeatherNoiseParams P, int y0, int y1, uint8_t* out) {
+    for (int y = y0; y < y1; y++) for (int x = 0; x < 512; x++) csky::weather_texel(seed, x, y, P, out + ((size_t)y * 512 + x) * 3);
+}
 
 }  // namespace
 namespace csky { thread_local char g_asset_err[256]; }   // shared with godot_import.cpp
@@ -89,6 +92,56 @@ int csky_generate_shape_noise_tuned(uint32_t seed, int n, const csky_shape_noise
 int csky_generate_detail_noise(uint32_t seed, int n, uint8_t* out_rgb8) {
     if (!out_rgb8 || n < 8 || n > 1024 || (n & (n - 1))) { snprintf(g_asset_err, sizeof g_asset_err, "generate_detail_noise: n must be a power of two in [8, 1024]"); return CSKY_ERR_INVALID; }
     for (int z = 0; z < n; z++) for (int y = 0; y < n; y++) for (int x = 0; x < n; x++) csky::detail_voxel(seed, n, x, y, z, out_rgb8 + ((((size_t)z * n + y) * n + x) * 3));
+    return CSKY_OK;
+}
+
+void csky_weather_default_params(csky_weather_params* p) {
+    if (!p) return;
+    const csky::WeatherNoiseParams d = csky::weather_noise_defaults();
+    static_assert(sizeof(csky_weather_params) == sizeof(csky::WeatherNoiseParams), "csky_weather_params mirrors noise_core.h::WeatherNoiseParams");
+    memcpy(p, &d, sizeof d);
+}
+int csky_check_weather_params(const csky_weather_params* p) {
+    // The one rule of every weather generator entry point (as csky_check_shape_noise_params is for the shape volume).  Frequencies >= 1: the
+    // lattices wrap with `i % freq`; <= 64 and octaves <= 8: `freq << (octaves - 1)` and the Worley fBm's `freq * 4` stay <= 8192, far inside an int and
+    // inside what a float holds exactly next to a fraction; every float finite and bounded, so that nothing non-finite or beyond the int range reaches
+    // floorf's conversion or the UNORM8 one.  |phase| <= 1024 keeps its fraction (w = phase - floor(phase)) a multiple of 2^-13 or finer.
+    const int max_freq = 64;
+    bool ok = p != nullptr;
+    if (ok) {
+        for (float f : {p->phase, p->coverage_gain, p->dilate, p->coverage_centre, p->coverage_contrast, p->coverage_offset, p->coverage_floor, p->type_mean, p->type_spread})
+            ok = ok && std::isfinite(f);
+        ok = ok && p->coverage_freq >= 1 && p->coverage_freq <= max_freq && p->type_freq >= 1 && p->type_freq <= max_freq &&
+             p->coverage_octaves >= 1 && p->coverage_octaves <= 8 && p->type_octaves >= 1 && p->type_octaves <= 8 &&
+             std::fabs(p->phase) <= 1024.0f && p->coverage_gain > 0.0f && p->coverage_gain <= 16.0f && p->dilate >= 0.0f && p->dilate <= 1.0f &&
+             std::fabs(p->coverage_centre) <= 4.0f && p->coverage_contrast > 0.0f && p->coverage_contrast <= 64.0f && std::fabs(p->coverage_offset) <= 4.0f &&
+             p->coverage_floor >= 0.0f && p->coverage_floor <= 1.0f && std::fabs(p->type_mean) <= 4.0f && std::fabs(p->type_spread) <= 16.0f;
+    }
+    if (!ok) {
+        snprintf(g_asset_err, sizeof g_asset_err, "weather parameters out of range (1 <= freqs <= %d, 1 <= octaves <= 8, finite floats, |phase| <= 1024, 0 < gain <= 16, 0 <= dilate, floor <= 1, "
+                 "|centre|, |offset|, |type_mean| <= 4, 0 < contrast <= 64, |type_spread| <= 16)", max_freq);
+        return CSKY_ERR_INVALID;
+    }
+    return CSKY_OK;
+}
+int csky_generate_weather(uint32_t seed, const csky_weather_params* params, uint8_t* out_rgb8) {
+    if (!out_rgb8) { snprintf(g_asset_err, sizeof g_asset_err, "generate_weather: out is NULL"); return CSKY_ERR_INVALID; }
+    csky::WeatherNoiseParams P = csky::weather_noise_defaults();
+    if (params) { int rc = csky_check_weather_params(params); if (rc) return rc; memcpy(&P, params, sizeof P); }
+    const int n = 512;
+    unsigned hw = std::thread::hardware_concurrency();
+    int nt = (int)(hw == 0 ? 1 : (hw > 32 ? 32 : hw));
+    std::vector<std::thread> th;
+    int done_to = 0;                                             // rows [0, done_to) are owned by a started thread
+    try {                                                        // (as csky_generate_shape_noise_tuned: nothing crosses the ABI)
+        for (int t = 0; t < nt; t++) {
+            int y0 = n * t / nt, y1 = n * (t + 1) / nt;
+            th.emplace_back(weather_rows, seed, P, y0, y1, out_rgb8);
+            done_to = y1;
+        }
+    } catch (...) {}
+    if (done_to < n) weather_rows(seed, P, done_to, n, out_rgb8);
+    for (auto& t : th) t.join();
     return CSKY_OK;
 }
 

@@ -1,6 +1,7 @@
 // bake_kernels.hip -- gfx950 kernels of csky_set_noise and the noise generators: everything that runs once per texture set.
 //
 //   shape_noise_kernel / detail_noise_kernel : the stand-in noise volumes, one voxel per lane (noise_core.h)
+//   weather_noise_kernel                     : the generated weather map, one texel per lane (noise_core.h)
 //   mip_level_kernel                         : 2x2x2 box mips of an 8-bit chain
 //   bake_{shape,detail,weather}[32]_kernel   : the device texture layouts, one texel per lane (bake_core.h)
 // Checked buffer by buffer against numpy in tests/test_gpu_bake.py (tests/bake_reference.py, oracle/noise_restatement.py), not against the host
@@ -41,6 +42,19 @@ __global__ __launch_bounds__(256) void detail_noise_kernel(uint32_t seed, int n,
 hipError_t launch_detail_noise(uint32_t seed, int n, uint8_t* d_out, hipStream_t s) {
     const size_t total = (size_t)n * n * n;
     detail_noise_kernel<<<(unsigned)((total + 255) / 256), 256, 0, s>>>(seed, n, d_out);
+    return hipGetLastError();
+}
+
+// the 512 x 512 RGB weather map (noise_core.h::weather_texel), one texel per lane, 3 bytes each: 1024 workgroups, four per CU of the device
+__global__ __launch_bounds__(256) void weather_noise_kernel(uint32_t seed, WeatherNoiseParams P, uint8_t* __restrict__ out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= WEATHER_N * WEATHER_N) return;
+    uint8_t o[3];
+    weather_texel(seed, i % WEATHER_N, i / WEATHER_N, P, o);
+    out[3 * i] = o[0]; out[3 * i + 1] = o[1]; out[3 * i + 2] = o[2];
+}
+hipError_t launch_weather_noise(uint32_t seed, const WeatherNoiseParams& P, uint8_t* d_out, hipStream_t s) {
+    weather_noise_kernel<<<(WEATHER_N * WEATHER_N + 255) / 256, 256, 0, s>>>(seed, P, d_out);
     return hipGetLastError();
 }
 
@@ -112,6 +126,10 @@ hipError_t launch_bake(const uint8_t* d_large_chain, const uint8_t* d_small_chai
     bake_weather_kernel<<<(WEATHER_N * WEATHER_N + 255) / 256, 256, 0, s>>>(d_weather, d_weather_out, d_inexact, d_range);
     return hipGetLastError();
 }
+hipError_t launch_bake_weather(const uint8_t* d_weather, uint4* d_weather_out, unsigned long long* d_inexact, int* d_range, hipStream_t s) {
+    bake_weather_kernel<<<(WEATHER_N * WEATHER_N + 255) / 256, 256, 0, s>>>(d_weather, d_weather_out, d_inexact, d_range);
+    return hipGetLastError();
+}
 
 // exact cells (bake_core.h: fp32 coefficients), built only for textures with coefficients fp16 cannot hold (or on request)
 __global__ __launch_bounds__(256) void bake_shape32_kernel(const uint8_t* __restrict__ chain, float4* __restrict__ out) {
@@ -147,6 +165,10 @@ hipError_t launch_bake32(const uint8_t* d_large_chain, const uint8_t* d_small_ch
     const size_t shape_total = chain_offset(SHAPE_N, SHAPE_LEVELS, 1), detail_total = chain_offset(DETAIL_N, DETAIL_LEVELS, 1);   // texels of all levels
     bake_shape32_kernel<<<(unsigned)((shape_total + 255) / 256), 256, 0, s>>>(d_large_chain, d_shape32);
     bake_detail32_kernel<<<(unsigned)((detail_total + 255) / 256), 256, 0, s>>>(d_small_chain, d_detail32);
+    bake_weather32_kernel<<<(WEATHER_N * WEATHER_N + 255) / 256, 256, 0, s>>>(d_weather, d_weather32);
+    return hipGetLastError();
+}
+hipError_t launch_bake_weather32(const uint8_t* d_weather, float4* d_weather32, hipStream_t s) {
     bake_weather32_kernel<<<(WEATHER_N * WEATHER_N + 255) / 256, 256, 0, s>>>(d_weather, d_weather32);
     return hipGetLastError();
 }

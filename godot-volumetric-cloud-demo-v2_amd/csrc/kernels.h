@@ -42,6 +42,8 @@ hipError_t launch_frame_setup_taps(const CloudParams& p, const float sun[3], con
 hipError_t launch_shape_noise(uint32_t seed, int n, const ShapeNoiseParams& P, uint32_t* d_out, hipStream_t s);
 // generated 32^3 RGB detail volume (noise_core.h::detail_voxel), 3 bytes per voxel
 hipError_t launch_detail_noise(uint32_t seed, int n, uint8_t* d_out, hipStream_t s);
+// generated 512 x 512 RGB8 weather map (noise_core.h::weather_texel), 3 bytes per texel, texel (x, y) at byte (y * 512 + x) * 3
+hipError_t launch_weather_noise(uint32_t seed, const WeatherNoiseParams& P, uint8_t* d_out, hipStream_t s);
 // 2x2x2 box mips of a device chain whose level 0 is filled (level l at chain_offset(n, l, ch))
 hipError_t launch_mip_chain(uint8_t* d_chain, int n, int ch, int levels, hipStream_t s);
 // the three device texture layouts from the 8-bit chains; *d_inexact += coefficients not exact in fp16; d_range = {min R, max R, max B} of the
@@ -50,6 +52,10 @@ hipError_t launch_bake(const uint8_t* d_large_chain, const uint8_t* d_small_chai
                        uint4* d_weather_out, unsigned long long* d_inexact, int* d_range, hipStream_t s);
 // exact cells (bake_core.h): fp32-coefficient layouts of the same three textures
 hipError_t launch_bake32(const uint8_t* d_large_chain, const uint8_t* d_small_chain, const uint8_t* d_weather, float4* d_shape32, float4* d_detail32, float4* d_weather32, hipStream_t s);
+
+// the weather map's share of the two above alone (csky_set_weather*): the same kernels, the same counters (its cells never add to *d_inexact)
+hipError_t launch_bake_weather(const uint8_t* d_weather, uint4* d_weather_out, unsigned long long* d_inexact, int* d_range, hipStream_t s);
+hipError_t launch_bake_weather32(const uint8_t* d_weather, float4* d_weather32, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------ cloud_kernels.hip
 // clouds.glsl main() over the rows described by `g`.  d_stats (may be null): [0] += in-cloud samples,

@@ -122,4 +122,41 @@ CSKY_HD void detail_voxel(uint32_t seed, int n, int x, int y, int z, uint8_t o[3
     }
 }
 
+// The knobs of the generated weather map, in the role of cloud_sky/weather.bmp (512 x 512 RGB8; clouds.glsl reads cloud type from R and coverage
+// from B).  == csky_weather_params of include/cloudsky.h, field for field.  The defaults are calibrated on the shipped weather.bmp's channel
+// statistics (a calibration, not a reconstruction).
+struct WeatherNoiseParams {
+    int coverage_freq, coverage_octaves;   // base period of the coverage field in cells per map edge, octaves of its Perlin fBm
+    int type_freq, type_octaves;           // the same for the cloud-type field
+    float phase;                           // the third coordinate of the tileable 3-D noise: the map evolves smoothly in it, period 1
+    float coverage_gain, dilate;           // p01 = clamp(fBm * gain + 0.5); pw = remap(p01, 0, 1, worley fBm * dilate, 1)
+    float coverage_centre, coverage_contrast, coverage_offset;   // b = clamp((pw - centre) * contrast + offset)
+    float coverage_floor;                  // B = floor + (1 - floor) * b: the least coverage of the map
+    float type_mean, type_spread;          // R = clamp(mean + fBm * spread)
+};
+CSKY_HD WeatherNoiseParams weather_noise_defaults() {
+    WeatherNoiseParams p;
+    p.coverage_freq = 2; p.coverage_octaves = 5; p.type_freq = 6; p.type_octaves = 3; p.phase = 0.0f;
+    p.coverage_gain = 0.9f; p.dilate = 0.55f; p.coverage_centre = 0.38f; p.coverage_contrast = 2.0f; p.coverage_offset = 0.06f; p.coverage_floor = 0.07f;
+    p.type_mean = 0.748f; p.type_spread = 0.32f;
+    return p;
+}
+
+// One texel of the generated weather map: B = a Perlin fBm dilated by a Worley fBm and pushed through a contrast curve above a floor (the shape
+// volume's R recipe in the plane w = phase), R = a second, smoother Perlin fBm about a mean, G = 0 (clouds.glsl never reads it).  Texel (x, y)
+// lies at byte (y * 512 + x) * 3.  Same arithmetic rules as shape_voxel: bit-identical on the host and on the GPU.
+CSKY_HD void weather_texel(uint32_t seed, int x, int y, const WeatherNoiseParams& P, uint8_t o[3]) {
+    const float u = ((float)x + 0.5f) / 512.0f, v = ((float)y + 0.5f) / 512.0f;
+    const float w = P.phase - floorf(P.phase);   // [0, 1): a feature point's (float)cell + offset rounds by the cell's magnitude, so p and p + 1 meet in the same cells
+    const float wf = worley_fbm(u, v, w, P.coverage_freq, seed * 307U + 19U);
+    const float pf = perlin_fbm(u, v, w, P.coverage_freq, P.coverage_octaves, seed * 307U + 5U);
+    const float p01 = clamp01(pf * P.coverage_gain + 0.5f);
+    const float pw = remapf(p01, 0.0f, 1.0f, wf * P.dilate, 1.0f);
+    float b = clamp01((pw - P.coverage_centre) * P.coverage_contrast + P.coverage_offset);
+    b = P.coverage_floor + (1.0f - P.coverage_floor) * b;
+    const float tf = perlin_fbm(u, v, w, P.type_freq, P.type_octaves, seed * 307U + 41U);
+    const float r = clamp01(P.type_mean + tf * P.type_spread);
+    o[0] = unorm8(r); o[1] = 0; o[2] = unorm8(b);
+}
+
 }  // namespace csky

@@ -61,6 +61,9 @@ inline ExactRejects exact_rejects(const WeatherRange& w, float coverage, bool us
 
 // ---- the state.  None of the steps touches a buffer: the caller does what the names say, in this order (api.cpp set_noise):
 //   arguments valid -> begin_rebind -> allocate, upload, bake, read back -> bound -> exact layouts built or released -> ready
+// and for the weather map alone (api.cpp set_weather), legal only while a set is had:
+//   arguments valid, have() -> the weather cells (and the exact ones when cell32()) baked, range read back -> reweathered
+// (a runtime failure after that bake has begun goes through begin_rebind: half-baked cells are not marched)
 // A step that fails returns between begin_rebind and ready, which leaves freed or half-baked textures: nothing is had, and no render runs until
 // a later bind succeeds.
 class NoiseHeld {
@@ -80,6 +83,15 @@ public:
         return cell32_ = inexact != 0 || exact_requested_;
     }
     void ready() { have_ = true; }
+    // A rebind of the weather map alone (api.cpp set_weather), between two frames of a set that is had: its range replaces the bound one and the
+    // cached rejects of the old range go.  A weather cell's coefficients always fit fp16 (bake_core.h::bake_weather_texel: all in [-510, 510]), so
+    // neither the inexact count nor the cell format can change, and a request for exact cells still waits for the next bound().  Returns whether
+    // the step was legal; without a set that is had it changes nothing.
+    bool reweathered(const WeatherRange& range) {
+        if (!have_) return false;
+        range_ = range; cached_ = false;
+        return true;
+    }
     // exact_rejects for the bound weather map, cached per coverage value (the bisections of height_window are not per-frame work).  Keyed on !=, so
     // a NaN coverage is computed every time.
     ExactRejects rejects(float coverage, bool use_window) {

@@ -118,6 +118,27 @@ int csky_noise_inexact_coeffs(csky_ctx* ctx, uint64_t* count);
 /* 1 = build and march the exact fp32-coefficient cells regardless of the count above (A/B and tests: for textures that fit fp16 the two cell
  * forms filter bit-identically); 0 = only when needed (default).  Takes effect at the next csky_set_noise*. */
 int csky_set_exact_cells(csky_ctx* ctx, int mode);
+/* ---- the weather map alone ---------------------------------------------------------
+ * The weather map is the one spatial control over the cloudscape (clouds.glsl: cloud type from R, coverage from B).  These calls replace it in a
+ * context that csky_set_noise* has bound, without touching the shape and detail volumes: 768 KiB read, 4 MiB of cells written, three integers back.
+ *   csky_set_weather           weather_rgb8: 512 x 512 RGB8 in HOST memory, weather.bmp's layout (row 0 = top row), as csky_set_noise takes it
+ *   csky_set_weather_device    the same bytes, tight, in memory of ctx's device; only read
+ *   csky_set_weather_generated the map of csky_generate_weather(seed, params), generated on the device into the context's own buffer: no host copy
+ *                              of the map in either direction
+ * Contract: after a successful call the context is, for every later call of this ABI, indistinguishable from one that was bound with
+ *   csky_set_noise* to the same shape and detail inputs and this map: the cells in both formats, the 8-bit copy, the map's channel ranges (and with
+ *   them the height window and the cloud-type specialisation of the march), every frame of every form, the in-cloud counts.  The shape and detail
+ *   cells and chains, csky_noise_inexact_coeffs and the cell format the context marches on, csky_last_warning, the LUTs, the sky LUT's reuse state
+ *   and the frame ring are as they were.  A weather cell's coefficients always fit fp16, so a map cannot change the count or the format;
+ *   csky_set_exact_cells still takes effect at the next csky_set_noise*, and a weather call is not one.
+ * Ordering: the call waits for the DEVICE first, as csky_set_noise does (frames on caller streams may be reading the cells), bakes on the context's
+ *   stream, and returns with the context idle.  The device form therefore takes no stream: whatever produced its buffer has finished after that
+ *   wait.  A frame submitted before the call (csky_submit_clouds) is a frame of the old map, the next one is of the new map.
+ * Errors, in csky_set_noise's order: a NULL ctx or pointer, or parameters csky_check_weather_params refuses: CSKY_ERR_INVALID; no set bound yet:
+ *   CSKY_ERR_STATE; a refused call leaves the bound set bound and rendering as before.  A runtime failure after the bake has begun leaves NOTHING
+ *   bound until a later csky_set_noise* succeeds. */
+int csky_set_weather(csky_ctx* ctx, const uint8_t* weather_rgb8);
+int csky_set_weather_device(csky_ctx* ctx, const void* d_weather_rgb8);
 /* clouds.glsl:228 (128 primary steps) and clouds.glsl:186 (6 light steps) are literals in the reference;
  * this generalises them (BASELINE config 2 is 64 x 4).  light_steps in [0,6], primary_steps in [1,1024]. */
 int csky_set_march(csky_ctx* ctx, int primary_steps, int light_steps);
@@ -849,6 +870,35 @@ int csky_generate_shape_noise_device(csky_ctx* ctx, uint32_t seed, int n, uint8_
  * statistics, noise_core.h), host and GPU (byte-identical): README.md:30 TODO 3 "generate the noise on the GPU". */
 int csky_generate_detail_noise(uint32_t seed, int n, uint8_t* out_rgb8);
 int csky_generate_detail_noise_device(csky_ctx* ctx, uint32_t seed, int n, uint8_t* out_rgb8);
+/* A generated 512 x 512 RGB8 weather map in the role of weather.bmp, host and GPU (byte-identical).  One texel (noise_core.h::weather_texel; fp32,
+ * IEEE + - * / sqrt and floor only, no contraction), texel (x, y) at byte (y * 512 + x) * 3:
+ *   u = (x + 0.5) / 512;  v = (y + 0.5) / 512;  w = phase - floor(phase)
+ *   wf  = worley_fbm(u, v, w, coverage_freq, seed * 307 + 19)
+ *   pf  = perlin_fbm(u, v, w, coverage_freq, coverage_octaves, seed * 307 + 5)
+ *   p01 = clamp01(pf * coverage_gain + 0.5)
+ *   pw  = remap(p01, 0, 1, wf * dilate, 1)
+ *   b   = clamp01((pw - coverage_centre) * coverage_contrast + coverage_offset);  b = coverage_floor + (1 - coverage_floor) * b
+ *   tf  = perlin_fbm(u, v, w, type_freq, type_octaves, seed * 307 + 41)
+ *   r   = clamp01(type_mean + tf * type_spread)
+ *   texel = { unorm8(r), 0, unorm8(b) }        G is not read by clouds.glsl
+ * (w is the phase's fraction, not the phase: a feature point's position is (float)cell + offset, which rounds by the cell's magnitude, so only
+ * in the same cells do phase p and p + 1 give the same bytes.)  The map tiles in x and y and evolves smoothly in phase with period 1.  The
+ * defaults are calibrated on the shipped weather.bmp's channel statistics; this is a calibration, not a reconstruction.
+ * csky_check_weather_params is the one rule of what every entry point below and csky_set_weather_generated refuse (CSKY_ERR_INVALID before any
+ * work; csky_assets_last_error says which bounds): 1 <= coverage_freq, type_freq <= 64; 1 <= octaves <= 8; every float finite; |phase| <= 1024;
+ * 0 < coverage_gain <= 16; 0 <= dilate <= 1; |coverage_centre|, |coverage_offset|, |type_mean| <= 4; 0 < coverage_contrast <= 64;
+ * 0 <= coverage_floor <= 1; |type_spread| <= 16.  params == NULL: the defaults. */
+typedef struct csky_weather_params {
+    int32_t coverage_freq, coverage_octaves, type_freq, type_octaves;
+    float phase;
+    float coverage_gain, dilate, coverage_centre, coverage_contrast, coverage_offset, coverage_floor;
+    float type_mean, type_spread;
+} csky_weather_params;
+void csky_weather_default_params(csky_weather_params* p);
+int csky_check_weather_params(const csky_weather_params* p);
+int csky_generate_weather(uint32_t seed, const csky_weather_params* params, uint8_t* out_rgb8);                    /* host, no GPU needed */
+int csky_generate_weather_device(csky_ctx* ctx, uint32_t seed, const csky_weather_params* params, uint8_t* out_rgb8);   /* the HIP kernel, to host memory */
+int csky_set_weather_generated(csky_ctx* ctx, uint32_t seed, const csky_weather_params* params);                   /* generate on the device and rebind (above) */
 size_t csky_mip_offset(int n, int level, int ch);
 /* 3-D mip chain (mipmaps/generate=true of the .import files): 2x2x2 box, (sum + 4) >> 3.  `vol` holds level 0 on entry and has room for
  * csky_mip_offset(n, levels, ch) bytes.  csky_build_mips runs on the host, csky_build_mips_device on the GPU (byte-identical); since round 2
