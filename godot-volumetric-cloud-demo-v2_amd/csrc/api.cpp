@@ -624,7 +624,7 @@ int csky_get_kernel_ms(csky_ctx* c, float* total_ms, int* launches) {
 }
 
 // The stats launch delivers the exact counts (the tally form of the kernel); the warm-up and timed launches pass no stats buffer and take the form
-// the headline path takes (cloud_kernels.hip march_compact, TALLY = false): what is reported is that path's time beside the full march's counts.
+// the headline path takes (march_compact.h march_compact, TALLY = false): what is reported is that path's time beside the full march's counts.
 int csky_time_clouds(csky_ctx* c, const csky_cloud_params* p, int tile_w, const csky_bands* bands, int warmup, int iters, float* mean_ms, csky_cloud_stats* stats) {
     if (!c) return fail(nullptr, CSKY_ERR_INVALID, "csky_time_clouds: ctx is NULL");
     if (iters < 1 || warmup < 0 || !mean_ms) return fail(c, CSKY_ERR_INVALID, "csky_time_clouds: bad iters/warmup/mean_ms");

@@ -748,7 +748,7 @@ CSKY_HD void shade_sample(const FrameConsts& fc, float phase, float t, float hf,
 // Both tests true => leaving out every later in-cloud sample of the ray stores the same four halfs.  Where the launch delivers the in-cloud tally the march
 // still takes the ray's primary samples (the tally counts t > 0 and is part of the contract); where it does not, the ray stops (march_compact, TALLY).  Headline view, coverage 0.2: 16 % of the rays fire, 9.4 % of the in-cloud samples fall
 // behind the firing (0.35: 27 %, 0.5: 43 %; tests/test_saturation_skip.py walks them and requires zero differing halfs).
-// Used by march_compact for whole-ray marches of the fp16-pair texture set only (cloud_kernels.hip); march() below and every other variant take all samples.
+// Used by march_compact for whole-ray marches of the fp16-pair texture set only (march_compact.h); march() below and every other variant take all samples.
 constexpr float SAT_ALPHA_MIN = 1.0f - 0.000244140625f;       // 1 - 2^-12
 constexpr float SAT_BEERS_MAX = 0.7699f;                      // > 4 / (3 sqrt 3)
 // the half a value is stored as, for 2^-14 <= x < 65520 (normal halfs, where v_cvt_f16_f32 in the default round-to-nearest-even mode is f2h whatever the

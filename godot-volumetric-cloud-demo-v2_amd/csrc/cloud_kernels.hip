@@ -1,18 +1,23 @@
 // cloud_kernels.hip -- gfx950 (CDNA4, wave64) kernels of clouds.glsl main(): one ray per lane, one 8x8-pixel tile per wavefront.
 //
-//   march_queue / march_compact / march_interleaved : the wave-cooperative marches (the lock-step one is cloud_core.h march())
+//   Pixel, footprint_pixel, store_pixel             : the pixel of a lane (the front ends of the two alternatives; render_block keeps its own copy)
+//   clouds_kernel_interleaved / clouds_kernel_lds   : measured alternatives (segments 5, variant 2)
 //   render_block, clouds_kernel<VARIANT, SEG, TS>   : a workgroup footprint of 4 / SEG tiles; <3, 1, TexSet> is the product's kernel
 //   clouds_kernel_persistent                        : the same as a launch the size of the chip that pops footprints from the order
-//   clouds_kernel_lds / clouds_kernel_interleaved   : measured alternatives (variant 2, segments 5)
-//   lpt_*_kernel, static_order_kernel               : the launch orders
-//   interleave_bands_kernel, sqrt_shell_kernel      : the band interleave of a gathered frame (what becomes of the bands these kernels
-//                                                     write when N ranks split a frame) and the test hook of cloud_core.h::sqrt_shell
+//   cloud_variant_*, cloud_resident_workgroups_per_cu*, launch_clouds : the variants' names, the size of a persistent launch, the launcher
 //   march_store and the direct march                : whole rays of a W x H image in natural order, one pixel per lane; each kernel is a lane pixel,
-//                                                     a direction, its own ray maker and the shared tail march_store:
+//                                                     a direction, its own ray maker and the shared tail march_store.  In this file
+//                                                     because in a file of its own its fp16-pair kernels are not the same code:
 //     clouds_rays_kernel<SRC, TS>                   :   caller-given directions or a camera view, from the reference's observer (§17)
 //     clouds_view_fresh_kernel / _reproject_kernel  :   the temporal split of a view frame: the fresh sub-grid; history taps and holes (§20)
 //     clouds_observer_kernel<SRC, TS>               :   the same rays from an observer's position (§21)
 //     clouds_observer_depth_kernel<SRC, KIND, TS>   :   those behind a per-pixel scene depth (§22)
+//
+// What these kernels call and what runs beside them:
+//   march_compact.h     : the compact march (variant 3), which every product frame and every direct-march frame runs
+//   march_variants.h    : march_queue and march_interleaved (variants 1 and 2, segments 5); the lock-step one is cloud_core.h march() (variant 0)
+//   order_kernels.hip   : the launch orders these kernels read and the band interleave of the frames they write
+//   primitives.hip      : the test hooks of the march's arithmetic (sqrt_shell among them)
 //
 // No MFMA anywhere: the path is fetch/latency-bound gather + fp32 VALU, not a contraction.
 // What was built here, measured and removed again is recorded in docs/EXPERIMENTS.md §5.
@@ -20,462 +25,18 @@
 #include "kernels.h"
 #include "cloud_core.h"
 #include "order_core.h"
+#include "march_compact.h"
+#include "march_variants.h"
+#include "rays_core.h"
+#include "view_update_core.h"
+#include "observer_core.h"
+#include "scene_depth_core.h"
 #include <type_traits>
-// FP contraction OFF for the code of this file, like section A of cloud_core.h: what a march adds and multiplies itself (the phase value's dot product,
-// the segments' compositing sums) rounds as written.  Stated here because otherwise the last header decides it, and cloud_core.h ends with contraction on.
+// FP contraction OFF for the code of this file, like section A of cloud_core.h: what a kernel adds and multiplies itself (the segments' compositing
+// sums) rounds as written.  Stated here, once, because otherwise the last header decides it, and every core header ends with contraction on.
 #pragma clang fp contract(off)
 
 namespace csky {
-
-// ---- wave-cooperative march (variant "queue") --------------------------------------------------------------
-// The lock-step march (cloud_core.h march()) runs the (light_steps+1)-sample light march on all 64 lanes whenever
-// ANY lane of the wavefront is inside a cloud.  Measured on the headline frame: a lane is in cloud on 15 % of its
-// steps, a wavefront on ~70 % of them, so ~4/5 of the light-march VALU work is masked off.  Here the two loops
-// are decoupled through a per-wavefront event queue in LDS:
-//   A. all lanes march their primary samples in lock step (uniform loop, clouds.glsl:172-178); every in-cloud
-//      sample (t > 0, clouds.glsl:184) is appended to the queue (position, t, height fraction) at
-//      slot = running count + mbcnt(ballot);
-//   B. when the queue may overflow (or the march ends) the n queued samples need n*(light_steps+1) independent
-//      density evaluations (clouds.glsl:186-199).  They are flattened as e = j*n + k and dealt out 64 per round,
-//      so every round runs with all lanes busy no matter which rays were in cloud;
-//   C. the queue is replayed step by step: the owning lane sums its light samples in the reference's order and
-//      composites the sample front to back (clouds.glsl:202-210).
-// No __syncthreads: wavefronts are independent; LDS operations of one wavefront complete in issue order and
-// wavefront-scope fences keep the compiler from reordering them.  Per-ray arithmetic and its order are unchanged.
-constexpr int QCAP = 96;                                    // events per wavefront queue (a flush is forced above QCAP-64)
-constexpr int QSTEPS = 48;                                  // steps-with-events per chunk (a flush is forced when full)
-constexpr int Q_FLOATS = 5 * QCAP + 7 * QCAP + 3 * QSTEPS;  // pos(3) t hf | lt[7] | per-step mask lo/hi + base  = 5.1 KB per wavefront
-
-__device__ __forceinline__ void wave_lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// the phase value of a ray's samples (0 for a ray that does not march)
-__device__ __forceinline__ float ray_phase(const FrameConsts& fc, const Ray& ray) {
-    float phase = 0.0f;
-    if (ray.above) {
-        const float ct = fc.ldir[0] * ray.dx + fc.ldir[1] * ray.dy + fc.ldir[2] * ray.dz;                       // clouds.glsl:158
-        phase = fmaxf(fmaxf(henyey_greenstein(ct, 0.6f), henyey_greenstein(ct, fc.hg_g2)), henyey_greenstein(ct, -0.2f));  // :160
-    }
-    return phase;
-}
-
-// Step B of the queue marches: the nb * (ls + 1) light-march evaluations of nb queued samples (clouds.glsl:186-199), flattened as e = j * nb + k
-// and dealt out 64 per round, so every round runs with all lanes busy no matter which rays were in cloud.  pos(k, x, y, z) delivers sample k's
-// position; the density of its cone sample j (j == ls: the distant sample) goes to lt[j * pitch + k].
-template <class Pos> __device__ __forceinline__ void light_march_batch(const TexSet& T, const FrameConsts& fc, const int ls, const int nb, const int lane, Pos&& pos,
-                                                                      float* __restrict__ lt, const int pitch) {
-    const int total = nb * (ls + 1);
-    const float rn = 1.0f / (float)nb;
-    for (int e0 = 0; e0 < total; e0 += 64) {
-        const int e = e0 + lane;
-        if (e < total) {
-            const int j = (int)(((float)e + 0.5f) * rn);          // e = j*nb + k (exact: e < 672, nb <= 96)
-            const int k = e - j * nb;
-            float lx, ly, lz;
-            pos(k, lx, ly, lz);
-            const bool distant = (j == ls);
-            // cone sample j: lp = p + sum_{i<=j} (ldir + RANDOM_VECTORS[i]*i)*lss, added one by one in fp32 like :187.
-            // e grows with the lane, so j is non-decreasing across the wavefront: the additions up to the first lane's j
-            // are wave-uniform (plain adds under a scalar branch), only the few beyond it need per-lane predication.
-            const int j_lo = __builtin_amdgcn_readfirstlane(j);
-            if (distant) {
-                advance(lx, ly, lz, fc.ldist[0], fc.ldist[1], fc.ldist[2]);                                // :195
-            } else {
-#pragma unroll
-                for (int jj = 0; jj < 6; jj++) {
-                    if (jj <= j_lo) advance(lx, ly, lz, fc.linc[jj][0], fc.linc[jj][1], fc.linc[jj][2]);
-                    else if (jj <= j) advance(lx, ly, lz, fc.linc[jj][0], fc.linc[jj][1], fc.linc[jj][2]);
-                }
-            }
-            const float lhf = height_fraction(length3_shell(lx, ly, lz));                                  // :188 / :196
-            const int lod_s = distant ? 3 : (j > 2 ? j - 2 : 0), lod_d = distant ? 5 : j;                  // textureLod(.., mip-2) / (.., mip)
-            float d = sample_density(T, fc, lx, ly, lz, lhf, distant ? 0.0f : fc.wpos_x, distant ? 0.0f : fc.wpos_y, lod_s, lod_d);  // :189-190 / :197-198
-            if (distant) d = fast_pow(d, (1.0f - lhf) * 0.8f + 0.5f);                                      // :198 second pow
-            lt[j * pitch + k] = d;
-        }
-    }
-}
-
-__device__ __forceinline__ MarchOut march_queue(const TexSet& T, const FrameConsts& fc, Ray ray, float* __restrict__ q, int step_begin, int step_end) {
-    float* __restrict__ ev_px = q;
-    float* __restrict__ ev_py = q + QCAP;
-    float* __restrict__ ev_pz = q + 2 * QCAP;
-    float* __restrict__ ev_t = q + 3 * QCAP;
-    float* __restrict__ ev_hf = q + 4 * QCAP;
-    float* __restrict__ ev_lt = q + 5 * QCAP;                               // [7][QCAP]
-    unsigned* __restrict__ st_lo = reinterpret_cast<unsigned*>(q + 12 * QCAP);   // [QSTEPS]
-    unsigned* __restrict__ st_hi = st_lo + QSTEPS;
-    unsigned* __restrict__ st_base = st_hi + QSTEPS;
-
-    MarchOut o; o.r = o.g = o.b = o.a = 0.0f; o.t = 1.0f; o.incloud = 0;
-    const int lane = threadIdx.x & 63;
-    const int ls = fc.light_steps, nl = ls + 1;
-    const float phase = ray_phase(fc, ray);
-    float Tr = 1.0f, alpha = 0.0f, Lr = 0.0f, Lg = 0.0f, Lb = 0.0f;
-    float px = ray.px, py = ray.py, pz = ray.pz;
-    const float nd = -fc.density;
-    bool live = ray.above;
-    int count = 0, cs = 0;                                    // queued events / steps-with-events in the current chunk (uniform)
-    if (!__any(live)) return o;
-    // a ray segment starts where the sequential march would be after step_begin steps: replay the fp32 additions
-    // (clouds.glsl:173) so every sample position is bit-identical to the unsegmented march
-    for (int i = 0; i < step_begin; i++) advance(px, py, pz, ray.sx, ray.sy, ray.sz);
-    for (int i = step_begin; i < step_end; i++) {
-        // ---- A: one primary sample per lane
-        float t = 0.0f, hf = 0.0f;
-        if (live) {
-            advance(px, py, pz, ray.sx, ray.sy, ray.sz);                                                       // :173
-            hf = height_fraction(length3_shell(px, py, pz));                                                   // :175
-            t = sample_density(T, fc, px, py, pz, hf, fc.wpos_x, fc.wpos_y, 0, 0);                             // :174, :177
-        }
-        const bool have = t > 0.0f;                                                                            // :184
-        const unsigned long long m = __ballot(have);
-        if (m != 0ull) {
-            const int slot = count + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-            if (have) { ev_px[slot] = px; ev_py[slot] = py; ev_pz[slot] = pz; ev_t[slot] = t; ev_hf[slot] = hf; }
-            if (lane == 0) { st_lo[cs] = (unsigned)m; st_hi[cs] = (unsigned)(m >> 32); st_base[cs] = (unsigned)count; }
-            count += __popcll(m);
-            cs++;
-        }
-        if (count <= QCAP - 64 && cs < QSTEPS && i + 1 < step_end) continue;
-        if (count == 0) continue;
-        // ---- B: count*(ls+1) light-march evaluations, 64 per round, all lanes busy
-        wave_lds_fence();
-        light_march_batch(T, fc, ls, count, lane, [&](int k, float& x, float& y, float& z) { x = ev_px[k]; y = ev_py[k]; z = ev_pz[k]; }, ev_lt, QCAP);
-        wave_lds_fence();
-        // ---- C: replay the chunk in step order; owners composite (:191,:199 sums in the reference's order, :202-210)
-        for (int s = 0; s < cs; s++) {
-            const unsigned lo = st_lo[s], hi = st_hi[s];
-            const bool mine = lane < 32 ? ((lo >> lane) & 1u) : ((hi >> (lane - 32)) & 1u);
-            if (mine) {
-                const int slot = (int)st_base[s] + (int)__builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo, 0u));
-                float cd = 0.0f;
-                for (int j = 0; j < nl; j++) cd += ev_lt[j * QCAP + slot];
-                const float et = ev_t[slot], ehf = ev_hf[slot];
-                const float dt = fast_exp(nd * et * ray.ss);                                                   // :178
-                shade_sample(fc, phase, et, ehf, dt, cd, Tr, alpha, Lr, Lg, Lb);
-                o.incloud++;
-            }
-        }
-        wave_lds_fence();
-        count = 0; cs = 0;
-        if (fc.early_eps > 0.0f) {                                     // build-side early-out (off by default, bounded error)
-            if (Tr < fc.early_eps) live = false;
-            if (!__any(live)) break;
-        }
-    }
-    o.r = Lr; o.g = Lg; o.b = Lb; o.a = sat(alpha); o.t = Tr;                                                  // :213-214
-    return o;
-}
-
-// ---- compacted light march (variant "compact") ------------------------------------------------------------------
-// Same decoupling as march_queue, but a flush always takes EXACTLY 64 queued samples, one per lane (k = lane): every lane
-// then runs the reference's whole light march (clouds.glsl:186-199) for its sample in registers.  The loop index j is
-// wave-uniform, so the LOD, the mip extent and offsets, the cone increment and the distant-sample special case are scalar
-// (SALU / immediates) instead of per-lane VALU selects, the cone position is carried in registers (3 adds per sample instead
-// of re-adding j+1 increments under predication), and the per-sample densities are summed in place (no lt[7][QCAP] array).
-// Samples beyond the 64th stay queued (moved to the front) together with the part of the last step that owns them; only
-// the final flush of a ray segment runs with idle lanes.
-constexpr int CQ_CAP = 128;                                  // a flush is taken as soon as 64 samples are queued: count <= 63 + 64
-constexpr int CQ_STEPS = 66;                                 // steps-with-events between flushes: <= 1 carried + 64 (>= 1 event each)
-constexpr int CQ_FLOATS = 5 * CQ_CAP + CQ_CAP / 4 + 3 * CQ_STEPS + 2 + 128 + 320;   // pos(3) t hf (after the light march: D(3) q dt) | owner lane (bytes) | per-step mask lo/hi + base | in-cloud tally | per-ray ss, phase | per-ray T, alpha, L between flushes = 5.2 KB per wavefront
-// The SLIM layout (march_compact<.., SLIM = true>: the specialised persistent forms only, so that eight of their workgroups fit a CU's LDS).  Same samples,
-// same order, same flushes; two arrays go:
-//   * st_base[CQ_STEPS]: a step's first slot is the previous step's plus the popcount of its mask, and the replay holds the mask as a scalar pair anyway;
-//   * ev_hf[64 .. CQ_CAP): a flush evaluates slots 0..63 only, so a sample queued at slot >= 64 is never read there: it is carried to the front first.  The
-//     carry recomputes its height fraction from the queued position (the same function of the same three floats as step A: the same bits), once per
-//     carried flush with all its lanes at once, not once per queued sample.
-constexpr int CQ_HF_SLIM = 64;
-// the first slot of the replayed step s: read from st_base, or (SLIM) counted up from the masks of the steps before it (the carried step, or the first
-// one after an empty queue, starts at 0).  Two types, so that the wide layout's replay is the code it was.
-template <bool SLIM> struct ReplayBase {
-    __device__ __forceinline__ int first(const unsigned* __restrict__ st_base, int s) const { return (int)st_base[s]; }
-    __device__ __forceinline__ void next(unsigned, unsigned) {}
-};
-template <> struct ReplayBase<true> {
-    int base = 0;
-    __device__ __forceinline__ int first(const unsigned* __restrict__, int) const { return base; }
-    __device__ __forceinline__ void next(unsigned lo, unsigned hi) { base += __builtin_popcount(lo) + __builtin_popcount(hi); }
-};
-constexpr int CQ_FLOATS_SLIM = 4 * CQ_CAP + CQ_HF_SLIM + CQ_CAP / 4 + 2 * CQ_STEPS + 2 + 128 + 320;   // 4 760 bytes per wavefront
-
-#ifndef CSKY_EAGER_LIGHT
-#define CSKY_EAGER_LIGHT 1
-#endif
-#if CSKY_EAGER_LIGHT
-#define CSKY_LIGHT_SAMPLE(CT) sample_density_eager<true, false, CT>
-#else
-#define CSKY_LIGHT_SAMPLE(CT) sample_density<CT>
-#endif
-#ifndef CSKY_EAGER_PRIMARY
-#define CSKY_EAGER_PRIMARY 0   // eager fetches in the PRIMARY march measured slower (1: weather + shape together +1 %, 2: all three +4.5 %): only
-                               // 56 % / 22 % of its samples need the shape / detail cell, the extra gathers cost more than the latency they hide
-#endif
-#if CSKY_EAGER_PRIMARY == 1
-#define CSKY_PRIMARY_SAMPLE(CT) sample_density_eager<false, false, CT>
-#elif CSKY_EAGER_PRIMARY == 2
-#define CSKY_PRIMARY_SAMPLE(CT) sample_density_eager<true, false, CT>
-#else
-#define CSKY_PRIMARY_SAMPLE(CT) sample_density<CT>
-#endif
-// Step B of the compact march for ONE queued in-cloud sample: the reference's light march (clouds.glsl:186-199) from its position and the
-// state-independent half of its shading (:178, :202-209).  In: position, density t, height fraction, the owner ray's step length and phase
-// value.  Out: D.rgb, 1 / max(1e-7, t), dt (shade_terms).  A function of those seven floats alone (round 4's packet exchange ran it on other
-// CUs' wavefronts and got byte-identical frames: docs/EXPERIMENTS.md §5).
-// `late(et, ehf, ess, eph)` delivers the four inputs the light march itself does not need AFTER it (the owner reads them from its LDS queue
-// then: four registers fewer across the march).
-#ifndef CSKY_LIGHT_STRAIGHT
-#define CSKY_LIGHT_STRAIGHT 1   // 0: the specialised persistent forms keep round 19's two loops (the A/B of the mode alone, profiles/r22/march_specialised_ab.txt)
-#endif
-#if CSKY_EAGER_LIGHT
-// Cone samples J, J + 1, ... 5 of the persistent form's light march as straight-line code: every sample index has its own copy of the body, so its
-// levels, their extents and offsets, the offset of linc[J] and whether the detail tap reads the LDS table (J = 3, 4), the global cell (J < 3) or nothing
-// (J = 5) are constants of the place, not scalar arithmetic and scalar branches per sample (round 19's rule carried to every index).  The wave-uniform
-// exit `J >= ls` stays in front of every sample: 0..6 light steps.
-template <int CT, int J, class TS>
-__device__ __forceinline__ void light_samples_from(const TS& T, const FrameConsts& fc, const int ls, float& lx, float& ly, float& lz, float& cd) {
-    if constexpr (J < 6) {
-        if (J >= ls) return;
-        advance(lx, ly, lz, fc.linc[J][0], fc.linc[J][1], fc.linc[J][2]);                              // :187
-        const float lhf = height_fraction(length3_shell(lx, ly, lz));                                  // :188
-        cd += sample_density_eager<true, (J > 2), CT>(T, fc, lx, ly, lz, lhf, fc.wpos_x, fc.wpos_y, J > 2 ? J - 2 : 0, J);   // :189-191
-        light_samples_from<CT, J + 1>(T, fc, ls, lx, ly, lz, cd);
-    }
-}
-#endif
-// CT: the cloud-type mode of cloud_core.h density_height_gradient (0: read from fc per evaluation).
-template <int CT = 0, class TS, class Late>
-__device__ __forceinline__ void light_march_terms(const TS& T, const FrameConsts& fc, const int ls, const float nd, float ex, float ey, float ez, Late&& late,
-                                                  float& Dr, float& Dg, float& Db, float& rq, float& dt) {
-    float lx = ex, ly = ey, lz = ez, cd = 0.0f;
-#if CSKY_EAGER_LIGHT
-    constexpr int JS = TS::small_detail ? 3 : 6;                // persistent launches: samples j = 3, 4 (and a j = 5 that taps nothing) run in code of their own
-    // persistent launches whose cloud-type mode is compiled in: one copy of the body per sample index (light_samples_from).  The generic form keeps the
-    // two loops: straight-line it has 273 / 288 basic blocks (the census build counts 256) and spills inside the flush loop (profiles/r22/march_specialised_ab.txt)
-    constexpr bool STRAIGHT = CSKY_LIGHT_STRAIGHT && TS::small_detail && CT != 0;
-#else
-    constexpr int JS = 6;
-    constexpr bool STRAIGHT = false;
-#endif
-    if constexpr (!STRAIGHT) {
-#pragma unroll 1                                                 // scalar j: one loop body (the plain kernel: 6x the code bought nothing in rounds 2 and 5, profiles/r05/kernel_experiments.txt)
-        for (int j = 0; j < JS; j++) {                                                                 // :186 (light_steps <= 6)
-            if (j >= ls) break;
-            advance(lx, ly, lz, fc.linc[j][0], fc.linc[j][1], fc.linc[j][2]);                          // :187
-            const float lhf = height_fraction(length3_shell(lx, ly, lz));                              // :188
-            cd += CSKY_LIGHT_SAMPLE(CT)(T, fc, lx, ly, lz, lhf, fc.wpos_x, fc.wpos_y, j > 2 ? j - 2 : 0, j);   // :189-191
-        }
-    }
-#if CSKY_EAGER_LIGHT
-    if constexpr (STRAIGHT) {
-        light_samples_from<CT, 0>(T, fc, ls, lx, ly, lz, cd);
-    } else if constexpr (TS::small_detail) {
-        // the same samples with their detail tap (LODs 3, 4) served from the LDS table: a second copy of the loop body, so that which path a tap takes is
-        // decided by where the code is, not by a branch per sample.  The one-loop form (a scalar branch on the level inside the tap: two more branches and
-        // ~4 SALU per light sample) took the same loads off the TA and gained 0.4 % of the headline; this form 3.5 %, of which 2.3 are the split's own (with j >= 3
-        // known the shape level and the levels' extents fold: SALU -13 %) and 1.2 the table's (profiles/r19/small_detail_lds_ab.txt)
-#pragma unroll 1
-        for (int j = JS; j < 6; j++) {
-            if (j >= ls) break;
-            advance(lx, ly, lz, fc.linc[j][0], fc.linc[j][1], fc.linc[j][2]);                          // :187
-            const float lhf = height_fraction(length3_shell(lx, ly, lz));                              // :188
-            cd += sample_density_eager<true, true, CT>(T, fc, lx, ly, lz, lhf, fc.wpos_x, fc.wpos_y, j - 2, j);   // :189-191
-        }
-    }
-#endif
-    {   // distant sample, :195-199
-        lx = ex; ly = ey; lz = ez;
-        advance(lx, ly, lz, fc.ldist[0], fc.ldist[1], fc.ldist[2]);
-        const float lhf = height_fraction(length3_shell(lx, ly, lz));
-        const float ld = CSKY_LIGHT_SAMPLE(CT)(T, fc, lx, ly, lz, lhf, 0.0f, 0.0f, 3, 5);              // :197 has no weather_pos
-        cd += fast_pow(ld, (1.0f - lhf) * 0.8f + 0.5f);                                                // :198 (second pow)
-    }
-    float et, ehf, ess, eph;
-    late(et, ehf, ess, eph);
-    dt = fast_exp(nd * et * ess);                                                                      // :178
-    shade_terms(fc, eph, et, ehf, dt, cd, Dr, Dg, Db, rq);                                             // :202-209
-}
-
-// WHOLE: the call marches whole rays (step_begin == 0, step_end == primary_steps; render_block with SEG == 1).  Only then, and only for the fp16-pair
-// texture set, the saturation skip applies (cloud_core.h ray_saturated: exact reject (4)): ray segments are combined as fp32 partial (L, T, alpha), which
-// the proof does not cover, and TexSet32 and variants 0-2 stay as they are for A/B.  A lane whose ray is saturated LATCHES: it keeps taking its primary
-// samples, but a t > 0 one is counted (ballot + popcount into a wave-uniform tally) instead of queued, so its light march and shading are never run and
-// `incloud` is what the full march counts.  The test runs once per flush, after the replay, on the state already in registers, and only when some lane not
-// yet latched has reached the alpha threshold; samples a latched ray still has in the queue are composited as usual (the bound covers any subset).
-// TALLY: the launch delivers `incloud` (launch_clouds: it was given d_stats or d_wg_cost).  Without it the count has no reader, and with SAT a latched
-// ray is DEAD: `live` goes false as on the early_eps path, the lane takes no further primary sample (weather, shape and detail taps, pow) and answers
-// false to `below_top`, so the every-4th-step ballot ends the wavefront once every lane is latched or above the window.  The queue receives the same
-// samples in the same order either way (a latched ray's were never queued), so flushes, latch tests and the stored halfs are those of TALLY = true
-// (tests/tilewalk emulates both per tile; tests/test_gpu_latched_rays.py compares the frames).  MarchOut::incloud is 0 and must not be read.
-// CT: the cloud-type mode of the frame as a compile-time value (cloud_core.h density_height_gradient); 0 reads fc.ct_mode per evaluation.
-// RISING: every ray of the call starts on the inner shell and runs outwards (every caller but clouds_observer_kernel).  It guards the early end below and
-// nothing else; without it the wavefront ends once no lane is live, which needs no assumption about the rays.
-// SLIM: the queue has the CQ_FLOATS_SLIM layout (above).
-template <bool WHOLE, bool TALLY, int CT = 0, class TS, bool RISING = true, bool SLIM = false>
-__device__ __forceinline__ MarchOut march_compact(const TS& T, const FrameConsts& fc, Ray ray, float* __restrict__ q, int step_begin, int step_end) {
-    constexpr bool SAT = WHOLE && !TS::cell32;
-    constexpr bool DEAD = SAT && !TALLY;                      // a latched ray stops marching
-    float* __restrict__ ev_px = q;
-    float* __restrict__ ev_py = q + CQ_CAP;
-    float* __restrict__ ev_pz = q + 2 * CQ_CAP;
-    float* __restrict__ ev_t = q + 3 * CQ_CAP;
-    float* __restrict__ ev_hf = q + 4 * CQ_CAP;                 // [CQ_CAP], SLIM: [CQ_HF_SLIM]
-    constexpr int HF_CAP = SLIM ? CQ_HF_SLIM : CQ_CAP;
-    unsigned char* __restrict__ ev_owner = reinterpret_cast<unsigned char*>(q + (4 * CQ_CAP + HF_CAP));   // the sample's owner lane: its step length and phase value are read from ray_ss / ray_ph
-    unsigned* __restrict__ st_lo = reinterpret_cast<unsigned*>(q + (4 * CQ_CAP + HF_CAP) + CQ_CAP / 4);  // [CQ_STEPS]
-    unsigned* __restrict__ st_hi = st_lo + CQ_STEPS;
-    unsigned* __restrict__ st_base = st_hi + CQ_STEPS;          // [CQ_STEPS], SLIM: absent (derived in the replay)
-
-    MarchOut o; o.r = o.g = o.b = o.a = 0.0f; o.t = 1.0f; o.incloud = 0;
-    const int lane = threadIdx.x & 63;
-    const int ls = fc.light_steps;
-    const float phase = ray_phase(fc, ray);
-    float px = ray.px, py = ray.py, pz = ray.pz;
-    const float nd = -fc.density;
-    bool live = ray.above;
-    int count = 0, cs = 0;                                    // queued samples / steps owning them (uniform)
-    bool latched = false;                                     // saturation skip: this lane's ray is saturated (SAT && TALLY only: a DEAD ray is `!live`)
-    unsigned skipped = 0u;                                    // in-cloud samples of latched rays, counted and not queued (uniform; TALLY only)
-    unsigned* __restrict__ tally = st_base + (SLIM ? 0 : CQ_STEPS);   // in-cloud samples composited by this wavefront, kept in LDS (round 4: neither a per-lane accumulator register
-    if constexpr (TALLY) { if (lane == 0) tally[0] = 0u; }    // in the march loops nor a scalar one in the SGPR-starved persistent form; one ds_add per flush)
-    // the two per-ray constants a queued sample carries (step length, phase value) live in LDS, not in registers held across the whole march: the
-    // persistent form had spilled `phase` to scratch and re-loaded it, behind a vmcnt(0), at every step with an in-cloud sample (round 4 census)
-    float* __restrict__ ray_ss = reinterpret_cast<float*>(tally + 2);
-    float* __restrict__ ray_ph = ray_ss + 64;
-    ray_ss[lane] = ray.ss; ray_ph[lane] = phase;
-    // The running state of the ray (T, alpha, L: clouds.glsl:151-153) is touched only while a flush is composited, ~20 times per tile: between
-    // flushes it rests in LDS, not in five registers the allocator had to copy between register sets around every light march (20 M v_mov per
-    // C3 frame, round-4 census) and hold across both march loops.
-    float* __restrict__ acc = ray_ph + 64;                      // [5][64]
-    acc[lane] = 1.0f; acc[64 + lane] = 0.0f; acc[128 + lane] = 0.0f; acc[192 + lane] = 0.0f; acc[256 + lane] = 0.0f;
-    if (__builtin_amdgcn_ballot_w64(live) == 0ull) return o;   // (the builtin takes the compare's own lane mask: HIP's __any / __ballot wrappers cost a v_cndmask + v_cmp_ne each)
-    for (int i = 0; i < step_begin; i++) advance(px, py, pz, ray.sx, ray.sy, ray.sz);   // segment start: replay the fp32 additions (:173)
-    int end = step_end;                                       // shrinks when the whole wavefront has left the height window
-    for (int i = step_begin;;) {
-        // ---- A: one primary sample per lane (none once the segment is exhausted and only carried samples remain)
-        if (i < end) {
-            float t, hf;                                     // (meaningful in live lanes only: every use below is guarded by `live` or by `have`)
-            bool have = false, below_top = false;
-            if (live) {
-                advance(px, py, pz, ray.sx, ray.sy, ray.sz);                                                   // :173
-                hf = height_fraction(length3_shell(px, py, pz));                                               // :175
-                t = CSKY_PRIMARY_SAMPLE(CT)(T, fc, px, py, pz, hf, fc.wpos_x, fc.wpos_y, 0, 0);                // :174, :177
-                have = t > 0.0f;                                                                               // :184
-                below_top = !(hf >= fc.hf_hi);
-            }
-            if constexpr (SAT && TALLY) {
-                skipped += (unsigned)__popcll(__builtin_amdgcn_ballot_w64(have && latched));
-                have = have && !latched;
-            }
-            // Exact early end of the march: a ray starts on the inner shell and |p| only grows along it (>= 14 m per step at 128 steps even
-            // for a grazing ray, 1.7 m at 1024 steps, against 0.5 m of fp32 noise; every ray of the C3 / C5 frames is walked by
-            // tests/test_hostsim_core.py), so once EVERY live ray of the wavefront is above the height window
-            // (density() == 0 there, cloud_core.h) all remaining samples are 0 too.  Checked every 4th step: one compare + ballot.
-            // 21 % of the wave-steps of the headline view lie above the window (tools/stage_trace).
-            if constexpr (RISING) {
-                if ((i & 3) == 3 && __builtin_amdgcn_ballot_w64(below_top) == 0ull) end = i + 1;
-            } else {                                         // rays that descend, or dip and rise: a lane above the window may come back into it
-                if ((i & 3) == 3 && __builtin_amdgcn_ballot_w64(live) == 0ull) end = i + 1;
-            }
-            const unsigned long long m = __builtin_amdgcn_ballot_w64(have);
-            if (m != 0ull) {
-                const int slot = count + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-                if constexpr (SLIM) {
-                    if (have) { ev_px[slot] = px; ev_py[slot] = py; ev_pz[slot] = pz; ev_t[slot] = t; ev_owner[slot] = (unsigned char)lane; if (slot < CQ_HF_SLIM) ev_hf[slot] = hf; }
-                    if (lane == 0) { st_lo[cs] = (unsigned)m; st_hi[cs] = (unsigned)(m >> 32); }
-                } else {
-                if (have) { ev_px[slot] = px; ev_py[slot] = py; ev_pz[slot] = pz; ev_t[slot] = t; ev_hf[slot] = hf; ev_owner[slot] = (unsigned char)lane; }
-                if (lane == 0) { st_lo[cs] = (unsigned)m; st_hi[cs] = (unsigned)(m >> 32); st_base[cs] = (unsigned)count; }
-                }
-                count += __popcll(m);
-                cs++;
-            }
-            i++;
-        }
-        const bool last = i >= end;
-        if (count == 0) { if (last) break; continue; }
-        if (count < 64 && !last) continue;
-        // ---- B: the light march of the first n = min(count, 64) queued samples, one per lane, and the state-independent half of their
-        //         shading (clouds.glsl:178, :202-209) while all lanes are busy: the replay below runs with ~1/6 of them (round 3: the census
-        //         put 15 % of the kernel's issue time in the replay loop, 43 VALU instructions per step incl. 4 transcendentals)
-        wave_lds_fence();
-        const int n = count < 64 ? count : 64;
-        unsigned long long carry = 0ull;                     // lanes of the last step whose sample is still queued
-        if constexpr (TALLY) { if (lane == 0) tally[0] += (unsigned)n; }
-        if (lane < n) {
-            float Dr, Dg, Db, rq, dt;
-            light_march_terms<CT>(T, fc, ls, nd, ev_px[lane], ev_py[lane], ev_pz[lane],
-                              [&](float& et, float& ehf, float& ess, float& eph) { et = ev_t[lane]; ehf = ev_hf[lane]; const int ow = ev_owner[lane]; ess = ray_ss[ow]; eph = ray_ph[ow]; }, Dr, Dg, Db, rq, dt);
-            ev_px[lane] = Dr; ev_py[lane] = Dg; ev_pz[lane] = Db; ev_t[lane] = rq; ev_hf[lane] = dt;           // the sample's slot now holds its terms
-        }
-        wave_lds_fence();
-        // ---- C: replay the steps in order; owners of evaluated samples (slot < n) composite (:207-210)
-        float Tr = acc[lane], alpha = acc[64 + lane], Lr = acc[128 + lane], Lg = acc[192 + lane], Lb = acc[256 + lane];
-        ReplayBase<SLIM> sb;
-        for (int s = 0; s < cs; s++) {
-            // the step's lane mask is wave-uniform: as a scalar pair it IS the execution mask of the owners (inverse ballot: no per-lane bit test)
-            const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)st_lo[s]), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)st_hi[s]);
-            const bool mine = __builtin_amdgcn_inverse_ballot_w64(((unsigned long long)hi << 32) | lo);
-            const int slot = sb.first(st_base, s) + (int)__builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo, 0u));
-            sb.next(lo, hi);
-            if (mine && slot < n) {
-                composite_sample(ev_hf[slot], ev_t[slot], ev_px[slot], ev_py[slot], ev_pz[slot], Tr, alpha, Lr, Lg, Lb);
-            }
-            if (s == cs - 1) carry = __builtin_amdgcn_ballot_w64(mine && slot >= n);
-        }
-        if constexpr (DEAD) {
-            const bool cand = live && alpha >= SAT_ALPHA_MIN;
-            if (fc.sat_skip != 0 && __builtin_amdgcn_ballot_w64(cand) != 0ull) {
-                float B[3];
-                ray_saturation_bound(fc, ray_ph[lane], B);
-                const float L[3] = {Lr, Lg, Lb};
-                if (cand && ray_saturated(fc, Tr, alpha, L, B)) live = false;
-            }
-        } else if constexpr (SAT) {
-            const bool cand = !latched && alpha >= SAT_ALPHA_MIN;
-            if (fc.sat_skip != 0 && __builtin_amdgcn_ballot_w64(cand) != 0ull) {
-                float B[3];
-                ray_saturation_bound(fc, ray_ph[lane], B);
-                const float L[3] = {Lr, Lg, Lb};
-                latched = latched || (cand && ray_saturated(fc, Tr, alpha, L, B));
-            }
-        }
-        acc[lane] = Tr; acc[64 + lane] = alpha; acc[128 + lane] = Lr; acc[192 + lane] = Lg; acc[256 + lane] = Lb;
-        wave_lds_fence();
-        // ---- keep what was not evaluated: samples n..count-1 move to the front, the last step keeps its unevaluated lanes
-        const int rem = count - n;
-        if (rem > 0) {
-            float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f, a4 = 0.0f; unsigned char a5 = 0;
-            if constexpr (SLIM) {                            // rem > 0: n == 64 == CQ_HF_SLIM, every carried sample lies where no height fraction was stored
-                if (lane < rem) { a0 = ev_px[n + lane]; a1 = ev_py[n + lane]; a2 = ev_pz[n + lane]; a3 = ev_t[n + lane]; a5 = ev_owner[n + lane]; a4 = height_fraction(length3_shell(a0, a1, a2)); }
-            } else {
-            if (lane < rem) { a0 = ev_px[n + lane]; a1 = ev_py[n + lane]; a2 = ev_pz[n + lane]; a3 = ev_t[n + lane]; a4 = ev_hf[n + lane]; a5 = ev_owner[n + lane]; }
-            }
-            wave_lds_fence();
-            if (lane < rem) { ev_px[lane] = a0; ev_py[lane] = a1; ev_pz[lane] = a2; ev_t[lane] = a3; ev_hf[lane] = a4; ev_owner[lane] = a5; }
-            if constexpr (SLIM) { if (lane == 0) { st_lo[0] = (unsigned)carry; st_hi[0] = (unsigned)(carry >> 32); } }
-            else { if (lane == 0) { st_lo[0] = (unsigned)carry; st_hi[0] = (unsigned)(carry >> 32); st_base[0] = 0u; } }
-            wave_lds_fence();
-            count = rem; cs = 1;
-        } else {
-            count = 0; cs = 0;
-        }
-        if (fc.early_eps > 0.0f) {                                     // build-side early-out (off by default, bounded error)
-            if (Tr < fc.early_eps) live = false;
-            if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
-        }
-        if (last && count == 0) break;                               // carried samples get one more (partial) flush
-    }
-    wave_lds_fence();
-    o.r = acc[128 + lane]; o.g = acc[192 + lane]; o.b = acc[256 + lane]; o.a = sat(acc[64 + lane]); o.t = acc[lane];   // :213-214
-    if constexpr (TALLY) o.incloud = lane == 0 ? tally[0] + skipped : 0u;
-    return o;
-}
-
-// (two primary steps and two light samples in flight per wavefront, kernel variant "compact-ilp": docs/EXPERIMENTS.md §5, removed experiments)
 
 // ---- the pixel of a lane -----------------------------------------------------------------------------------------------------
 // Workgroup footprint `logical` = slab * tiles_x + bx is bw x 8 pixels; the wavefront's 8x8 tile is its tile-th (lane = ly*8 + lx).  The front ends of
@@ -496,111 +57,7 @@ __device__ __forceinline__ void store_pixel(uint2* __restrict__ out, const Rende
     out[(size_t)(G.out_full ? gy : lr) * G.pitch_px + gx] = pack_half4(f2h(r), f2h(g), f2h(b), f2h(a));   // imageStore, clouds.glsl:264
 }
 
-// ---- interleaved ray segments (small launches) ------------------------------------------------------------------
-// One workgroup = ONE 8x8 tile; wavefront w marches the primary samples i = 4m + w of every ray of the tile.  In-cloud
-// samples cluster in a few step ranges of a ray, so splitting a ray by step RANGE leaves one wavefront with most of the
-// light march; dealing the steps out round-robin gives all four SIMDs of the CU a quarter of the tile's light march
-// (the heaviest tile of the headline frame has 4.2x the mean in-cloud samples and is the critical path of a launch that
-// holds only a few wavefronts per SIMD: one GPU's share of a frame split 8 ways).
-// Front-to-back compositing needs T_i = prod_{k<i} dt_k across ALL wavefronts' samples: per chunk of 32 steps every
-// wavefront publishes the step transmittances dt of its samples (1 for samples outside cloud), 16 lanes per wavefront
-// scan them into exclusive prefix products, and each wavefront then shades its own samples with L_w += T_i * (...).
-// The partial L_w are summed in wavefront order and alpha = 1 - T_end (clouds.glsl:207 is the same product).  Sample
-// positions and densities are bit-identical to the sequential march; only the compositing sums are re-associated.
-constexpr int IL_CHUNK = 32, IL_OWN = IL_CHUNK / 4, IL_BATCH = 96;
-constexpr int IL_WAVE_FLOATS = 5 * IL_OWN * 64 + (IL_OWN * 64) / 2 + 7 * IL_BATCH;     // dense px,py,pz,t,hf | idx (u16) | lt
-constexpr int IL_BLOCK_FLOATS = 4 * IL_WAVE_FLOATS + 2 * IL_CHUNK * 64 + 4 * 4 * 64;     // + D, P planes + combine
-
-__device__ __forceinline__ void march_interleaved(const TexSet& T, const FrameConsts& fc, const Ray& ray, float* __restrict__ smem, int wave, int lane,
-                                                  float& out_r, float& out_g, float& out_b, float& out_a, unsigned& incloud) {
-    float* __restrict__ wq = smem + wave * IL_WAVE_FLOATS;
-    float* __restrict__ d_px = wq;                              // [IL_OWN][64]; reused for cd after the light march
-    float* __restrict__ d_py = wq + IL_OWN * 64;
-    float* __restrict__ d_pz = wq + 2 * IL_OWN * 64;
-    float* __restrict__ d_t = wq + 3 * IL_OWN * 64;
-    float* __restrict__ d_hf = wq + 4 * IL_OWN * 64;
-    unsigned short* __restrict__ ev_idx = reinterpret_cast<unsigned short*>(wq + 5 * IL_OWN * 64);   // [IL_OWN*64]
-    float* __restrict__ lt = wq + 5 * IL_OWN * 64 + (IL_OWN * 64) / 2;                                  // [7][IL_BATCH]
-    float* __restrict__ D = smem + 4 * IL_WAVE_FLOATS;          // [IL_CHUNK][64] step transmittance of every sample of the chunk
-    float* __restrict__ P = D + IL_CHUNK * 64;                  // [IL_CHUNK][64] exclusive prefix products
-    float* __restrict__ comb = P + IL_CHUNK * 64;               // [4][4][64]
-
-    const int steps = fc.primary_steps, ls = fc.light_steps, nl = ls + 1;
-    const float nd = -fc.density;
-    const float phase = ray_phase(fc, ray);
-    float Lr = 0.0f, Lg = 0.0f, Lb = 0.0f;
-    float px = ray.px, py = ray.py, pz = ray.pz;
-    int replay = wave + 1;                                      // additions of dir*ss needed to reach this wavefront's next sample
-    float carry = 1.0f;                                         // scan lanes (lane < 16): T of ray 16*wave + lane after the chunks so far
-    incloud = 0;
-    const int nchunks = (steps + IL_CHUNK - 1) / IL_CHUNK;
-    for (int c = 0; c < nchunks; c++) {
-        // ---- A: this wavefront's 8 samples of the chunk
-        int count = 0;
-        for (int q = 0; q < IL_OWN; q++) {
-            const int i = c * IL_CHUNK + 4 * q + wave;
-            float t = 0.0f, hf = 0.0f;
-            if (ray.above && i < steps) {
-                for (int a = 0; a < replay; a++) advance(px, py, pz, ray.sx, ray.sy, ray.sz);     // clouds.glsl:173, one add per step
-                hf = height_fraction(length3_shell(px, py, pz));
-                t = sample_density(T, fc, px, py, pz, hf, fc.wpos_x, fc.wpos_y, 0, 0);
-            }
-            replay = 4;
-            const bool have = t > 0.0f;
-            d_t[q * 64 + lane] = t;
-            D[(4 * q + wave) * 64 + lane] = have ? fast_exp(nd * t * ray.ss) : 1.0f;               // clouds.glsl:178
-            const unsigned long long m = __ballot(have);
-            if (m != 0ull) {
-                const int slot = count + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-                if (have) { ev_idx[slot] = (unsigned short)(q * 64 + lane); d_px[q * 64 + lane] = px; d_py[q * 64 + lane] = py; d_pz[q * 64 + lane] = pz; d_hf[q * 64 + lane] = hf; }
-                count += __popcll(m);
-            }
-        }
-        wave_lds_fence();
-        // ---- B: light march of the chunk's events, IL_BATCH events at a time, 64 evaluations per round
-        for (int b0 = 0; b0 < count; b0 += IL_BATCH) {
-            const int nb = (count - b0) < IL_BATCH ? (count - b0) : IL_BATCH;
-            light_march_batch(T, fc, ls, nb, lane, [&](int k, float& x, float& y, float& z) { const int id = ev_idx[b0 + k]; x = d_px[id]; y = d_py[id]; z = d_pz[id]; }, lt, IL_BATCH);
-            wave_lds_fence();
-            for (int k = lane; k < nb; k += 64) {               // cd of each event, summed in the reference's order (:191, :199)
-                float cd = 0.0f;
-                for (int j = 0; j < nl; j++) cd += lt[j * IL_BATCH + k];
-                d_px[ev_idx[b0 + k]] = cd;                      // the position is consumed: its x slot now holds cd
-            }
-            wave_lds_fence();
-        }
-        __syncthreads();
-        // ---- scan: exclusive prefix products of the chunk's step transmittances, 16 rays per wavefront
-        if (lane < 16) {
-            const int r = wave * 16 + lane;
-            float Tp = carry;
-            for (int s = 0; s < IL_CHUNK; s++) { P[s * 64 + r] = Tp; Tp *= D[s * 64 + r]; }
-            carry = Tp;
-        }
-        __syncthreads();
-        // ---- C: shade this wavefront's in-cloud samples (clouds.glsl:202-209) with T_i from the scan
-        for (int q = 0; q < IL_OWN; q++) {
-            const float t = d_t[q * 64 + lane];
-            if (t > 0.0f) {
-                const float hf = d_hf[q * 64 + lane], cd = d_px[q * 64 + lane];
-                const float dt = D[(4 * q + wave) * 64 + lane];
-                float Tr = P[(4 * q + wave) * 64 + lane], alpha_unused = 0.0f;
-                shade_sample(fc, phase, t, hf, dt, cd, Tr, alpha_unused, Lr, Lg, Lb);
-                incloud++;
-            }
-        }
-        __syncthreads();                                        // D/P/dense buffers are rewritten by the next chunk
-    }
-    // ---- combine: L = sum of the wavefronts' partial sums (wavefront order), alpha = 1 - T_end
-    comb[(wave * 4 + 0) * 64 + lane] = Lr; comb[(wave * 4 + 1) * 64 + lane] = Lg; comb[(wave * 4 + 2) * 64 + lane] = Lb;
-    if (lane < 16) comb[(0 * 4 + 3) * 64 + wave * 16 + lane] = carry;
-    __syncthreads();
-    out_r = comb[(0 * 4 + 0) * 64 + lane]; out_g = comb[(0 * 4 + 1) * 64 + lane]; out_b = comb[(0 * 4 + 2) * 64 + lane];
-#pragma unroll
-    for (int w = 1; w < 4; w++) { out_r += comb[(w * 4 + 0) * 64 + lane]; out_g += comb[(w * 4 + 1) * 64 + lane]; out_b += comb[(w * 4 + 2) * 64 + lane]; }
-    out_a = sat(1.0f - comb[(0 * 4 + 3) * 64 + lane]);
-}
-
+// ---- interleaved ray segments (small launches): march_variants.h march_interleaved, one 8x8 tile per workgroup ---------------------
 template <int DUMMY>
 __global__ __launch_bounds__(256) void clouds_kernel_interleaved(TexSet T, const FrameConsts* __restrict__ fcp, RenderGeom G, const uint32_t* __restrict__ order,
                                                                  uint2* __restrict__ out, unsigned long long* __restrict__ stats, uint32_t* __restrict__ wg_cost) {
@@ -678,10 +135,7 @@ __global__ __launch_bounds__(1024) void clouds_kernel_lds(TexSet T, const FrameC
 //              segments divide it by SEG.  Sample positions stay bit-identical; the compositing sums are re-associated.
 // Workgroup order: physical workgroup b runs on XCD b % 8 (observed, speed only); `order` (clouds_launch.cpp::clouds_dev)
 // maps b to a workgroup footprint.
-#ifndef CSKY_COMPACT_WAVES
-#define CSKY_COMPACT_WAVES 7   // waves/SIMD asked of the "compact" variant.  With the eager light-march fetches (three gathers of a sample in flight
-                               // together) 7 waves x 72 VGPRs beat 8 waves x 64 VGPRs + spills: whole frame 1.83 -> 1.80 ms, 1/4 frame 0.49 -> 0.48
-#endif
+// (CSKY_COMPACT_WAVES, the waves/SIMD asked of the "compact" variant: march_compact.h)
 #ifndef CSKY_PERSISTENT_SLIM_WAVES
 #define CSKY_PERSISTENT_SLIM_WAVES 8   // waves/SIMD asked of the specialised persistent forms (clouds_kernel_persistent<3, false, 1 | 2>) alone: 64 VGPRs without a
                                        // VGPR spill since round 22's straight-line light march, and the slim queue (CQ_FLOATS_SLIM) lets eight workgroups share a CU's LDS
@@ -853,99 +307,6 @@ __global__ __launch_bounds__(256, persistent_slim(VARIANT, TALLY, CT) ? CSKY_PER
 
 // (helpers serving other wavefronts' light marches once the order is empty, and three ways of filling a launch's tail: docs/EXPERIMENTS.md §5, removed experiments)
 
-// ---- cost-feedback schedule (clouds_launch.cpp, schedule mode 7) ------------------------------------------------------------
-// Workgroups differ 10x in cost (in-cloud samples per tile) and a C3 frame is only ~4 waves of resident workgroups deep, so
-// the order they start in decides the tail.  Every launch records a cost per workgroup (wg_cost: in-cloud samples + live rays);
-// these three kernels turn it into the NEXT launch's order, heaviest first (longest-processing-time-first list scheduling;
-// consecutive blocks land on consecutive XCDs, so each XCD also receives a descending sequence).  Counting sort on 1024 cost
-// buckets; ties are placed in arrival order (the schedule may differ run to run, the frame cannot: every ray's arithmetic is
-// independent of where and when its workgroup runs, tests/test_gpu_parity.py::test_variants_and_schedules_agree).
-// (LPT_BUCKETS and lpt_bucket: order_core.h; bucket 0 = heaviest)
-__global__ __launch_bounds__(256) void lpt_hist_kernel(const uint32_t* __restrict__ cost, int n, int shift, uint32_t* __restrict__ hist) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) atomicAdd(&hist[lpt_bucket(cost[i], shift)], 1u);
-}
-__global__ __launch_bounds__(LPT_BUCKETS) void lpt_scan_kernel(uint32_t* __restrict__ hist, uint32_t* __restrict__ offsets) {
-    __shared__ uint32_t sh[LPT_BUCKETS];                       // counts -> exclusive offsets; the histogram is left zeroed for the next launch
-    const int t = threadIdx.x;
-    const uint32_t own = hist[t];
-    hist[t] = 0u;
-    sh[t] = own;
-    __syncthreads();
-    for (int off = 1; off < LPT_BUCKETS; off <<= 1) {
-        const uint32_t v = t >= off ? sh[t - off] : 0u;
-        __syncthreads();
-        sh[t] += v;
-        __syncthreads();
-    }
-    offsets[t] = sh[t] - own;
-}
-__global__ __launch_bounds__(256) void lpt_scatter_kernel(uint32_t* __restrict__ cost, int n, int shift, uint32_t* __restrict__ offsets,
-                                                          uint32_t* __restrict__ order) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) {
-        order[atomicAdd(&offsets[lpt_bucket(cost[i], shift)], 1u)] = (uint32_t)i;
-        cost[i] = 0u;                                          // the next launch accumulates into a clean array: no memset nodes per frame
-    }
-}
-// d_cost[n] and d_scratch[2 * LPT_BUCKETS] must be zero before their first use (clouds_launch.cpp clears them at allocation); both are left zeroed
-hipError_t launch_lpt_order(uint32_t* d_cost, int n, int shift, uint32_t* d_scratch, uint32_t* d_order, hipStream_t s) {
-    if (n <= 0) return hipSuccess;
-    lpt_hist_kernel<<<(n + 255) / 256, 256, 0, s>>>(d_cost, n, shift, d_scratch);
-    lpt_scan_kernel<<<1, LPT_BUCKETS, 0, s>>>(d_scratch, d_scratch + LPT_BUCKETS);
-    lpt_scatter_kernel<<<(n + 255) / 256, 256, 0, s>>>(d_cost, n, shift, d_scratch + LPT_BUCKETS, d_order);
-    return hipGetLastError();
-}
-
-// ---- static workgroup orders, generated on the device (clouds_launch.cpp::ensure_order) --------------------------------
-// Physical workgroup b runs on XCD b % 8 (observed placement, used for speed only).  A "slab" is one 32 x 8 pixel workgroup
-// footprint (bw x 8 for segmented launches); `grid` entries, 0xffffffff = idle padding.
-// The entry of workgroup b in modes 1, 2 and 5 is order_core.h::static_order_entry, which the host tests walk too.
-// Written by a kernel on the launch's own stream: no host table, no pageable copy, no device-wide synchronisation when the
-// geometry changes (a 64-tile walk re-uses the table anyway: these orders depend on the launch geometry only).
-__global__ __launch_bounds__(256) void static_order_kernel(int mode, int tiles_x, int slabs, int grid, uint32_t* __restrict__ out) {
-    const int b = blockIdx.x * 256 + threadIdx.x;
-    if (b >= grid) return;
-    out[b] = static_order_entry(mode, tiles_x, slabs, b);
-}
-hipError_t launch_static_order(int mode, int tiles_x, int slabs, int grid, uint32_t* d_order, hipStream_t s) {
-    if (grid <= 0) return hipSuccess;
-    static_order_kernel<<<(grid + 255) / 256, 256, 0, s>>>(mode, tiles_x, slabs, grid, d_order);
-    return hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------------------ band interleave (gathering rank, N > 1)
-// The gather leaves rank-major compact bands ([member][local band][rows]); the frame wants band k = member k % n, local band k / n.  A plain
-// strided copy, deliberately on FEW workgroups: it is HBM-bound (32 MiB per 2048x1024 frame) beside marches that are not, so 48 workgroups
-// streaming 16-byte chunks take it off the critical path instead of sweeping the whole chip for 15 us per frame (torch's permute + copy).
-__global__ __launch_bounds__(256) void interleave_bands_kernel(const uint4* __restrict__ src, size_t member_stride16, int members, uint32_t band16, uint32_t total_bands,
-                                                              uint4* __restrict__ dst) {
-    const size_t total = (size_t)band16 * total_bands;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const uint32_t k = (uint32_t)(i / band16), c = (uint32_t)(i - (size_t)k * band16);
-        dst[i] = src[(size_t)(k % members) * member_stride16 + (size_t)(k / members) * band16 + c];
-    }
-}
-hipError_t launch_interleave_bands(const void* d_gathered, size_t member_stride_bytes, int members, size_t band_bytes, int total_bands, void* d_frame, hipStream_t s) {
-    const size_t chunks = band_bytes / 16 * (size_t)total_bands;
-    if (!chunks) return hipSuccess;
-    const unsigned grid = (unsigned)(chunks / 256 + 1 < 48 ? chunks / 256 + 1 : 48);
-    interleave_bands_kernel<<<grid, 256, 0, s>>>(reinterpret_cast<const uint4*>(d_gathered), member_stride_bytes / 16, members, (uint32_t)(band_bytes / 16), (uint32_t)total_bands,
-                                                 reinterpret_cast<uint4*>(d_frame));
-    return hipGetLastError();
-}
-
-// test hook (csky_test_sqrt_shell): cloud_core.h::sqrt_shell over an array, for the exhaustive check against the host's sqrtf
-__global__ __launch_bounds__(256) void sqrt_shell_kernel(const float* __restrict__ in, float* __restrict__ out, size_t n) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] = sqrt_shell(in[i]);
-}
-hipError_t launch_sqrt_shell(const float* d_in, float* d_out, size_t n, hipStream_t s) {
-    if (n == 0) return hipSuccess;
-    sqrt_shell_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(d_in, d_out, n);
-    return hipGetLastError();
-}
-
 static const char* const kVariantNames[] = {"lockstep", "queue", "queue-lds", "compact"};
 int cloud_resident_workgroups_per_cu() { return CSKY_COMPACT_WAVES; }
 int cloud_resident_workgroups_per_cu_slim() {
@@ -1017,8 +378,6 @@ hipError_t launch_clouds(int variant, int seg, const TexSet& t, const FrameConst
     return hipGetLastError();
 }
 
-}  // namespace csky
-
 // ---- the direct march: caller-given rays ------------------------------------------------------------------------
 // clouds.glsl sky(dir) for the directions of a W x H image the caller describes (a buffer of directions, or a camera view) instead of the
 // hemi-octahedral grid's: render_block's whole-ray form with another front end.  One pixel per lane, an 8x8 tile per wavefront, four tiles side by
@@ -1028,10 +387,6 @@ hipError_t launch_clouds(int variant, int seg, const TexSet& t, const FrameConst
 //
 // Every kernel from here to the end of the file is this one with another front end, and is written as: the lane's pixel (csky_common.h tile_pixel),
 // its direction (rays_core.h rays_lane_dir, or the update's view_update_dir), the kernel's own ray maker, march_store.
-#include "rays_core.h"
-#pragma clang fp contract(off)   // (rays_core.h ends with contraction on, like cloud_core.h)
-
-namespace csky {
 
 // The shared tail.  The lanes with `marches` run `ray` whole through march_compact on their wavefront's quarter of the workgroup's queues and store
 // the texel at pixel (i, j) of `out` (store_pixel's packing); the others take no sample, compute no texture address and store nothing.  The queues
@@ -1065,17 +420,11 @@ hipError_t launch_clouds_rays(const TexSet& t, const TexSet32* t32, const FrameC
     return hipGetLastError();
 }
 
-}  // namespace csky
-
 // ---- the temporal split of a view frame ----------------------------------------------------------------------------
 // One pixel of every B x B block of a view is marched per call (the fresh pixels), the others are taken from the previous view frame through the
 // previous camera, and a pixel that frame does not cover (a hole) is marched.  Two launches that write disjoint pixels: the order between them does
 // not matter.  Both are clouds_rays_kernel's shape: one pixel per lane, an 8x8 tile per wavefront, four tiles per workgroup, the same LDS queue and
 // launch bound, march_compact<true, false> on the frame constants the cloud frame's set-up kernel wrote.
-#include "view_update_core.h"
-#pragma clang fp contract(off)   // (view_update_core.h ends with contraction on, like rays_core.h)
-
-namespace csky {
 
 // The fresh pixels, run over the SUB-GRID: lane (p.i, p.j) of G.sub_w x G.sub_h marches pixel (p.i * B + px, p.j * B + py) and stores there.  The
 // fresh rays fill whole 8x8 tiles: a wavefront of 64 fresh rays, not 4 lanes of every wavefront of the image.
@@ -1121,17 +470,11 @@ hipError_t launch_clouds_view_update(const TexSet& t, const TexSet32* t32, const
     return hipGetLastError();
 }
 
-}  // namespace csky
-
 // ---- the direct march from an observer's position -------------------------------------------------------------------
 // clouds_rays_kernel with another front end: observer_core.h observer_ray makes the lane's Ray from its direction AND the observer's position (under,
 // inside or above the layer; the first segment through the layer, capped).  The same shape: one pixel per lane, an 8x8 tile per wavefront, four
 // tiles per workgroup, the same LDS queue and launch bound, a plain launch in natural order.  march_compact<true, false, 0, TS, false>: these rays
 // descend, or dip and rise, so the wavefront's early end is "no lane is live" and not "every lane is above the window".
-#include "observer_core.h"
-#pragma clang fp contract(off)   // (observer_core.h ends with contraction on, like rays_core.h)
-
-namespace csky {
 
 // SRC: rays_lane_dir's, on G.g
 template <int SRC, class TS>
@@ -1153,18 +496,12 @@ hipError_t launch_clouds_observer(const TexSet& t, const TexSet32* t32, const Fr
     return hipGetLastError();
 }
 
-}  // namespace csky
-
 // ---- the observer's march behind a per-pixel scene depth -------------------------------------------------------------
 // clouds_observer_kernel with one more input: scene_depth_core.h scene_depth_ray ends the lane's segment at its own pixel's depth texel (metres along
 // the ray, or along the camera's forward axis) as well as at the frame's max_distance.  The same shape: one pixel per lane, an 8x8 tile per wavefront,
 // four tiles per workgroup, the same LDS queue and launch bound, a plain launch in natural order, march_compact<true, false, 0, TS, false>.  A lane
 // inside the image makes one 4-byte load of its texel (a row of a tile is eight consecutive floats); a lane outside it loads nothing.  A wavefront
 // whose lanes are all occluded returns at march_compact's first ballot.
-#include "scene_depth_core.h"
-#pragma clang fp contract(off)   // (scene_depth_core.h ends with contraction on, like observer_core.h)
-
-namespace csky {
 
 // SRC as clouds_observer_kernel's (0: directions from `dirs`, [H][W][3] floats; 1: the view of G.og.g).  KIND: DEPTH_DISTANCE or DEPTH_VIEW_Z (view form only), compiled in: the distance form has no dot product or divide.
 // depth: G.og.g.h rows of G.og.g.w floats, G.depth_pitch floats apart; it does not overlap out.

@@ -28,7 +28,7 @@ TexSet32 texset32(const csky_ctx* c) {
 
 namespace {
 
-// The static workgroup order of ring slot `slot` for this launch, on stream s (cloud_kernels.hip::static_order_kernel; modes 1, 2, 5).  Measured on
+// The static workgroup order of ring slot `slot` for this launch, on stream s (order_kernels.hip::static_order_kernel; modes 1, 2, 5).  Measured on
 // the headline frame (queue kernel, round 1): 5 (slab rows round-robin over the XCDs) 3.93 ms, 1 (contiguous eighths) 4.80 ms, 2 (natural) 4.92 ms;
 // azimuth-wedge and horizon-first orders (5.3-5.8 / 4.77 ms) were dropped in round 2.  The table depends on the launch geometry
 // only (not on update_position: the reference's tile walk re-uses it) and is written by a kernel on the launch's stream.

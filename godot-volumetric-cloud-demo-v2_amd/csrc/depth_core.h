@@ -64,7 +64,7 @@ CSKY_HD DepthTexel depth_texel_of(const DepthAcc& a, float alpha) {
 
 // The N samples of one ray; returns the stored texel.  `live`: the lane has a pixel whose ray is above the horizon (the other lanes only take
 // part in the votes).  Every fourth step the wavefront stops when each of its lanes is above the height window for good: |p| only grows along
-// a ray that starts on the inner shell (the argument and the margins of cloud_kernels.hip march_compact).  `taken`, `incloud` (may be null):
+// a ray that starts on the inner shell (the argument and the margins of march_compact.h march_compact).  `taken`, `incloud` (may be null):
 // += the samples this lane took, and those of them with t > 0.
 template <class TS>
 CSKY_HD DepthTexel depth_march(const TS& T, const FrameConsts& fc, const DepthConsts& dc, const Ray& ray, float t0, bool live, unsigned long long* taken,

@@ -8,7 +8,7 @@
 
 namespace csky {
 
-// Everything a static order table (cloud_kernels.hip::static_order_kernel) is a function of.  tiles_x counts workgroup FOOTPRINTS per row, not pixels:
+// Everything a static order table (order_kernels.hip::static_order_kernel) is a function of.  tiles_x counts workgroup FOOTPRINTS per row, not pixels:
 // in mode 1 a 33-pixel-wide launch of one slab has a grid of 8 both as whole rays (2 footprints) and as two segments (3 footprints), and a key that
 // could not tell them apart handed the second form the first one's table, one footprint short.
 struct OrderKey {

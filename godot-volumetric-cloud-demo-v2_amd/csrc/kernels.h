@@ -60,7 +60,7 @@ hipError_t launch_bake_weather32(const uint8_t* d_weather, float4* d_weather32, 
 // ------------------------------------------------------------------------------------------------ cloud_kernels.hip
 // clouds.glsl main() over the rows described by `g`.  d_stats (may be null): [0] += in-cloud samples,
 // [1] += rays above the horizon.  With neither d_stats nor d_wg_cost the whole-ray compact kernel (variant 3, seg 1, fp16-pair cells) runs without its
-// in-cloud tally and stops marching a ray once its stored pixel is final (cloud_kernels.hip march_compact, TALLY = false); the frame is the same.
+// in-cloud tally and stops marching a ray once its stored pixel is final (march_compact.h march_compact, TALLY = false); the frame is the same.
 // census_lean: launch that form although d_stats is given (csky_census_clouds: the census build's block counters are the buffer's only writers then).
 // seg = ray segments per ray (1, 2 or 4; variant 1 only): a workgroup covers 4/seg tiles of 8x8 pixels.
 // d_order[grid]: physical workgroup -> workgroup-footprint id (0xffffffff = idle), see clouds_launch.cpp::clouds_dev.
@@ -75,6 +75,8 @@ int cloud_resident_workgroups_per_cu();
 int cloud_resident_workgroups_per_cu_slim();
 int cloud_variant_count();
 const char* cloud_variant_name(int v);
+
+// ------------------------------------------------------------------------------------------------ order_kernels.hip
 // next launch's workgroup order from this launch's per-workgroup costs, heaviest first.  d_cost[n] and d_scratch[2048] must be zero
 // before their first use and are left zeroed (the cloud kernel accumulates the next costs into d_cost).
 hipError_t launch_lpt_order(uint32_t* d_cost, int n, int shift, uint32_t* d_scratch, uint32_t* d_order, hipStream_t s);
@@ -82,8 +84,8 @@ hipError_t launch_lpt_order(uint32_t* d_cost, int n, int shift, uint32_t* d_scra
 hipError_t launch_static_order(int mode, int tiles_x, int slabs, int grid, uint32_t* d_order, hipStream_t s);
 // frame band k (band_bytes each, total_bands of them) = member k % members, local band k / members of a gathered rank-major buffer
 hipError_t launch_interleave_bands(const void* d_gathered, size_t member_stride_bytes, int members, size_t band_bytes, int total_bands, void* d_frame, hipStream_t s);
-// test hook: cloud_core.h::sqrt_shell over an array
-hipError_t launch_sqrt_shell(const float* d_in, float* d_out, size_t n, hipStream_t s);
+
+// ------------------------------------------------------------------------------------------------ cloud_kernels.hip, the direct march
 // the direct march (rays_core.h): g.w x g.h RGBA16F texels into d_out, row pitch g.pitch_px pixels, for the directions of d_dirs ([h][w][3] floats),
 // or for the view of g when d_dirs is null.  d_fc: the cloud frame's own frame constants (launch_frame_setup*).  t32: march on the exact
 // fp32-coefficient cells.  A plain launch in natural order; g travels as a kernel argument.
@@ -159,5 +161,7 @@ hipError_t launch_radiance_filter(const float4* d_tab, const float4* d_src_cones
 // test hook: primitive `op` (primitives_core.h PrimOp) over n elements, one per lane.  d_in / d_out: prim_shape(op) words per element each; an
 // array the op does not use may be null.
 hipError_t launch_primitive(int op, const uint32_t* const d_in[3], uint32_t* const d_out[2], size_t n, hipStream_t s);
+// test hook: cloud_core.h::sqrt_shell over an array
+hipError_t launch_sqrt_shell(const float* d_in, float* d_out, size_t n, hipStream_t s);
 
 }  // namespace csky

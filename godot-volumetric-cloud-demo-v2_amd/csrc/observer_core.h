@@ -3,7 +3,7 @@
 //
 // rays_core.h makes the march's Ray from a direction as clouds.glsl does: from camPos = (0, g_radius, 0), inner shell to outer shell.  This file
 // makes it from a direction and a POSITION: the observer may stand under the layer, inside it or above it, the ray's first segment through the layer
-// runs up, down or level, and a distance cap may end it early.  The march behind it is the same (cloud_kernels.hip march_compact, cloud_core.h
+// runs up, down or level, and a distance cap may end it early.  The march behind it is the same (march_compact.h march_compact, cloud_core.h
 // march()): density, height window and light march are functions of position.
 //
 // Host+device (CSKY_HD) like rays_core.h: tests/observer_host runs this per-lane code on a CPU.  The product instantiates it inside

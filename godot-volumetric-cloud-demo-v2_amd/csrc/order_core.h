@@ -1,6 +1,6 @@
 // order_core.h -- the index arithmetic of the launch orders: which workgroup footprint a physical workgroup renders.
 //
-// Shared, like lut_core.h and tlut_core.h, by the device (cloud_kernels.hip: static_order_kernel, the lpt_* kernels, the pop loop of
+// Shared, like lut_core.h and tlut_core.h, by the device (order_kernels.hip: static_order_kernel, the lpt_* kernels; cloud_kernels.hip: the pop loop of
 // clouds_kernel_persistent), the host layer (clouds_launch.cpp: the grid of a static order, the bucket shift of the cost feedback) and
 // tests/hostsim, which compiles it with g++ so that tests/test_launch_order.py checks every function here against a numpy restatement of
 // what the orders MEAN, without a GPU.  No HIP, no state.

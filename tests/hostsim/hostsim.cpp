@@ -119,7 +119,7 @@ void hostsim_clouds(const uint8_t* large_chain, const uint8_t* small_chain, cons
     if (incloud) *incloud = ic;
 }
 
-// Precondition of the march's exact early end (cloud_kernels.hip::march_compact): a ray starts on the inner shell and its radius only grows, so once
+// Precondition of the march's exact early end (march_compact.h::march_compact): a ray starts on the inner shell and its radius only grows, so once
 // a sample is at or above the top of the height window every later sample of that ray is too.  Walks every ray of a W x H frame with the
 // kernel's own ray set-up and fp32 position updates.  out[0] = above-horizon rays, out[1] = rays whose height-fraction sequence ever
 // decreases, out[2] = samples with hf < hi AFTER a sample with hf >= hi, out[3] = smallest radius gain of a step in metres (unclamped).

@@ -1,4 +1,4 @@
-"""Launches that deliver no in-cloud count stop marching a ray whose stored pixel is final (cloud_kernels.hip march_compact, TALLY = false): the C3-size
+"""Launches that deliver no in-cloud count stop marching a ray whose stored pixel is final (march_compact.h march_compact, TALLY = false): the C3-size
 frame through csky_render_clouds_device, which passes no stats buffer, against the same frame through a stats launch (TALLY = true, the march as it was).
 Frames must be equal array for array, and the stats launch's in-cloud count the full march's: the figure the kernel delivered before the change
 (measured with the parent commit's library on an MI355X: profiles/r12/counts_parent_and_change.txt; the CPU walk of tests/tilewalk counts 6 and 7 samples

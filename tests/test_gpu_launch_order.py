@@ -1,4 +1,4 @@
-"""The order kernels on the device (cloud_kernels.hip: static_order_kernel, lpt_hist / lpt_scan / lpt_scatter) through the two lab-bench hooks
+"""The order kernels on the device (order_kernels.hip: static_order_kernel, lpt_hist / lpt_scan / lpt_scatter) through the two lab-bench hooks
 csky_test_static_order and csky_test_lpt_order: the static tables entry for entry against the host's (tests/hostsim, which tests/test_launch_order.py
 checks against a numpy restatement on the CPU), the counting sort against numpy."""
 import numpy as np

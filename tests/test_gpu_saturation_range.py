@@ -1,4 +1,4 @@
-"""The saturation skip on the device over the range its proof assumes (cloud_core.h ray_saturated, the comment above it; cloud_kernels.hip march_compact).
+"""The saturation skip on the device over the range its proof assumes (cloud_core.h ray_saturated, the comment above it; march_compact.h march_compact).
 The headline path -- csky_render_clouds_device without a stats buffer, whole rays, TALLY = false, a latched ray is DEAD -- rests on that proof and on the
 device's v_exp_f32 / v_rcp_f32 / v_cvt_f16_f32 behaving as it assumes.  Every scene of tests/saturation_scenes.py (light energies 0 .. 1e30, a dark colour
 channel, a bright ground, density 0 and 5, suns below the horizon, 1 .. 1024 primary steps, a stratus-only weather map, the early-out, blocks the guard of

@@ -1,4 +1,4 @@
-"""The saturation skip on the GPU (cloud_kernels.hip march_compact; cloud_core.h ray_saturated): csky_set_height_window(1) against (0), which switches
+"""The saturation skip on the GPU (march_compact.h march_compact; cloud_core.h ray_saturated): csky_set_height_window(1) against (0), which switches
 the exact specialisations -- this one included -- off.  Frames must be equal array for array and the sample tallies equal."""
 import numpy as np
 import pytest

@@ -101,7 +101,7 @@ def test_height_window_reject_is_exact(hostsim, pkg, oracle, noise, o_skies):
 
 
 def test_radius_only_grows_along_a_ray_precondition_of_the_early_march_end(hostsim, oracle):
-    """cloud_kernels.hip::march_compact ends a wavefront's march once every live ray is at or above the top of the height window.  That is exact
+    """march_compact.h::march_compact ends a wavefront's march once every live ray is at or above the top of the height window.  That is exact
     iff no ray ever comes back below a height fraction it has reached.  Every above-horizon ray of the headline frame (2048x1024, 128 steps),
     of the 4096x2048 frame and of a small frame, walked with the kernel's own ray set-up and fp32 position updates: the height fraction
     never decreases, no sample falls back below the window top (default 0.788, and other levels), and the smallest radius gain of any step

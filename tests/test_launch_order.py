@@ -1,5 +1,5 @@
 """The launch orders on the host: csrc/order_core.h, compiled with g++ by tests/hostsim, against a numpy restatement of what each order MEANS
-(cloud_kernels.hip, "static workgroup orders" and "cost-feedback schedule"; clouds_kernel_persistent).  The restatement builds every table from the
+(order_kernels.hip, "static workgroup orders" and "cost-feedback schedule"; cloud_kernels.hip clouds_kernel_persistent).  The restatement builds every table from the
 sequences the eight XCDs are meant to walk, not from the C expressions, and the properties the launch relies on are asserted on their own:
 every footprint exactly once, idle entries everywhere else, the grid the launch code uses.
 
@@ -107,8 +107,8 @@ def test_static_order_grid_is_what_the_launch_code_uses(hostsim):
     launch = open(os.path.join(csrc, "clouds_launch.cpp")).read()
     assert "const int grid = static_order_grid(mode, tiles_x, slabs);" in launch
     assert ">> 3) * 8" not in launch and ">> 3) * tiles_x" not in launch
-    kern = open(os.path.join(csrc, "cloud_kernels.hip")).read()
-    assert "out[b] = static_order_entry(mode, tiles_x, slabs, b);" in kern and "persistent_pop_index(j, y, n_items, i)" in kern
+    order_kern, kern = (open(os.path.join(csrc, f)).read() for f in ("order_kernels.hip", "cloud_kernels.hip"))
+    assert "out[b] = static_order_entry(mode, tiles_x, slabs, b);" in order_kern and "persistent_pop_index(j, y, n_items, i)" in kern
     for mode in MODES:
         for tiles_x, slabs in REAL + [(1, 1), (3, 7), (70, 140)]:
             assert hostsim.hostsim_static_order_grid(mode, tiles_x, slabs) == reference_grid(mode, tiles_x, slabs)

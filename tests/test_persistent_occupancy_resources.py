@@ -2,7 +2,7 @@
 
 A gfx950 CU has 160 KB of LDS and 512 VGPRs per lane, so eight 256-thread workgroups (eight waves per SIMD) fit only with at most 64 VGPRs and at most
 163 840 / 8 = 20 480 bytes of LDS each, and the eighth wave is worth nothing if it is paid with scratch traffic.  The kernel states the LDS sum in a
-static_assert; it is restated here from the CQ_* constants as the source spells them (they live in cloud_kernels.hip, which no host build includes), and
+static_assert; it is restated here from the CQ_* constants as the source spells them (they live in march_compact.h, which no host build includes), and
 checked against what the compiler reports for the two forms.  Every other persistent form keeps the wide queue and seven waves."""
 import os
 import re
@@ -21,8 +21,8 @@ PERSISTENT = "_ZN4csky24clouds_kernel_persistentILi3ELb%dELi%dEEE"
 
 
 def constants():
-    """the `constexpr int CQ_* = ...;` lines of cloud_kernels.hip, evaluated in order"""
-    text = open(os.path.join(CSRC, "cloud_kernels.hip")).read()
+    """the `constexpr int CQ_* = ...;` lines of march_compact.h, evaluated in order"""
+    text = open(os.path.join(CSRC, "march_compact.h")).read()
     env = {}
     for name, expr in re.findall(r"^constexpr int (CQ_\w+) = ([^;]+);", text, re.M):
         assert re.fullmatch(r"[\w\s+*/()-]+", expr), (name, expr)

@@ -1,5 +1,5 @@
 """The compact march per 8x8 tile on the CPU (tests/tilewalk: lock-step primary steps, the 64-sample flush, the in-order replay, the saturation test after
-the replay, the carry), in both forms of the kernel's TALLY parameter (cloud_kernels.hip march_compact): the launch that delivers the in-cloud count, where a
+the replay, the carry), in both forms of the kernel's TALLY parameter (march_compact.h march_compact): the launch that delivers the in-cloud count, where a
 latched ray keeps taking primary samples, and the launch that does not, where a latched ray is dead.  Required on the frames tests/test_saturation_skip.py
 walks: no ray stores a different half than the plain walk in either form, the counting form delivers the plain walk's in-cloud count, and the dead-lane form
 removes primary lane-steps.  The floors are a third of the cut the emulation measured when the change was proposed (-7.9 % of the in-window lane-steps

@@ -1,4 +1,4 @@
-// tile_walk.cpp -- TEST TOOL ONLY.  A CPU emulation of the compact march (cloud_kernels.hip march_compact, whole rays, fp16-pair cells) on the kernel
+// tile_walk.cpp -- TEST TOOL ONLY.  A CPU emulation of the compact march (march_compact.h march_compact, whole rays, fp16-pair cells) on the kernel
 // cores (cloud_core.h, compiled for the host): per 8x8-pixel tile, 64 rays in lock step exactly as one wavefront runs them --
 //   A. one primary sample per live lane and step; the lanes whose sample is in cloud append it to the tile's queue in lane order, the step records its
 //      lane mask and base slot; every 4th step the march ends if no lane is below the top of the height window;
@@ -43,7 +43,7 @@ struct Sample { float px, py, pz, t, hf; int owner; };
 struct Step { uint64_t mask; int base; };
 struct Terms { float Dr, Dg, Db, rq, dt; };
 
-// the light march of one queued sample and the state-independent half of its shading (cloud_kernels.hip light_march_terms)
+// the light march of one queued sample and the state-independent half of its shading (march_compact.h light_march_terms)
 static Terms light_terms(const TexSet& T, const FrameConsts& fc, const Sample& e, float ss, float phase) {
     const float nd = -fc.density;
     float lx = e.px, ly = e.py, lz = e.pz, cd = 0.0f;

@@ -25,7 +25,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "godot-volumetric-cloud-demo-v2_amd", "csrc")
-CLOUD_SRC = "cloud_kernels.hip"      # the file of the march: what the census, the instrumented build and the line profile look at
+CLOUD_SRC = "cloud_kernels.hip"      # the hemisphere's kernels, with the march they include (march_compact.h): what the census, the instrumented build and the line profile look at
 
 FULL = ("v_fma_f32", "v_fmac_f32", "v_mul_f32", "v_add_f32", "v_sub_f32", "v_subrev_f32", "v_mov_b32", "v_and_b32", "v_or_b32", "v_xor_b32",
         "v_add_u32", "v_sub_u32", "v_subrev_u32", "v_add_co_u32", "v_addc_co_u32", "v_sub_co_u32", "v_subb_co_u32", "v_not_b32", "v_mac_f32", "v_madak_f32", "v_madmk_f32",

@@ -35,7 +35,7 @@ import isa_census as IC  # noqa: E402
 CSRC = os.path.join(ROOT, "godot-volumetric-cloud-demo-v2_amd", "csrc")
 LLVM = "/opt/rocm/lib/llvm/bin"
 # "plain" / "persistent": the instantiations the headline path and every timed launch run, without the in-cloud tally and with latched rays stopped
-# (cloud_kernels.hip march_compact, TALLY = false): what csky_census_clouds launches, and what bench.py compares with the hardware counters;
+# (march_compact.h march_compact, TALLY = false): what csky_census_clouds launches, and what bench.py compares with the hardware counters;
 # "*_tally": the ones a launch with a stats buffer runs, which csky_census_clouds launches with CSKY_CENSUS_TALLY=1 in the environment
 # The persistent form is compiled per cloud-type mode (cloud_kernels.hip clouds_kernel_persistent<3, TALLY, CT>; launch_clouds picks CT from the bound
 # weather map): the shipped map's red channel is >= 128 everywhere, so every timed launch and csky_census_clouds run CT = 1, and that is what is counted.

@@ -4,7 +4,8 @@
 Block execution counts of a census run (tools/isa_profile.py run -> profiles/rNN/census_counts_*.json) x the per-block instructions of the
 CURRENT device assembly built with line tables (isa_census.build_asm: -gline-tables-only, same code generation).  The block structure must
 match the census build's (same number of blocks and the same instruction kinds per block); the tool refuses otherwise.  Where the kernel's
-issue time goes, by line of cloud_core.h / cloud_kernels.hip: the map the instruction diet of round 4 was planned with."""
+issue time goes, by line of cloud_core.h / march_compact.h / cloud_kernels.hip (a line carries the name of the file it is written in: the march's
+lines are march_compact.h's, the kernel's own cloud_kernels.hip's): the map the instruction diet of round 4 was planned with."""
 import argparse, collections, json, os, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
