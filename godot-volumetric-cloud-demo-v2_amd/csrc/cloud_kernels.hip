@@ -472,7 +472,8 @@ hipError_t launch_clouds_view_update(const TexSet& t, const TexSet32* t32, const
 
 // ---- the direct march from an observer's position -------------------------------------------------------------------
 // clouds_rays_kernel with another front end: observer_core.h observer_ray makes the lane's Ray from its direction AND the observer's position (under,
-// inside or above the layer; the first segment through the layer, capped).  The same shape: one pixel per lane, an 8x8 tile per wavefront, four
+// inside or above the layer; the first segment through the layer, capped; a segment too short to have a direction in fp32 is not marched: a zero
+// Ray, as scene_depth_ray_k's).  The same shape: one pixel per lane, an 8x8 tile per wavefront, four
 // tiles per workgroup, the same LDS queue and launch bound, a plain launch in natural order.  march_compact<true, false, 0, TS, false>: these rays
 // descend, or dip and rise, so the wavefront's early end is "no lane is live" and not "every lane is above the window".
 

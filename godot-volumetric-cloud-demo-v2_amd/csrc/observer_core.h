@@ -101,16 +101,30 @@ CSKY_HD bool observer_segment(const float o[3], float max_dist, float dx, float 
 // The ray of a direction as a lane uses it; `above` means "marched".  Not marched: `above = false`, zero fields (no sample, a zero texel), as
 // rays_ray's.  The tail from `shelldist` on restates cloud_core.h ray_from_dir's (sharing it through a helper would change that function's own
 // compiled code): with position (0, 0, 0) and no cap all eleven fields are rays_ray's bit for bit (tests/test_observer_host.py O1).
+//
+// The last clause of `marched`: a segment long enough to have a direction.  World positions are near 6e6 m, where fp32 has a quantum of 0.5 m, so a
+// max_distance within that quantum of t0 (1500.2 m straight up from the ground: t0 = 1500) passes `t1 > t0` and still rounds the end onto the start:
+// shelldist = 0, ss = 0, dir = 0 / 0.  From inside the layer on the axis (t0 = 0, o.x = o.z = 0) a cap of 1e-22 m gives a shelldist > 0 whose raystep's
+// squares underflow, and the same NaN.  So both square roots of the tail must take an argument inside sqrt_exact's specified range:
+// |end - start|^2 >= 2^-102 and |raystep|^2 >= 2^-102, scene_depth_core.h scene_depth_ray_k's clause.  On that range host and device agree bit for
+// bit and dir is a unit vector.  Otherwise the ray is not marched.
 CSKY_HD Ray observer_ray(const FrameConsts& fc, const ObserverGeom& G, float ex, float ey, float ez) {
     Ray r;
     float t0 = 0.0f, t1 = 0.0f;
     r.above = observer_accept(ex, ey, ez) && observer_segment(G.o, G.max_dist, ex, ey, ez, t0, t1);
+    float s0x = 0.0f, s0y = 0.0f, s0z = 0.0f, rx = 0.0f, ry = 0.0f, rz = 0.0f, ss2 = 0.0f;
+    if (r.above) {
+        s0x = G.o[0] + ex * t0; s0y = G.o[1] + ey * t0; s0z = G.o[2] + ez * t0;                                            // start
+        const float e0x = G.o[0] + ex * t1, e0y = G.o[1] + ey * t1, e0z = G.o[2] + ez * t1;                                // end
+        const float qx = e0x - s0x, qy = e0y - s0y, qz = e0z - s0z;
+        const float sd2 = qx * qx + qy * qy + qz * qz;                                 // length3_exact's own argument
+        const float shelldist = sqrt_exact(sd2);
+        rx = ex * shelldist / fc.steps_f; ry = ey * shelldist / fc.steps_f; rz = ez * shelldist / fc.steps_f;              // clouds.glsl:230
+        ss2 = rx * rx + ry * ry + rz * rz;
+        r.above = sd2 >= SQRT_EXACT_MIN && ss2 >= SQRT_EXACT_MIN;
+    }
     if (!r.above) { r.px = r.py = r.pz = r.sx = r.sy = r.sz = r.dx = r.dy = r.dz = r.ss = 0.0f; return r; }
-    const float s0x = G.o[0] + ex * t0, s0y = G.o[1] + ey * t0, s0z = G.o[2] + ez * t0;  // start
-    const float e0x = G.o[0] + ex * t1, e0y = G.o[1] + ey * t1, e0z = G.o[2] + ez * t1;  // end
-    const float shelldist = length3_exact(e0x - s0x, e0y - s0y, e0z - s0z);
-    const float rx = ex * shelldist / fc.steps_f, ry = ey * shelldist / fc.steps_f, rz = ez * shelldist / fc.steps_f;  // clouds.glsl:230
-    r.ss = length3_exact(rx, ry, rz);                                                  // :143
+    r.ss = sqrt_exact(ss2);                                                            // :143
     r.dx = rx / r.ss; r.dy = ry / r.ss; r.dz = rz / r.ss;                              // :144
     r.sx = r.dx * r.ss; r.sy = r.dy * r.ss; r.sz = r.dz * r.ss;
     r.px = s0x; r.py = s0y; r.pz = s0z;                                                // hash() == 0 (ray_from_dir): p = start

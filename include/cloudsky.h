@@ -645,9 +645,14 @@ int csky_render_clouds_view_update_device(csky_ctx* ctx, const csky_cloud_params
  *            inside: t0 = 0;  t1 = (b < 0 and D(B) >= 0) ? near(B) : far(T)
  *            above : no segment unless b < 0 and D(T) >= 0;  t0 = near(T);  t1 = D(B) >= 0 ? near(B) : far(T)
  *   cap      t1 = fminf(t1, max_distance)
- *   marched  accepted, a segment, and t1 > t0  (NaN fails).  Otherwise the texel is (0, 0, 0, 0) and the ray takes no sample
  *   ray      start = o + e*t0, end = o + e*t1; shelldist = |end - start|; raystep = e * shelldist / N; ss = |raystep|; dir = raystep / ss; p = start
+ *   marched  accepted, a segment, t1 > t0, |end - start|^2 >= 2^-102 and |raystep|^2 >= 2^-102  (NaN fails; the two sums of three squares whose
+ *            roots are shelldist and ss).  Otherwise the texel is (0, 0, 0, 0) and the ray takes no sample
  *   texel    march() of clouds.glsl:139-215 on that ray: N samples, the first one full step past `start`, L.rgb, alpha, four halves
+ * The last two clauses of `marched`: world positions are near 6e6 m, where fp32 has a quantum of 0.5 m.  A max_distance within that quantum of a
+ * ray's t0 (1500.2 m straight up from the ground observer, whose t0 is 1500) passes t1 > t0 and still rounds the end onto the start: ss = 0 and
+ * dir = 0 / 0.  shelldist > 0 alone does not exclude it (from an observer on the axis inside the layer a max_distance of 1e-22 m has shelldist > 0
+ * and still ss = 0), so both roots must take an argument a float square root resolves.  Such a ray is not marched: a zero texel.
  * Only the first segment through the layer is marched: a ray from above that leaves through the bottom, or a tangent ray that leaves through the
  * top, does not re-enter.  With position = (0, 0, 0) and max_distance = +inf the calls give the bytes of csky_render_clouds_view / _dirs.
  * Limits: the frame constants (sun, ambient and ground colours from the sky LUT) stay those of the ground observer, the atmosphere LUT's eye does

@@ -11,9 +11,10 @@ For a direction e, the observer's world position o = (position[0], G_RADIUS + po
              inside: t0 = 0;  t1 = (b < 0 and D(B) >= 0) ? near(B) : far(T)
              above : no segment unless b < 0 and D(T) >= 0;  t0 = near(T);  t1 = D(B) >= 0 ? near(B) : far(T)
     cap      t1 = min(t1, max_distance)
-    marched  accepted, a segment, and t1 > t0                                               (NaN fails)
     ray      start = o + e*t0, end = o + e*t1; shelldist = |end - start|; raystep = e * shelldist / N; ss = |raystep|; dir = raystep / ss;
              inc = dir * ss; p = start
+    marched  accepted, a segment, t1 > t0, |end - start|^2 >= 2^-102 and |raystep|^2 >= 2^-102    (NaN fails)
+             (the squares as summed for the two square roots; a segment too short to have a direction in fp32 is not marched)
 
 Written from the definition, one operation per line, not from csrc/observer_core.h: float32 throughout, in the order written (dot products summed
 left to right; numpy's float32 add, multiply, divide and sqrt are IEEE: exactly the operations of code compiled without contraction)."""
@@ -22,6 +23,7 @@ import numpy as np
 from ray_reference import RB, RG, RT
 
 F = np.float32
+SQRT_EXACT_MIN = F(2.0 ** -102)                                 # cloud_core.h: both square roots of the ray's tail take at least this
 
 
 def origin(position):
@@ -93,6 +95,38 @@ def segment(position, max_distance, e):
     return t0.astype(F), t1, has
 
 
+def classify(position, e, dtype=F):
+    """(where, has, chord, t1_on_top) of directions float32 [..., 3], before the cap: where the definition puts the observer (0 below, 1 inside, 2
+    above: one value, the observer's), whether the line has a segment, whether that segment leaves the layer's height range downwards and comes
+    back (above: in through the top and out through it; inside: b < 0 and the inner shell missed), and whether its far end is on the outer shell.
+    The definition's own tests, evaluated in `dtype`: float32 is what `segment` decides, float64 the geometry of the same fp32 inputs."""
+    T = dtype
+    e = np.asarray(e, F).astype(T)
+    o = origin(position).astype(T)
+    x, y, z = e[..., 0], e[..., 1], e[..., 2]
+    with np.errstate(all="ignore"):
+        a = x * x
+        a = a + y * y
+        a = a + z * z
+        b = x * o[0]
+        b = b + y * o[1]
+        b = b + z * o[2]
+        b = T(2.0) * b
+        c0 = o[0] * o[0]
+        c0 = c0 + o[1] * o[1]
+        c0 = c0 + o[2] * o[2]
+        cb, ct, cg = T(c0 - T(RB) * T(RB)), T(c0 - T(RT) * T(RT)), T(c0 - T(RG) * T(RG))
+        k = T(4.0) * a
+        Db, Dt, Dg = b * b - k * cb, b * b - k * ct, b * b - k * cg
+        no = np.zeros(a.shape, bool)
+        if cb < 0:
+            return 0, ~((b <= 0) & (Dg >= 0)), no, ~no
+        if ct > 0:
+            return 2, (b < 0) & (Dt >= 0), Db < 0, Db < 0
+        down = (b < 0) & (Db >= 0)
+        return 1, ~no, (b < 0) & (Db < 0), ~down
+
+
 def ray(position, max_distance, e, steps):
     """float32 [..., 11] (p, inc, dir, ss, marched as 1 / 0) of directions float32 [..., 3]; all zero where the ray is not marched."""
     e = np.asarray(e, F)
@@ -108,11 +142,13 @@ def ray(position, max_distance, e, steps):
         sd = qx * qx
         sd = sd + qy * qy
         sd = sd + qz * qz
+        marched = marched & (sd >= SQRT_EXACT_MIN)
         sd = np.sqrt(sd)
         rx, ry, rz = x * sd / n, y * sd / n, z * sd / n
         ss = rx * rx
         ss = ss + ry * ry
         ss = ss + rz * rz
+        marched = marched & (ss >= SQRT_EXACT_MIN)
         ss = np.sqrt(ss)
         ux, uy, uz = rx / ss, ry / ss, rz / ss
         out = np.stack([sx, sy, sz, ux * ss, uy * ss, uz * ss, ux, uy, uz, ss, np.ones_like(ss)], -1).astype(F)
